@@ -13,7 +13,10 @@ Monte-Carlo instances, so ranks share nothing on the data path (weak scaling: ev
 same workload with its own seed); the single collective is the all-gather of per-filter NIS/NEES
 summaries at the end of the timed region.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the headline (with the dense pass's
+roofline from the events inside the timed region); --dump-outputs DIR writes what the last timed step computed.  Everything else --
+the decision check, the untimed windows that time the chain kernel alone, the chain record, the CPU baselines, the secondary
+configurations and config 5's legs -- runs with --full.
 """
 import argparse
 import json
@@ -381,8 +384,40 @@ def host_cpu_record():
     return rec
 
 
-def measure(pkg, mc, torch, dist, coll_device, rank, world, dev_id, workload, K, W, M, max_pending, graph, flush_profile, check=True, alone=True, latency=False):
-    """One workload, timed as the contract says (timed_steps); returns its record."""
+DUMP_P_ENTRIES = 1 << 21  # P entries sampled across the batch by --dump-outputs: 16 MB of values and 16 MB of indices at most
+
+
+def dump_outputs(f, out_dir, gathered, K, M):
+    """--dump-outputs: what the last timed step hands its caller, one float64 .npy file each -- x (batch, n); P's diagonal and a fixed
+    sample of P's entries (the same seeded flat indices in every filter, P_sample_index; all of P when it fits); the poses; the branch,
+    matched landmark and Mahalanobis distance of the step's M measurements; the gathered (mean NIS, mean NEES) per filter."""
+    import numpy as np
+    xs, diag, sample, idx = [], [], [], None
+    for b in range(f.batch):
+        x, P = f.get_state(b)
+        if idx is None:
+            per = DUMP_P_ENTRIES // f.batch
+            idx = np.arange(P.size) if P.size <= per else np.unique(np.random.default_rng(0).integers(0, P.size, size=per))
+        xs.append(x)
+        diag.append(np.diag(P).copy())
+        sample.append(P.ravel()[idx])
+        del P
+    out = {"x": np.stack(xs), "P_diag": np.stack(diag), "P_sample": np.stack(sample), "P_sample_index": idx, "poses": f.poses(),
+           "nis_nees": gathered}
+    if M:
+        last = np.array([f.decisions(b, K * M)[-M:] for b in range(f.batch)], dtype=np.float64)  # (batch, M, [decision, matched, mahal])
+        out.update({"decision": last[..., 0], "matched": last[..., 1], "mahalanobis": last[..., 2]})
+    out = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    assert total <= 64 << 20, "the dump would be %d bytes" % total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
+def measure(pkg, mc, torch, dist, coll_device, rank, world, dev_id, workload, K, W, M, max_pending, graph, flush_profile, check=True, alone=True, latency=False,
+            dump_dir=None):
+    """One workload, timed as the contract says (timed_steps); returns its record.  `dump_dir`: dump_outputs() right after the timed steps."""
     import numpy as np
     N, B, _, _, seed, extent, min_sep = WORKLOADS[workload]
     lo, hi = mc.shard_range(B * world, rank, world)
@@ -405,6 +440,8 @@ def measure(pkg, mc, torch, dist, coll_device, rank, world, dev_id, workload, K,
             assert [d[1] for d in dec] == want, "filter %d matched an unintended landmark" % b
         st = f.stats()
         assert all(s["n_old"] == K * M and s["n_new"] == 0 and s["n_ignore"] == 0 for s in st)
+    if dump_dir:
+        dump_outputs(f, dump_dir, gathered, K, M)
     lat = None
     if latency:
         # per-step latency: one scripted step per call, host clock from the call to the moment the pose of
@@ -450,7 +487,7 @@ def measure(pkg, mc, torch, dist, coll_device, rank, world, dev_id, workload, K,
         alone_launches, alone_ms = f.flush_profile_read()
         chain_alone_us = chain_alone_ms * 1e3 / (4 * win_steps * M) if M else None
     roof = roofline_record(pkg, f, workload, B, N, K, M, window, launches, flush_ms, alone_launches, alone_ms, dev_ms, elapsed)
-    rep = mc.consistency_report(gathered, K * M, K)
+    rep = mc.consistency_report(gathered, K * M, K) if check else None
     overlap = int(f.overlap)
     f.close()
     return {"workload": workload, "N": N, "B": B, "K": K, "W": W, "M": M, "window": window, "overlap": overlap, "elapsed": elapsed, "dev_ms": dev_ms,
@@ -687,7 +724,7 @@ def dry_run(args, rank, world, ekf_env):
         # the record a real run builds (config5_leg_record), with no GPU work behind it: value and the roofline's numbers are None
         c5[leg] = config5_leg_record(total, hi - lo, world, 1, None, out.shape[0], per_rank, el * 1e6, None)
     # which ranks would time the CPU baselines in a real run of this shape (gathered so that the test sees every rank's answer)
-    mine = 1.0 if runs_cpu_baseline(rank, world, args.no_cpu_baseline) else 0.0
+    mine = 1.0 if args.full and runs_cpu_baseline(rank, world, args.no_cpu_baseline) else 0.0
     cpu_ranks = [mine]
     if world > 1:
         tl = [torch.zeros(1, dtype=torch.float64) for _ in range(world)]
@@ -742,19 +779,23 @@ def main():
     ap.add_argument("--max-pending", type=int, default=0, help="measurements folded per dense pass over P_LL (1 = a dense pass per measurement, as the reference does); "
                     "0 = the workload's own default: 16, and 32 for the batch of one-workgroup filters (k_solo's long window)")
     ap.add_argument("--graph", type=int, default=0, help="replay steps through HIP graphs (one k_chain launch already covers several steps; plain launches keep the per-launch dense-pass events)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary records (configs 1, 2, 4 and M = 1) that ride on the default line")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the decision check, the chain kernel timed alone and the chain record, "
+                    "the CPU baselines, the secondary records, and config 5's legs for --gpus N > 1 or --workload batch256")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float64; "
+                    "a fixed sample of P): the same arguments give the same inputs, so two builds can be compared output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary records (configs 1, 2, 4 and M = 1)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, the real thing) or gloo (rehearsal of the multi-rank path on a one-GPU box)")
     ap.add_argument("--device", type=int, default=None, help="force a device id (rehearsal only; default LOCAL_RANK)")
     ap.add_argument("--no-flush-profile", action="store_true", help="do not bracket the dense pass with hipEvents")
-    ap.add_argument("--no-config5", action="store_true", help="with --gpus N > 1: skip the config-5 legs (256 filters/GPU weak, 2048 filters strong)")
+    ap.add_argument("--no-config5", action="store_true", help="with --full: skip the config-5 legs (256 filters/GPU weak, 2048 filters strong)")
     ap.add_argument("--config5-steps", type=int, default=None, help="timed steps of the config-5 legs (default: the batch256 workload's 200)")
     ap.add_argument("--secondary-only", action="store_true", help="(internal) run only the secondary records and print them: bench.py starts itself this way as a child, so that a fault or a hang in a secondary leg cannot cost the headline")
     ap.add_argument("--secondary-budget", type=float, default=420.0, help="wall-clock limit in seconds of the child that measures the secondary records")
     ap.add_argument("--cpu-structured-child", action="store_true", help="(internal) one timed run of the structured CPU oracle in a process whose OpenMP runtime starts with the pinning variables set")
     ap.add_argument("--threads", type=int, default=1, help="(internal) OpenMP threads of --cpu-structured-child")
     ap.add_argument("--verbose", action="store_true", help="put the prose fields (byte model, window note, environment notes) on the JSON line; the default line carries numbers and stays under 8 KB (the driver keeps an 8 KB tail)")
-    ap.add_argument("--config5", action="store_true", help="run both config-5 legs (weak 256 filters/GPU, strong 2048 in all) whatever the world size; by default they run for --gpus N > 1, and the weak leg alone rides on a one-GPU --workload batch256 line")
+    ap.add_argument("--config5", action="store_true", help="run both config-5 legs (weak 256 filters/GPU, strong 2048 in all) whatever the world size; with --full they run for --gpus N > 1, and the weak leg alone rides on a one-GPU --workload batch256 line")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous / shard / all-gather plumbing only, no GPU work: every rank gathers synthetic per-filter rows of its config-5 shards (CPU rehearsal, gloo)")
     args = ap.parse_args()
     if args.cpu_structured_child:
@@ -800,10 +841,11 @@ def main():
     coll_device = torch.device("cuda", dev_id) if args.dist_backend == "nccl" else torch.device("cpu")
 
     # ---- the headline: inputs built on the host and moved to HBM (untimed), warm-up (untimed), exactly K timed steps -------
-    head = None if args.secondary_only else measure(pkg, mc, torch, dist, coll_device, rank, world, dev_id, args.workload, K, W, M, args.max_pending, bool(args.graph), not args.no_flush_profile)
+    head = None if args.secondary_only else measure(pkg, mc, torch, dist, coll_device, rank, world, dev_id, args.workload, K, W, M, args.max_pending, bool(args.graph),
+                                                    not args.no_flush_profile, check=args.full, alone=args.full, dump_dir=args.dump_outputs if rank == 0 else None)
 
     config5 = None
-    if not args.secondary_only and not args.no_config5 and (world > 1 or args.config5 or args.workload == "batch256"):
+    if not args.secondary_only and not args.no_config5 and (args.config5 or (args.full and (world > 1 or args.workload == "batch256"))):
         legs = ("weak", "strong") if (world > 1 or args.config5) else ("weak",)  # (one GPU, --workload batch256: the weak leg is config 4 itself, carrying config 5's keys)
         config5 = config5_legs(pkg, mc, torch, dist, coll_device, rank, world, dev_id, M, args.max_pending, args.config5_steps, legs)
 
@@ -845,18 +887,18 @@ def main():
         return
 
     cpu = cpu_strong = None
-    if runs_cpu_baseline(rank, world, args.no_cpu_baseline):
+    if args.full and runs_cpu_baseline(rank, world, args.no_cpu_baseline):
         cpu = cpu_baseline(pkg, N, M, seed, extent, min_sep)
         cpu_strong = cpu_baseline_structured(args.workload, M)
         if cpu and cpu_strong and cpu_strong.get("value"):
             cpu_strong["gpu_over_cpu"] = {"faithful_dense_1_thread": head["value"] / cpu["value"], "structured_all_cores": head["value"] / cpu_strong["value"],
                                           }  # (a ratio says nothing about kernel quality; the roofline does)
 
-    if world == 1 and not args.no_secondary and args.workload == "n4096":
+    if args.full and world == 1 and not args.no_secondary and args.workload == "n4096":
         secondary = secondary_in_a_child(args, dev_id)
 
     chain = None
-    if B == 1:
+    if args.full and B == 1:
         pipe = None
         if secondary and isinstance(secondary.get("config3_512_steps"), dict) and args.workload == "n4096":
             pipe = secondary["config3_512_steps"].get("device_us_per_measurement")
@@ -864,7 +906,7 @@ def main():
     rep = head["report"]
     # the steady workload feeds 0.5-sigma measurement noise and a noise-free truth (margins
     # for the gate), so NIS/NEES below their dof are expected here; the chi-square verdict is for config 1 style runs
-    mc_stats = {k: (None if v is None else {"mean": v["mean"], "dof": v["dof"], "filters": v["filters"]}) for k, v in rep.items()}
+    mc_stats = None if rep is None else {k: (None if v is None else {"mean": v["mean"], "dof": v["dof"], "filters": v["filters"]}) for k, v in rep.items()}
     elapsed, dev_ms, window = head["elapsed"], head["dev_ms"], head["window"]
     line = {
         "metric": "EKF steps/sec (propagate+full update) at N landmarks",

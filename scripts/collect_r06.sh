@@ -47,8 +47,8 @@ echo "collect_r06 fused done"
 fi
 if [ "$WHAT" = bench ]; then
 cd $R
-python bench.py > gpurun_out/r06_bench_default_full.json 2> gpurun_out/r06_bench_default_full.err
-for i in 1 2 3; do python bench.py --steps 20 --warmup 5 > gpurun_out/r06_bench_driver_$i.json 2> gpurun_out/r06_bench_driver_$i.err; done
-python bench.py --workload batch256 --no-secondary --no-cpu-baseline > gpurun_out/r06_bench_batch256.json 2> gpurun_out/r06_bench_batch256.err
+python bench.py --full > profiles/r06_bench_default_full.json
+for i in 1 2 3; do python bench.py --steps 20 --warmup 5 --full > profiles/r06_bench_driver_$i.json; done
+python bench.py --workload batch256 --no-secondary --no-cpu-baseline --full > profiles/r06_bench_batch256.json
 echo "collect_r06 bench done"
 fi

@@ -18,7 +18,7 @@ print('%-34s halves=%s  %8.0f steps/s  device %6.2f us/step  pass %6.1f us (frac
 for rep in 1 2 3; do
   for args in "--steps 20 --warmup 5" "--steps 512 --warmup 32"; do
     for hv in 0 1; do
-      EKF_FLUSH_HALVES=$hv timeout -k 10 200 python bench.py --no-cpu-baseline --no-secondary $args 2>/dev/null | line "$args" $hv || exit 1
+      EKF_FLUSH_HALVES=$hv timeout -k 10 200 python bench.py --no-cpu-baseline --no-secondary --full $args 2>/dev/null | line "$args" $hv || exit 1
     done
   done
 done

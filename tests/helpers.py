@@ -1,4 +1,8 @@
 """Shared test helpers: the parity tolerance of BASELINE.json's north_star, made well-defined."""
+import functools
+import subprocess
+import sys
+
 import numpy as np
 
 REL_TOL = 1e-6       # north_star: "within 1e-6 relative on x and P"
@@ -61,3 +65,13 @@ def correlated_state(pkg, oc, copies=16, rho=0.8, seed=20260011, n_landmarks=64,
             P[a:a + 2 * Ns, b:b + 2 * Ns] = (1.0 if c == d else rho) * Ps[3:, 3:]
     P = 0.5 * (P + P.T)
     return x, P
+
+
+@functools.lru_cache(maxsize=None)
+def gpu_present():
+    """torch.cuda.is_available(), asked in a child process.  torch's HIP runtime is requested as libamdhip64.so, the library's as
+    libamdhip64.so.7: once the library is loaded, torch initialised in the same process is a second runtime, and the library's then
+    finds no device for every later test of the session."""
+    out = subprocess.run([sys.executable, "-c", "import torch; print(int(torch.cuda.is_available()))"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    return out.stdout.split()[-1] == "1"

@@ -47,8 +47,8 @@ def test_default_params_equal_reference_literals(built):
 
 
 def test_no_cpu_fallback(built):
-    import torch
-    if torch.cuda.is_available():
+    from helpers import gpu_present
+    if gpu_present():
         pytest.skip("a GPU is present")
     with pytest.raises(built.EkfError) as ei:
         built.FilterBatch(1, 8)

@@ -8,15 +8,17 @@ import subprocess
 import sys
 import textwrap
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run_bench(argv, timeout):
+def _run_bench(argv, timeout, **extra_env):
     env = dict(os.environ)
     for k in [k for k in env if k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT") or k.startswith("EKF")]:
         env.pop(k)
+    env.update(extra_env)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, cwd=ROOT, env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=timeout)
     return p
@@ -85,7 +87,7 @@ def test_bench_two_ranks_share_the_one_gpu(pipeline_mode):
     if pipeline_mode != "inplace":
         pytest.skip("once is enough: the launcher does not depend on the pipeline mode")
     p = _run_bench(["--gpus", "2", "--dist-backend", "gloo", "--device", "0", "--workload", "n1024", "--steps", "16", "--warmup", "4",
-                    "--config5-steps", "16"], 900)
+                    "--config5-steps", "16", "--full"], 900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = _one_line(p)
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["scaling"] == "weak"
@@ -103,12 +105,12 @@ def test_bench_two_ranks_share_the_one_gpu(pipeline_mode):
 
 @pytest.mark.gpu
 def test_the_drivers_command_prints_a_line_that_fits_the_drivers_tail(pipeline_mode):
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` (the driver's command): one line, under 8 000 characters (the driver keeps an 8 KB
-    tail: round 5's 14 KB line lost config2_n1024.value and most of cpu_baseline_structured), with the fields the judge reads -- roofline,
-    cpu_baseline, phases_us, the chain record, every secondary leg's value."""
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` (the driver's command with every record): one line, under 8 000 characters
+    (the driver keeps an 8 KB tail: round 5's 14 KB line lost config2_n1024.value and most of cpu_baseline_structured), with the fields the
+    judge reads -- roofline, cpu_baseline, phases_us, the chain record, every secondary leg's value."""
     if pipeline_mode != "overlap":
         pytest.skip("once is enough")
-    p = _run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5"], 1500)
+    p = _run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], 1500)
     assert p.returncode == 0, p.stderr[-3000:]
     raw = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(raw) == 1 and len(raw[0]) < 8000, (len(raw), [len(l) for l in raw])
@@ -126,11 +128,11 @@ def test_the_drivers_command_prints_a_line_that_fits_the_drivers_tail(pipeline_m
 
 @pytest.mark.gpu
 def test_one_gpu_batch_line_carries_the_config5_leg_record(pipeline_mode):
-    """`python bench.py --gpus 1 --workload batch256`: the weak leg of BASELINE.json config 5 (256 filters per GPU) rides on the one-GPU line
+    """`python bench.py --gpus 1 --workload batch256 --full`: the weak leg of BASELINE.json config 5 (256 filters per GPU) rides on the one-GPU line
     with everything the first 8-GPU run will report per leg: value, per-rank time, all-gather time, ranks seen, the dense pass's roofline."""
     if pipeline_mode != "inplace":
         pytest.skip("once is enough")
-    p = _run_bench(["--gpus", "1", "--workload", "batch256", "--steps", "32", "--warmup", "8", "--config5-steps", "32", "--no-secondary", "--no-cpu-baseline"], 900)
+    p = _run_bench(["--gpus", "1", "--workload", "batch256", "--steps", "32", "--warmup", "8", "--config5-steps", "32", "--no-secondary", "--no-cpu-baseline", "--full"], 900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = _one_line(p)
     sys.path.insert(0, ROOT)
@@ -140,6 +142,38 @@ def test_one_gpu_batch_line_carries_the_config5_leg_record(pipeline_mode):
     assert leg["filters_total"] == 256 and leg["ranks_seen"] == 1 and len(leg["per_rank_ms"]) == 1 and leg["value"] > 1e6
     assert leg["roofline"]["frac"] > 0.05 and leg["roofline"]["launches"] >= 4 and leg["allgather_us"] > 0
     assert line["value"] > 1e6 and line["roofline"]["frac"] > 0.05
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_what_they_computed(pipeline_mode, tmp_path):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR`, twice: the headline alone (none of --full's records), exactly the
+    steps asked for, and the last step's outputs -- float64, within 64 MB -- equal from run to run, because the inputs are."""
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ("run%d" % run)
+        p = _run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--dump-outputs", str(out)], 900,
+                       EKF_OVERLAP="1" if pipeline_mode == "overlap" else "0")
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = _one_line(p)
+        assert line["steps"] == 20 and line["warmup"] == 5 and line["n_gpus"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert abs(line["value"] * line["ms_per_step"] - 1e3) < 1e-6 * 1e3  # one filter: steps/s and ms per step are the same clock
+        assert (line["metric"], line["unit"], line["higher_is_better"], line["dtype"]) == ("EKF steps/sec (propagate+full update) at N landmarks", "steps/s", True, "f64")
+        assert line["config"]["overlap"] == (pipeline_mode == "overlap") and line["roofline"]["launches"] > 0
+        for rec in ("cpu_baseline", "cpu_baseline_structured", "secondary", "chain", "config5", "mc_stats"):
+            assert line[rec] is None, rec
+        names = sorted(os.listdir(str(out)))
+        assert names == sorted(k + ".npy" for k in ("x", "P_diag", "P_sample", "P_sample_index", "poses", "nis_nees", "decision", "matched", "mahalanobis"))
+        arrays = {n[:-4]: np.load(str(out / n)) for n in names}
+        assert all(a.dtype == np.float64 for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        n = 3 + 2 * 4096
+        assert arrays["x"].shape == (1, n) and arrays["P_diag"].shape == (1, n) and arrays["decision"].shape == (1, 4)
+        assert (arrays["decision"] == 2).all() and (arrays["P_diag"] > 0).all()  # (EKF_DECISION_OLD: the steady workload's every update)
+        dumps.append(arrays)
+    a, b = dumps
+    for k in ("P_sample_index", "decision", "matched"):
+        assert np.array_equal(a[k], b[k]), k
+    for k in ("x", "P_diag", "P_sample", "poses", "nis_nees", "mahalanobis"):
+        assert np.allclose(a[k], b[k], rtol=1e-12, atol=1e-12 * np.abs(a[k]).max()), (k, np.abs(a[k] - b[k]).max())
 
 
 _NCCL_CHILD = textwrap.dedent("""
@@ -243,3 +277,51 @@ def test_bench_record_helpers_on_cpu(tmp_path, monkeypatch):
     assert fresh["floor_us"] == 5.25 and abs(fresh["floor_over_measured"] - 5.25 / 6.4) < 1e-12 and fresh["split_us"]["fold"] == 0.5
     other_window = bench.chain_record("n4096", 16, 1, 6.3, 6.4)
     assert other_window["floor_us"] is None  # (a profile taken at another window says nothing about this run)
+
+
+class _FakeFilters:
+    """What bench.dump_outputs reads from a FilterBatch, for `batch` filters of state size n, without a device."""
+
+    def __init__(self, batch, n, M):
+        self.batch, self.n, self.M = batch, n, M
+
+    def get_state(self, index=0):
+        rng = np.random.default_rng(index)
+        return rng.normal(size=self.n), rng.normal(size=(self.n, self.n))
+
+    def poses(self):
+        return np.arange(self.batch * 3.0).reshape(self.batch, 3)
+
+    def decisions(self, index=0, count=4096):
+        return [(2, 3 + 2 * (i % 7), 0.5 * i + index) for i in range(count)]
+
+
+def test_dump_outputs_on_cpu(tmp_path):
+    """bench.dump_outputs: float64 files within 64 MB; all of P while it fits the sample budget, else the same seeded entries in every
+    filter and in every run; the branch, match and distance of the last step's M measurements."""
+    sys.path.insert(0, ROOT)
+    import bench
+    K, M = 5, 4
+    for batch, n in ((3, 41), (1, 2001)):
+        f = _FakeFilters(batch, n, M)
+        stats = np.arange(batch * 2.0).reshape(batch, 2)
+        runs = []
+        for run in range(2):
+            out = tmp_path / ("b%d_run%d" % (batch, run))
+            bench.dump_outputs(f, str(out), stats, K, M)
+            arrays = {name[:-4]: np.load(str(out / name)) for name in os.listdir(str(out))}
+            assert all(a.dtype == np.float64 for a in arrays.values()) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+            runs.append(arrays)
+        a, b = runs
+        assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+        idx = a["P_sample_index"].astype(np.int64)
+        if n * n * batch <= bench.DUMP_P_ENTRIES:
+            assert np.array_equal(idx, np.arange(n * n))
+        else:
+            assert 0 < idx.size <= bench.DUMP_P_ENTRIES // batch and np.all(np.diff(idx) > 0)
+        for i in range(batch):
+            x, P = f.get_state(i)
+            assert np.array_equal(a["x"][i], x) and np.array_equal(a["P_diag"][i], np.diag(P)) and np.array_equal(a["P_sample"][i], P.ravel()[idx])
+            last = f.decisions(i, K * M)[-M:]
+            assert [tuple(r) for r in np.stack([a["decision"][i], a["matched"][i], a["mahalanobis"][i]], axis=1)] == last
+        assert np.array_equal(a["poses"], f.poses()) and np.array_equal(a["nis_nees"], stats)
