@@ -2078,6 +2078,108 @@ extern "C" int ekf_broadcast_state(ekf_handle h) {
     return refresh_bounds(h);
 }
 
+// ---- map management -------------------------------------------------------------------------------
+// Marginalise landmarks out on the device: gather by destination over the tile layout (k_rm_gather), in overlap mode into the other Bm
+// buffer (then flipped, as settle() does behind a pass; the buffer read is cleared), in place through a transient scratch copied back
+// (k_rm_finish); x, R, D compacted by k_rm_vec.  Every buffer ends as ekf_set_state of the reduced state would leave it; the buffer
+// addresses do not change (captured graphs and streaming launches hold EkfDev by value).
+static int remove_impl(ekf_batch *h, const unsigned char *keep, int ld_keep, int index, int *n_out) {
+    HIP_TRY(hipSetDevice(h->device));
+    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
+    int rc = refresh_bounds(h);  // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT ends it here
+    if (rc) return rc;
+    rc = sticky_status(h, true);  // ... and a sticky EKF_ERR_CAPACITY: the state stays as it is
+    if (rc) return rc;
+    rc = settle(h);  // every deferred slot folded, both streams idle
+    if (rc) return rc;
+    EkfDev &dv = h->dv;
+    const int B = dv.B, mstride = dv.Ncap > 0 ? dv.Ncap : 1;
+    std::vector<int> rm((size_t)B * (2 + mstride), 0);
+    int nTo = 0, nTn = 0;
+    bool any = false;
+    for (int b = 0; b < B; b++) {
+        const int n_old = h->h_int[b];
+        const unsigned char *k = index < 0 ? keep + (size_t)b * ld_keep : (b == index ? keep : nullptr);
+        int *map = rm.data() + 2 * B + (size_t)b * mstride;
+        int n_new = 0;
+        for (int l = 0; l < n_old; l++)
+            if (!k || l >= ld_keep || k[l]) map[n_new++] = l;  // (landmarks without an entry are kept)
+        rm[2 * b] = n_old, rm[2 * b + 1] = n_new;
+        any = any || n_new != n_old;
+        const int to = (2 * n_old + 63) / 64, tn = (2 * n_new + 63) / 64;
+        nTo = to > nTo ? to : nTo;
+        nTn = tn > nTn ? tn : nTn;
+        if (n_out) n_out[b] = n_new;
+    }
+    if (!any) return index < 0 ? EKF_OK : rm[2 * index + 1];
+    hipStream_t s = h->s_chain;
+    int *rm_d = nullptr;
+    double *scratch = nullptr;
+    const size_t scratch_stride = (size_t)nTn * (nTn + 1) / 2 * 4096;
+    hipError_t e = hipMalloc((void **)&rm_d, rm.size() * sizeof(int));
+    if (e == hipSuccess && !h->overlap && scratch_stride) e = hipMalloc((void **)&scratch, (size_t)B * scratch_stride * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpyAsync(rm_d, rm.data(), rm.size() * sizeof(int), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && nTo > 0) {
+        const dim3 grid((unsigned)(nTo * (nTo + 1) / 2), (unsigned)B);
+        if (h->overlap) {
+            hipLaunchKernelGGL(k_rm_gather, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d, mstride, nTo, dv.Bm[h->buf_in ^ 1], dv.T, dv.bm_stride, 0);
+            hipLaunchKernelGGL(k_rm_finish, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d, nTo, (const double *)nullptr, 0, (size_t)0);
+        } else {
+            if (scratch)
+                hipLaunchKernelGGL(k_rm_gather, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d, mstride, nTo, scratch, nTn, scratch_stride, 1);
+            hipLaunchKernelGGL(k_rm_finish, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d, nTo, (const double *)scratch, nTn, scratch_stride);
+        }
+    }
+    if (e == hipSuccess) {
+        // D is read by the gather (landmarks' own blocks): compacted behind it
+        hipLaunchKernelGGL(k_rm_vec, dim3(7, B), dim3(1024), 0, s, dv, (const int *)rm_d, mstride);
+        e = hipMemsetAsync(dv.FA, 0, sizeof(double) * (size_t)B * 2 * dv.f_stride, s);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(dv.FB, 0, sizeof(double) * (size_t)B * 2 * dv.f_stride, s);
+    if (e == hipSuccess) {
+        if (h->overlap) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, s, dv.pass_flag, h->pass_seq);
+        for (int b = 0; b < B; b++) hipLaunchKernelGGL(k_set_meta, dim3(1), dim3(64), 0, s, dv, b, rm[2 * b + 1]);  // counts, slots, host mirror
+        e = stream_wait(s);
+    }
+    if (rm_d) hipFree(rm_d);
+    if (scratch) hipFree(scratch);
+    if (e != hipSuccess) return set_error(EKF_ERR_HIP, hipGetErrorString(e));
+    rc = check_launch();
+    if (rc) return rc;
+    if (h->overlap && nTo > 0) h->buf_in ^= 1;  // the gather's output
+    h->mirror_by_chain = false;
+    rc = refresh_bounds(h);
+    if (rc) return rc;
+    return index < 0 ? EKF_OK : rm[2 * index + 1];
+}
+
+extern "C" int ekf_remove_landmarks(ekf_handle h, int index, const unsigned char *keep, int count) {
+    if (!h || index < 0 || index >= h->dv.B || !keep || count < 0) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return remove_impl(h, keep, count, index, nullptr);
+}
+
+extern "C" int ekf_batch_remove_landmarks(ekf_handle h, const unsigned char *keep, int ld_keep, int *n_out) {
+    if (!h || !keep || ld_keep < 0) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return remove_impl(h, keep, ld_keep, -1, n_out);
+}
+
+extern "C" int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max) {
+    if (!h || index < 0 || index >= h->dv.B || n_max < 0 || (!cov_out && n_max > 0)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    int rc = refresh_bounds(h);  // the chain stream idle (a resident streaming launch leaves first); no pass, the flush stream untouched
+    if (rc) return rc;
+    const int N = h->h_int[index];
+    const int cnt = N < n_max ? N : n_max;
+    if (cnt == 0) return N;
+    std::vector<double> comp((size_t)3 * cnt);  // the three components of the always-current diagonal blocks
+    HIP_TRY(hipMemcpy2DAsync(comp.data(), (size_t)cnt * sizeof(double), h->dv.D + (size_t)index * 3 * h->dv.dn, (size_t)h->dv.dn * sizeof(double),
+                             (size_t)cnt * sizeof(double), 3, hipMemcpyDeviceToHost, h->s_chain));
+    HIP_TRY(stream_wait(h->s_chain));
+    for (int l = 0; l < cnt; l++)
+        for (int c = 0; c < 3; c++) cov_out[3 * l + c] = comp[(size_t)c * cnt + l];
+    return N;
+}
+
 // ---- scripts --------------------------------------------------------------------------------------
 static inline int ops_per_step(const ekf_batch *h) { return 1 + h->script_M + (h->script_has_truth ? 1 : 0); }
 

@@ -195,6 +195,40 @@ __host__ __device__ inline size_t bm_offset(int T, int ip, int jp) {
     return t * 4096 + (size_t)chain * 256 + (size_t)(r >> 1) * 128 + (size_t)(g * 16 + c) * 2 + (r & 1);
 }
 
+// The inverse of bm_offset inside one tile: tile-local offset o (0..4095) -> tile-local row il, column jl.
+__host__ __device__ inline void bm_tile_coords(int o, int *il, int *jl) {
+    const int chain = o >> 8, h = (o >> 7) & 1, lane = (o >> 1) & 63, e = o & 1;
+    *il = (chain >> 2) * 16 + (lane >> 4) + 4 * (2 * h + e);
+    *jl = (chain & 3) * 16 + (lane & 15);
+}
+
+// Landmark removal (ekf_remove_landmarks) gathers by destination.  map[l'] = old number of kept landmark l' (increasing), n_new kept
+// landmarks: landmark-space row i' of the reduced map is old row remove_row(...), or -1 beyond the reduced map.
+__host__ __device__ inline int remove_row(const int *map, int n_new, int ip) {
+    return ip < 2 * n_new ? 2 * map[ip >> 1] + (ip & 1) : -1;
+}
+
+// Where element (i', j') of the reduced P_LL comes from, given its old rows si = remove_row(i'), sj = remove_row(j'): exactly what
+// k_import of the dense export with the rows and columns deleted would store there.  A landmark's own 2x2 block comes from D
+// (offset comp * dn + landmark), every other element from the upper-triangle home (min, max) in Bm (map is increasing, so an element of an
+// upper-triangle tile reads an upper-triangle tile at or after it in both tile coordinates); beyond the reduced map: zero.
+enum { RM_ZERO = 0, RM_BM = 1, RM_D = 2 };
+struct RmSource {
+    int where;
+    size_t off;
+};
+__host__ __device__ inline RmSource remove_source(int T, int dn, int si, int sj) {
+    RmSource s;
+    if (si < 0 || sj < 0) {
+        s.where = RM_ZERO, s.off = 0;
+    } else if ((si >> 1) == (sj >> 1)) {
+        s.where = RM_D, s.off = (size_t)((si & 1) + (sj & 1)) * dn + (si >> 1);
+    } else {
+        s.where = RM_BM, s.off = si < sj ? bm_offset(T, si, sj) : bm_offset(T, sj, si);
+    }
+    return s;
+}
+
 // Offset (doubles) of row i' of slot PAIR p inside one (filter, set) of FA / FB: 4 doubles, slot 2p in
 // [0..1], slot 2p+1 in [2..3].
 __host__ __device__ inline size_t pair_offset(int rows, int ip, int p) {

@@ -2257,6 +2257,103 @@ __global__ void k_set_meta(EkfDev dv, int b, int n_lm) {
     for (int m = 0; m < 2 * dv.maxp; m++) dv.slot_active[(size_t)b * 2 * dv.maxp + m] = 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Landmark removal (ekf_remove_landmarks): the kept rows and columns of x and P, no arithmetic.  `rm` = [B][2] (old, new landmark
+// count; new == old: the filter keeps everything) then [B][mstride] maps (ekf_device.h: remove_row).  Every buffer ends as k_import
+// of the reduced dense state would leave it.  Run with every slot folded in and both streams idle.
+// ---------------------------------------------------------------------------------------------
+// (I, J) of upper-triangle tile t of a triangle with side nT (t = I*nT - I(I-1)/2 + J - I)
+__device__ inline void rm_tile_ij(int t, int nT, int *I, int *J) {
+    int i = 0;
+    while (t >= nT - i) t -= nT - i, i++;
+    *I = i, *J = i + t;
+}
+
+// One workgroup per destination tile (blockIdx.x over the triangle of side nT_grid) and filter (blockIdx.y): every element reads its
+// source through L2 and the tile goes out as wave-contiguous 16-byte stores.  dst: the other Bm buffer (layout dv.T, stride
+// dv.bm_stride; tiles up to the old map) or, in place, a scratch of side Tdst (tiles up to the reduced map).
+__global__ __launch_bounds__(256) void k_rm_gather(EkfDev dv, int buf_src, const int *rm, int mstride, int nT_grid, double *dst, int Tdst,
+                                                   size_t dst_stride, int to_scratch) {
+    __shared__ int srow[64], scol[64];
+    const int b = blockIdx.y;
+    const int n_old = rm[2 * b], n_new = rm[2 * b + 1];
+    const int limit = to_scratch ? (2 * n_new + 63) >> 6 : (2 * n_old + 63) >> 6;
+    if (to_scratch && n_new == n_old) return;  // in place, nothing to move for this filter
+    int I, J;
+    rm_tile_ij(blockIdx.x, nT_grid, &I, &J);
+    if (J >= limit) return;
+    const int *map = rm + 2 * dv.B + (size_t)b * mstride;
+    const int tid = threadIdx.x;
+    if (tid < 64) srow[tid] = remove_row(map, n_new, 64 * I + tid);
+    else if (tid < 128) scol[tid - 64] = remove_row(map, n_new, 64 * J + tid - 64);
+    __syncthreads();
+    const double *src = dv.Bm[buf_src] + (size_t)b * dv.bm_stride;
+    const double *Dx = dv.D + (size_t)b * 3 * dv.dn;
+    double *out = dst + (size_t)b * dst_stride + ((size_t)I * Tdst - ((size_t)I * (I - 1)) / 2 + (size_t)(J - I)) * 4096;
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        const int o = (q * 256 + tid) * 2;
+        double v[2];
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            int il, jl;
+            bm_tile_coords(o + e, &il, &jl);
+            const RmSource s = remove_source(dv.T, dv.dn, srow[il], scol[jl]);
+            v[e] = s.where == RM_BM ? src[s.off] : s.where == RM_D ? Dx[s.off] : 0.0;
+        }
+        *(double2_t *)(out + o) = (double2_t){v[0], v[1]};
+    }
+}
+
+// Second half of a removal, tiles up to each filter's old map: in place, the scratch copied back into Bm[buf] (zeros from the reduced
+// map's last tile on); in overlap mode (scratch == nullptr) the buffer the gather read from is cleared, as ekf_set_state leaves it.
+__global__ __launch_bounds__(256) void k_rm_finish(EkfDev dv, int buf, const int *rm, int nT_grid, const double *scratch, int Tdst, size_t scratch_stride) {
+    const int b = blockIdx.y;
+    const int n_old = rm[2 * b], n_new = rm[2 * b + 1];
+    if (scratch && n_new == n_old) return;
+    int I, J;
+    rm_tile_ij(blockIdx.x, nT_grid, &I, &J);
+    if (J >= (2 * n_old + 63) >> 6) return;
+    const bool copy = scratch && J < (2 * n_new + 63) >> 6;
+    const double *in = copy ? scratch + (size_t)b * scratch_stride + ((size_t)I * Tdst - ((size_t)I * (I - 1)) / 2 + (size_t)(J - I)) * 4096 : nullptr;
+    double *out = dv.Bm[buf] + (size_t)b * dv.bm_stride + ((size_t)I * dv.T - ((size_t)I * (I - 1)) / 2 + (size_t)(J - I)) * 4096;
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        const int o = (q * 256 + threadIdx.x) * 2;
+        double2_t v = (double2_t){0.0, 0.0};
+        if (copy) v = *(const double2_t *)(in + o);
+        *(double2_t *)(out + o) = v;
+    }
+}
+
+// x, the three R rows and the three D components of filter blockIdx.y (row blockIdx.x: 0 = x, 1..3 = R, 4..6 = D), compacted in place:
+// chunks in increasing order, each read whole before it is stored (a destination never lies after its source), zeros behind the
+// reduced map.  The robot entries (first three of x and R) stay where they are.
+__global__ __launch_bounds__(1024) void k_rm_vec(EkfDev dv, const int *rm, int mstride) {
+    const int b = blockIdx.y, row = blockIdx.x;
+    const int n_old = rm[2 * b], n_new = rm[2 * b + 1];
+    if (n_new == n_old) return;
+    const int *map = rm + 2 * dv.B + (size_t)b * mstride;
+    const bool isD = row >= 4;
+    double *v = isD ? dv.D + ((size_t)b * 3 + (row - 4)) * dv.dn
+                    : row == 0 ? dv.x + (size_t)b * dv.xs : dv.R + ((size_t)b * 3 + (row - 1)) * dv.xs;
+    const int len = isD ? n_old : 3 + 2 * n_old;
+    for (int c0 = 0; c0 < len; c0 += 1024) {
+        const int k = c0 + threadIdx.x;
+        double val = 0.0;
+        if (k < len) {
+            if (isD) val = k < n_new ? v[map[k]] : 0.0;
+            else if (k < 3) val = v[k];
+            else {
+                const int s = remove_row(map, n_new, k - 3);
+                val = s >= 0 ? v[3 + s] : 0.0;
+            }
+        }
+        __syncthreads();
+        if (k < len) v[k] = val;
+    }
+}
+
 // Probe pair for ekf_api's concurrency check: the waiter spins (bounded, about 2 ms) until the setter, launched on ANOTHER
 // stream after it, has run; out[0] = 1 when it saw the flag.  Under tools that serialise kernel execution it times out.
 __global__ void k_probe_wait(int *flag, int *out) {

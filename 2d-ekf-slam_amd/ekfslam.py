@@ -23,6 +23,7 @@ ABI_SYMBOLS = [
     "ekf_broadcast_state", "ekf_script_load", "ekf_script_run", "ekf_sync", "ekf_flush", "ekf_close_window", "ekf_timer_start",
     "ekf_timer_stop", "ekf_flush_profile", "ekf_flush_profile_read", "ekf_fused_pass", "ekf_get_decisions", "ekf_get_stats",
     "ekf_reset_stats", "ekf_stats_means_device", "ekf_record_truth", "ekf_stream", "ekf_device_bytes", "ekf_debug_windows", "ekf_debug_stream", "ekf_debug_stream_ring",
+    "ekf_remove_landmarks", "ekf_batch_remove_landmarks", "ekf_get_landmark_covs",
 ]
 
 
@@ -95,6 +96,9 @@ def load():
     L.ekf_get_state.argtypes = [_H, ctypes.c_int, _dp, _dp, ctypes.c_int]
     L.ekf_set_state.argtypes = [_H, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_int]
     L.ekf_broadcast_state.argtypes = [_H]
+    L.ekf_remove_landmarks.argtypes = [_H, ctypes.c_int, _up, ctypes.c_int]
+    L.ekf_batch_remove_landmarks.argtypes = [_H, _up, ctypes.c_int, _ip]
+    L.ekf_get_landmark_covs.argtypes = [_H, ctypes.c_int, _dp, ctypes.c_int]
     L.ekf_script_load.argtypes = [_H, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _up, _dp]
     L.ekf_script_run.argtypes = [_H, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.ekf_sync.argtypes = [_H]
@@ -246,6 +250,30 @@ class FilterBatch:
     def broadcast_state(self):
         _chk(self.L.ekf_broadcast_state(self.h))
 
+    # -- map management ------------------------------------------------------------------------
+    def remove_landmarks(self, keep, index=None):
+        """Marginalise landmarks out on the device (ekf_remove_landmarks): keep[l] true keeps landmark l (state rows 3+2l, 4+2l).
+        index=None: keep is [batch][N], one pass over every filter (ekf_batch_remove_landmarks); returns the new counts (batch,).
+        With an index: keep is [N] for that filter; returns its new count."""
+        if index is None:
+            k = np.ascontiguousarray(keep, dtype=bool).astype(np.uint8)
+            if k.ndim == 1 and self.batch == 1:
+                k = k.reshape(1, -1)
+            if k.ndim != 2 or k.shape[0] != self.batch:
+                raise ValueError("keep must be [batch][N]")
+            n_out = np.empty(self.batch, dtype=np.int32)
+            _chk(self.L.ekf_batch_remove_landmarks(self.h, k.ctypes.data_as(_up), k.shape[1], n_out.ctypes.data_as(_ip)))
+            return n_out
+        k = np.ascontiguousarray(keep, dtype=bool).astype(np.uint8).reshape(-1)
+        return _chk(self.L.ekf_remove_landmarks(self.h, int(index), k.ctypes.data_as(_up), k.size))
+
+    def landmark_covs(self, index=0):
+        """The 2x2 covariance of every landmark of filter `index` as (N, 3) rows (xx, xy, yy) (ekf_get_landmark_covs: the always-
+        current diagonal blocks; no dense pass, the open window stays open)."""
+        out = np.empty((max(int(self.capacity), 1), 3))
+        n = _chk(self.L.ekf_get_landmark_covs(self.h, int(index), _p(out), int(self.capacity)))
+        return out[:n].copy()
+
     def script_load(self, ctrl, z, R, valid=None, truth=None):
         """ctrl (steps, batch, 3); z (steps, M, batch, 2); R (steps, M, batch, 4) column-major blocks;
         valid (steps, M, batch); truth (steps, batch, 3)."""
@@ -392,4 +420,10 @@ class KalmanFilter:
 
     def set_state(self, x, P):
         self._f.set_state(x, P, 0)
+        self._mirror()
+
+    def remove_landmarks(self, keep):
+        """Marginalise the landmarks whose keep[l] is false out of the map (kept ones are renumbered in order); refreshes
+        Num_Landmarks.  A decision's matched index m names landmark (m - 3) // 2."""
+        self._f.remove_landmarks(keep, 0)
         self._mirror()

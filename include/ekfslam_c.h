@@ -90,7 +90,8 @@ void ekf_default_params(ekf_params *p);
 
 /* KalmanFilter::KalmanFilter, kalmanfilter.cpp:4-12: x = 0_3, P = 0_3x3, no landmarks.
  * capacity_landmarks bounds N; all device memory is allocated here, none later (except a transient
- * staging buffer inside ekf_get_state / ekf_set_state).
+ * staging buffer inside ekf_get_state / ekf_set_state, and inside ekf_remove_landmarks / ekf_batch_remove_landmarks the
+ * landmark maps and, in the in-place pipeline (ekf_overlap() == 0), a scratch copy of the reduced maps' tiles).
  * The sequential part of a filter runs on a few workgroups that exchange their arg-min candidates while they
  * run, so all of them must be resident on the GPU at once: creation fails with EKF_ERR_STATE when this
  * handle's workgroups do not fit beside those of the handles already live on the device (in this process).
@@ -162,6 +163,27 @@ int ekf_get_state(ekf_handle h, int index, double *x_out, double *P_out, int ld)
 int ekf_set_state(ekf_handle h, int index, const double *x, const double *P, int ld, int n);
 /* Copy filter 0's state into every other filter of the batch (device-side). */
 int ekf_broadcast_state(ekf_handle h);
+
+/* ---- map management: marginalising landmarks out, per-landmark covariances ------------------------ */
+
+/* Marginalise landmarks out of filter `index`: keep[l] != 0 keeps landmark l (0-based; state rows 3+2l, 4+2l; an
+ * ekf_decision.matched m names landmark (m-3)/2).  Entries l >= that filter's landmark count are ignored; count is the
+ * length of keep (landmarks l >= count have no entry and are kept).  Kept landmarks stay in order and are renumbered
+ * 0..N'-1; x and P become exactly the kept rows/columns (no arithmetic, bitwise).  Deferred slots are folded first.
+ * Synchronises.  Returns N' or a negative status.
+ * Pose, P_RR, the counters (ekf_get_stats) and the host mirror's pose are unchanged; ekf_num_landmarks reports N'.  Decision-log
+ * entries are NOT rewritten: they keep the indices they were written with.  A sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY is returned
+ * unchanged and the state is left as it was; bad arguments return EKF_ERR_BAD_ARG and leave the handle untouched.  Every device
+ * buffer of the filter ends as ekf_set_state of the reduced state would leave it: later New landmarks reuse the freed rows, the
+ * capacity stays, a loaded script stays loaded, ekf_reserve works before and after, immediate-mode calls stream again afterwards. */
+int ekf_remove_landmarks(ekf_handle h, int index, const unsigned char *keep, int count);
+/* The same for every filter of a batch in one pass: keep [batch][ld_keep]; n_out[batch] (may be NULL) receives N'.  Returns
+ * EKF_OK or a negative status. */
+int ekf_batch_remove_landmarks(ekf_handle h, const unsigned char *keep, int ld_keep, int *n_out);
+/* The 2x2 covariance of every landmark of filter `index`: cov_out[l][3] = (xx, xy, yy) for l < min(N, n_max), taken from
+ * the always-current diagonal blocks.  It does NOT fold the open window and does not launch a dense pass.  Synchronises.
+ * Returns N. */
+int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max);
 
 /* ---- device-resident step scripts (benchmarks, Monte-Carlo runs) ------------------------------
  * A script is `steps` steps; step s of filter b is
