@@ -2163,6 +2163,98 @@ extern "C" int ekf_batch_remove_landmarks(ekf_handle h, const unsigned char *kee
     return remove_impl(h, keep, ld_keep, -1, n_out);
 }
 
+// Frame changes on the device (ekf_kernels.hip: k_reframe_vec, k_reframe_tiles, k_reframe_finish), the order of steps as in
+// remove_impl.  frames == nullptr: anchor at the robot; else one (t_x, t_y, theta) per filter of the launch.  index < 0: every
+// filter, one launch sequence with the grid over the filters.  Bm is rewritten in place in the settled buffer (either pipeline
+// mode: no second buffer, no scratch); the only transient allocation is the BATCH rigid call's frame table (48 bytes per filter; a
+// one-filter call carries its frame in the kernel arguments); the anchor's per-row operands use slot set 0 of FA / FB, which are
+// cleared afterwards as a removal clears them.
+static int reframe_impl(ekf_batch *h, int index, const double *frames) {
+    HIP_TRY(hipSetDevice(h->device));
+    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
+    int rc = refresh_bounds(h);  // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT ends it here
+    if (rc) return rc;
+    rc = sticky_status(h, true);  // ... and a sticky EKF_ERR_CAPACITY: the state stays as it is
+    if (rc) return rc;
+    rc = settle(h);  // every deferred slot folded, both streams idle
+    if (rc) return rc;
+    EkfDev &dv = h->dv;
+    const int b_off = index < 0 ? 0 : index, nb = index < 0 ? dv.B : 1;
+    int nT = 0;
+    for (int b = b_off; b < b_off + nb; b++) {
+        const int t = (2 * h->h_int[b] + 63) / 64;
+        nT = t > nT ? t : nT;
+    }
+    hipStream_t s = h->s_chain;
+    double *fr_d = nullptr;
+    hipError_t e = hipSuccess;
+    ReframeFrame one = {{0.0, 0.0, 1.0, 0.0, 0.0, 0.0}};
+    if (frames) {
+        std::vector<double> fr((size_t)nb * 6, 0.0);
+        for (int k = 0; k < nb; k++) {
+            const double *f = frames + 3 * (size_t)k;
+            fr[6 * k] = f[0], fr[6 * k + 1] = f[1], fr[6 * k + 2] = cos(f[2]), fr[6 * k + 3] = sin(f[2]), fr[6 * k + 4] = f[2];
+        }
+        if (nb == 1) {
+            for (int k = 0; k < 6; k++) one.v[k] = fr[k];
+        } else {
+            e = hipMalloc((void **)&fr_d, fr.size() * sizeof(double));
+            if (e == hipSuccess) e = hipMemcpy(fr_d, fr.data(), fr.size() * sizeof(double), hipMemcpyHostToDevice);  // (fr leaves scope: synchronous)
+        }
+    }
+    if (e == hipSuccess) {
+        const double *frc = fr_d;
+        if (nT > 0) {
+            const dim3 gv((unsigned)cdiv(32 * nT, 256), (unsigned)nb), gt((unsigned)(nT * (nT + 1) / 2), (unsigned)nb);
+            if (frames) {
+                hipLaunchKernelGGL(k_reframe_vec<false>, gv, dim3(256), 0, s, dv, one, frc, b_off);
+                hipLaunchKernelGGL(k_reframe_tiles<false>, gt, dim3(256), 0, s, dv, h->buf_in, one, frc, b_off, nT);
+            } else {
+                hipLaunchKernelGGL(k_reframe_vec<true>, gv, dim3(256), 0, s, dv, one, frc, b_off);
+                hipLaunchKernelGGL(k_reframe_tiles<true>, gt, dim3(256), 0, s, dv, h->buf_in, one, frc, b_off, nT);
+            }
+        }
+        if (frames) hipLaunchKernelGGL(k_reframe_finish<false>, dim3(nb), dim3(64), 0, s, dv, one, frc, b_off);
+        else hipLaunchKernelGGL(k_reframe_finish<true>, dim3(nb), dim3(64), 0, s, dv, one, frc, b_off);
+        e = hipMemsetAsync(dv.FA + (size_t)b_off * 2 * dv.f_stride, 0, sizeof(double) * (size_t)nb * 2 * dv.f_stride, s);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(dv.FB + (size_t)b_off * 2 * dv.f_stride, 0, sizeof(double) * (size_t)nb * 2 * dv.f_stride, s);
+    if (e == hipSuccess) {
+        if (h->overlap) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, s, dv.pass_flag, h->pass_seq);
+        e = stream_wait(s);
+    }
+    if (fr_d) hipFree(fr_d);
+    if (e != hipSuccess) return set_error(EKF_ERR_HIP, hipGetErrorString(e));
+    rc = check_launch();
+    if (rc) return rc;
+    h->mirror_by_chain = false;
+    return refresh_bounds(h);
+}
+
+static bool finite3(const double *f) { return __builtin_isfinite(f[0]) && __builtin_isfinite(f[1]) && __builtin_isfinite(f[2]); }
+
+extern "C" int ekf_transform_frame(ekf_handle h, int index, const double frame[3]) {
+    if (!h || index < 0 || index >= h->dv.B || !frame || !finite3(frame)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return reframe_impl(h, index, frame);
+}
+
+extern "C" int ekf_batch_transform_frame(ekf_handle h, const double *frames) {
+    if (!h || !frames) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    for (int b = 0; b < h->dv.B; b++)
+        if (!finite3(frames + 3 * (size_t)b)) return set_error(EKF_ERR_BAD_ARG, "a frame is not finite");
+    return reframe_impl(h, -1, frames);
+}
+
+extern "C" int ekf_anchor_at_robot(ekf_handle h, int index) {
+    if (!h || index < 0 || index >= h->dv.B) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return reframe_impl(h, index, nullptr);
+}
+
+extern "C" int ekf_batch_anchor_at_robot(ekf_handle h) {
+    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
+    return reframe_impl(h, -1, nullptr);
+}
+
 extern "C" int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max) {
     if (!h || index < 0 || index >= h->dv.B || n_max < 0 || (!cov_out && n_max > 0)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->device));

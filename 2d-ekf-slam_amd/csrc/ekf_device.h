@@ -229,6 +229,34 @@ __host__ __device__ inline RmSource remove_source(int T, int dn, int si, int sj)
     return s;
 }
 
+// Frame changes (ekf_transform_frame / ekf_anchor_at_robot) rewrite every off-diagonal 2x2 landmark block of P_LL in place.  A
+// tile is 512 WORK ITEMS of eight doubles: item q reads the two 32-byte pieces at tile-local offsets off and off + 32 (bm_offset:
+// +32 doubles = the next row, +2 = the next column, +1 = four rows down), which are exactly two complete 2x2 blocks -- rows
+// (row[k], row[k] + 1) x columns (col, col + 1) for k = 0, 1 -- so no value crosses a lane.  Value v (0..3) of piece s (0..1) is
+// element (row[v & 1] + s, col + (v >> 1)).  64 consecutive items (one wave) cover two whole chains; 16 consecutive items one 1 KiB
+// piece of a chain, as two interleaved 256-byte runs per load.
+struct ReframeItem {
+    int off;     // tile-local offset (doubles) of the first piece; the second is at off + 32
+    int row[2];  // tile-local first (even) row of block 0 and of block 1 (= row[0] + 4)
+    int col;     // tile-local first (even) column of both blocks
+    int chain;   // the item's chain: (row16-block << 2) | col16-block
+};
+__host__ __device__ inline ReframeItem reframe_item(int q) {
+    ReframeItem it;
+    const int chain = q >> 5, h = (q >> 4) & 1, gp = (q >> 3) & 1, c2 = q & 7;
+    it.chain = chain;
+    it.off = chain * 256 + h * 128 + gp * 64 + c2 * 4;
+    it.row[0] = (chain >> 2) * 16 + 8 * h + 2 * gp;
+    it.row[1] = it.row[0] + 4;
+    it.col = (chain & 3) * 16 + 2 * c2;
+    return it;
+}
+// Offset inside a chain (0..255) of element (rho, c) of its 16x16 block: bm_offset without the tile and chain terms.
+__host__ __device__ inline int bm_chain_offset(int rho, int c) {
+    const int r = rho >> 2, g = rho & 3;
+    return (r >> 1) * 128 + (g * 16 + c) * 2 + (r & 1);
+}
+
 // Offset (doubles) of row i' of slot PAIR p inside one (filter, set) of FA / FB: 4 doubles, slot 2p in
 // [0..1], slot 2p+1 in [2..3].
 __host__ __device__ inline size_t pair_offset(int rows, int ip, int p) {

@@ -2354,6 +2354,240 @@ __global__ __launch_bounds__(1024) void k_rm_vec(EkfDev dv, const int *rm, int m
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Frame changes (ekf_transform_frame / ekf_anchor_at_robot): x' = g(x), P' = J P J^T with J block diagonal over the landmarks
+// (Q = Rot(-theta) resp. Rot(-phi)) plus, for the anchor, three dense robot columns A_l = -Q [I | S (L_l - p)].  With
+// W_l = Q P_lR + A_l P_RR / 2 every landmark block is  P_lm' = Q P_lm Q^T + A_l W_m^T + W_l A_m^T  (rigid: A = W = 0), so a stored
+// tile depends on nothing but itself and six doubles per row and column.  Launch order on the chain stream, every slot folded in
+// and both streams idle:  k_reframe_vec (landmark entries of x, R, D; the anchor's operands; reads the robot entries, which it
+// leaves alone)  ->  k_reframe_tiles (Bm in place)  ->  k_reframe_finish (robot entries, bookkeeping, host mirror).
+// A rigid frame is six doubles: t_x, t_y, cos(theta), sin(theta), theta (cos / sin taken on the host).  A one-filter call carries it in
+// the kernel arguments (`one`); a batch call passes a table `fr` = [filters of the launch][6] instead.  The anchor takes cos / sin of
+// the filter's own heading on the device, the same expression in both kernels.  The launch covers filters b_off + blockIdx.y.
+// The anchor's operands live in slot set 0 of FA (A rows) and FB (W rows), four doubles per landmark-space row (f_stride >= 8 *
+// rows): the window is folded, nobody reads the slot arrays, and the host clears them behind the tile kernel.
+// ---------------------------------------------------------------------------------------------
+struct Rot2 {
+    double c, s;  // Q = [[c, s], [-s, c]]
+};
+struct ReframeFrame {
+    double v[6];
+};
+// value k of the frame of the launch's filter `by`: from the table when there is one
+__device__ inline double frame_value(const ReframeFrame &one, const double *fr, int by, int k) { return fr ? fr[6 * by + k] : one.v[k]; }
+// Q M Q^T of a general 2x2 block (m00 m01; m10 m11); c = 1, s = 0 returns M bit for bit
+__device__ inline void rot_block(const Rot2 q, double m00, double m01, double m10, double m11, double o[4]) {
+    const double a00 = q.c * m00 + q.s * m10, a01 = q.c * m01 + q.s * m11;
+    const double a10 = q.c * m10 - q.s * m00, a11 = q.c * m11 - q.s * m01;
+    o[0] = a00 * q.c + a01 * q.s, o[1] = a01 * q.c - a00 * q.s;
+    o[2] = a10 * q.c + a11 * q.s, o[3] = a11 * q.c - a10 * q.s;
+}
+// the rank-3 pair A_r W_c^T + W_r A_c^T of one element: rows of [A (3) . W (3) .] as the operands are stored
+__device__ inline double cross_term(const double *r, const double *c) {
+    return r[0] * c[4] + r[1] * c[5] + r[2] * c[6] + r[4] * c[0] + r[5] * c[1] + r[6] * c[2];
+}
+
+template <bool ANCHOR>
+__global__ __launch_bounds__(256) void k_reframe_vec(EkfDev dv, ReframeFrame one, const double *fr, int b_off) {
+    const int b = b_off + blockIdx.y;
+    const int n = dv.n_lm[b];
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if (l >= 32 * ((2 * n + 63) >> 6)) return;  // landmark slots of the map's last tile row included: their operands are zeros
+    double *x = dv.x + (size_t)b * dv.xs;
+    double *R0 = dv.R + (size_t)b * 3 * dv.xs;
+    double *Dx = dv.D + (size_t)b * 3 * dv.dn;
+    double *opA = dv.FA + (size_t)b * 2 * dv.f_stride + (size_t)l * 8;
+    double *opW = dv.FB + (size_t)b * 2 * dv.f_stride + (size_t)l * 8;
+    if (l >= n) {
+        if (ANCHOR)
+            for (int k = 0; k < 8; k++) opA[k] = 0.0, opW[k] = 0.0;
+        return;
+    }
+    // everything this landmark needs is read before anything is stored; the robot entries are not written in this kernel
+    const double px = x[0], py = x[1];
+    Rot2 q;
+    double tx, ty;
+    if (ANCHOR) q.c = cos(x[2]), q.s = sin(x[2]), tx = px, ty = py;
+    else tx = frame_value(one, fr, blockIdx.y, 0), ty = frame_value(one, fr, blockIdx.y, 1), q.c = frame_value(one, fr, blockIdx.y, 2), q.s = frame_value(one, fr, blockIdx.y, 3);
+    const double dx = x[3 + 2 * l] - tx, dy = x[4 + 2 * l] - ty;
+    const double lx = q.c * dx + q.s * dy, ly = q.c * dy - q.s * dx;
+    double r[3][2];  // P_Rl
+    for (int k = 0; k < 3; k++) r[k][0] = R0[(size_t)k * dv.xs + 3 + 2 * l], r[k][1] = R0[(size_t)k * dv.xs + 4 + 2 * l];
+    const double xx = Dx[l], xy = Dx[dv.dn + l], yy = Dx[2 * (size_t)dv.dn + l];
+    double d[4];
+    rot_block(q, xx, xy, xy, yy, d);  // (d[1] is the stored xy: one expression, so the block stays symmetric by construction)
+    if (!ANCHOR) {
+        double v[3][2];  // P_Rl Q^T, then J_R = diag(Q, 1) from the left
+        for (int k = 0; k < 3; k++) v[k][0] = r[k][0] * q.c + r[k][1] * q.s, v[k][1] = r[k][1] * q.c - r[k][0] * q.s;
+        for (int e = 0; e < 2; e++) {
+            R0[3 + 2 * l + e] = q.c * v[0][e] + q.s * v[1][e];
+            R0[(size_t)dv.xs + 3 + 2 * l + e] = q.c * v[1][e] - q.s * v[0][e];
+            R0[2 * (size_t)dv.xs + 3 + 2 * l + e] = v[2][e];
+        }
+        x[3 + 2 * l] = lx, x[4 + 2 * l] = ly;
+        Dx[l] = d[0], Dx[dv.dn + l] = d[1], Dx[2 * (size_t)dv.dn + l] = d[3];
+        return;
+    }
+    double prr[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) prr[i][j] = R0[(size_t)i * dv.xs + j];
+    // A_l = -Q [I | S (L - p)] with Q S (L - p) = S L' = (-L'_y, L'_x);  W_l = Q P_lR + A_l P_RR / 2
+    const double A[2][3] = {{-q.c, -q.s, ly}, {q.s, -q.c, -lx}};
+    double W[2][3];
+    for (int k = 0; k < 3; k++) {
+        W[0][k] = q.c * r[k][0] + q.s * r[k][1] + 0.5 * (A[0][0] * prr[0][k] + A[0][1] * prr[1][k] + A[0][2] * prr[2][k]);
+        W[1][k] = q.c * r[k][1] - q.s * r[k][0] + 0.5 * (A[1][0] * prr[0][k] + A[1][1] * prr[1][k] + A[1][2] * prr[2][k]);
+    }
+    double row[2][8];
+    for (int e = 0; e < 2; e++) {
+        for (int k = 0; k < 3; k++) row[e][k] = A[e][k], row[e][4 + k] = W[e][k];
+        row[e][3] = 0.0, row[e][7] = 0.0;
+    }
+    Dx[l] = d[0] + cross_term(row[0], row[0]);
+    Dx[dv.dn + l] = d[1] + cross_term(row[0], row[1]);
+    Dx[2 * (size_t)dv.dn + l] = d[3] + cross_term(row[1], row[1]);
+    x[3 + 2 * l] = lx, x[4 + 2 * l] = ly;
+    for (int k = 0; k < 3; k++) R0[(size_t)k * dv.xs + 3 + 2 * l] = 0.0, R0[(size_t)k * dv.xs + 4 + 2 * l] = 0.0;
+    for (int e = 0; e < 2; e++)
+        for (int k = 0; k < 4; k++) opA[4 * e + k] = row[e][k], opW[4 * e + k] = row[e][4 + k];
+}
+
+// One workgroup per stored tile (blockIdx.x over the triangle of side nT_grid) and filter: one read and one write of every live
+// chain, in place in Bm[buf].  A thread owns two work items (ekf_device.h: reframe_item), i.e. four 32-byte loads in flight and
+// four complete 2x2 blocks, all loaded before the first store; a wave's loads and stores are whole 256-byte runs.  Tiles beyond
+// the filter's map and the dead chains of a diagonal tile (block row > block column) are skipped as the dense pass skips them;
+// elements beyond the map inside a live tile are zeros with zero operands and stay zeros.
+// Diagonal chains of a diagonal tile (4 of its 10 live chains; 0.4 % of all chains at N = 4096) also hold places that are nobody's
+// home -- the landmarks' own blocks (home: D) and the blocks below the diagonal -- which are stale in normal operation.  They are
+// never transformed: a wave takes the chain with one lane per 2x2 block (eight-byte accesses that together cover the chain's 2 KiB
+// exactly once), lane (a, c) with a < c transforms its block and stores it twice, at home and transposed at (c, a); lane (a, a)
+// writes the own block from the NEW D (k_reframe_vec has run).  That is what k_import of the transformed state stores there.
+template <bool ANCHOR>
+__global__ __launch_bounds__(256) void k_reframe_tiles(EkfDev dv, int buf, ReframeFrame one, const double *fr, int b_off, int nT_grid) {
+    __shared__ double ops[128][8];  // [tile row | 64 + tile column][A row . W row .]
+    const int b = b_off + blockIdx.y;
+    const int n = dv.n_lm[b];
+    int I, J;
+    rm_tile_ij(blockIdx.x, nT_grid, &I, &J);
+    if (J >= (2 * n + 63) >> 6) return;
+    const int tid = threadIdx.x;
+    Rot2 q;
+    double4_t opa = {0.0, 0.0, 0.0, 0.0}, opw = {0.0, 0.0, 0.0, 0.0};
+    if (ANCHOR) {
+        const double phi = dv.x[(size_t)b * dv.xs + 2];  // (k_reframe_finish zeroes it behind this kernel)
+        q.c = cos(phi), q.s = sin(phi);
+        if (tid < 128) {  // the operand rows of the tile's 64 rows and 64 columns: requested here, staged in LDS behind the tile's own loads
+            const size_t rowi = (size_t)64 * (tid < 64 ? I : J) + (tid & 63);
+            opa = *(const double4_t *)(dv.FA + (size_t)b * 2 * dv.f_stride + rowi * 4);
+            opw = *(const double4_t *)(dv.FB + (size_t)b * 2 * dv.f_stride + rowi * 4);
+        }
+    } else {
+        q.c = frame_value(one, fr, blockIdx.y, 2), q.s = frame_value(one, fr, blockIdx.y, 3);
+    }
+    const bool diag = I == J;
+    double *tp = dv.Bm[buf] + (size_t)b * dv.bm_stride + ((size_t)I * dv.T - ((size_t)I * (I - 1)) / 2 + (size_t)(J - I)) * 4096;
+    ReframeItem it[2];
+    bool live[2];
+    double4_t v[2][2];
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        it[r] = reframe_item(r * 256 + tid);
+        live[r] = !diag || (it[r].chain >> 2) < (it[r].chain & 3);
+        if (live[r]) {
+            v[r][0] = *(const double4_t *)(tp + it[r].off);
+            v[r][1] = *(const double4_t *)(tp + it[r].off + 32);
+        }
+    }
+    if (ANCHOR) {
+        if (tid < 128) {
+            *(double4_t *)&ops[tid][0] = opa;
+            *(double4_t *)&ops[tid][4] = opw;
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        if (!live[r]) continue;
+        double o[2][4];
+#pragma unroll
+        for (int k = 0; k < 2; k++) {  // value v of piece s is element (row[v & 1] + s, col + (v >> 1))
+            rot_block(q, v[r][0][k], v[r][0][2 + k], v[r][1][k], v[r][1][2 + k], o[k]);
+            if (ANCHOR) {
+                const double *r0 = ops[it[r].row[k]], *r1 = ops[it[r].row[k] + 1], *c0 = ops[64 + it[r].col], *c1 = ops[64 + it[r].col + 1];
+                o[k][0] += cross_term(r0, c0), o[k][1] += cross_term(r0, c1);
+                o[k][2] += cross_term(r1, c0), o[k][3] += cross_term(r1, c1);
+            }
+        }
+        __builtin_nontemporal_store(((double4_t){o[0][0], o[1][0], o[0][1], o[1][1]}), (double4_t *)(tp + it[r].off));
+        __builtin_nontemporal_store(((double4_t){o[0][2], o[1][2], o[0][3], o[1][3]}), (double4_t *)(tp + it[r].off + 32));
+    }
+    if (!diag) return;
+    const int w = tid >> 6, a = (tid >> 3) & 7, c = tid & 7;  // wave w: chain (w, w); lane: block row a, block column c of its 8 x 8 blocks
+    if (a > c) return;
+    double *ch = tp + w * 5 * 256;
+    int at[2][2], mirror[2][2];
+    for (int d = 0; d < 2; d++)
+        for (int e = 0; e < 2; e++) at[d][e] = bm_chain_offset(2 * a + d, 2 * c + e), mirror[d][e] = bm_chain_offset(2 * c + e, 2 * a + d);
+    if (a == c) {
+        const double *Dx = dv.D + (size_t)b * 3 * dv.dn;
+        const int l = 32 * I + 8 * w + a;  // (l < dn = 32 T; zeros beyond the map)
+        const double xy = Dx[dv.dn + l];
+        ch[at[0][0]] = Dx[l], ch[at[0][1]] = xy, ch[at[1][0]] = xy, ch[at[1][1]] = Dx[2 * (size_t)dv.dn + l];
+        return;
+    }
+    double o[4];
+    rot_block(q, ch[at[0][0]], ch[at[0][1]], ch[at[1][0]], ch[at[1][1]], o);
+    if (ANCHOR) {
+        const double *r0 = ops[16 * w + 2 * a], *r1 = r0 + 8, *c0 = ops[64 + 16 * w + 2 * c], *c1 = c0 + 8;
+        o[0] += cross_term(r0, c0), o[1] += cross_term(r0, c1), o[2] += cross_term(r1, c0), o[3] += cross_term(r1, c1);
+    }
+    for (int d = 0; d < 2; d++)
+        for (int e = 0; e < 2; e++) ch[at[d][e]] = o[2 * d + e], ch[mirror[d][e]] = o[2 * d + e];
+}
+
+// Thread 0 of block blockIdx.x = filter b_off + blockIdx.x: the robot entries (pose, P_RR) and, as k_set_meta does behind a removal,
+// the bookkeeping and the host mirror; the landmark count stays.
+template <bool ANCHOR>
+__global__ void k_reframe_finish(EkfDev dv, ReframeFrame one, const double *fr, int b_off) {
+    if (threadIdx.x != 0) return;
+    const int b = b_off + blockIdx.x;
+    double *x = dv.x + (size_t)b * dv.xs;
+    double *R0 = dv.R + (size_t)b * 3 * dv.xs;
+    double p[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
+    if (ANCHOR) {
+        x[0] = 0.0, x[1] = 0.0, x[2] = 0.0;
+    } else {
+        double f[5];
+        for (int k = 0; k < 5; k++) f[k] = frame_value(one, fr, blockIdx.x, k);
+        const Rot2 q = {f[2], f[3]};
+        const double dx = x[0] - f[0], dy = x[1] - f[1];
+        x[0] = q.c * dx + q.s * dy, x[1] = q.c * dy - q.s * dx, x[2] = x[2] - f[4];
+        // J_R P_RR J_R^T, J_R = diag(Q, 1), from the upper triangle and mirrored
+        double d[4];
+        rot_block(q, R0[0], R0[1], R0[1], R0[(size_t)dv.xs + 1], d);
+        const double p02 = R0[2], p12 = R0[(size_t)dv.xs + 2];
+        p[0][0] = d[0], p[0][1] = p[1][0] = d[1], p[1][1] = d[3];
+        p[0][2] = p[2][0] = q.c * p02 + q.s * p12;
+        p[1][2] = p[2][1] = q.c * p12 - q.s * p02;
+        p[2][2] = R0[2 * (size_t)dv.xs + 2];
+    }
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) R0[(size_t)i * dv.xs + j] = p[i][j];
+    const int n_lm = dv.n_lm[b];
+    dv.n_lm_sweep[b] = n_lm;
+    dv.n_lm_flush[(size_t)b * 2] = n_lm;
+    dv.n_lm_flush[(size_t)b * 2 + 1] = n_lm;
+    dv.status[b] = 0;
+    EkfMirror *mr = dv.mirror + b;
+    for (int i = 0; i < 3; i++) mr->pose[i] = x[i];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) mr->Prr[i * 3 + j] = p[i][j];
+    mr->n_lm = n_lm;
+    mr->status = 0;
+    mr->log_count = dv.log_count[b];
+    for (int m = 0; m < 2 * dv.maxp; m++) dv.slot_active[(size_t)b * 2 * dv.maxp + m] = 0;
+}
+
 // Probe pair for ekf_api's concurrency check: the waiter spins (bounded, about 2 ms) until the setter, launched on ANOTHER
 // stream after it, has run; out[0] = 1 when it saw the flag.  Under tools that serialise kernel execution it times out.
 __global__ void k_probe_wait(int *flag, int *out) {

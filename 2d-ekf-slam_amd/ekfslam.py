@@ -24,6 +24,7 @@ ABI_SYMBOLS = [
     "ekf_timer_stop", "ekf_flush_profile", "ekf_flush_profile_read", "ekf_fused_pass", "ekf_get_decisions", "ekf_get_stats",
     "ekf_reset_stats", "ekf_stats_means_device", "ekf_record_truth", "ekf_stream", "ekf_device_bytes", "ekf_debug_windows", "ekf_debug_stream", "ekf_debug_stream_ring",
     "ekf_remove_landmarks", "ekf_batch_remove_landmarks", "ekf_get_landmark_covs",
+    "ekf_transform_frame", "ekf_batch_transform_frame", "ekf_anchor_at_robot", "ekf_batch_anchor_at_robot",
 ]
 
 
@@ -99,6 +100,10 @@ def load():
     L.ekf_remove_landmarks.argtypes = [_H, ctypes.c_int, _up, ctypes.c_int]
     L.ekf_batch_remove_landmarks.argtypes = [_H, _up, ctypes.c_int, _ip]
     L.ekf_get_landmark_covs.argtypes = [_H, ctypes.c_int, _dp, ctypes.c_int]
+    L.ekf_transform_frame.argtypes = [_H, ctypes.c_int, _dp]
+    L.ekf_batch_transform_frame.argtypes = [_H, _dp]
+    L.ekf_anchor_at_robot.argtypes = [_H, ctypes.c_int]
+    L.ekf_batch_anchor_at_robot.argtypes = [_H]
     L.ekf_script_load.argtypes = [_H, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _up, _dp]
     L.ekf_script_run.argtypes = [_H, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.ekf_sync.argtypes = [_H]
@@ -274,6 +279,31 @@ class FilterBatch:
         n = _chk(self.L.ekf_get_landmark_covs(self.h, int(index), _p(out), int(self.capacity)))
         return out[:n].copy()
 
+    def transform_frame(self, frame, index=None):
+        """A known rigid transform of the whole estimate on the device (ekf_transform_frame): frame = (t_x, t_y, theta), the pose of
+        the new frame's origin in the current frame.  index=None: frame is [batch][3], one frame per filter in one pass
+        (ekf_batch_transform_frame).  The heading is not wrapped; compass readings shift by -theta."""
+        if index is None:
+            fr = _f64(frame)
+            if fr.ndim == 1 and self.batch == 1:
+                fr = fr.reshape(1, 3)
+            if fr.shape != (self.batch, 3):
+                raise ValueError("frame must be [batch][3]")
+            _chk(self.L.ekf_batch_transform_frame(self.h, _p(fr)))
+            return
+        fr = _f64(frame).reshape(-1)
+        if fr.size != 3:
+            raise ValueError("frame must be (t_x, t_y, theta)")
+        _chk(self.L.ekf_transform_frame(self.h, int(index), _p(fr)))
+
+    def anchor_at_robot(self, index=None):
+        """Re-express the map relative to the robot's estimated pose on the device (ekf_anchor_at_robot; index=None: every filter,
+        ekf_batch_anchor_at_robot): the pose becomes exactly (0, 0, 0) with P_RR = 0, its uncertainty moves into the landmarks."""
+        if index is None:
+            _chk(self.L.ekf_batch_anchor_at_robot(self.h))
+        else:
+            _chk(self.L.ekf_anchor_at_robot(self.h, int(index)))
+
     def script_load(self, ctrl, z, R, valid=None, truth=None):
         """ctrl (steps, batch, 3); z (steps, M, batch, 2); R (steps, M, batch, 4) column-major blocks;
         valid (steps, M, batch); truth (steps, batch, 3)."""
@@ -426,4 +456,15 @@ class KalmanFilter:
         """Marginalise the landmarks whose keep[l] is false out of the map (kept ones are renumbered in order); refreshes
         Num_Landmarks.  A decision's matched index m names landmark (m - 3) // 2."""
         self._f.remove_landmarks(keep, 0)
+        self._mirror()
+
+    def transform_frame(self, frame):
+        """A known rigid transform of the estimate, frame = (t_x, t_y, theta) = the new origin's pose in the current frame; refreshes
+        X, Y, Phi (Phi is not wrapped).  Compass readings passed to doUpdateCompass afterwards must be shifted by -theta."""
+        self._f.transform_frame(frame, 0)
+        self._mirror()
+
+    def anchor_at_robot(self):
+        """Re-express the map relative to the estimated pose: X = Y = Phi = 0 with zero robot covariance afterwards."""
+        self._f.anchor_at_robot(0)
         self._mirror()

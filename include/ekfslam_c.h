@@ -185,6 +185,29 @@ int ekf_batch_remove_landmarks(ekf_handle h, const unsigned char *keep, int ld_k
  * Returns N. */
 int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max);
 
+/* Frame changes on the device, P <- J P J^T in place (no trip through ekf_get_state / ekf_set_state).
+ * ekf_transform_frame: a KNOWN rigid transform of the whole estimate of filter `index`.  frame = (t_x, t_y, theta) is the pose of
+ * the NEW frame's origin expressed in the CURRENT frame; with Q = Rot(-theta): p' = Q (p - t), L_l' = Q (L_l - t), phi' = phi - theta,
+ * and every block of P is rotated accordingly (theta = 0: P is unchanged bit for bit and x is the single subtraction).  cos(theta) and
+ * sin(theta) are taken once on the host (libm).  The heading is NOT wrapped (the filter wraps it nowhere).  A compass measurement is
+ * absolute: after a rigid transform the caller's compass readings shift by -theta.  A loaded script's truth poses are not transformed.
+ * ekf_anchor_at_robot: re-expresses every landmark relative to the robot's ESTIMATED pose, L_l' = Rot(-phi) (L_l - p), and moves the
+ * pose uncertainty into the landmarks (P' = J P J^T with the Jacobian of that map): afterwards the pose is exactly (0, 0, 0) and every
+ * robot row and column of P exactly zero -- the reference's start state with a map -- and the landmark blocks are the joint covariance
+ * of the predicted relative measurements.  Because P_RR = 0, a NEES sample (ekf_record_truth) is meaningless until the next
+ * propagation, and the caller's truth must be re-expressed in the new frame too.
+ * Both: deferred slots are folded first (at most one window closes, none on a settled handle); a streaming launch is stopped and
+ * immediate-mode calls stream again afterwards; synchronise; return EKF_OK or a negative status.  The landmark count, the counters
+ * (ekf_get_stats) and the decision log are unchanged (log entries are frame-free); the host mirror shows the new pose and P_RR.  A
+ * sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY is returned unchanged and the state is left as it was; bad arguments (index out of
+ * range, NULL, a non-finite frame) return EKF_ERR_BAD_ARG and leave the handle untouched.  Every device buffer ends as
+ * ekf_set_state of the transformed state would leave it: the capacity stays, a loaded script stays loaded, ekf_reserve works before
+ * and after.  The batch forms transform every filter in one launch sequence (frames [batch][3]: one frame per filter). */
+int ekf_transform_frame(ekf_handle h, int index, const double frame[3]);
+int ekf_batch_transform_frame(ekf_handle h, const double *frames /*[batch][3]*/);
+int ekf_anchor_at_robot(ekf_handle h, int index);
+int ekf_batch_anchor_at_robot(ekf_handle h);
+
 /* ---- device-resident step scripts (benchmarks, Monte-Carlo runs) ------------------------------
  * A script is `steps` steps; step s of filter b is
  *     Propagate(ctrl[s][b] = v, w, dt)  with Q from params as ekf_propagate does,
