@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ekf_device.h"
+#include "ekf_geometry.h"
 
 // single translation unit: the kernels are compiled together with their launch sites
 #include "ekf_kernels.hip"
@@ -40,6 +41,26 @@ int ekf_set_last_error(int code, const char *what) { return set_error(code, what
             return set_error(EKF_ERR_HIP, buf_);                                             \
         }                                                                                    \
     } while (0)
+
+// ... and for the library's own int status chains (the callee has set the error text)
+#define EKF_TRY(expr)        \
+    do {                     \
+        int rc_ = (expr);    \
+        if (rc_) return rc_; \
+    } while (0)
+
+// A transient device allocation that frees itself, so that HIP_TRY / EKF_TRY may return past it.
+template <typename T>
+struct DevTmp {
+    T *p = nullptr;
+    DevTmp() = default;
+    DevTmp(const DevTmp &) = delete;
+    DevTmp &operator=(const DevTmp &) = delete;
+    ~DevTmp() {
+        if (p) hipFree(p);
+    }
+    hipError_t alloc(size_t count) { return hipMalloc((void **)&p, count * sizeof(T)); }
+};
 
 struct GraphEntry {
     int steps, M, has_truth;
@@ -82,9 +103,8 @@ struct ekf_batch {
     int ngroups = 1;
     std::vector<hipStream_t> s_grp;
     hipEvent_t ev_fork = nullptr;
-    std::vector<hipEvent_t> ev_join;
-    int stagger_ticks = 0; // phase shift between consecutive groups at the start of a grouped run, in ticks of the 100 MHz clock
-    int chain_wgs;        // k_chain workgroups per filter
+    std::vector<hipEvent_t> ev_join;  // (tn.solo_stagger_ticks: the phase shift between consecutive groups at the start of a grouped run)
+    int chain_wgs;       // k_chain workgroups per filter
     int chain_filters;    // filters per k_chain launch (all of the batch when its workgroups are resident together)
     int claimed_cus;      // CUs this handle's chain workgroups occupy when they run (residency registry, below)
     int solo_cus = 0;     // one-workgroup handles: CUs their launches occupy while they run (they claim none: g_cus_solo)
@@ -92,9 +112,7 @@ struct ekf_batch {
     size_t chain_lds;     // dynamic LDS of a k_chain launch: the own-row cache
     bool chain_one = false;  // k_chain<true>: several workgroups per filter, at most one landmark per worker thread (EKF_CHAIN_ONE=0: the general kernel)
     double *bm1_base;     // allocation behind dv.Bm[1] (overlap mode)
-    std::vector<int *> tile_maps;  // [nT]: XCD-aware wave -> tile tables of the row-block dense pass, built on demand
-    bool xcd_map;         // EKF_XCD_MAP (default on)
-    bool batch_interleave; // EKF_BATCH_INTERLEAVE (default on): batches run a filter's dense-pass workgroups on one XCD
+    std::vector<int *> tile_maps;  // [nT]: XCD-aware wave -> tile tables of the row-block dense pass, built on demand (tn.xcd_map)
     size_t device_bytes;
     int chain_threads;
     // host-side tracking
@@ -102,13 +120,12 @@ struct ekf_batch {
     int cur_set;    // slot set being filled
     int pending;    // slots used in cur_set
     int buf_in;     // Bm buffer the chain kernels read (complete up to the sets still open or in flight)
-    bool flush_alternate; // EKF_FLUSH_ALTERNATE (default on): dense passes walk the tiles alternately first-to-last and last-to-first
-    int flush_dir;        // direction of the next dense pass (0 = first to last)
-    // Product tunables (read from the environment at ekf_*_create, listed in include/ekfslam_c.h "Tunables"; every one of them
-    // changes scheduling only, never results): EKF_BALANCED_TAIL, EKF_OVERLAP, EKF_PERSIST, EKF_CHAIN_ONE, EKF_CHAIN_HELPERS,
-    // EKF_INLINE_REC, EKF_XCD_MAP, ... -- bench.py records every EKF_* variable it saw.
-    bool balanced_tail = true;          // EKF_BALANCED_TAIL=0: windows always close at max_pending (launch_ops)
-    long long windows_closed = 0;       // windows handed to a dense pass by close_set since create (ekf_debug_windows)
+    int flush_dir;        // direction of the next dense pass (0 = first to last; tn.flush_alternate)
+    // Product tunables and experiment variables (read from the environment at ekf_*_create by read_tunables, listed in
+    // include/ekfslam_c.h "Tunables" and INTEGRATION.md; every one of them changes scheduling only, never results) -- bench.py
+    // records every EKF_* variable it saw.
+    Tunables tn;
+    long long windows_closed = 0;      // windows handed to a dense pass by close_set since create (ekf_debug_windows)
     int last_window_slots = 0;          // ... and the slots of the last one
     // Test / experiment hooks.  They exist only in the debug variant of the library (make debug: -DEKF_DEBUG_HOOKS,
     // libekfslam_hip_debug.so); in the product build the fields keep these values and no environment variable can change them.
@@ -170,11 +187,50 @@ extern "C" void ekf_default_params(ekf_params *p) {
     p->overlap = -1;
 }
 
-// EKF_TRACE=1: progress marks of handle creation / destruction on stderr (diagnostic)
-static bool trace_on() {
-    static int on = -1;
-    if (on < 0) on = getenv("EKF_TRACE") ? atoi(getenv("EKF_TRACE")) : 0;
-    return on != 0;
+// ---- the environment ----------------------------------------------------------------------------------------------------------
+// Read here and nowhere else: once per process (process_tunables), at every ekf_*_create (read_tunables, into the handle's
+// Tunables) and, in the debug variant, at create and ekf_set_state (read_debug_hooks, below).
+static EnvInt env_int(const char *name) {
+    EnvInt e;
+    if (const char *s = getenv(name)) e.set = true, e.v = atoi(s);
+    return e;
+}
+
+struct ProcessTunables {
+    bool trace;       // EKF_TRACE=1: progress marks of handle creation / destruction on stderr (diagnostic)
+    bool inline_rec;  // EKF_INLINE_REC=0: an immediate-mode call's record always travels through the ring
+};
+static const ProcessTunables &process_tunables() {
+    static const ProcessTunables t = {env_int("EKF_TRACE").v != 0, env_int("EKF_INLINE_REC").flag(true)};
+    return t;
+}
+static bool trace_on() { return process_tunables().trace; }
+
+static Tunables read_tunables() {
+    Tunables t;
+    t.overlap = env_int("EKF_OVERLAP");
+    t.solo = env_int("EKF_SOLO");
+    t.chain_wgs = env_int("EKF_CHAIN_WGS");
+    t.solo_long_window = env_int("EKF_SOLO_LONG_WINDOW");
+    t.solo_fuse = env_int("EKF_SOLO_FUSE");
+    t.chain_one = env_int("EKF_CHAIN_ONE");
+    t.chain_helpers = env_int("EKF_CHAIN_HELPERS");
+    t.solo_stagger_ticks = env_int("EKF_SOLO_STAGGER_US").set ? env_int("EKF_SOLO_STAGGER_US").v * 100 : 3500;
+    t.bm_skew_bytes = getenv("EKF_BM_SKEW") ? atol(getenv("EKF_BM_SKEW")) : 4096;
+    t.stream_ring_host = env_int("EKF_STREAM_RING_HOST").flag(false);
+    t.balanced_tail = env_int("EKF_BALANCED_TAIL").flag(true);
+    t.chain_cus = env_int("EKF_CHAIN_CUS");
+    t.inkernel_wait = env_int("EKF_INKERNEL_WAIT").flag(true);
+    t.solo_groups = env_int("EKF_SOLO_GROUPS").or_else(1);
+    t.flush_alternate = env_int("EKF_FLUSH_ALTERNATE").flag(true);
+    t.persist = env_int("EKF_PERSIST").flag(true);
+    t.stream = env_int("EKF_STREAM").flag(true);
+    t.xcd_map = env_int("EKF_XCD_MAP").flag(true);
+    t.batch_interleave = env_int("EKF_BATCH_INTERLEAVE").flag(true);
+    t.overlap_serial = getenv("EKF_OVERLAP_SERIAL") != nullptr;
+    t.solo_fuse_stagger_ticks = env_int("EKF_SOLO_FUSE_STAGGER_US").v * 100;
+    t.inline_rec = process_tunables().inline_rec;
+    return t;
 }
 #define TRACE(msg)                                          \
     do {                                                    \
@@ -236,29 +292,33 @@ static int concurrent_kernels_ok(int device, hipStream_t a, hipStream_t b) {
     static std::vector<int> cache(64, -1);
     std::lock_guard<std::mutex> lk(mu);
     if (device >= 0 && device < (int)cache.size() && cache[device] >= 0) return cache[device];
-    int *d = nullptr, h[2] = {0, 0};
-    int ok = 0;
-    if (hipMalloc((void **)&d, 2 * sizeof(int)) == hipSuccess && hipMemset(d, 0, 2 * sizeof(int)) == hipSuccess) {
-        hipLaunchKernelGGL(k_probe_wait, dim3(1), dim3(64), 0, a, d, d + 1);
-        hipLaunchKernelGGL(k_probe_set, dim3(1), dim3(64), 0, b, d);
-        if (hipStreamSynchronize(a) == hipSuccess && hipStreamSynchronize(b) == hipSuccess &&
-            hipMemcpy(h, d, 2 * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess)
-            ok = h[1] == 1;
+    int h[2] = {0, 0}, ok = 0;
+    {
+        DevTmp<int> d;
+        if (d.alloc(2) == hipSuccess && hipMemset(d.p, 0, 2 * sizeof(int)) == hipSuccess) {
+            hipLaunchKernelGGL(k_probe_wait, dim3(1), dim3(64), 0, a, d.p, d.p + 1);
+            hipLaunchKernelGGL(k_probe_set, dim3(1), dim3(64), 0, b, d.p);
+            if (hipStreamSynchronize(a) == hipSuccess && hipStreamSynchronize(b) == hipSuccess &&
+                hipMemcpy(h, d.p, 2 * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess)
+                ok = h[1] == 1;
+        }
     }
-    if (d) hipFree(d);
     (void)hipGetLastError();
     if (device >= 0 && device < (int)cache.size()) cache[device] = ok;
     return ok;
 }
 
-template <typename T>
-static hipError_t dev_alloc_zero(T **p, size_t count, size_t *total, hipStream_t s) {
-    size_t bytes = count * sizeof(T);
-    if (bytes == 0) bytes = sizeof(T);
-    hipError_t e = hipMalloc((void **)p, bytes);
+static hipError_t dev_alloc_zero_bytes(void **p, size_t count, size_t elem, size_t *total, hipStream_t s) {
+    size_t bytes = count * elem;
+    if (bytes == 0) bytes = elem;
+    hipError_t e = hipMalloc(p, bytes);
     if (e != hipSuccess) return e;
     *total += bytes;
     return hipMemsetAsync(*p, 0, bytes, s);
+}
+template <typename T>
+static hipError_t dev_alloc_zero(T **p, size_t count, size_t *total, hipStream_t s) {
+    return dev_alloc_zero_bytes((void **)p, count, sizeof(T), total, s);
 }
 
 // Residency registry.  The workgroups of a filter's chain kernel exchange their arg-min candidates while they run, so all
@@ -272,6 +332,105 @@ static int g_cus_claimed[64];
 // co-residency and claim nothing above -- but a 256-filter k_solo launch does fill the GPU, and a multi-segment chain launch of
 // ANOTHER handle, whose gated dense passes need free CUs, must know (launch_ops: persist).
 static int g_cus_solo[64];
+
+// ---- the device arrays of a handle, named once ----------------------------------------------------------------------------------
+// Allocation (create_impl), release (ekf_destroy), "clear filter b" (ekf_set_state) and "copy filter 0 to filter b"
+// (ekf_broadcast_state) walk this table; a new buffer is one more row.  Not in it, and handled where they are used: Bm[1] (an alias
+// of Bm[0] in place; in overlap mode an allocation of its own behind a skewed base, bm1_base, cleared with Bm[0] and zeroed by a
+// broadcast), the tile maps, a loaded script and the host-mapped blocks.
+enum : unsigned { AR_CLEAR = 1, AR_COPY = 2 };  // ekf_set_state clears the filter's part; ekf_broadcast_state copies filter 0's
+struct DevArray {
+    void **slot;    // the pointer in EkfDev (or the handle)
+    size_t elem;    // bytes per element
+    size_t stride;  // elements per filter; 0: one array per handle
+    size_t tail;    // elements behind the per-filter part
+    unsigned ops;
+    size_t count(int B) const { return (size_t)B * stride + tail; }
+    size_t filter_bytes() const { return stride * elem; }
+    char *at(size_t b) const { return (char *)*slot + b * stride * elem; }
+};
+static std::vector<DevArray> device_arrays(ekf_batch *h) {
+    EkfDev &dv = h->dv;
+#define EKF_ARRAY(ptr, stride, tail, ops) DevArray{(void **)&(ptr), sizeof(*(ptr)), (size_t)(stride), (size_t)(tail), ops}
+#ifdef EKF_CHAIN_STAMPS
+    const size_t dbg_words = 32 + 65 * 2048;  // + publish times of every workgroup, 2048 exchanges (scripts/history/r04_skew.py)
+#else
+    const size_t dbg_words = 32;
+#endif
+    return {
+        EKF_ARRAY(dv.x, dv.xs, 0, AR_CLEAR | AR_COPY),
+        EKF_ARRAY(dv.R, 3 * dv.xs, 0, AR_CLEAR | AR_COPY),
+        EKF_ARRAY(dv.D, 3 * dv.dn, 0, AR_CLEAR | AR_COPY),
+        EKF_ARRAY(dv.Bm[0], dv.bm_stride, 0, AR_CLEAR | AR_COPY),  // (a broadcast copies Bm[buf_in]: the settled buffer)
+        EKF_ARRAY(dv.FA, 2 * dv.f_stride, 0, AR_CLEAR | AR_COPY),
+        EKF_ARRAY(dv.FB, 2 * dv.f_stride, 0, AR_CLEAR | AR_COPY),
+        EKF_ARRAY(dv.slot_active, 2 * dv.maxp, EKF_MAX_PENDING, AR_COPY),  // (+ EKF_MAX_PENDING: k_flush_rb reads that many entries of a row unconditionally)
+        EKF_ARRAY(dv.n_lm, 1, 0, AR_COPY),
+        EKF_ARRAY(dv.n_lm_sweep, 1, 0, AR_COPY),
+        EKF_ARRAY(dv.n_lm_flush, 2, 0, AR_COPY),
+        EKF_ARRAY(dv.status, 1, 0, AR_COPY),
+        EKF_ARRAY(dv.slot_meta, 2 * dv.maxp, 0, 0),
+        EKF_ARRAY(dv.pass_flag, 0, 1, 0),
+        EKF_ARRAY(dv.seg_count, 0, EKF_PLAN_MAX, 0),
+        EKF_ARRAY(dv.bar, 2, 0, 0),
+        EKF_ARRAY(dv.dbg, 0, dbg_words, 0),
+        EKF_ARRAY(dv.part, 2 * dv.nrec * EKF_REC_DOUBLES, 0, 0),
+        EKF_ARRAY(dv.log, dv.logcap, 0, 0),
+        EKF_ARRAY(dv.log_count, 1, 0, AR_COPY),
+        EKF_ARRAY(dv.stats, 1, 0, 0),
+        EKF_ARRAY(h->cursor_d, 0, 1, 0),
+        EKF_ARRAY(dv.sfw, 0, 40, 0),
+    };
+#undef EKF_ARRAY
+}
+
+// ---- one launcher per kernel family ---------------------------------------------------------------------------------------------
+// The chain kernel of a handle: k_solo<LONG, STREAM> for one-workgroup maps of up to 256 landmarks, k_chain<ONE, STREAM> otherwise.
+// The only place that names an instantiation.
+typedef void (*ChainKernel)(EkfDev, const double *, const int *, ChainPlan, int);
+static ChainKernel chain_kernel(bool solo_kernel, bool long_or_one, bool streaming) {
+    static const ChainKernel table[2][2][2] = {{{k_chain<false, false>, k_chain<false, true>}, {k_chain<true, false>, k_chain<true, true>}},
+                                               {{k_solo<false, false>, k_solo<false, true>}, {k_solo<true, false>, k_solo<true, true>}}};
+    return table[solo_kernel][long_or_one][streaming];
+}
+static ChainKernel chain_kernel(const ekf_batch *h, bool streaming) {
+    return chain_kernel(h->solo_kernel, h->solo_kernel ? h->solo_long : h->chain_one, streaming);
+}
+
+// One chain launch over filters [b0, b0 + nb) on stream s.  on_packet: the hipExt form, whose start / stop events (either may be null)
+// ride on the dispatch packet itself; else the plain form.
+static void launch_chain(const ekf_batch *h, hipStream_t s, bool streaming, bool on_packet, hipEvent_t ev0, hipEvent_t ev1, const double *in, const int *cursor,
+                         const ChainPlan &plan, int b0, int nb) {
+    const ChainKernel k = chain_kernel(h, streaming);
+    const dim3 grid(h->chain_wgs, nb), block(h->chain_threads);
+    if (on_packet) hipExtLaunchKernelGGL(k, grid, block, h->chain_lds, s, ev0, ev1, 0, h->dv, in, cursor, plan, b0);
+    else hipLaunchKernelGGL(k, grid, block, h->chain_lds, s, h->dv, in, cursor, plan, b0);
+}
+
+// One dense pass (k_flush_rb) over nslots slots of slot set `set` of filters [b0, b0 + nb), Bm[fin] -> Bm[fout], on stream s; e0 / e1
+// ride on the dispatch packet (no extra barrier packets).  interleave: a filter's workgroups on one XCD (batches); else tmap, if any.
+static void launch_pass(const EkfDev &dv, hipStream_t s, hipEvent_t e0, hipEvent_t e1, bool interleave, int nT_hi, int set, int nslots, int fin, int fout,
+                        const int *tmap, int rev, int b0, int nb) {
+    const int nwg = (nT_hi * (nT_hi + 1) / 2 + 3) / 4;
+    if (interleave)
+        hipExtLaunchKernelGGL(k_flush_rb, dim3((unsigned)((nb + 7) / 8 * 8 * nwg), 1), dim3(256), 0, s, e0, e1, 0, dv, nT_hi, set, nslots, fin, fout, (const int *)nullptr, nwg, rev, b0, nb);
+    else
+        hipExtLaunchKernelGGL(k_flush_rb, dim3(nwg, nb), dim3(256), 0, s, e0, e1, 0, dv, nT_hi, set, nslots, fin, fout, tmap, 0, rev, b0, nb);
+}
+
+// Advance *i over operations until the window holds `limit` slots or EKF_CHAIN_MAX_OPS operations have been taken; `used` slots are
+// taken already.  Returns the slots used afterwards (consumes[q] != 0: operation q takes a slot).
+static int take_ops(const unsigned char *consumes, int nops, int *i, int used, int limit) {
+    const int start = *i;
+    while (*i < nops && *i - start < EKF_CHAIN_MAX_OPS) {
+        if (consumes[*i]) {
+            if (used == limit) break;
+            used++;
+        }
+        (*i)++;
+    }
+    return used;
+}
 
 static int create_impl(ekf_batch *h, int batch, int capacity_landmarks, int device_id, const ekf_params *params, const hipDeviceProp_t &prop);
 
@@ -325,26 +484,27 @@ static int create_impl(ekf_batch *h, int batch, int capacity_landmarks, int devi
     ekf_default_params(&h->params);
     if (params) h->params = *params;
     h->params_requested = h->params;  // (ekf_reserve builds the larger handle from what the caller asked for, not from what this capacity allowed)
-    if (h->params.max_pending < 1) h->params.max_pending = 1;
-    if (h->params.max_pending > EKF_MAX_PENDING) h->params.max_pending = EKF_MAX_PENDING;
     if (h->params.log_capacity < 16) h->params.log_capacity = 16;
-    h->device_bytes = 0;
-    if (!pool_take(device_id, -1, &h->s_chain)) {
-        TRACE("create: stream");
-        HIP_TRY(hipStreamCreateWithFlags(&h->s_chain, hipStreamNonBlocking));
-        TRACE("create: stream done");
-    }
 
+    // ---- tunables -> geometry (ekf_geometry.h: the whole decision, checked on the CPU) ----
+    h->tn = read_tunables();
+    const Tunables &tn = h->tn;
+    const ChainGeometry geo = plan_geometry(batch, capacity_landmarks, h->params, prop.sharedMemPerBlock, tn);
+    if (geo.error) return set_error(geo.error, geo.what);
+    h->params.max_pending = geo.max_pending;  // the effective window, see ekf_window()
+    h->params.overlap = geo.overlap ? 1 : 0;
+    h->overlap = geo.overlap;
+    h->solo = geo.solo, h->solo_kernel = geo.solo_kernel, h->solo_long = geo.solo_long, h->solo_fuse = geo.solo_fuse;
+    h->chain_wgs = geo.chain_wgs, h->chain_filters = geo.chain_filters, h->chain_threads = geo.chain_threads;
+    h->chain_lds = geo.chain_lds, h->chain_one = geo.chain_one;
     EkfDev &dv = h->dv;
     memset(&dv, 0, sizeof dv);
     dv.B = batch;
     dv.Ncap = capacity_landmarks;
-    dv.T = (2 * capacity_landmarks + 63) / 64;
-    dv.xs = ((3 + 64 * dv.T) + 63) / 64 * 64;
-    dv.dn = 32 * dv.T;
+    dv.T = geo.T, dv.xs = geo.xs, dv.dn = geo.dn, dv.rows = geo.rows, dv.bm_stride = geo.bm_stride;
+    dv.maxp = geo.max_pending, dv.maxpairs = geo.maxpairs, dv.f_stride = geo.f_stride, dv.vs_cap = geo.cache_slots;
+    dv.gmax = geo.chain_wgs, dv.lpw = geo.lpw, dv.hpw = geo.hpw, dv.nrec = geo.nrec;
     dv.logcap = h->params.log_capacity;
-    dv.bm_stride = (size_t)dv.T * (dv.T + 1) / 2 * 4096;
-    dv.rows = 64 * dv.T;
     dv.gamma_max = h->params.gamma_max;
     dv.gamma_min = h->params.gamma_min;
     dv.spin_limit = 1LL << 24;
@@ -356,127 +516,15 @@ static int create_impl(ekf_batch *h, int batch, int capacity_landmarks, int devi
         long double kappa = L <= 1.0L ? 0.0L : 0.5L - 1.0L / (L * L + 1.0L);
         dv.cond_k2 = (double)(kappa * kappa);
     }
-    // k_chain geometry.  About one landmark per worker thread, at most 32 workgroups per filter, and few
-    // enough workgroups in total (<= 256) that all of them are resident at once: the cross-workgroup
-    // barrier needs every workgroup of a filter running.  Every workgroup keeps its landmarks' rows of every
-    // slot of the open window in LDS (64 bytes per landmark and slot), so landmarks-per-workgroup x window
-    // must fit the CU's LDS next to the kernel's static 16 KB: more workgroups first, then a shorter window.
-    const int max_workers = EKF_CHAIN_MAX_THREADS - 64;
-    const long lds_budget = (long)prop.sharedMemPerBlock - 16384;  // (k_chain's static LDS: 16.2 KB)
-    if (lds_budget < 64 * 64) return set_error(EKF_ERR_NO_DEVICE, "device reports too little LDS per workgroup");
-    int maxp = h->params.max_pending;
-    // overlap (params.overlap, EKF_OVERLAP overrides): automatic = on when two windows of every landmark's slot rows fit
-    // the LDS of at most 64 resident workgroups per filter, i.e. when it does not cost window length
-    int want_overlap = getenv("EKF_OVERLAP") ? atoi(getenv("EKF_OVERLAP")) : h->params.overlap;
-    if (want_overlap < 0) {
-        int g_max = batch >= 256 ? 1 : (EKF_CHAIN_MAX_WGS < 256 / batch ? EKF_CHAIN_MAX_WGS : 256 / batch);
-        if (g_max < 1) g_max = 1;
-        long lpw_min = ((capacity_landmarks + g_max - 1) / g_max + 63) / 64 * 64;  // (the LDS cache is laid out in chunks of 64 landmarks)
-        want_overlap = (lpw_min * maxp * 2 * 32 <= lds_budget) ? 1 : 0;
-        // ... and when there is a dense pass worth hiding.  Round 4 (scripts/history/r04_geometry.py): with several windows per chain launch
-        // the overlapped pipeline also saves the launch boundaries between chain kernel and pass, and wins from P_LL = 10 MB on
-        // (N = 768: 39.2 k against 35.3 k steps/s in place; N = 1024: 38.5 k against 35.3 k; N = 2048: 37.8 k against 32.3 k; N = 512,
-        // 4 MB: 37.6 k against 36.9 k -- a draw; the threshold is 8 MB).  The threshold was 128 MB in rounds 1-3, measured on one-window launches.
-        size_t T = (2 * (size_t)capacity_landmarks + 63) / 64;
-        if ((size_t)batch * (T * (T + 1) / 2) * 4096 * sizeof(double) < ((size_t)8 << 20)) want_overlap = 0;
-    }
-    h->overlap = want_overlap != 0;
-    h->params.overlap = h->overlap ? 1 : 0;
-    const int sets_in_lds = h->overlap ? 2 : 1;  // overlap: the set being folded by the dense pass in flight is still needed
-    int G = (capacity_landmarks + max_workers - 1) / max_workers;
-    int G_lds = (int)((((long)capacity_landmarks + 63) / 64 * 64 * maxp * sets_in_lds * 32 + lds_budget - 1) / lds_budget);
-    if (G_lds > G) G = G_lds;
-    // Round 4: about 64 landmarks -- ONE worker wave -- per workgroup is the fastest shape wherever the GPU has the CUs for it, up to
-    // 32 workgroups per filter (fewer waves to keep in step at every barrier; N = 512: 8 workgroups 36.9 k against 3 workgroups
-    // 34.4 k steps/s, N = 1024: 16 against 6: 35.3 k against 32.5 k in place, N = 2048: 32 against 16: 37.8 k against 36.3 k
-    // overlapped; at N = 4096 the rule gives the 32 workgroups of 128 landmarks the LDS budget asked for already, and 64
-    // workgroups of 64 were slower there: 29.7 k against 31.6 k, the dense pass loses too many CUs)
+
+    // ---- residency claim ----
+    for (int k = 0; k < 8; k++)  // one setting for every handle and every chain kernel
+        HIP_TRY(hipFuncSetAttribute((const void *)chain_kernel((k & 4) != 0, (k & 2) != 0, (k & 1) != 0), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)chain_lds_budget(prop.sharedMemPerBlock)));
     {
-        int G_pref = (capacity_landmarks + 63) / 64;
-        if (G_pref > 32) G_pref = 32;
-        if (G_pref > G) G = G_pref;
-    }
-    if (G > EKF_CHAIN_MAX_WGS) G = EKF_CHAIN_MAX_WGS;
-    if (G * batch > 256) G = 256 / batch;  // (batches of more than 256 filters: one workgroup per filter, several launches)
-    if (G < 1) G = 1;
-    // the cache holds whole chunks of 64 landmarks per workgroup: a few more workgroups can save a whole chunk each
-    // (N = 4096, window 16, two sets: 28 workgroups of 147 landmarks would need 3 chunks, 32 of 128 need 2)
-    {
-        auto lds_need = [&](int g) { return ((long)(capacity_landmarks + g - 1) / g + 63) / 64 * 64 * maxp * sets_in_lds * 32; };
-        const int g_cap = batch >= 256 ? 1 : (EKF_CHAIN_MAX_WGS < 256 / batch ? EKF_CHAIN_MAX_WGS : 256 / batch);
-        while (G < g_cap && lds_need(G) > lds_budget) G++;
-    }
-    // One workgroup per filter and one slot set ("solo").  Maps of up to 256 landmarks whose window fits one CU's LDS are run by
-    // k_solo (ekf_solo.hip): one landmark per thread, no control wave, no exchange, one barrier per measurement.  EKF_SOLO=0
-    // keeps k_chain for them (A/B comparisons, tests of k_chain's one-workgroup path).
-    const bool want_solo_kernel = !h->overlap && (getenv("EKF_SOLO") ? atoi(getenv("EKF_SOLO")) != 0 : true) && !getenv("EKF_CHAIN_WGS");
-    // (k_solo runs windows of up to twice what its cache holds -- ekf_solo.hip, SOLO_HALF -- so 16 slots of cache are enough for any window)
-    if (want_solo_kernel && capacity_landmarks <= 256 &&
-        ((long)capacity_landmarks + 63) / 64 * 64 * (maxp > 2 * 16 ? maxp : (maxp > 16 ? 16 : maxp)) * 32 <= lds_budget) G = 1;
-    if (getenv("EKF_CHAIN_WGS")) G = atoi(getenv("EKF_CHAIN_WGS")) > 0 ? atoi(getenv("EKF_CHAIN_WGS")) : G;
-    if (G > EKF_CHAIN_MAX_WGS) G = EKF_CHAIN_MAX_WGS;
-    if (G * batch > 256) G = 256 / batch > 0 ? 256 / batch : 1;
-    h->solo = !h->overlap && G == 1;
-    h->solo_kernel = h->solo && want_solo_kernel && capacity_landmarks <= 256;
-    h->stagger_ticks = getenv("EKF_SOLO_STAGGER_US") ? atoi(getenv("EKF_SOLO_STAGGER_US")) * 100 : 3500;
-    h->chain_wgs = G;
-    h->chain_filters = batch * G <= 256 ? batch : 256 / G;  // every workgroup of a launch resident at once
-    dv.gmax = G;
-    dv.lpw = (capacity_landmarks + G - 1) / G;
-    const long lpw64 = ((long)dv.lpw + 63) / 64 * 64;  // the own-row cache holds whole chunks of 64 landmarks
-    int cache_slots = maxp * sets_in_lds;  // slots of own rows in LDS
-    if (lpw64 * maxp * sets_in_lds * 32 > lds_budget) {
-        const bool two_halves = h->solo_kernel && lds_budget / (lpw64 * 32) >= 16 && !(getenv("EKF_SOLO_LONG_WINDOW") && atoi(getenv("EKF_SOLO_LONG_WINDOW")) == 0);
-        if (two_halves) {
-            // k_solo: the window's first 16 slots move into registers when the cache is full (ekf_solo.hip: SOLO_HALF): a window of
-            // up to 32 with 16 slots of cache -- one dense pass per 32 measurements for a map of 256 landmarks
-            if (maxp > 32) maxp = 32;
-            cache_slots = 16;
-        } else {
-            maxp = (int)(lds_budget / (lpw64 * sets_in_lds * 32));
-            if (maxp > 1) maxp &= ~1;  // whole slot pairs
-            cache_slots = maxp * sets_in_lds;
-        }
-    }
-    if (maxp < 1) return set_error(EKF_ERR_BAD_ARG, "capacity too large for this batch size (one window slot does not fit LDS)");
-    h->params.max_pending = maxp;  // the effective window, see ekf_window()
-    dv.maxp = maxp;
-    dv.maxpairs = (dv.maxp + 1) / 2;
-    dv.f_stride = (size_t)(dv.maxpairs + 1) * dv.rows * 4;
-    dv.vs_cap = cache_slots;
-    h->solo_long = h->solo_kernel && maxp > cache_slots;
-    // (the tile of the in-kernel pass lives in a128..a255 -- the registers of a long window's first half, free otherwise --, the A operands of
-    // a tile row in the own-row cache, dead while the pass runs: 2 KiB per pair and wave -- 8 or 16 pairs -- against 2 KiB per cached slot)
-    h->solo_fuse = h->solo_kernel && cache_slots >= ((((maxp + 1) >> 1) + 7) & ~7) && (getenv("EKF_SOLO_FUSE") ? atoi(getenv("EKF_SOLO_FUSE")) != 0 : true);
-    h->chain_lds = (size_t)lpw64 * cache_slots * 32;
-    HIP_TRY(hipFuncSetAttribute((const void *)k_chain<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget));  // one setting for every handle
-    HIP_TRY(hipFuncSetAttribute((const void *)k_chain<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_chain<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_chain<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_solo<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_solo<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_solo<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget));
-    HIP_TRY(hipFuncSetAttribute((const void *)k_solo<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_budget));
-    int workers = (dv.lpw + 63) / 64 * 64;
-    if (workers > max_workers) workers = max_workers;
-    if (dv.lpw > 64 && dv.lpw <= 128) workers = 192;  // two owner waves and a third that shares their fold (k_chain: helper_on)
-    // one owner wave and two that take a third of its fold each (round 4: N = 768 / 12 workgroups 39.2 k -> 40.5 k steps/s, N = 1024 / 16:
-    // 38.0 k -> 39.5 k; with 32 workgroups -- N = 2048 -- the two extra waves at every barrier cost more than the shorter fold gives:
-    // 37.0 k -> 35.8 k, so only up to 16 workgroups)
-    if (dv.lpw <= 64 && G > 1 && G <= 16) workers = 192;
-    // ... and, whatever the number of workgroups, where the fold is long: 48 virtual slots and more (round 5: N = 4096 as 64 workgroups of 64 landmarks
-    // with two windows of 32 in LDS: 36.6 k steps/s with the helper waves, 32.9 k without)
-    if (dv.lpw <= 64 && G > 1 && cache_slots >= 48) workers = 192;
-    if (getenv("EKF_CHAIN_HELPERS") && dv.lpw <= 64 && G > 1) workers = atoi(getenv("EKF_CHAIN_HELPERS")) != 0 ? 192 : (dv.lpw + 63) / 64 * 64;  // (experiments: force / forbid the two helper waves)
-    h->chain_threads = 64 + workers;  // wave 0 is the control wave
-    if (h->solo_kernel) h->chain_threads = (capacity_landmarks + 63) / 64 * 64;  // k_solo: one landmark per thread, no control wave
-    dv.hpw = (dv.lpw + 63) / 64;
-    h->chain_one = !h->solo_kernel && G > 1 && dv.lpw <= h->chain_threads - 64 && G * dv.hpw <= EKF_CHAIN_MAX_WGS && !(getenv("EKF_CHAIN_ONE") && atoi(getenv("EKF_CHAIN_ONE")) == 0);
-    if (!h->chain_one) dv.hpw = 1;
-    dv.nrec = G * dv.hpw;
-    {
+        const int G = h->chain_wgs;
         int per_cu = 0;
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, h->solo_kernel ? (h->solo_long ? (const void *)k_solo<true> : (const void *)k_solo<false>) : (h->chain_one ? (const void *)k_chain<true> : (const void *)k_chain<false>), h->chain_threads, h->chain_lds));
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)chain_kernel(h, false), h->chain_threads, h->chain_lds));
         if (per_cu < 1) return set_error(EKF_ERR_STATE, "the chain kernel does not fit a CU with this capacity / window");
         // (one-workgroup filters wait for nobody: they need no co-residency and claim nothing)
         const int need = h->solo ? 0 : (G * h->chain_filters + per_cu - 1) / per_cu;
@@ -494,47 +542,31 @@ static int create_impl(ekf_batch *h, int batch, int capacity_landmarks, int devi
         g_cus_solo[device_id] += h->solo_cus;
         h->ncu = prop.multiProcessorCount;
     }
-    size_t B = batch;
-    hipStream_t s = h->s_chain;
-    HIP_TRY(dev_alloc_zero(&dv.x, B * dv.xs, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.R, B * 3 * dv.xs, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.D, B * 3 * dv.dn, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.Bm[0], B * dv.bm_stride, &h->device_bytes, s));
-    if (h->overlap) {  // the dense pass goes buffer to buffer
-        // The second buffer is shifted by 4 KB against the first so that a tile's source and destination differ in DRAM
-        // channel/bank phase: 107-108 us per pass instead of 110-111 (scripts/history/exp_skew.sh; EKF_BM_SKEW overrides, bytes)
-        size_t skew = (getenv("EKF_BM_SKEW") ? (size_t)atol(getenv("EKF_BM_SKEW")) : (size_t)4096) / sizeof(double);
-        HIP_TRY(dev_alloc_zero(&h->bm1_base, B * dv.bm_stride + skew, &h->device_bytes, s));
-        dv.Bm[1] = h->bm1_base + skew;
-    }
-    else dv.Bm[1] = dv.Bm[0];  // one buffer: the dense pass runs in place
-    HIP_TRY(dev_alloc_zero(&dv.FA, B * 2 * dv.f_stride, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.FB, B * 2 * dv.f_stride, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.n_lm, B, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.n_lm_sweep, B, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.n_lm_flush, B * 2, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.status, B, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.slot_active, B * 2 * dv.maxp + EKF_MAX_PENDING, &h->device_bytes, s));  // (+ EKF_MAX_PENDING: k_flush_rb reads that many entries of a row unconditionally)
-    HIP_TRY(dev_alloc_zero(&dv.slot_meta, B * 2 * dv.maxp, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.pass_flag, 1, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.seg_count, EKF_PLAN_MAX, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.bar, B * 2, &h->device_bytes, s));
-#ifdef EKF_CHAIN_STAMPS
-    HIP_TRY(dev_alloc_zero(&dv.dbg, 32 + 65 * 2048, &h->device_bytes, s));  // + publish times of every workgroup, 2048 exchanges (scripts/history/r04_skew.py)
-#else
-    HIP_TRY(dev_alloc_zero(&dv.dbg, 32, &h->device_bytes, s));
-#endif
-    HIP_TRY(dev_alloc_zero(&dv.part, B * 2 * dv.nrec * EKF_REC_DOUBLES, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.log, B * dv.logcap, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.log_count, B, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&dv.stats, B, &h->device_bytes, s));
-    HIP_TRY(dev_alloc_zero(&h->cursor_d, 1, &h->device_bytes, s));
 
+    // ---- buffers ----
+    if (!pool_take(device_id, -1, &h->s_chain)) {
+        TRACE("create: stream");
+        HIP_TRY(hipStreamCreateWithFlags(&h->s_chain, hipStreamNonBlocking));
+        TRACE("create: stream done");
+    }
+    const size_t B = batch;
+    hipStream_t s = h->s_chain;
+    for (const DevArray &a : device_arrays(h)) {
+        HIP_TRY(dev_alloc_zero_bytes(a.slot, a.count(batch), a.elem, &h->device_bytes, s));
+        if (a.slot != (void **)&dv.Bm[0]) continue;
+        if (h->overlap) {  // the dense pass goes buffer to buffer
+            // The second buffer is shifted by 4 KB against the first so that a tile's source and destination differ in DRAM
+            // channel/bank phase: 107-108 us per pass instead of 110-111 (scripts/history/exp_skew.sh; EKF_BM_SKEW overrides, bytes)
+            const size_t skew = (size_t)tn.bm_skew_bytes / sizeof(double);
+            HIP_TRY(dev_alloc_zero(&h->bm1_base, B * dv.bm_stride + skew, &h->device_bytes, s));
+            dv.Bm[1] = h->bm1_base + skew;
+        }
+        else dv.Bm[1] = dv.Bm[0];  // one buffer: the dense pass runs in place
+    }
     TRACE("create: device buffers queued");
     HIP_TRY(hipHostMalloc((void **)&h->mirror_h, B * sizeof(EkfMirror), hipHostMallocMapped));
     memset(h->mirror_h, 0, B * sizeof(EkfMirror));
     HIP_TRY(hipHostGetDevicePointer((void **)&dv.mirror, h->mirror_h, 0));
-    HIP_TRY(dev_alloc_zero(&dv.sfw, 40, &h->device_bytes, s));
     HIP_TRY(hipHostMalloc((void **)&h->sctl_h, sizeof(StreamCtl), hipHostMallocMapped));
     memset(h->sctl_h, 0, sizeof(StreamCtl));
     HIP_TRY(hipHostGetDevicePointer((void **)&dv.sctl, h->sctl_h, 0));
@@ -542,9 +574,8 @@ static int create_impl(ekf_batch *h, int batch, int capacity_landmarks, int devi
         // the command ring in device memory where the host can write it (large BAR; EKF_STREAM_RING_HOST=1 keeps it in host memory)
         int large_bar = 0;
         if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, h->device) != hipSuccess) large_bar = 0, (void)hipGetLastError();
-        const bool want_host = getenv("EKF_STREAM_RING_HOST") && atoi(getenv("EKF_STREAM_RING_HOST")) != 0;
         dv.sring = dv.sctl, h->sring_h = h->sctl_h;
-        if (large_bar && !want_host) {
+        if (large_bar && !tn.stream_ring_host) {
             StreamCtl *d = nullptr;
             if (hipExtMallocWithFlags((void **)&d, sizeof(StreamCtl), hipDeviceMallocFinegrained) == hipSuccess) {
                 HIP_TRY(hipMemsetAsync(d, 0, sizeof(StreamCtl), s));
@@ -555,43 +586,24 @@ static int create_impl(ekf_batch *h, int batch, int capacity_landmarks, int devi
             }
         }
     }
-    size_t rec_bytes = B * 8 * sizeof(double);
+    const size_t rec_bytes = B * 8 * sizeof(double);
     long ring_ops = (long)((16u << 20) / rec_bytes);
     if (ring_ops > 1024) ring_ops = 1024;
     if (ring_ops < 2 * EKF_CHAIN_MAX_OPS) ring_ops = 2 * EKF_CHAIN_MAX_OPS;
     h->ring_ops = (int)ring_ops;
     HIP_TRY(hipHostMalloc((void **)&h->ring_h, rec_bytes * h->ring_ops, hipHostMallocMapped));
     HIP_TRY(hipHostGetDevicePointer((void **)&h->ring_d, h->ring_h, 0));
-    h->ring_pos = 0;
-    for (int i = 0; i < 2; i++) {
-        HIP_TRY(hipEventCreateWithFlags(&h->ring_ev[i], hipEventDisableTiming));
-        h->ring_ev_valid[i] = false;
-    }
+
+    // ---- streams and events (the handle was value-initialised: every count, flag and cursor of the pipeline starts at zero) ----
+    for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreateWithFlags(&h->ring_ev[i], hipEventDisableTiming));
     HIP_TRY(hipEventCreate(&h->t0));
     HIP_TRY(hipEventCreate(&h->t1));
-    h->balanced_tail = !(getenv("EKF_BALANCED_TAIL") && atoi(getenv("EKF_BALANCED_TAIL")) == 0);
-    h->prof_flush = false;
-    h->prof_used = 0;
-    h->prof_launches = 0;
-    h->prof_ms = 0;
-    h->n_lm_hi = 0;
-    h->cur_set = 0;
-    h->pending = 0;
-    h->buf_in = 0;
-    h->prev_pending = 0;
-    h->ev_idx = 0;
-    h->chain_signalled = false;
-    h->chain_seq = 0;
-    h->pass_seq = 0;
-    h->need_pass = 0;
-    h->inkernel_wait = false;
-    h->mirror_by_chain = false;
     h->s_flush = h->s_chain;
     if (h->overlap) {
         // The chain kernel needs its workgroups' CUs the moment it is launched; a dense pass that owns every CU
         // would make it queue behind whole tiles.  The dense pass therefore gets a stream restricted to the CUs
         // the chain does not need (EKF_CHAIN_CUS overrides the number kept free).
-        int keep = getenv("EKF_CHAIN_CUS") ? atoi(getenv("EKF_CHAIN_CUS")) : (G * batch < 32 ? G * batch : 32);  // (measured: 32 beats 64 even for 64 workgroups)
+        int keep = tn.chain_cus.or_else(h->chain_wgs * batch < 32 ? h->chain_wgs * batch : 32);  // (measured: 32 beats 64 even for 64 workgroups)
         int ncu = prop.multiProcessorCount;
         if (keep > ncu / 2) keep = ncu / 2;
         h->flush_keep = keep > 0 ? keep : -1;
@@ -621,14 +633,12 @@ static int create_impl(ekf_batch *h, int batch, int capacity_landmarks, int devi
         // In-kernel waiting only where the pass has a queue of its own CUs and kernels of the two streams were seen to run
         // side by side; everywhere else (unmasked fallback stream, serialising tools) the chain stream waits for the
         // pass's event.
-        h->inkernel_wait = (getenv("EKF_INKERNEL_WAIT") ? atoi(getenv("EKF_INKERNEL_WAIT")) != 0 : true) && h->flush_masked &&
-                           concurrent_kernels_ok(device_id, h->s_chain, h->s_flush) != 0;
+        h->inkernel_wait = tn.inkernel_wait && h->flush_masked && concurrent_kernels_ok(device_id, h->s_chain, h->s_flush) != 0;
         HIP_TRY(hipEventCreate(&h->ev_chain));  // (stop events of dispatch packets)
         for (int i = 0; i < 2; i++) HIP_TRY(hipEventCreate(&h->ev_flush[i]));
-        h->chain_signalled = false;
     }
     if (h->solo) {
-        int ng = getenv("EKF_SOLO_GROUPS") ? atoi(getenv("EKF_SOLO_GROUPS")) : 1;
+        int ng = tn.solo_groups;
         if (ng > 8) ng = 8;
         if (ng < 1 || batch < 16 * ng) ng = 1;  // (small batches: one launch for all filters)
         h->ngroups = ng;
@@ -641,20 +651,14 @@ static int create_impl(ekf_batch *h, int batch, int capacity_landmarks, int devi
             HIP_TRY(hipEventCreateWithFlags(&h->ev_join[g], hipEventDisableTiming));
         }
     }
-    h->flush_alternate = getenv("EKF_FLUSH_ALTERNATE") ? atoi(getenv("EKF_FLUSH_ALTERNATE")) != 0 : true;
     {
         int can_wait_value = 0;
         (void)hipDeviceGetAttribute(&can_wait_value, hipDeviceAttributeCanUseStreamWaitValue, device_id);
-        h->persist = (getenv("EKF_PERSIST") ? atoi(getenv("EKF_PERSIST")) != 0 : true) && can_wait_value != 0;
+        h->persist = tn.persist && can_wait_value != 0;
     }
-    h->flush_dir = 0;
     read_debug_hooks(h);
     // streaming immediate-mode calls: every handle of ONE filter (k_chain above 256 landmarks, k_solo up to 256)
-    h->stream_calls = batch == 1 && !(getenv("EKF_STREAM") && atoi(getenv("EKF_STREAM")) == 0);
-    h->xcd_map = getenv("EKF_XCD_MAP") ? atoi(getenv("EKF_XCD_MAP")) != 0 : true;
-    h->batch_interleave = getenv("EKF_BATCH_INTERLEAVE") ? atoi(getenv("EKF_BATCH_INTERLEAVE")) != 0 : true;
-    h->script_d = nullptr;
-    h->script_steps = h->script_M = h->script_has_truth = 0;
+    h->stream_calls = batch == 1 && tn.stream;
     h->h_int.resize(B);
     TRACE("create: final sync");
     HIP_TRY(hipStreamSynchronize(h->s_chain));
@@ -704,19 +708,14 @@ extern "C" int ekf_destroy(ekf_handle h) {
         if (h->ev_flush[i]) hipEventDestroy(h->ev_flush[i]);
     if (h->bm1_base) hipFree(h->bm1_base);
     for (auto &g : h->graphs) hipGraphExecDestroy(g.exec);
-    EkfDev &dv = h->dv;
-    hipFree(dv.x), hipFree(dv.R), hipFree(dv.D), hipFree(dv.Bm[0]), hipFree(dv.FA), hipFree(dv.FB);
-    hipFree(dv.n_lm), hipFree(dv.n_lm_sweep), hipFree(dv.n_lm_flush), hipFree(dv.status), hipFree(dv.slot_active), hipFree(dv.slot_meta), hipFree(dv.pass_flag), hipFree(dv.seg_count);
-    hipFree(dv.bar), hipFree(dv.part), hipFree(dv.dbg);
-    hipFree(dv.log), hipFree(dv.log_count), hipFree(dv.stats);
-    hipFree(h->cursor_d);
+    for (const DevArray &a : device_arrays(h))
+        if (*a.slot) hipFree(*a.slot);
     for (int *m : h->tile_maps)
         if (m) hipFree(m);
     if (h->script_d) hipFree(h->script_d);
     if (h->ring_h) hipHostFree(h->ring_h);
     if (h->sring_in_hbm) hipFree(h->dv.sring);
     if (h->sctl_h) hipHostFree(h->sctl_h);
-    if (h->dv.sfw) hipFree(h->dv.sfw);
     if (h->mirror_h) hipHostFree(h->mirror_h);
     for (int i = 0; i < 2; i++)
         if (h->ring_ev[i]) hipEventDestroy(h->ring_ev[i]);
@@ -805,7 +804,7 @@ static int check_launch() {
 // (I mod 2, J mod 4) = w mod 8, consecutive tiles of a class sharing their tile row; a class that runs dry takes from the
 // fullest one.  Built once per nT (the map only grows), uploaded synchronously.
 static const int *tile_map_for(ekf_batch *h, int nT) {
-    if (!h->xcd_map || nT < 8) return nullptr;  // small maps: nothing to share
+    if (!h->tn.xcd_map || nT < 8) return nullptr;  // small maps: nothing to share
     if ((int)h->tile_maps.size() <= nT) h->tile_maps.resize(nT + 1, nullptr);
     if (h->tile_maps[nT]) return h->tile_maps[nT];
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -864,6 +863,13 @@ static int prof_reserve(ekf_batch *h, size_t pairs) {
     }
     return EKF_OK;
 }
+// A start / stop pair from the pool (recycled after a read, which leaves both streams idle), growing it for a caller that outran
+// the pool of ekf_flush_profile / ekf_script_load.
+static int prof_take_pair(ekf_batch *h, hipEvent_t *e0, hipEvent_t *e1) {
+    if (h->prof_pool.size() < h->prof_used + 2) EKF_TRY(prof_reserve(h, 8));
+    *e0 = h->prof_pool[h->prof_used++], *e1 = h->prof_pool[h->prof_used++];
+    return EKF_OK;
+}
 static size_t prof_pairs_for_script(const ekf_batch *h) {
     if (!h->script_d) return 8;
     // a window closes after at least maxp / 2 measurements (the balanced tail) -- and once more per call (terminal passes)
@@ -891,18 +897,7 @@ static int stream_start(ekf_batch *h, long long consumed0, int slot0) {
     h->stream_launch = h->stream_launch >= 0xffff ? 1 : h->stream_launch + 1;  // (16 bits of it tag the forwards)
     plan.stream = h->stream_launch;
     __atomic_store_n(&h->sctl_h->state, ((unsigned long long)(unsigned)plan.stream << 2) | EKF_STREAM_RUNNING, __ATOMIC_SEQ_CST);
-    if (h->solo_kernel && h->solo_long)
-        hipExtLaunchKernelGGL((k_solo<true, true>), dim3(1, 1), dim3(h->chain_threads), h->chain_lds, h->s_chain, nullptr, nullptr, 0, h->dv,
-                              (const double *)h->ring_d, (const int *)nullptr, plan, 0);
-    else if (h->solo_kernel)
-        hipExtLaunchKernelGGL((k_solo<false, true>), dim3(1, 1), dim3(h->chain_threads), h->chain_lds, h->s_chain, nullptr, nullptr, 0, h->dv,
-                              (const double *)h->ring_d, (const int *)nullptr, plan, 0);
-    else if (h->chain_one)
-        hipExtLaunchKernelGGL((k_chain<true, true>), dim3(h->chain_wgs, 1), dim3(h->chain_threads), h->chain_lds, h->s_chain, nullptr, nullptr, 0, h->dv,
-                              (const double *)h->ring_d, (const int *)nullptr, plan, 0);
-    else
-        hipExtLaunchKernelGGL((k_chain<false, true>), dim3(h->chain_wgs, 1), dim3(h->chain_threads), h->chain_lds, h->s_chain, nullptr, nullptr, 0, h->dv,
-                              (const double *)h->ring_d, (const int *)nullptr, plan, 0);
+    launch_chain(h, h->s_chain, /*streaming*/ true, /*on_packet*/ true, nullptr, nullptr, (const double *)h->ring_d, nullptr, plan, 0, 1);
     h->stream_alive = true;
     h->chain_signalled = false;
     h->stream_starts++;
@@ -928,8 +923,7 @@ static int stream_wait_consumed(ekf_batch *h, long long seq) {
             if (consumed >= seq || ++relaunches > 4) return set_error(EKF_ERR_STATE, "a streaming launch left without publishing what it consumed");
             // (queued behind the old launch; it resumes at the slot the first unconsumed command was posted at -- the window has not changed:
             // a window only closes behind a command that is known to have been executed)
-            int rc = stream_start(h, consumed, h->stream_slot_before[(unsigned long long)(consumed + 1) % EKF_STREAM_RING]);
-            if (rc) return rc;
+            EKF_TRY(stream_start(h, consumed, h->stream_slot_before[(unsigned long long)(consumed + 1) % EKF_STREAM_RING]));
         }
         if ((spin & 255) == 255) {
             clock_gettime(CLOCK_MONOTONIC, &t1);
@@ -993,8 +987,7 @@ static int stream_op(ekf_batch *h, const double *rec, int n_slots) {
     h->stream_slot_before[(unsigned long long)seq % EKF_STREAM_RING] = h->pending;
     if (!h->stream_alive) {
         // (every earlier streamed command has been executed: a launch is only written off behind stream_wait_consumed -- stream_stop, a closing command)
-        int rc = stream_start(h, seq - 1, h->pending);
-        if (rc) return rc;
+        EKF_TRY(stream_start(h, seq - 1, h->pending));
     } else {
         // "write mine, fence, read yours": the launch does the same with its state word and this command slot before it leaves by itself, so
         // normally one of the two sees the other.  RUNNING: the launch will find the command.  Anything else: wait for the outcome (the
@@ -1002,8 +995,7 @@ static int stream_op(ekf_batch *h, const double *rec, int n_slots) {
         __atomic_thread_fence(__ATOMIC_SEQ_CST);
         const unsigned long long launch = (unsigned long long)(unsigned)h->stream_launch;
         if (__atomic_load_n(&c->state, __ATOMIC_ACQUIRE) != ((launch << 2) | EKF_STREAM_RUNNING)) {
-            int rc = stream_wait_consumed(h, seq);
-            if (rc) return rc;
+            EKF_TRY(stream_wait_consumed(h, seq));
         }
     }
     h->mirror_by_chain = true;
@@ -1023,8 +1015,7 @@ static int stream_op(ekf_batch *h, const double *rec, int n_slots) {
             HIP_TRY(hipEventRecord(h->ev_chain, h->s_chain));  // (behind the launch that filled the window)
             h->chain_signalled = true;
             EnqueueList pass;
-            rc = close_set(h, false, &pass);  // the host's state now describes the next window; the pass's calls wait in `pass`
-            if (rc) return rc;
+            EKF_TRY(close_set(h, false, &pass));  // the host's state now describes the next window; the pass's calls wait in `pass`
             rc = stream_start(h, seq, h->pending);
             for (auto &enq : pass) {
                 hipError_t e = enq();
@@ -1040,19 +1031,15 @@ static int stream_op(ekf_batch *h, const double *rec, int n_slots) {
             h->pending = 0;
             return stream_start(h, seq, 0);
         }
-        rc = close_set(h, false, nullptr);  // (in place: the pass runs on the chain's stream, the next launch behind it)
-        if (rc) return rc;
+        EKF_TRY(close_set(h, false, nullptr));  // (in place: the pass runs on the chain's stream, the next launch behind it)
         return stream_start(h, seq, h->pending);
     }
     return EKF_OK;
 }
 
 static int close_set(ekf_batch *h, bool terminal = false, EnqueueList *defer = nullptr) {
-    if (h->pending == 0) return stream_stop(h);
-    {
-        int rc_s = stream_stop(h);
-        if (rc_s) return rc_s;
-    }
+    EKF_TRY(stream_stop(h));
+    if (h->pending == 0) return EKF_OK;
     int nT_hi = (2 * h->n_lm_hi + 63) / 64;
     const int fin = (h->overlap && h->prev_pending > 0) ? h->buf_in ^ 1 : h->buf_in;
     // terminal: the caller asked for everything to be folded (ekf_flush, settle), so no chain kernel will run beside this
@@ -1078,25 +1065,17 @@ static int close_set(ekf_batch *h, bool terminal = false, EnqueueList *defer = n
     }
     const bool do_pass = !h->dbg_skip_flush && (nT_hi > 0 || h->overlap);
     if (nT_hi < 1) nT_hi = 1;
-    const int total = nT_hi * (nT_hi + 1) / 2;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (do_pass) {
         if (h->overlap && !terminal) e1 = h->ev_flush[h->ev_idx ^ 1];  // pass k's completion, signalled by its own dispatch packet
-        if (h->prof_flush) {
-            if (h->prof_pool.size() < h->prof_used + 2) {  // (a caller that outran the pool of ekf_flush_profile / ekf_script_load)
-                int rc = prof_reserve(h, 8);
-                if (rc) return rc;
-            }
-            e0 = h->prof_pool[h->prof_used++], e1 = h->prof_pool[h->prof_used++];  // (recycled after a read, which leaves both streams idle; e1 doubles as the pass's completion event)
-        }
+        if (h->prof_flush) EKF_TRY(prof_take_pair(h, &e0, &e1));  // (e1 doubles as the pass's completion event)
     }
     // Passes alternate direction: a pass starts on the tiles the previous pass touched last, which are the ones the
     // 256 MB Infinity Cache still holds (P_LL of N=4096 is 270 MB per buffer: walked the same way every time, the
     // cache has evicted a tile long before the next pass comes back to it).
-    const int rev = h->flush_alternate ? h->flush_dir : 0;
+    const int rev = h->tn.flush_alternate ? h->flush_dir : 0;
     if (do_pass) h->flush_dir ^= 1;
-    const int nwg = cdiv(total, 4);
-    const bool interleave = h->dv.B > 1 && h->batch_interleave;  // a filter's workgroups on one XCD
+    const bool interleave = h->dv.B > 1 && h->tn.batch_interleave;  // a filter's workgroups on one XCD
     const int *tmap = (do_pass && !interleave && h->dv.B == 1) ? tile_map_for(h, nT_hi) : (const int *)nullptr;
     const EkfDev dv = h->dv;
     const int set = h->cur_set, nslots = h->pending, B = h->dv.B;
@@ -1126,7 +1105,7 @@ static int close_set(ekf_batch *h, bool terminal = false, EnqueueList *defer = n
         done_ev = (h->prof_flush && do_pass) ? e1 : h->ev_flush[h->ev_idx];
         if (!do_pass) record_done = true, done_ev = h->ev_flush[h->ev_idx];  // (no pass kernel to carry the event: a marker)
         h->pass_done[h->ev_idx] = done_ev;
-        serial = getenv("EKF_OVERLAP_SERIAL") != nullptr;  // experiment: no concurrency
+        serial = h->tn.overlap_serial;  // experiment: no concurrency
         wait_done_on_chain = serial;
         h->buf_in = fin;
         h->prev_pending = h->pending;
@@ -1143,15 +1122,7 @@ static int close_set(ekf_batch *h, bool terminal = false, EnqueueList *defer = n
             if (record_chain && (e = hipEventRecord(ev_chain, sc)) != hipSuccess) return e;
             if (wait_chain && (e = hipStreamWaitEvent(sf, ev_chain, 0)) != hipSuccess) return e;
         }
-        if (do_pass) {
-            // (start/stop events ride on the dispatch packet itself: no extra barrier packets)
-            if (interleave) {
-                dim3 g1((unsigned)(cdiv(B, 8) * 8 * nwg), 1);
-                hipExtLaunchKernelGGL(k_flush_rb, g1, dim3(256), 0, sf, e0, e1, 0, dv, nT_hi, set, nslots, fin, fout, (const int *)nullptr, nwg, rev, 0, B);
-            } else {
-                hipExtLaunchKernelGGL(k_flush_rb, dim3(nwg, B), dim3(256), 0, sf, e0, e1, 0, dv, nT_hi, set, nslots, fin, fout, tmap, 0, rev, 0, B);
-            }
-        }
+        if (do_pass) launch_pass(dv, sf, e0, e1, interleave, nT_hi, set, nslots, fin, fout, tmap, rev, 0, B);
         if (!terminal && wait_prev && (e = hipStreamWaitEvent(sc, wait_prev, 0)) != hipSuccess) return e;
         if (mark) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, sf, dv.pass_flag, mark_value);
         if (record_done && (e = hipEventRecord(done_ev, sf)) != hipSuccess) return e;
@@ -1169,8 +1140,7 @@ static int close_set(ekf_batch *h, bool terminal = false, EnqueueList *defer = n
 
 // Everything folded into Bm[buf_in], streams idle.
 static int settle(ekf_batch *h) {
-    int rc = close_set(h, true);
-    if (rc) return rc;
+    EKF_TRY(close_set(h, true));
     HIP_TRY(stream_wait(h->s_chain));
     if (h->overlap) {
         HIP_TRY(stream_wait(h->s_flush));
@@ -1191,14 +1161,8 @@ static int launch_ops_grouped(ekf_batch *h, const double *in, int k0, const unsi
 static int launch_ops(ekf_batch *h, const double *in, const int *cursor, int k0, const unsigned char *consumes, int nops, bool defer_last_close = false) {
     if (h->stream_calls && cursor == nullptr && in == h->ring_d && nops > 0) {
         // an immediate-mode call of a one-filter handle: its operations go to the resident streaming launch, one command each
-        if (h->pending == h->dv.maxp) {  // a set whose close a scripted run deferred: more work follows, regular pass
-            int rc = close_set(h);
-            if (rc) return rc;
-        }
-        for (int q = 0; q < nops; q++) {
-            int rc = stream_op(h, h->ring_h + (size_t)(k0 + q) * 8, consumes[q] ? 1 : 0);
-            if (rc) return rc;
-        }
+        if (h->pending == h->dv.maxp) EKF_TRY(close_set(h));  // a set whose close a scripted run deferred: more work follows, regular pass
+        for (int q = 0; q < nops; q++) EKF_TRY(stream_op(h, h->ring_h + (size_t)(k0 + q) * 8, consumes[q] ? 1 : 0));
         return EKF_OK;
     }
     if (h->stream_calls && cursor == nullptr && in == h->script_d && nops > 0 && nops <= EKF_CHAIN_MAX_OPS) {
@@ -1210,34 +1174,24 @@ static int launch_ops(ekf_batch *h, const double *in, const int *cursor, int k0,
         int slots = 0;
         for (int q = 0; q < nops; q++) slots += consumes[q] ? 1 : 0;
         if (2 * slots <= h->dv.maxp) {
-            if (h->pending == h->dv.maxp) {
-                int rc = close_set(h);
-                if (rc) return rc;
-            }
+            if (h->pending == h->dv.maxp) EKF_TRY(close_set(h));
             int q0 = 0;
             while (q0 < nops) {
-                int q1 = q0, used = 0;
-                while (q1 < nops && !(consumes[q1] && h->pending + used == h->dv.maxp)) used += consumes[q1] ? 1 : 0, q1++;  // (up to, and including, the measurement that fills the window)
+                int q1 = q0;
+                const int used = take_ops(consumes, nops, &q1, h->pending, h->dv.maxp) - h->pending;  // (up to, and including, the measurement that fills the window)
                 double rec[8] = {0, 0, 0, 0, 0, 0, 0, (double)OP_SCRIPT};
                 const long long bits = (long long)(size_t)h->script_d;
                 memcpy(&rec[0], &bits, sizeof bits);
                 rec[1] = (double)(k0 + q0), rec[2] = (double)(q1 - q0);
-                int rc = stream_op(h, rec, used);
-                if (rc) return rc;
+                EKF_TRY(stream_op(h, rec, used));
                 q0 = q1;
             }
             return EKF_OK;
         }
     }
-    {
-        int rc = stream_stop(h);
-        if (rc) return rc;
-    }
+    EKF_TRY(stream_stop(h));
     int i = 0;
-    if (h->pending == h->dv.maxp && nops > 0) {  // a set whose close the previous call deferred: more work follows, regular pass
-        int rc = close_set(h);
-        if (rc) return rc;
-    }
+    if (h->pending == h->dv.maxp && nops > 0) EKF_TRY(close_set(h));  // a set whose close the previous call deferred: more work follows, regular pass
     // Scripted runs in overlap mode: the launches of one call become the segments of one launch (up to EKF_PLAN_MAX at a
     // time).  The workgroups stay resident across window boundaries -- no launch gap (5 us), no refill of the LDS caches
     // from memory (7 us per 16-measurement window at N = 4096) -- and the dense passes are enqueued behind stream gates that
@@ -1265,13 +1219,12 @@ static int launch_ops(ekf_batch *h, const double *in, const int *cursor, int k0,
     memset(&plan, 0, sizeof plan);
     EnqueueList passes;
     int next_drop = 0;
-    static const bool inline_rec = !(getenv("EKF_INLINE_REC") && atoi(getenv("EKF_INLINE_REC")) == 0);
     auto launch_plan = [&](hipEvent_t stop_ev) -> int {
         if (plan.nseg == 0) return EKF_OK;
         // one filter, one segment of one operation, its record in the host-mapped ring (an immediate-mode call, slam.cpp:136-170): the
         // record rides in the kernel arguments -- the kernel's first trip to host memory brings it along, the ring costs a second one
         plan.inl_n = 0;
-        if (inline_rec && h->dv.B == 1 && plan.nseg == 1 && plan.s[0].nops == 1 && cursor == nullptr && in == h->ring_d) {
+        if (h->tn.inline_rec && h->dv.B == 1 && plan.nseg == 1 && plan.s[0].nops == 1 && cursor == nullptr && in == h->ring_d) {
             memcpy(plan.inl, h->ring_h + (size_t)plan.s[0].k0 * 8, 8 * sizeof(double));
             plan.inl_n = 1;
         }
@@ -1282,14 +1235,9 @@ static int launch_ops(ekf_batch *h, const double *in, const int *cursor, int k0,
             // EKF_SOLO_FUSE_STAGGER_US: a one-off phase shift between the filters of a batch (four groups), so that their own passes take
             // turns in HBM.  Measured: nothing to gain (6.53 M filter-steps/s without, 6.51 / 6.42 / 6.35 M with 35 / 67 / 90 us: one wave
             // per SIMD is latency-bound on its own tile, not bandwidth-bound), so the default is none.
-            static const int fuse_stagger = getenv("EKF_SOLO_FUSE_STAGGER_US") ? atoi(getenv("EKF_SOLO_FUSE_STAGGER_US")) * 100 : 0;
-            plan.s[0].stagger = (sp >= 4 && h->dv.B >= 16) ? fuse_stagger : 0;
+            plan.s[0].stagger = (sp >= 4 && h->dv.B >= 16) ? h->tn.solo_fuse_stagger_ticks : 0;
             if (h->prof_flush && sp > 0) {  // the passes live inside this launch: time the launch, count the passes
-                if (h->prof_pool.size() < h->prof_used + 2) {
-                    int rc = prof_reserve(h, 8);
-                    if (rc) return rc;
-                }
-                pe0 = h->prof_pool[h->prof_used++], pe1 = h->prof_pool[h->prof_used++];
+                EKF_TRY(prof_take_pair(h, &pe0, &pe1));
                 h->prof_fused_passes += sp;
                 h->prof_solo_pairs++;
             }
@@ -1297,16 +1245,8 @@ static int launch_ops(ekf_batch *h, const double *in, const int *cursor, int k0,
         for (int b0 = 0; b0 < h->dv.B; b0 += h->chain_filters) {
             const int nb = h->dv.B - b0 < h->chain_filters ? h->dv.B - b0 : h->chain_filters;
             const bool last = b0 + nb >= h->dv.B;
-            if (solo) {
-                hipEvent_t ev0 = b0 == 0 ? pe0 : nullptr, ev1 = last ? (pe1 ? pe1 : stop_ev) : nullptr;
-                if (h->solo_long) hipExtLaunchKernelGGL(k_solo<true>, dim3(1, nb), dim3(h->chain_threads), h->chain_lds, h->s_chain, ev0, ev1, 0, h->dv, in, cursor, plan, b0);
-                else hipExtLaunchKernelGGL(k_solo<false>, dim3(1, nb), dim3(h->chain_threads), h->chain_lds, h->s_chain, ev0, ev1, 0, h->dv, in, cursor, plan, b0);
-            } else if (h->chain_one)
-                hipExtLaunchKernelGGL(k_chain<true>, dim3(h->chain_wgs, nb), dim3(h->chain_threads), h->chain_lds, h->s_chain, nullptr, last ? stop_ev : nullptr, 0, h->dv, in,
-                                      cursor, plan, b0);
-            else
-                hipExtLaunchKernelGGL(k_chain<false>, dim3(h->chain_wgs, nb), dim3(h->chain_threads), h->chain_lds, h->s_chain, nullptr, last ? stop_ev : nullptr, 0, h->dv, in,
-                                      cursor, plan, b0);
+            // (the stop event on the last launch's dispatch packet; a fused k_solo launch is bracketed by its profiling pair instead)
+            launch_chain(h, h->s_chain, /*streaming*/ false, /*on_packet*/ true, b0 == 0 ? pe0 : nullptr, last ? (pe1 ? pe1 : stop_ev) : nullptr, in, cursor, plan, b0, nb);
         }
         if (plan.signal)
             for (int q = 0; q < plan.nseg; q++) h->seg_count_base[q] = plan.s[q].gate;
@@ -1328,7 +1268,7 @@ static int launch_ops(ekf_batch *h, const double *in, const int *cursor, int k0,
     // second window (16 pairs, 165 us beside the chain kernel) outlasted the 16 measurements after it (100 us) and the last window's pass
     // waited behind it -- 170 us exposed after the chain kernel's end; 32 | 24 | 24 hides the second pass under the third segment and leaves
     // one 12-pair pass exposed.  Nothing changes for a run whose length is a multiple of the window, nor in the steady state of a long one.
-    const bool balanced_tail = h->balanced_tail;
+    const bool balanced_tail = h->tn.balanced_tail;
     int slots_left = 0;  // slot-consuming operations of this call from op i on
     for (int q = 0; q < nops; q++) slots_left += consumes[q] ? 1 : 0;
     int limit = h->dv.maxp;  // where the window being filled closes (a window carried over from an earlier call: max_pending)
@@ -1341,27 +1281,17 @@ static int launch_ops(ekf_batch *h, const double *in, const int *cursor, int k0,
                 if (limit > h->dv.maxp) limit = h->dv.maxp;  // (an odd max_pending: rounding up to a slot pair must not pass the window -- slot_meta rows, the own-row cache and the pass are sized for maxp)
             }
         }
-        while (i < nops && i - start < EKF_CHAIN_MAX_OPS) {
-            if (consumes[i]) {
-                if (used == limit) break;
-                used++;
-                slots_left--;
-            }
-            i++;
-        }
+        used = take_ops(consumes, nops, &i, used, limit);
+        slots_left -= used - h->pending;
         if (i == start) {  // set already full (cannot happen: full sets are closed above and below)
-            int rc = close_set(h, false, persist ? &passes : nullptr);
-            if (rc) return rc;
+            EKF_TRY(close_set(h, false, persist ? &passes : nullptr));
             continue;
         }
         // overlap: the launch that fills the set signals ev_chain from its own dispatch packet (no marker packet)
         const bool closes = h->overlap && used == limit;
         ChainSeg sg;
         sg.k0 = k0 + start, sg.nops = i - start, sg.slot0 = h->pending, sg.set = h->cur_set, sg.buf_read = h->buf_in, sg.n_prev = h->prev_pending;
-        if (next_drop > 0 && next_drop < h->prev_pending) {  // (the LDS shift moves whole windows: start a new launch instead)
-            int rc = launch_plan(nullptr);
-            if (rc) return rc;
-        }
+        if (next_drop > 0 && next_drop < h->prev_pending) EKF_TRY(launch_plan(nullptr));  // (the LDS shift moves whole windows: start a new launch instead)
         sg.need_pass = h->need_pass, sg.drop = next_drop;
         sg.seq = ++h->chain_seq;  // (one number per segment: every filter's mirror reaches it)
         sg.gate = h->seg_count_base[plan.nseg] + (unsigned long long)h->chain_wgs * h->dv.B;  // every workgroup of the launch has finished this segment
@@ -1375,8 +1305,7 @@ static int launch_ops(ekf_batch *h, const double *in, const int *cursor, int k0,
         h->stats_in_mirror = true;
         h->pending = used;
         if (!multi) {
-            int rc = launch_plan(closes ? h->ev_chain : nullptr);
-            if (rc) return rc;
+            EKF_TRY(launch_plan(closes ? h->ev_chain : nullptr));
             h->chain_signalled = closes;
         } else {
             h->chain_signalled = false;
@@ -1386,14 +1315,10 @@ static int launch_ops(ekf_batch *h, const double *in, const int *cursor, int k0,
             h->cur_set ^= 1;  // folded by the launch itself: the next segment starts an empty window
             h->pending = 0;
         } else if (used == limit && !(defer_last_close && i == nops)) {
-            int rc = close_set(h, false, persist ? &passes : nullptr);
-            if (rc) return rc;
+            EKF_TRY(close_set(h, false, persist ? &passes : nullptr));
             next_drop = sg.n_prev;  // the next segment starts a window: the set whose pass has finished leaves the LDS caches
         }
-        if (multi && plan.nseg == EKF_PLAN_MAX) {
-            int rc = launch_plan(nullptr);
-            if (rc) return rc;
-        }
+        if (multi && plan.nseg == EKF_PLAN_MAX) EKF_TRY(launch_plan(nullptr));
     }
     return launch_plan(nullptr);
 }
@@ -1411,9 +1336,9 @@ static int launch_ops_grouped(ekf_batch *h, const double *in, int k0, const unsi
     if ((e = hipEventRecord(h->ev_fork, h->s_chain)) != hipSuccess) return set_error(EKF_ERR_HIP, hipGetErrorString(e));
     for (int g = 1; g < ng; g++) {
         if ((e = hipStreamWaitEvent(h->s_grp[g], h->ev_fork, 0)) != hipSuccess) return set_error(EKF_ERR_HIP, hipGetErrorString(e));  // (nothing has been launched on a group stream yet)
-        if (h->stagger_ticks > 0) hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, h->s_grp[g], (long long)g * h->stagger_ticks);
+        if (h->tn.solo_stagger_ticks > 0) hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, h->s_grp[g], (long long)g * h->tn.solo_stagger_ticks);
     }
-    const bool interleave = h->batch_interleave;
+    const bool interleave = h->tn.batch_interleave;
     // The group streams have been forked off s_chain: whatever happens from here on, they are joined back before this function
     // returns -- later work on s_chain (ring reuse, memsets of ekf_set_state, the hipFree of a staging buffer) must not run beside
     // chain and pass kernels still queued on a group stream.  An error on the way is remembered, the join still happens (where even
@@ -1423,25 +1348,11 @@ static int launch_ops_grouped(ekf_batch *h, const double *in, int k0, const unsi
         long passes = 0, used_ = h->pending;
         for (int q = 0; q < nops; q++)
             if (consumes[q] && ++used_ == maxp) passes++, used_ = 0;
-        while (h->prof_pool.size() < h->prof_used + 2 * (size_t)ng * (size_t)(passes + 1)) {
-            hipEvent_t ev;
-            if (hipEventCreate(&ev) != hipSuccess) {
-                rc_pending = set_error(EKF_ERR_HIP, "hipEventCreate failed (dense-pass profiling)");
-                break;
-            }
-            h->prof_pool.push_back(ev);
-        }
+        rc_pending = prof_reserve(h, (size_t)ng * (size_t)(passes + 1));
     }
     int i = 0;
     while (i < nops && rc_pending == EKF_OK) {
-        int start = i, used = h->pending;
-        while (i < nops && i - start < EKF_CHAIN_MAX_OPS) {
-            if (consumes[i]) {
-                if (used == maxp) break;
-                used++;
-            }
-            i++;
-        }
+        const int start = i, used = take_ops(consumes, nops, &i, h->pending, maxp);
         ChainPlan plan;
         memset(&plan, 0, sizeof plan);
         ChainSeg &sg = plan.s[0];
@@ -1455,22 +1366,15 @@ static int launch_ops_grouped(ekf_batch *h, const double *in, int k0, const unsi
         const bool fold = used == maxp;
         int nT_hi = (2 * h->n_lm_hi + 63) / 64;
         const bool do_pass = fold && !h->dbg_skip_flush && nT_hi > 0;
-        const int total = nT_hi * (nT_hi + 1) / 2, nwg = cdiv(total, 4);
-        const int rev = h->flush_alternate ? h->flush_dir : 0;
+        const int rev = h->tn.flush_alternate ? h->flush_dir : 0;
         for (int g = 0; g < ng; g++) {
             const int b0 = g * per, nb = B - b0 < per ? B - b0 : per;
             if (nb <= 0) break;
-            if (h->solo_kernel && h->solo_long) hipLaunchKernelGGL(k_solo<true>, dim3(1, nb), dim3(h->chain_threads), h->chain_lds, h->s_grp[g], h->dv, in, (const int *)nullptr, plan, b0);
-            else if (h->solo_kernel) hipLaunchKernelGGL(k_solo<false>, dim3(1, nb), dim3(h->chain_threads), h->chain_lds, h->s_grp[g], h->dv, in, (const int *)nullptr, plan, b0);
-            else hipLaunchKernelGGL(k_chain<false>, dim3(1, nb), dim3(h->chain_threads), h->chain_lds, h->s_grp[g], h->dv, in, (const int *)nullptr, plan, b0);
+            launch_chain(h, h->s_grp[g], /*streaming*/ false, /*on_packet*/ false, nullptr, nullptr, in, nullptr, plan, b0, nb);
             if (!do_pass) continue;
             hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (h->prof_flush && h->prof_used + 2 <= h->prof_pool.size()) e0 = h->prof_pool[h->prof_used++], e1 = h->prof_pool[h->prof_used++];  // (created above)
-            if (interleave)
-                hipExtLaunchKernelGGL(k_flush_rb, dim3((unsigned)(cdiv(nb, 8) * 8 * nwg), 1), dim3(256), 0, h->s_grp[g], e0, e1, 0, h->dv, nT_hi, h->cur_set, maxp, h->buf_in, h->buf_in,
-                                      (const int *)nullptr, nwg, rev, b0, nb);
-            else
-                hipExtLaunchKernelGGL(k_flush_rb, dim3(nwg, nb), dim3(256), 0, h->s_grp[g], e0, e1, 0, h->dv, nT_hi, h->cur_set, maxp, h->buf_in, h->buf_in, (const int *)nullptr, 0, rev, b0, nb);
+            if (h->prof_flush && h->prof_used + 2 <= h->prof_pool.size()) (void)prof_take_pair(h, &e0, &e1);  // (reserved above: never grows here, between a fork and its join)
+            launch_pass(h->dv, h->s_grp[g], e0, e1, interleave, nT_hi, h->cur_set, maxp, h->buf_in, h->buf_in, nullptr, rev, b0, nb);
         }
         if (fold) {
             if (do_pass) h->flush_dir ^= 1;
@@ -1547,8 +1451,7 @@ static int refresh_bounds(ekf_batch *h, bool full = true) {
         }
     }
     if (!done) {
-        int rc_ = stream_stop(h);  // (a resident streaming launch leaves first: the stream would not drain before its idle time is over)
-        if (rc_) return rc_;
+        EKF_TRY(stream_stop(h));  // (a resident streaming launch leaves first: the stream would not drain before its idle time is over)
         HIP_TRY(stream_wait(h->s_chain));
     }
     int mx = 0;
@@ -1575,8 +1478,7 @@ extern "C" int ekf_batch_propagate_q(ekf_handle h, const double *v, const double
     HIP_TRY(hipSetDevice(h->device));
     double *rec;
     int k;
-    int rc = ring_reserve(h, 1, &rec, &k);
-    if (rc) return rc;
+    EKF_TRY(ring_reserve(h, 1, &rec, &k));
     for (int b = 0; b < h->dv.B; b++) {
         double *r = rec + (size_t)b * 8;
         r[0] = v[b], r[1] = w[b], r[2] = dt[b];
@@ -1617,8 +1519,7 @@ extern "C" int ekf_batch_update(ekf_handle h, const double *z, const double *R, 
         int cnt = n_z - j0 < half ? n_z - j0 : half;
         double *rec;
         int k;
-        int rc = ring_reserve(h, cnt, &rec, &k);
-        if (rc) return rc;
+        EKF_TRY(ring_reserve(h, cnt, &rec, &k));
         for (int jj = 0; jj < cnt; jj++) {
             int j = j0 + jj;
             for (int b = 0; b < B; b++) {
@@ -1633,8 +1534,7 @@ extern "C" int ekf_batch_update(ekf_handle h, const double *z, const double *R, 
         }
         consumes.assign(cnt, 1);
         bump_bound(h, cnt);
-        rc = launch_ops(h, h->ring_d, nullptr, k, consumes.data(), cnt);
-        if (rc) return rc;
+        EKF_TRY(launch_ops(h, h->ring_d, nullptr, k, consumes.data(), cnt));
     }
     if (decisions_out) return fetch_decisions(h, n_z, decisions_out);
     return EKF_OK;
@@ -1650,8 +1550,7 @@ extern "C" int ekf_batch_update_compass(ekf_handle h, const double *z, const dou
     HIP_TRY(hipSetDevice(h->device));
     double *rec;
     int k;
-    int rc = ring_reserve(h, 1, &rec, &k);
-    if (rc) return rc;
+    EKF_TRY(ring_reserve(h, 1, &rec, &k));
     for (int b = 0; b < h->dv.B; b++) {
         double *r = rec + (size_t)b * 8;
         r[0] = z[b], r[1] = R[b];
@@ -1672,8 +1571,7 @@ extern "C" int ekf_record_truth(ekf_handle h, const double *truth) {
     HIP_TRY(hipSetDevice(h->device));
     double *rec;
     int k;
-    int rc = ring_reserve(h, 1, &rec, &k);
-    if (rc) return rc;
+    EKF_TRY(ring_reserve(h, 1, &rec, &k));
     for (int b = 0; b < h->dv.B; b++) {
         double *r = rec + (size_t)b * 8;
         r[0] = truth[3 * b], r[1] = truth[3 * b + 1], r[2] = truth[3 * b + 2];
@@ -1707,10 +1605,63 @@ static int sticky_status(ekf_batch *h, bool include_capacity) {
     return EKF_OK;
 }
 
+// ---- bringing a handle to rest --------------------------------------------------------------------------------------------------
+// Every entry point that enqueues on the chain stream behind the launches, reads device memory or rewrites state comes through
+// quiesce() first (the immediate-mode operations themselves and the host mirror's readers do not).  It selects the device and has
+// the resident streaming launch leave; then, in this order:
+//   rule  != ST_NONE       the chain stream is drained and the host's bounds (h_int[], n_lm_hi) are refreshed; a sticky
+//                          EKF_ERR_TIMEOUT (the state is invalid) ends the call -- ST_INVALID_OR_FULL: a sticky EKF_ERR_CAPACITY too
+//   level == QUIET_SETTLED everything is folded into Bm[buf_in] by a terminal pass, both streams idle
+//
+//   entry point                                        level          rule                 what follows
+//   ekf_sync, ekf_flush_profile_read                   QUIET_STREAM   ST_NONE              wait for both streams (ekf_sync: any sticky status)
+//   ekf_get_decisions, ekf_stats_means_device,
+//   ekf_script_load, ekf_debug_stamps                  QUIET_STREAM   ST_NONE              own work on the chain stream, waited for
+//   ekf_reset_stats, ekf_timer_start, ekf_timer_stop   QUIET_STREAM   ST_NONE              own work on the chain stream, not waited for
+//   ekf_get_x                                          QUIET_STREAM   ST_INVALID           copy
+//   ekf_get_state                                      QUIET_STREAM   ST_INVALID           size only: returns; else settle(), export
+//   ekf_set_state                                      QUIET_SETTLED  ST_NONE              (the way out of a timed-out handle: no status ends it)
+//   ekf_broadcast_state                                QUIET_SETTLED  ST_NONE
+//   ekf_reserve                                        QUIET_SETTLED  ST_NONE              refreshes the bounds AFTER the settle; only EKF_ERR_TIMEOUT ends it
+//   ekf_remove_landmarks, ekf_transform_frame,
+//   ekf_anchor_at_robot (and the batch forms)          QUIET_SETTLED  ST_INVALID_OR_FULL   the state stays as it is under either status
+// (ekf_get_landmark_covs and the mirror's readers go through refresh_bounds alone; ekf_flush / ekf_close_window through close_set.)
+enum QuietLevel { QUIET_STREAM, QUIET_SETTLED };
+enum StatusRule { ST_NONE, ST_INVALID, ST_INVALID_OR_FULL };
+static int quiesce(ekf_batch *h, QuietLevel level, StatusRule rule) {
+    HIP_TRY(hipSetDevice(h->device));
+    EKF_TRY(stream_stop(h));
+    if (rule != ST_NONE) EKF_TRY(refresh_bounds(h));
+    if (rule == ST_INVALID_OR_FULL) EKF_TRY(sticky_status(h, true));
+    if (level == QUIET_SETTLED) EKF_TRY(settle(h));
+    return EKF_OK;
+}
+
+// The end of a state rewrite on the settled handle (ekf_set_state, removal, frame change), behind the caller's own kernels on the
+// chain stream.  rearm: clear the slot rows (FA / FB) of filters [b0, b0 + nb) and, in overlap mode, store the host's pass count
+// into dv.pass_flag (ekf_set_state has done both itself, in front of its import).  counts: the new landmark count of filter
+// b0 + k at counts[k * count_stride] for k_set_meta (counts, slots, host mirror), or null: the counts did not change.  Then: wait,
+// report a failed launch, flip_buf: the rewrite went into the other Bm buffer; the mirror is no chain launch's; refresh the bounds.
+static int finish_rewrite(ekf_batch *h, int b0, int nb, bool rearm, const int *counts, int count_stride, bool flip_buf) {
+    EkfDev &dv = h->dv;
+    hipStream_t s = h->s_chain;
+    if (rearm) {
+        HIP_TRY(hipMemsetAsync(dv.FA + (size_t)b0 * 2 * dv.f_stride, 0, sizeof(double) * (size_t)nb * 2 * dv.f_stride, s));
+        HIP_TRY(hipMemsetAsync(dv.FB + (size_t)b0 * 2 * dv.f_stride, 0, sizeof(double) * (size_t)nb * 2 * dv.f_stride, s));
+        if (h->overlap) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, s, dv.pass_flag, h->pass_seq);
+    }
+    if (counts)
+        for (int k = 0; k < nb; k++) hipLaunchKernelGGL(k_set_meta, dim3(1), dim3(64), 0, s, dv, b0 + k, counts[(size_t)k * count_stride]);
+    HIP_TRY(stream_wait(s));
+    EKF_TRY(check_launch());
+    if (flip_buf) h->buf_in ^= 1;
+    h->mirror_by_chain = false;
+    return refresh_bounds(h);
+}
+
 extern "C" int ekf_sync(ekf_handle h) {
     if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_NONE));
     HIP_TRY(stream_wait(h->s_chain));
     if (h->overlap) HIP_TRY(stream_wait(h->s_flush));
     // Every bounded wait that runs out stores EKF_ERR_TIMEOUT into the host-mapped mirror itself, at once (and nothing but
@@ -1735,8 +1686,7 @@ extern "C" int ekf_close_window(ekf_handle h) {
 extern "C" int ekf_batch_get_pose(ekf_handle h, double *pose_out) {
     if (!h || !pose_out) return set_error(EKF_ERR_BAD_ARG, "null argument");
     HIP_TRY(hipSetDevice(h->device));
-    int rc = refresh_bounds(h, false);
-    if (rc) return rc;
+    EKF_TRY(refresh_bounds(h, false));
     for (int b = 0; b < h->dv.B; b++)
         for (int i = 0; i < 3; i++) pose_out[3 * b + i] = h->mirror_h[b].pose[i];
     return EKF_OK;
@@ -1750,8 +1700,7 @@ extern "C" int ekf_get_pose(ekf_handle h, double pose_out[3]) {
 extern "C" int ekf_batch_num_landmarks(ekf_handle h, int *n_out) {
     if (!h || !n_out) return set_error(EKF_ERR_BAD_ARG, "null argument");
     HIP_TRY(hipSetDevice(h->device));
-    int rc = refresh_bounds(h, false);
-    if (rc) return rc;
+    EKF_TRY(refresh_bounds(h, false));
     for (int b = 0; b < h->dv.B; b++) n_out[b] = h->h_int[b];
     return EKF_OK;
 }
@@ -1784,10 +1733,7 @@ extern "C" int ekf_get_robot_cov(ekf_handle h, double P_RR_out[9]) {
 
 extern "C" int ekf_get_x(ekf_handle h, int index, double *x_out, int n_max) {
     if (!h || index < 0 || index >= h->dv.B || !x_out || n_max < 0) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
-    int rc = refresh_bounds(h);
-    if (rc) return rc;
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
     int n = 3 + 2 * h->h_int[index];
     int cnt = n < n_max ? n : n_max;
     HIP_TRY(hipMemcpy(x_out, h->dv.x + (size_t)index * h->dv.xs, sizeof(double) * cnt, hipMemcpyDeviceToHost));
@@ -1798,8 +1744,7 @@ static int fetch_decisions(ekf_batch *h, int n_z, ekf_decision *out) {
     // [batch][n_z]: the last entries of every filter's log.  Masked measurements leave no entry, so a
     // filter with fewer real entries gets zeroed records in front.
     int B = h->dv.B;
-    int rc = refresh_bounds(h, false);  // synchronises
-    if (rc) return rc;
+    EKF_TRY(refresh_bounds(h, false));  // synchronises
     for (int b = 0; b < B; b++) {
         long long cnt = h->mirror_h[b].log_count;
         long long have = cnt < n_z ? cnt : n_z;
@@ -1819,8 +1764,7 @@ static int fetch_decisions(ekf_batch *h, int n_z, ekf_decision *out) {
 
 extern "C" int ekf_get_decisions(ekf_handle h, int index, ekf_decision *out, int count) {
     if (!h || !out || index < 0 || index >= h->dv.B || count < 0) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_NONE));
     long long cnt;
     HIP_TRY(hipMemcpyAsync(&cnt, h->dv.log_count + index, sizeof cnt, hipMemcpyDeviceToHost, h->s_chain));
     HIP_TRY(stream_wait(h->s_chain));
@@ -1838,8 +1782,7 @@ extern "C" int ekf_get_stats(ekf_handle h, ekf_stats *out) {
     if (h->mirror_by_chain && h->stats_in_mirror && h->chain_seq > 0) {
         // the newest chain launch copies every filter's counters into the host-mapped mirror: no device-to-host copy
         // (a copy into pageable memory costs 40-100 us, a sizeable part of a short run)
-        int rc = refresh_bounds(h, false);
-        if (rc) return rc;
+        EKF_TRY(refresh_bounds(h, false));
         for (int b = 0; b < h->dv.B; b++) out[b] = h->mirror_h[b].stats;
         return EKF_OK;
     }
@@ -1850,8 +1793,7 @@ extern "C" int ekf_get_stats(ekf_handle h, ekf_stats *out) {
 
 extern "C" int ekf_stats_means_device(ekf_handle h, double *out_device) {
     if (!h || !out_device) return set_error(EKF_ERR_BAD_ARG, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_NONE));
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, out_device) != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged)) {
         (void)hipGetLastError();
@@ -1864,8 +1806,7 @@ extern "C" int ekf_stats_means_device(ekf_handle h, double *out_device) {
 
 extern "C" int ekf_reset_stats(ekf_handle h) {
     if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_NONE));
     HIP_TRY(hipMemsetAsync(h->dv.stats, 0, sizeof(ekf_stats) * h->dv.B, h->s_chain));
     h->stats_in_mirror = false;  // until the next chain launch writes the mirror
     return EKF_OK;
@@ -1874,26 +1815,18 @@ extern "C" int ekf_reset_stats(ekf_handle h) {
 // ---- dense state injection / extraction -----------------------------------------------------------
 extern "C" int ekf_get_state(ekf_handle h, int index, double *x_out, double *P_out, int ld) {
     if (!h || index < 0 || index >= h->dv.B) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
-    int rc = refresh_bounds(h);
-    if (rc) return rc;
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
     int n = 3 + 2 * h->h_int[index];
-    if (!x_out && !P_out) return n;
+    if (!x_out && !P_out) return n;  // (the size alone: nothing is folded)
     if (!x_out || !P_out || ld < n) return set_error(EKF_ERR_BAD_ARG, "bad output buffers");
-    rc = settle(h);
-    if (rc) return rc;
-    double *stage = nullptr;  // transient staging: dense n x n + x
-    HIP_TRY(hipMalloc((void **)&stage, ((size_t)n * n + n) * sizeof(double)));
-    double *xd = stage + (size_t)n * n;
-    hipLaunchKernelGGL(k_export, dim3(cdiv(n, 256), n), dim3(256), 0, h->s_chain, h->dv, index, h->buf_in, xd, stage, n, n);
-    hipError_t e = hipMemcpyAsync(x_out, xd, sizeof(double) * n, hipMemcpyDeviceToHost, h->s_chain);
-    if (e == hipSuccess)
-        e = hipMemcpy2DAsync(P_out, (size_t)ld * sizeof(double), stage, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n,
-                             hipMemcpyDeviceToHost, h->s_chain);
-    if (e == hipSuccess) e = stream_wait(h->s_chain);
-    hipFree(stage);
-    if (e != hipSuccess) return set_error(EKF_ERR_HIP, hipGetErrorString(e));
+    EKF_TRY(settle(h));
+    DevTmp<double> stage;  // transient staging: dense n x n + x
+    HIP_TRY(stage.alloc((size_t)n * n + n));
+    double *xd = stage.p + (size_t)n * n;
+    hipLaunchKernelGGL(k_export, dim3(cdiv(n, 256), n), dim3(256), 0, h->s_chain, h->dv, index, h->buf_in, xd, stage.p, n, n);
+    HIP_TRY(hipMemcpyAsync(x_out, xd, sizeof(double) * n, hipMemcpyDeviceToHost, h->s_chain));
+    HIP_TRY(hipMemcpy2DAsync(P_out, (size_t)ld * sizeof(double), stage.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost, h->s_chain));
+    HIP_TRY(stream_wait(h->s_chain));
     return n;
 }
 
@@ -1901,10 +1834,7 @@ extern "C" int ekf_set_state(ekf_handle h, int index, const double *x, const dou
     if (!h || index < 0 || index >= h->dv.B || !x || !P || n < 3 || ((n - 3) & 1) || ld < n) return set_error(EKF_ERR_BAD_ARG, "bad argument");
     int N = (n - 3) / 2;
     if (N > h->dv.Ncap) return set_error(EKF_ERR_CAPACITY, "state larger than capacity_landmarks");
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
-    int rc = settle(h);
-    if (rc) return rc;
+    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_NONE));
     EkfDev &dv = h->dv;
     hipStream_t s = h->s_chain;
     // Both streams are idle here.  A launch that gave up (EKF_ERR_TIMEOUT) leaves the segment counters ahead of the host's
@@ -1916,45 +1846,32 @@ extern "C" int ekf_set_state(ekf_handle h, int index, const double *x, const dou
     for (int q = 0; q < EKF_PLAN_MAX; q++) h->seg_count_base[q] = 0;
     h->open_set_gate = 0;
     if (h->overlap) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, s, dv.pass_flag, h->pass_seq);
-    double *stage = nullptr;
-    HIP_TRY(hipMalloc((void **)&stage, ((size_t)n * n + n) * sizeof(double)));
-    double *xd = stage + (size_t)n * n;
-    hipError_t e = hipMemcpyAsync(xd, x, sizeof(double) * n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        e = hipMemcpy2DAsync(stage, (size_t)n * sizeof(double), P, (size_t)ld * sizeof(double), (size_t)n * sizeof(double), n,
-                             hipMemcpyHostToDevice, s);
-    size_t b = index;
-    if (e == hipSuccess) e = hipMemsetAsync(dv.x + b * dv.xs, 0, sizeof(double) * dv.xs, s);
-    if (e == hipSuccess) e = hipMemsetAsync(dv.R + b * 3 * dv.xs, 0, sizeof(double) * 3 * dv.xs, s);
-    if (e == hipSuccess) e = hipMemsetAsync(dv.D + b * 3 * dv.dn, 0, sizeof(double) * 3 * dv.dn, s);
-    if (e == hipSuccess) e = hipMemsetAsync(dv.Bm[0] + b * dv.bm_stride, 0, sizeof(double) * dv.bm_stride, s);
-    if (e == hipSuccess && h->overlap) e = hipMemsetAsync(dv.Bm[1] + b * dv.bm_stride, 0, sizeof(double) * dv.bm_stride, s);
-    if (e == hipSuccess) e = hipMemsetAsync(dv.FA + b * 2 * dv.f_stride, 0, sizeof(double) * 2 * dv.f_stride, s);
-    if (e == hipSuccess) e = hipMemsetAsync(dv.FB + b * 2 * dv.f_stride, 0, sizeof(double) * 2 * dv.f_stride, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_import, dim3(cdiv(n, 256), n), dim3(256), 0, s, dv, index, h->buf_in, (const double *)xd, (const double *)stage, n, n);
-        hipLaunchKernelGGL(k_set_meta, dim3(1), dim3(64), 0, s, dv, index, N);
-        h->mirror_by_chain = false;
-        e = stream_wait(s);
+    DevTmp<double> stage;
+    HIP_TRY(stage.alloc((size_t)n * n + n));
+    double *xd = stage.p + (size_t)n * n;
+    HIP_TRY(hipMemcpyAsync(xd, x, sizeof(double) * n, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpy2DAsync(stage.p, (size_t)n * sizeof(double), P, (size_t)ld * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyHostToDevice, s));
+    for (const DevArray &a : device_arrays(h)) {
+        if (!(a.ops & AR_CLEAR)) continue;
+        HIP_TRY(hipMemsetAsync(a.at(index), 0, a.filter_bytes(), s));
+        if (a.slot == (void **)&dv.Bm[0] && h->overlap) HIP_TRY(hipMemsetAsync(dv.Bm[1] + (size_t)index * dv.bm_stride, 0, sizeof(double) * dv.bm_stride, s));
     }
-    hipFree(stage);
-    if (e != hipSuccess) return set_error(EKF_ERR_HIP, hipGetErrorString(e));
+    hipLaunchKernelGGL(k_import, dim3(cdiv(n, 256), n), dim3(256), 0, s, dv, index, h->buf_in, (const double *)xd, (const double *)stage.p, n, n);
     if (N > h->n_lm_hi) h->n_lm_hi = N;
-    return refresh_bounds(h);
+    return finish_rewrite(h, index, 1, /*rearm*/ false, &N, 1, /*flip_buf*/ false);
 }
 
 // Grow a handle's landmark capacity (the reference grows x and P with every New landmark, Update.cpp:158-177 /
 // kalmanfilter.cpp:78-84, and never fails).  A second set of device buffers of the larger capacity is built, every filter's state
 // moves over on the device (k_export into a dense staging matrix, k_import from it: the tile numbering depends on the capacity),
 // the counters, the decision log and a loaded script move with it, and the handle keeps its address.
+static int reserve_move_state(ekf_batch *h, ekf_batch *nh, const std::vector<int> &n_lm);
+
 extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     if (!h || capacity_landmarks < 1 || capacity_landmarks > EKF_MAX_CAPACITY) return set_error(EKF_ERR_BAD_ARG, "bad handle / capacity (EKF_MAX_CAPACITY)");
     if (capacity_landmarks <= h->dv.Ncap) return EKF_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
-    int rc = settle(h);  // every deferred slot folded, both streams idle
-    if (rc) return rc;
-    rc = refresh_bounds(h);  // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT (invalid state) ends it here
+    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_NONE));  // every deferred slot folded, both streams idle
+    int rc = refresh_bounds(h);  // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT (invalid state) ends it here
     if (rc == EKF_ERR_TIMEOUT) return rc;
     const int B = h->dv.B;
     std::vector<int> n_lm(h->h_int.begin(), h->h_int.begin() + B);
@@ -1971,7 +1888,8 @@ extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     ekf_batch *nh = new ekf_batch();
     nh->device = h->device;
     rc = create_impl(nh, B, capacity_landmarks, h->device, &h->params_requested, prop);
-    if (rc != EKF_OK) {
+    if (rc == EKF_OK) rc = reserve_move_state(h, nh, n_lm);
+    if (rc != EKF_OK) {  // the handle stays as it was, with its claim
         std::string keep = g_last_error;
         ekf_destroy(nh);
         (void)hipGetLastError();
@@ -1980,40 +1898,6 @@ extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
         g_cus_claimed[h->device] += had_claimed, g_cus_solo[h->device] += had_solo;
         h->claimed_cus = had_claimed, h->solo_cus = had_solo;
         return rc;
-    }
-    hipError_t e = hipSuccess;
-    int n_max = 3;
-    for (int b = 0; b < B; b++) n_max = 3 + 2 * n_lm[b] > n_max ? 3 + 2 * n_lm[b] : n_max;
-    double *stage = nullptr;
-    e = hipMalloc((void **)&stage, ((size_t)n_max * n_max + n_max) * sizeof(double));
-    for (int b = 0; b < B && e == hipSuccess; b++) {
-        const int n = 3 + 2 * n_lm[b];
-        double *xd = stage + (size_t)n * n;
-        hipLaunchKernelGGL(k_export, dim3(cdiv(n, 256), n), dim3(256), 0, h->s_chain, h->dv, b, h->buf_in, xd, stage, n, n);
-        e = stream_wait(h->s_chain);
-        if (e != hipSuccess) break;
-        hipLaunchKernelGGL(k_import, dim3(cdiv(n, 256), n), dim3(256), 0, nh->s_chain, nh->dv, b, nh->buf_in, (const double *)xd, (const double *)stage, n, n);
-        e = stream_wait(nh->s_chain);
-    }
-    if (stage) hipFree(stage);
-    // counters, decision log (entries name state indices, which do not depend on the capacity), then the bookkeeping kernel
-    // (landmark counts, host mirror: pose, count, log position; it also clears the sticky capacity status -- there is room now)
-    const bool same_log = nh->dv.logcap == h->dv.logcap;
-    if (e == hipSuccess) e = hipMemcpyAsync(nh->dv.stats, h->dv.stats, sizeof(ekf_stats) * B, hipMemcpyDeviceToDevice, nh->s_chain);
-    if (e == hipSuccess && same_log) e = hipMemcpyAsync(nh->dv.log, h->dv.log, sizeof(ekf_decision) * (size_t)B * h->dv.logcap, hipMemcpyDeviceToDevice, nh->s_chain);
-    if (e == hipSuccess && same_log) e = hipMemcpyAsync(nh->dv.log_count, h->dv.log_count, sizeof(long long) * B, hipMemcpyDeviceToDevice, nh->s_chain);
-    if (e == hipSuccess) {
-        for (int b = 0; b < B; b++) hipLaunchKernelGGL(k_set_meta, dim3(1), dim3(64), 0, nh->s_chain, nh->dv, b, n_lm[b]);
-        e = stream_wait(nh->s_chain);
-    }
-    if (e != hipSuccess || check_launch() != EKF_OK) {
-        std::string keep = e != hipSuccess ? std::string(hipGetErrorString(e)) : g_last_error;
-        ekf_destroy(nh);
-        (void)hipGetLastError();
-        std::lock_guard<std::mutex> lk(g_res_mu);
-        g_cus_claimed[h->device] += had_claimed, g_cus_solo[h->device] += had_solo;
-        h->claimed_cus = had_claimed, h->solo_cus = had_solo;
-        return set_error(EKF_ERR_HIP, keep.c_str());
     }
     for (int b = 0; b < B; b++) {  // the host mirror's newest decisions and counters (ekf_get_stats / the compat shim read them there)
         memcpy(nh->mirror_h[b].last, h->mirror_h[b].last, sizeof nh->mirror_h[b].last);
@@ -2049,29 +1933,53 @@ extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     return refresh_bounds(h);
 }
 
+// ekf_reserve: every filter's state from h's settled buffers into nh's, through a dense staging matrix.
+static int reserve_move_state(ekf_batch *h, ekf_batch *nh, const std::vector<int> &n_lm) {
+    const int B = h->dv.B;
+    int n_max = 3;
+    for (int b = 0; b < B; b++) n_max = 3 + 2 * n_lm[b] > n_max ? 3 + 2 * n_lm[b] : n_max;
+    {
+        DevTmp<double> stage;
+        HIP_TRY(stage.alloc((size_t)n_max * n_max + n_max));
+        for (int b = 0; b < B; b++) {
+            const int n = 3 + 2 * n_lm[b];
+            double *xd = stage.p + (size_t)n * n;
+            hipLaunchKernelGGL(k_export, dim3(cdiv(n, 256), n), dim3(256), 0, h->s_chain, h->dv, b, h->buf_in, xd, stage.p, n, n);
+            HIP_TRY(stream_wait(h->s_chain));
+            hipLaunchKernelGGL(k_import, dim3(cdiv(n, 256), n), dim3(256), 0, nh->s_chain, nh->dv, b, nh->buf_in, (const double *)xd, (const double *)stage.p, n, n);
+            HIP_TRY(stream_wait(nh->s_chain));
+        }
+    }
+    // counters, decision log (entries name state indices, which do not depend on the capacity), then the bookkeeping kernel
+    // (landmark counts, host mirror: pose, count, log position; it also clears the sticky capacity status -- there is room now)
+    const bool same_log = nh->dv.logcap == h->dv.logcap;
+    HIP_TRY(hipMemcpyAsync(nh->dv.stats, h->dv.stats, sizeof(ekf_stats) * B, hipMemcpyDeviceToDevice, nh->s_chain));
+    if (same_log) {
+        HIP_TRY(hipMemcpyAsync(nh->dv.log, h->dv.log, sizeof(ekf_decision) * (size_t)B * h->dv.logcap, hipMemcpyDeviceToDevice, nh->s_chain));
+        HIP_TRY(hipMemcpyAsync(nh->dv.log_count, h->dv.log_count, sizeof(long long) * B, hipMemcpyDeviceToDevice, nh->s_chain));
+    }
+    for (int b = 0; b < B; b++) hipLaunchKernelGGL(k_set_meta, dim3(1), dim3(64), 0, nh->s_chain, nh->dv, b, n_lm[b]);
+    HIP_TRY(stream_wait(nh->s_chain));
+    return check_launch();
+}
+
 extern "C" int ekf_broadcast_state(ekf_handle h) {
     if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
-    int rc = settle(h);
-    if (rc) return rc;
+    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_NONE));
     EkfDev &dv = h->dv;
     hipStream_t s = h->s_chain;
-    for (int b = 1; b < dv.B; b++) {
-        HIP_TRY(hipMemcpyAsync(dv.x + (size_t)b * dv.xs, dv.x, sizeof(double) * dv.xs, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(dv.R + (size_t)b * 3 * dv.xs, dv.R, sizeof(double) * 3 * dv.xs, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(dv.D + (size_t)b * 3 * dv.dn, dv.D, sizeof(double) * 3 * dv.dn, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(dv.Bm[h->buf_in] + (size_t)b * dv.bm_stride, dv.Bm[h->buf_in], sizeof(double) * dv.bm_stride, hipMemcpyDeviceToDevice, s));
-        if (h->overlap) HIP_TRY(hipMemsetAsync(dv.Bm[h->buf_in ^ 1] + (size_t)b * dv.bm_stride, 0, sizeof(double) * dv.bm_stride, s));  // no stale tiles beyond the copied map
-        HIP_TRY(hipMemcpyAsync(dv.FA + (size_t)b * 2 * dv.f_stride, dv.FA, sizeof(double) * 2 * dv.f_stride, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(dv.FB + (size_t)b * 2 * dv.f_stride, dv.FB, sizeof(double) * 2 * dv.f_stride, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(dv.slot_active + (size_t)b * 2 * dv.maxp, dv.slot_active, sizeof(int) * 2 * dv.maxp, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(dv.n_lm + b, dv.n_lm, sizeof(int), hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(dv.n_lm_sweep + b, dv.n_lm_sweep, sizeof(int), hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(dv.n_lm_flush + 2 * (size_t)b, dv.n_lm_flush, 2 * sizeof(int), hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(dv.status + b, dv.status, sizeof(int), hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(dv.log_count + b, dv.log_count, sizeof(long long), hipMemcpyDeviceToDevice, s));
-    }
+    const std::vector<DevArray> arrays = device_arrays(h);
+    for (int b = 1; b < dv.B; b++)
+        for (const DevArray &a : arrays) {
+            if (!(a.ops & AR_COPY)) continue;
+            if (a.slot != (void **)&dv.Bm[0]) {
+                HIP_TRY(hipMemcpyAsync(a.at(b), a.at(0), a.filter_bytes(), hipMemcpyDeviceToDevice, s));
+                continue;
+            }
+            // (the covariance tiles: the settled buffer, whichever of the two it is)
+            HIP_TRY(hipMemcpyAsync(dv.Bm[h->buf_in] + (size_t)b * dv.bm_stride, dv.Bm[h->buf_in], sizeof(double) * dv.bm_stride, hipMemcpyDeviceToDevice, s));
+            if (h->overlap) HIP_TRY(hipMemsetAsync(dv.Bm[h->buf_in ^ 1] + (size_t)b * dv.bm_stride, 0, sizeof(double) * dv.bm_stride, s));  // no stale tiles beyond the copied map
+        }
     HIP_TRY(stream_wait(s));
     for (int b = 1; b < dv.B; b++) hipLaunchKernelGGL(k_set_meta, dim3(1), dim3(64), 0, s, dv, b, h->mirror_h[0].n_lm);  // also refreshes the host mirror
     h->mirror_by_chain = false;
@@ -2084,14 +1992,9 @@ extern "C" int ekf_broadcast_state(ekf_handle h) {
 // (k_rm_finish); x, R, D compacted by k_rm_vec.  Every buffer ends as ekf_set_state of the reduced state would leave it; the buffer
 // addresses do not change (captured graphs and streaming launches hold EkfDev by value).
 static int remove_impl(ekf_batch *h, const unsigned char *keep, int ld_keep, int index, int *n_out) {
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
-    int rc = refresh_bounds(h);  // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT ends it here
-    if (rc) return rc;
-    rc = sticky_status(h, true);  // ... and a sticky EKF_ERR_CAPACITY: the state stays as it is
-    if (rc) return rc;
-    rc = settle(h);  // every deferred slot folded, both streams idle
-    if (rc) return rc;
+    // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
+    // every deferred slot folded, both streams idle
+    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
     EkfDev &dv = h->dv;
     const int B = dv.B, mstride = dv.Ncap > 0 ? dv.Ncap : 1;
     std::vector<int> rm((size_t)B * (2 + mstride), 0);
@@ -2113,43 +2016,26 @@ static int remove_impl(ekf_batch *h, const unsigned char *keep, int ld_keep, int
     }
     if (!any) return index < 0 ? EKF_OK : rm[2 * index + 1];
     hipStream_t s = h->s_chain;
-    int *rm_d = nullptr;
-    double *scratch = nullptr;
+    DevTmp<int> rm_d;
+    DevTmp<double> scratch;
     const size_t scratch_stride = (size_t)nTn * (nTn + 1) / 2 * 4096;
-    hipError_t e = hipMalloc((void **)&rm_d, rm.size() * sizeof(int));
-    if (e == hipSuccess && !h->overlap && scratch_stride) e = hipMalloc((void **)&scratch, (size_t)B * scratch_stride * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(rm_d, rm.data(), rm.size() * sizeof(int), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && nTo > 0) {
+    HIP_TRY(rm_d.alloc(rm.size()));
+    if (!h->overlap && scratch_stride) HIP_TRY(scratch.alloc((size_t)B * scratch_stride));
+    HIP_TRY(hipMemcpyAsync(rm_d.p, rm.data(), rm.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    if (nTo > 0) {
         const dim3 grid((unsigned)(nTo * (nTo + 1) / 2), (unsigned)B);
         if (h->overlap) {
-            hipLaunchKernelGGL(k_rm_gather, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d, mstride, nTo, dv.Bm[h->buf_in ^ 1], dv.T, dv.bm_stride, 0);
-            hipLaunchKernelGGL(k_rm_finish, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d, nTo, (const double *)nullptr, 0, (size_t)0);
+            hipLaunchKernelGGL(k_rm_gather, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, mstride, nTo, dv.Bm[h->buf_in ^ 1], dv.T, dv.bm_stride, 0);
+            hipLaunchKernelGGL(k_rm_finish, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, nTo, (const double *)nullptr, 0, (size_t)0);
         } else {
-            if (scratch)
-                hipLaunchKernelGGL(k_rm_gather, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d, mstride, nTo, scratch, nTn, scratch_stride, 1);
-            hipLaunchKernelGGL(k_rm_finish, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d, nTo, (const double *)scratch, nTn, scratch_stride);
+            if (scratch.p)
+                hipLaunchKernelGGL(k_rm_gather, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, mstride, nTo, scratch.p, nTn, scratch_stride, 1);
+            hipLaunchKernelGGL(k_rm_finish, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, nTo, (const double *)scratch.p, nTn, scratch_stride);
         }
     }
-    if (e == hipSuccess) {
-        // D is read by the gather (landmarks' own blocks): compacted behind it
-        hipLaunchKernelGGL(k_rm_vec, dim3(7, B), dim3(1024), 0, s, dv, (const int *)rm_d, mstride);
-        e = hipMemsetAsync(dv.FA, 0, sizeof(double) * (size_t)B * 2 * dv.f_stride, s);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(dv.FB, 0, sizeof(double) * (size_t)B * 2 * dv.f_stride, s);
-    if (e == hipSuccess) {
-        if (h->overlap) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, s, dv.pass_flag, h->pass_seq);
-        for (int b = 0; b < B; b++) hipLaunchKernelGGL(k_set_meta, dim3(1), dim3(64), 0, s, dv, b, rm[2 * b + 1]);  // counts, slots, host mirror
-        e = stream_wait(s);
-    }
-    if (rm_d) hipFree(rm_d);
-    if (scratch) hipFree(scratch);
-    if (e != hipSuccess) return set_error(EKF_ERR_HIP, hipGetErrorString(e));
-    rc = check_launch();
-    if (rc) return rc;
-    if (h->overlap && nTo > 0) h->buf_in ^= 1;  // the gather's output
-    h->mirror_by_chain = false;
-    rc = refresh_bounds(h);
-    if (rc) return rc;
+    // D is read by the gather (landmarks' own blocks): compacted behind it
+    hipLaunchKernelGGL(k_rm_vec, dim3(7, B), dim3(1024), 0, s, dv, (const int *)rm_d.p, mstride);
+    EKF_TRY(finish_rewrite(h, 0, B, /*rearm*/ true, &rm[1], 2, /*flip_buf: the gather's output*/ h->overlap && nTo > 0));
     return index < 0 ? EKF_OK : rm[2 * index + 1];
 }
 
@@ -2170,14 +2056,9 @@ extern "C" int ekf_batch_remove_landmarks(ekf_handle h, const unsigned char *kee
 // one-filter call carries its frame in the kernel arguments); the anchor's per-row operands use slot set 0 of FA / FB, which are
 // cleared afterwards as a removal clears them.
 static int reframe_impl(ekf_batch *h, int index, const double *frames) {
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
-    int rc = refresh_bounds(h);  // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT ends it here
-    if (rc) return rc;
-    rc = sticky_status(h, true);  // ... and a sticky EKF_ERR_CAPACITY: the state stays as it is
-    if (rc) return rc;
-    rc = settle(h);  // every deferred slot folded, both streams idle
-    if (rc) return rc;
+    // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
+    // every deferred slot folded, both streams idle
+    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
     EkfDev &dv = h->dv;
     const int b_off = index < 0 ? 0 : index, nb = index < 0 ? dv.B : 1;
     int nT = 0;
@@ -2186,8 +2067,7 @@ static int reframe_impl(ekf_batch *h, int index, const double *frames) {
         nT = t > nT ? t : nT;
     }
     hipStream_t s = h->s_chain;
-    double *fr_d = nullptr;
-    hipError_t e = hipSuccess;
+    DevTmp<double> fr_d;
     ReframeFrame one = {{0.0, 0.0, 1.0, 0.0, 0.0, 0.0}};
     if (frames) {
         std::vector<double> fr((size_t)nb * 6, 0.0);
@@ -2198,37 +2078,21 @@ static int reframe_impl(ekf_batch *h, int index, const double *frames) {
         if (nb == 1) {
             for (int k = 0; k < 6; k++) one.v[k] = fr[k];
         } else {
-            e = hipMalloc((void **)&fr_d, fr.size() * sizeof(double));
-            if (e == hipSuccess) e = hipMemcpy(fr_d, fr.data(), fr.size() * sizeof(double), hipMemcpyHostToDevice);  // (fr leaves scope: synchronous)
+            HIP_TRY(fr_d.alloc(fr.size()));
+            HIP_TRY(hipMemcpy(fr_d.p, fr.data(), fr.size() * sizeof(double), hipMemcpyHostToDevice));  // (fr leaves scope: synchronous)
         }
     }
-    if (e == hipSuccess) {
-        const double *frc = fr_d;
-        if (nT > 0) {
-            const dim3 gv((unsigned)cdiv(32 * nT, 256), (unsigned)nb), gt((unsigned)(nT * (nT + 1) / 2), (unsigned)nb);
-            if (frames) {
-                hipLaunchKernelGGL(k_reframe_vec<false>, gv, dim3(256), 0, s, dv, one, frc, b_off);
-                hipLaunchKernelGGL(k_reframe_tiles<false>, gt, dim3(256), 0, s, dv, h->buf_in, one, frc, b_off, nT);
-            } else {
-                hipLaunchKernelGGL(k_reframe_vec<true>, gv, dim3(256), 0, s, dv, one, frc, b_off);
-                hipLaunchKernelGGL(k_reframe_tiles<true>, gt, dim3(256), 0, s, dv, h->buf_in, one, frc, b_off, nT);
-            }
-        }
-        if (frames) hipLaunchKernelGGL(k_reframe_finish<false>, dim3(nb), dim3(64), 0, s, dv, one, frc, b_off);
-        else hipLaunchKernelGGL(k_reframe_finish<true>, dim3(nb), dim3(64), 0, s, dv, one, frc, b_off);
-        e = hipMemsetAsync(dv.FA + (size_t)b_off * 2 * dv.f_stride, 0, sizeof(double) * (size_t)nb * 2 * dv.f_stride, s);
+    const double *frc = fr_d.p;
+    const auto k_vec = frames ? k_reframe_vec<false> : k_reframe_vec<true>;  // <ANCHOR>
+    const auto k_tiles = frames ? k_reframe_tiles<false> : k_reframe_tiles<true>;
+    const auto k_finish = frames ? k_reframe_finish<false> : k_reframe_finish<true>;
+    if (nT > 0) {
+        const dim3 gv((unsigned)cdiv(32 * nT, 256), (unsigned)nb), gt((unsigned)(nT * (nT + 1) / 2), (unsigned)nb);
+        hipLaunchKernelGGL(k_vec, gv, dim3(256), 0, s, dv, one, frc, b_off);
+        hipLaunchKernelGGL(k_tiles, gt, dim3(256), 0, s, dv, h->buf_in, one, frc, b_off, nT);
     }
-    if (e == hipSuccess) e = hipMemsetAsync(dv.FB + (size_t)b_off * 2 * dv.f_stride, 0, sizeof(double) * (size_t)nb * 2 * dv.f_stride, s);
-    if (e == hipSuccess) {
-        if (h->overlap) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, s, dv.pass_flag, h->pass_seq);
-        e = stream_wait(s);
-    }
-    if (fr_d) hipFree(fr_d);
-    if (e != hipSuccess) return set_error(EKF_ERR_HIP, hipGetErrorString(e));
-    rc = check_launch();
-    if (rc) return rc;
-    h->mirror_by_chain = false;
-    return refresh_bounds(h);
+    hipLaunchKernelGGL(k_finish, dim3(nb), dim3(64), 0, s, dv, one, frc, b_off);
+    return finish_rewrite(h, b_off, nb, /*rearm*/ true, nullptr, 0, /*flip_buf*/ false);
 }
 
 static bool finite3(const double *f) { return __builtin_isfinite(f[0]) && __builtin_isfinite(f[1]) && __builtin_isfinite(f[2]); }
@@ -2258,8 +2122,7 @@ extern "C" int ekf_batch_anchor_at_robot(ekf_handle h) {
 extern "C" int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max) {
     if (!h || index < 0 || index >= h->dv.B || n_max < 0 || (!cov_out && n_max > 0)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
-    int rc = refresh_bounds(h);  // the chain stream idle (a resident streaming launch leaves first); no pass, the flush stream untouched
-    if (rc) return rc;
+    EKF_TRY(refresh_bounds(h));  // the chain stream idle (a resident streaming launch leaves first); no pass, the flush stream untouched
     const int N = h->h_int[index];
     const int cnt = N < n_max ? N : n_max;
     if (cnt == 0) return N;
@@ -2278,8 +2141,7 @@ static inline int ops_per_step(const ekf_batch *h) { return 1 + h->script_M + (h
 extern "C" int ekf_script_load(ekf_handle h, int steps, int M, const double *ctrl, const double *z, const double *R,
                                const unsigned char *valid, const double *truth) {
     if (!h || steps < 1 || M < 0 || !ctrl || (M > 0 && (!z || !R))) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_NONE));
     HIP_TRY(stream_wait(h->s_chain));
     for (auto &g : h->graphs) hipGraphExecDestroy(g.exec);
     h->graphs.clear();
@@ -2357,8 +2219,7 @@ extern "C" int ekf_script_run(ekf_handle h, int first_step, int n_steps, int use
         int S = graph_block_steps(h);
         if (end - s >= S) {
             // a graph starts from the settled state (its predecessor in the stream has fully finished)
-            int rc = close_set(h);  // (a resident streaming launch leaves here)
-            if (rc) return rc;
+            EKF_TRY(close_set(h));  // (a resident streaming launch leaves here)
             GraphEntry *ge = nullptr;
             for (auto &g : h->graphs)
                 if (g.steps == S && g.M == h->script_M && g.has_truth == h->script_has_truth) ge = &g;
@@ -2407,8 +2268,7 @@ extern "C" int ekf_script_run(ekf_handle h, int first_step, int n_steps, int use
     }
     if (s < end) {
         bump_bound(h, (end - s) * h->script_M);
-        int rc = enqueue_script_steps(h, nullptr, s * ops, end - s);
-        if (rc) return rc;
+        EKF_TRY(enqueue_script_steps(h, nullptr, s * ops, end - s));
     }
     return check_launch();
 }
@@ -2437,8 +2297,7 @@ extern "C" int ekf_debug_stream_ring(ekf_handle h) {
 
 extern "C" int ekf_debug_stamps(ekf_handle h, long long *out16, int reset) {
     if (!h || !out16) return EKF_ERR_BAD_ARG;
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_NONE));
     HIP_TRY(stream_wait(h->s_chain));
     HIP_TRY(hipMemcpy(out16, h->dv.dbg, 32 * sizeof(long long), hipMemcpyDeviceToHost));
     if (reset) HIP_TRY(hipMemset(h->dv.dbg, 0, 32 * sizeof(long long)));
@@ -2450,8 +2309,7 @@ extern "C" int ekf_debug_stamps(ekf_handle h, long long *out16, int reset) {
 // exchanges of the handle, row 64 = the moment workgroup 0's poll saw all of them.  out: [65][2048].
 extern "C" int ekf_debug_exchange_trace(ekf_handle h, long long *out) {
     if (!h || !out) return EKF_ERR_BAD_ARG;
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_NONE));
     HIP_TRY(stream_wait(h->s_chain));
     HIP_TRY(hipMemcpy(out, h->dv.dbg + 32, (size_t)65 * 2048 * sizeof(long long), hipMemcpyDeviceToHost));
     return EKF_OK;
@@ -2461,16 +2319,14 @@ extern "C" int ekf_debug_exchange_trace(ekf_handle h, long long *out) {
 // ---- timing ---------------------------------------------------------------------------------------
 extern "C" int ekf_timer_start(ekf_handle h) {
     if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_NONE));
     HIP_TRY(hipEventRecord(h->t0, h->s_chain));
     return EKF_OK;
 }
 
 extern "C" int ekf_timer_stop(ekf_handle h, double *ms_out) {
     if (!h || !ms_out) return set_error(EKF_ERR_BAD_ARG, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_NONE));
     if (h->overlap && h->prev_pending > 0) HIP_TRY(hipStreamWaitEvent(h->s_chain, h->pass_done[h->ev_idx], 0));  // the pass in flight counts
     HIP_TRY(hipEventRecord(h->t1, h->s_chain));
     HIP_TRY(event_wait(h->t1));
@@ -2494,8 +2350,7 @@ extern "C" int ekf_fused_pass(ekf_handle h) { return h && h->solo_fuse ? 1 : 0; 
 
 extern "C" int ekf_flush_profile_read(ekf_handle h, long long *launches_out, double *total_ms_out) {
     if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
-    HIP_TRY(hipSetDevice(h->device));
-    { int rc_ = stream_stop(h); if (rc_) return rc_; }  // (a resident streaming launch leaves first)
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_NONE));
     HIP_TRY(stream_wait(h->s_chain));
     if (h->overlap) HIP_TRY(stream_wait(h->s_flush));
     for (size_t i = 0; i + 1 < h->prof_used; i += 2) {

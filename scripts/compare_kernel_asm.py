@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Is the device code of two builds the same?  Compares two `make -C 2d-ekf-slam_amd/csrc asm` outputs (lib/asm of each tree):
+
+  * ekf_kernels.s, split per kernel symbol: the same set of kernels, and every kernel's text and kernel descriptor identical -- ignoring
+    .file / .ident lines, the order of the kernels in the file and the function numbers in local labels and loop comments
+    (BB<n>_<k>, .Lfunc_end<n>) and inline-assembly labels, which follow the order of template instantiation and may move with host code;
+  * resource_usage.txt, per kernel name: registers, spills, scratch, LDS and occupancy.
+
+usage: compare_kernel_asm.py PARENT/lib/asm PR/lib/asm      (exit status 0: identical)
+A change to the host side of ekf_api.hip must leave all of it unchanged."""
+import os
+import re
+import sys
+
+
+def normalise(line):
+    line = re.sub(r"BB\d+_", "BB_", line)  # (labels .LBB<n>_<k> and the loop comments that name them)
+    line = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", line)
+    return line.rstrip()
+
+
+def renumber(lines):
+    """Labels of inline assembly (L<name>_<unique id>, clang's %=) count inline-asm instances over the whole file: number them per kernel,
+    in order of first appearance."""
+    seen = {}
+
+    def sub(m):
+        return "%s_#%d" % (m.group(1), seen.setdefault(m.group(2), len(seen)))
+
+    return [re.sub(r"(?<![.\w])(L[A-Za-z]\w*?)_(\d+)\b", sub, line) for line in lines]
+
+
+def kernels(path):
+    """symbol -> (text lines, descriptor lines)"""
+    text, desc, cur, kind = {}, {}, None, None
+    for line in open(path):
+        if re.match(r"\s*\.(file|ident)\b", line):
+            continue
+        m = re.match(r"\s*\.type\s+(\S+),@function", line)
+        if m:
+            cur, kind = m.group(1), text
+            text[cur] = []
+        m = re.match(r"\s*\.amdhsa_kernel\s+(\S+)", line)
+        if m:
+            cur, kind = m.group(1), desc
+            desc[cur] = []
+        if cur is not None:
+            kind[cur].append(normalise(line))
+            if (kind is text and re.match(r"\s*\.size\s+%s," % re.escape(cur), line)) or (kind is desc and ".end_amdhsa_kernel" in line):
+                cur = None
+    return {k: renumber(v) for k, v in text.items()}, desc
+
+
+def resources(path):
+    """kernel name -> {field: value}"""
+    out, cur = {}, None
+    for line in open(path):
+        m = re.search(r"remark:\s+(.*?)\s*\[-Rpass-analysis=kernel-resource-usage\]", line)
+        if not m:
+            continue
+        body = m.group(1)
+        if body.startswith("Function Name:"):
+            cur = body.split(":", 1)[1].strip()
+            out[cur] = {}
+        elif cur and ":" in body:
+            k, v = body.rsplit(":", 1)
+            out[cur][k.strip()] = v.strip()
+    return out
+
+
+def main():
+    if len(sys.argv) != 3:
+        print(__doc__)
+        return 2
+    a, b = sys.argv[1], sys.argv[2]
+    bad = 0
+    ta, da = kernels(os.path.join(a, "ekf_kernels.s"))
+    tb, db = kernels(os.path.join(b, "ekf_kernels.s"))
+    for what, x, y in (("kernel text", ta, tb), ("kernel descriptor", da, db)):
+        if sorted(x) != sorted(y):
+            print("%s: the sets of symbols differ: only in A %s, only in B %s" % (what, sorted(set(x) - set(y)), sorted(set(y) - set(x))))
+            bad += 1
+        same = [k for k in x if k in y and x[k] == y[k]]
+        for k in sorted(set(x) & set(y)):
+            if x[k] != y[k]:
+                print("%s DIFFERS: %s (%d against %d lines)" % (what, k, len(x[k]), len(y[k])))
+                bad += 1
+        print("%s: %d symbols in A, %d in B, %d identical (%d lines)" % (what, len(x), len(y), len(same), sum(len(x[k]) for k in same)))
+    ra, rb = resources(os.path.join(a, "resource_usage.txt")), resources(os.path.join(b, "resource_usage.txt"))
+    if sorted(ra) != sorted(rb):
+        print("resource usage: the sets of kernels differ")
+        bad += 1
+    for k in sorted(set(ra) & set(rb)):
+        if ra[k] != rb[k]:
+            print("resource usage DIFFERS: %s: %s" % (k, {f: (ra[k].get(f), rb[k].get(f)) for f in set(ra[k]) | set(rb[k]) if ra[k].get(f) != rb[k].get(f)}))
+            bad += 1
+    print("resource usage: %d kernels in A, %d in B, %d identical" % (len(ra), len(rb), sum(1 for k in ra if rb.get(k) == ra[k])))
+    print("device code identical" if not bad else "device code DIFFERS (%d findings)" % bad)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -74,6 +74,24 @@ def test_hbm_index_maps_are_bijections(tmp_path):
     assert out.returncode == 0 and "layout ok" in out.stdout, out.stdout + out.stderr
 
 
+def test_chain_geometry_matches_the_recorded_table(tmp_path):
+    """plan_geometry (csrc/ekf_geometry.h) decides workgroups, threads, LDS, kernel and window of every handle.  The table was dumped
+    from create_impl's own text before the function was cut out of it; every field of every row must agree, and a doctored row must
+    make the check fail."""
+    exe = str(tmp_path / "geometry_check")
+    table = os.path.join(ROOT, "tests", "golden", "chain_geometry.csv")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "cpp", "geometry_check.cpp")])
+    out = subprocess.run([exe, table], capture_output=True, text=True)
+    assert out.returncode == 0 and "geometry ok" in out.stdout, out.stdout + out.stderr
+    rows = open(table).read().splitlines()
+    at = next(i for i, r in enumerate(rows) if r.startswith("1,4096,32,-1,163840,-99,-99,-99,-99,-99,-99,-99,0,1,64,"))  # DESIGN.md 4.2: 64 workgroups
+    rows[at] = rows[at].replace(",0,1,64,", ",0,1,63,", 1)
+    doctored = tmp_path / "doctored.csv"
+    doctored.write_text("\n".join(rows) + "\n")
+    out = subprocess.run([exe, str(doctored)], capture_output=True, text=True)
+    assert out.returncode == 1 and "chain_wgs = 64, want 63" in out.stdout, out.stdout + out.stderr
+
+
 def test_generated_assembly_passes_the_exec_mask_lint(built):
     """The build's guard against the live-range-split miscompile: no run of register copies directly
     in front of an exec-widening s_or_b64 in any kernel."""
