@@ -1,0 +1,260 @@
+// ekf_filter_math.h -- the part of the reference's filter arithmetic that k_chain and k_solo share, once: the robot block of Propagate
+// (odometry/Propagate.cpp:15-75), the NEES sample, the association sweep (odometry/Update.cpp:98-148: sweep_const, sweep_one, sweep_single,
+// cand_better), the header of the Old branch and the robot rows of its gain (Update.cpp:181-189: old_header, old_robot_row), sym_u and the
+// per-landmark state LmState.  The gate, the New branch, the compass update and the Old landmark update are not here: each kernel still
+// writes them out (ekf_solo.hip says why).
+//
+// Pure __device__ __forceinline__ functions over values, small structs and pointers to doubles.  Nothing here touches LDS or global memory on
+// its own, waits at a barrier or knows who calls it: k_chain (ekf_kernels.hip: a control lane and worker waves, headers handed over through
+// LDS) and k_solo (ekf_solo.hip: every thread carries the robot block) decide where the inputs come from and where the results go, and
+// both round exactly as these expressions say.  A pointer argument may point into LDS (the functions are inlined into their callers);
+// outputs never alias inputs unless a function says so.
+#pragma once
+#include "ekf_device.h"
+
+// 0.5 * (T_i . K_j + K_i . T_j): one entry of sym(K S K^T) = 0.5 (T K^T + K T^T), T = K S.
+// Bitwise symmetric in (i, j).
+__device__ __forceinline__ double sym_u(double ti0, double ti1, double ki0, double ki1, double tj0, double tj1,
+                                        double kj0, double kj1) {
+    double d1 = fma(ti1, kj1, ti0 * kj0);
+    double d2 = fma(ki1, tj1, ki0 * tj0);
+    return 0.5 * (d1 + d2);
+}
+
+__device__ __forceinline__ bool cand_better(double da, int ia, double db, int ib) {
+    // strict '>' with ascending scan order (Update.cpp:140): smaller d wins, ties -> lower index
+    return (da < db) | ((da == db) & (ia < ib));  // bitwise: no short-circuit branches in the reductions
+}
+
+struct LmState {  // everything the filter keeps per landmark
+    double x0, x1;   // position estimate
+    double rc[6];    // P[0:3, Li:Li+2], 3x2 row-major
+    double dxx, dxy, dyy;
+};
+
+// ---- Propagate -------------------------------------------------------------------------------------------------------------------
+
+// robot block of Propagate.cpp:15-75; rec = (v, w, dt, q00, q10, q01, q11).  In / Out: any struct with pose[3], c, s (cos / sin of pose[2])
+// and Prr[9]; in and out may alias.  pa, pb: Phi_R(0,2), Phi_R(1,2), what the landmarks' robot rows need of this Propagate.
+template <class In, class Out>
+__device__ __forceinline__ void propagate_robot_block(const In &in, Out &out, const double *rec, double &pa_out, double &pb_out) {
+    const double v = rec[0], w = rec[1], dt = rec[2];
+    const double so = in.s, co = in.c;
+    const double pa = -dt * v * so, pb = dt * v * co;  // Phi_R = [[1,0,pa],[0,1,pb],[0,0,1]], :42-44
+    double Q[4] = {rec[3], rec[5], rec[4], rec[6]};    // row-major from column-major
+    double Prr[9], pose[3];
+#pragma unroll
+    for (int i = 0; i < 9; i++) Prr[i] = in.Prr[i];
+#pragma unroll
+    for (int i = 0; i < 3; i++) pose[i] = in.pose[i];
+    out.pose[0] = pose[0] + dt * (v * co);  // :33-38
+    out.pose[1] = pose[1] + dt * (v * so);
+    out.pose[2] = pose[2] + dt * w;
+    double Phi[9] = {1, 0, pa, 0, 1, pb, 0, 0, 1};
+    double Gm[6] = {-dt * co, 0, -dt * so, 0, 0, -dt};  // :46-48
+    double t1[9], t2[9], GQ[6], Pn[9];
+    // (Phi * P_RR) * Phi^T + (G * Q) * G^T, :53
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) t1[i * 3 + j] = Phi[i * 3] * Prr[j] + Phi[i * 3 + 1] * Prr[3 + j] + Phi[i * 3 + 2] * Prr[6 + j];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) t2[i * 3 + j] = t1[i * 3] * Phi[j * 3] + t1[i * 3 + 1] * Phi[j * 3 + 1] + t1[i * 3 + 2] * Phi[j * 3 + 2];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++) GQ[i * 2 + j] = Gm[i * 2] * Q[j] + Gm[i * 2 + 1] * Q[2 + j];
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) Pn[i * 3 + j] = t2[i * 3 + j] + (GQ[i * 2] * Gm[j * 2] + GQ[i * 2 + 1] * Gm[j * 2 + 1]);
+    // 0.5 (P + P^T), :66-67 (a no-op outside this block: P enters bitwise symmetric)
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) out.Prr[i * 3 + j] = 0.5 * (Pn[i * 3 + j] + Pn[j * 3 + i]);
+    sincos(out.pose[2], &out.s, &out.c);
+    pa_out = pa, pb_out = pb;
+}
+
+// NEES sample e^T P_RR^-1 e of the pose against the truth rec = (x, y, phi)
+__device__ __forceinline__ void nees_sample(const double *pose, const double *Prr, const double *rec, ekf_stats &st) {
+    double e0 = pose[0] - rec[0], e1 = pose[1] - rec[1], e2 = pose[2] - rec[2];
+    e2 -= 6.283185307179586 * floor((e2 + 3.141592653589793) / 6.283185307179586);
+    double a = Prr[0], bb = Prr[1], c = Prr[2], d = Prr[4], e = Prr[5], f = Prr[8];
+    double A = d * f - e * e, Bc = c * e - bb * f, Cc = bb * e - c * d;
+    double det = a * A + bb * Bc + c * Cc;
+    double Dd = a * f - c * c, Ee = bb * c - a * e, Ff = a * d - bb * bb;
+    double q = e0 * (A * e0 + Bc * e1 + Cc * e2) + e1 * (Bc * e0 + Dd * e1 + Ee * e2) + e2 * (Cc * e0 + Ee * e1 + Ff * e2);
+    double nees = q / det;
+    if (det > 0.0 && nees >= 0.0 && nees < EKF_INF) {  // a fresh filter has P_RR = 0: no sample then
+        st.nees_sum += nees;
+        st.nees_count++;
+    }
+}
+
+// ---- the association sweep -------------------------------------------------------------------------------------------------------
+
+struct SweepBest {
+    double d;
+    int lm;
+    double w[16];  // res(2) S00,S01,S11 hcol(2) P_R,Li(6) D(3)
+};
+
+// What the association sweep needs of the robot block, the same for every landmark of a measurement:
+// with H_R = [-C^T | h] (Update.cpp:112-114) the term H_R P_RR H_R^T is M0 - u h^T - h u^T + pff h h^T,
+// M0 = C^T P_xy C, u = C^T p_phi.
+struct SweepConst {
+    double c, s, px, py;
+    double M0[3];  // 00, 01 (symmetrised), 11
+    double u0, u1, pff;
+    double R00, R01, R10, R11;
+};
+
+__device__ __forceinline__ SweepConst sweep_const(double c, double s, double px, double py, const double *Prr, const double *Rm) {
+    SweepConst k;
+    k.c = c, k.s = s, k.px = px, k.py = py;
+    // C^T X C for X = P_xy, C^T = [[c, s], [-s, c]]
+    double a00 = c * Prr[0] + s * Prr[3], a01 = c * Prr[1] + s * Prr[4];
+    double a10 = -s * Prr[0] + c * Prr[3], a11 = -s * Prr[1] + c * Prr[4];
+    double m00 = a00 * c + a01 * s, m01 = -a00 * s + a01 * c;
+    double m10 = a10 * c + a11 * s, m11 = -a10 * s + a11 * c;
+    k.M0[0] = m00, k.M0[1] = 0.5 * (m01 + m10), k.M0[2] = m11;
+    k.u0 = c * Prr[2] + s * Prr[5];
+    k.u1 = -s * Prr[2] + c * Prr[5];
+    k.pff = Prr[8];
+    k.R00 = Rm[0], k.R01 = Rm[1], k.R10 = Rm[2], k.R11 = Rm[3];
+    return k;
+}
+
+// one landmark of the association sweep, Update.cpp:103-148.  S (:122) is assembled from the per-
+// measurement constants above plus C^T P_xy,Li C, a_phi C and C^T P_LiLi C; same value as the
+// reference's four products up to rounding (about 50 multiply-adds instead of 140).
+__device__ __forceinline__ void sweep_one(int lm, const LmState &st, double z0, double z1, const SweepConst &k, double cond_k2,
+                                          SweepBest &best) {
+    const double c = k.c, s = k.s;
+    double dp0 = st.x0 - k.px, dp1 = st.x1 - k.py;
+    // z_hat = C^T dp (:109), res = z - z_hat (:111)
+    double res0 = z0 - (c * dp0 + s * dp1);
+    double res1 = z1 - (-s * dp0 + c * dp1);
+    // third column of H_R = -C^T J dp (:112-114)
+    double h0 = -s * dp0 + c * dp1;
+    double h1 = -c * dp0 - s * dp1;
+    const double *A = st.rc;  // P_RLi 3x2: rows x, y, phi
+    // V = C^T A_xy C, w = a_phi C
+    double b00 = c * A[0] + s * A[2], b01 = c * A[1] + s * A[3];
+    double b10 = -s * A[0] + c * A[2], b11 = -s * A[1] + c * A[3];
+    double v00 = b00 * c + b01 * s, v01 = -b00 * s + b01 * c;
+    double v10 = b10 * c + b11 * s, v11 = -b10 * s + b11 * c;
+    double w0 = A[4] * c + A[5] * s, w1 = -A[4] * s + A[5] * c;
+    // X = H_R P_RLi H_Li^T = -V + h w   (and its transpose is H_Li P_LiR H_R^T)
+    double x00 = h0 * w0 - v00, x01 = h0 * w1 - v01, x10 = h1 * w0 - v10, x11 = h1 * w1 - v11;
+    // L = C^T P_LiLi C
+    double l00 = c * st.dxx + s * st.dxy, l01 = c * st.dxy + s * st.dyy;
+    double l10 = -s * st.dxx + c * st.dxy, l11 = -s * st.dxy + c * st.dyy;
+    double q00 = l00 * c + l01 * s, q01 = -l00 * s + l01 * c;
+    double q10 = l10 * c + l11 * s, q11 = -l10 * s + l11 * c;
+    // S = H_R P_RR H_R^T + X^T + X + L + R (:122), then 0.5 (S + S^T) (:123-124)
+    double S00 = (k.M0[0] - 2.0 * k.u0 * h0 + k.pff * h0 * h0) + 2.0 * x00 + q00 + k.R00;
+    double S11 = (k.M0[2] - 2.0 * k.u1 * h1 + k.pff * h1 * h1) + 2.0 * x11 + q11 + k.R11;
+    double S01 = (k.M0[1] - k.u0 * h1 - k.u1 * h0 + k.pff * h0 * h1) + (x01 + x10) + 0.5 * (q01 + q10) + 0.5 * (k.R01 + k.R10);
+    // condition number = sigma_max / sigma_min of the symmetric 2x2 (:127-128) = (q + r) / |q - r| with q = |e|,
+    // r = sqrt(f^2 + S01^2).  Only "cond >= limit" is needed (:131), and (q + r) >= L |q - r|  <=>  q r >= kappa (q^2 + r^2)
+    // with kappa = (L^2 - 1) / (2 (L^2 + 1))  <=>  q^2 r^2 >= kappa^2 (q^2 + r^2)^2: no square root and no division on
+    // the measurement's critical path (about 25 dependent fp64 operations of 13 ns each).  NaN compares false: not skipped,
+    // as in the reference; q = r (cond = inf) is skipped.
+    double e = 0.5 * (S00 + S11), f = 0.5 * (S00 - S11);
+    double q2 = e * e, r2 = f * f + S01 * S01, sum = q2 + r2;
+    if (!(q2 * r2 >= cond_k2 * (sum * sum))) {
+        double det = S00 * S11 - S01 * S01;
+        double d = (res0 * (S11 * res0 - S01 * res1) + res1 * (S00 * res1 - S01 * res0)) / det;  // :135-136
+        if (best.d > d) {  // :140 (false for NaN); ascending lm, so ties keep the lower index
+            best.d = d, best.lm = lm;
+            best.w[0] = res0, best.w[1] = res1, best.w[2] = S00, best.w[3] = S01, best.w[4] = S11, best.w[5] = h0, best.w[6] = h1;
+            for (int i = 0; i < 6; i++) best.w[7 + i] = A[i];
+            best.w[13] = st.dxx, best.w[14] = st.dxy, best.w[15] = st.dyy;
+        }
+    }
+}
+
+// The same landmark of the same sweep for the kernel instantiation that holds ONE landmark per worker thread (k_chain<true>): a lane has
+// one candidate at most, so there is no running best to keep -- the winner record's entries are this lane's own sweep values
+// (res, S, h) and its landmark's state (P_R,Li and the 2x2 block: r0 itself), used only if the lane turns out to own the filter-wide
+// winner.  Expression for expression sweep_one; d = EKF_INF when the landmark is skipped (condition number) or cannot win (NaN).
+struct SweepOne {
+    double d;
+    double res0, res1, S00, S01, S11, h0, h1;
+};
+__device__ __forceinline__ SweepOne sweep_single(const LmState &st, double z0, double z1, const SweepConst &k, double cond_k2) {
+    const double c = k.c, s = k.s;
+    double dp0 = st.x0 - k.px, dp1 = st.x1 - k.py;
+    double res0 = z0 - (c * dp0 + s * dp1);
+    double res1 = z1 - (-s * dp0 + c * dp1);
+    double h0 = -s * dp0 + c * dp1;
+    double h1 = -c * dp0 - s * dp1;
+    const double *A = st.rc;
+    double b00 = c * A[0] + s * A[2], b01 = c * A[1] + s * A[3];
+    double b10 = -s * A[0] + c * A[2], b11 = -s * A[1] + c * A[3];
+    double v00 = b00 * c + b01 * s, v01 = -b00 * s + b01 * c;
+    double v10 = b10 * c + b11 * s, v11 = -b10 * s + b11 * c;
+    double w0 = A[4] * c + A[5] * s, w1 = -A[4] * s + A[5] * c;
+    double x00 = h0 * w0 - v00, x01 = h0 * w1 - v01, x10 = h1 * w0 - v10, x11 = h1 * w1 - v11;
+    double l00 = c * st.dxx + s * st.dxy, l01 = c * st.dxy + s * st.dyy;
+    double l10 = -s * st.dxx + c * st.dxy, l11 = -s * st.dxy + c * st.dyy;
+    double q00 = l00 * c + l01 * s, q01 = -l00 * s + l01 * c;
+    double q10 = l10 * c + l11 * s, q11 = -l10 * s + l11 * c;
+    double S00 = (k.M0[0] - 2.0 * k.u0 * h0 + k.pff * h0 * h0) + 2.0 * x00 + q00 + k.R00;
+    double S11 = (k.M0[2] - 2.0 * k.u1 * h1 + k.pff * h1 * h1) + 2.0 * x11 + q11 + k.R11;
+    double S01 = (k.M0[1] - k.u0 * h1 - k.u1 * h0 + k.pff * h0 * h1) + (x01 + x10) + 0.5 * (q01 + q10) + 0.5 * (k.R01 + k.R10);
+    double e = 0.5 * (S00 + S11), f = 0.5 * (S00 - S11);
+    double q2 = e * e, r2 = f * f + S01 * S01, sum = q2 + r2;
+    SweepOne o;
+    o.res0 = res0, o.res1 = res1, o.S00 = S00, o.S01 = S01, o.S11 = S11, o.h0 = h0, o.h1 = h1;
+    const bool kept = !(q2 * r2 >= cond_k2 * (sum * sum));  // Update.cpp:131 (NaN: not skipped)
+    double det = S00 * S11 - S01 * S01;
+    double d = (res0 * (S11 * res0 - S01 * res1) + res1 * (S00 * res1 - S01 * res0)) / det;  // :135-136
+    o.d = (kept && EKF_INF > d) ? d : EKF_INF;  // :140 (false for NaN)
+    return o;
+}
+
+// ---- Old, Update.cpp:181-194 -----------------------------------------------------------------------------------------------------
+
+// Header of the Old branch (Update.cpp:181-189): a pure function of the heading the sweep ran with and of the
+// winner record.  Whoever needs it (k_chain: the control lane for the robot block and every worker for its landmarks;
+// k_solo: every thread) builds it independently; contraction is off so that all copies round identically.
+struct OldHdr {
+    double c, s, h0, h1;       // H_R^T rows are (-c, s), (-s, -c), (h0, h1)
+    double Si00, Si01, Si11;   // S^-1
+    double S00, S01, S11;
+    double res0, res1;
+};
+
+__device__ __forceinline__ OldHdr old_header(double c, double s, const double *w) {
+#pragma clang fp contract(off)
+    OldHdr h;
+    h.c = c, h.s = s, h.h0 = w[5], h.h1 = w[6];
+    h.S00 = w[2], h.S01 = w[3], h.S11 = w[4];
+    double det = h.S00 * h.S11 - h.S01 * h.S01;
+    double idet = 1.0 / det;
+    h.Si00 = h.S11 * idet, h.Si01 = -h.S01 * idet, h.Si11 = h.S00 * idet;
+    h.res0 = w[0], h.res1 = w[1];
+    return h;
+}
+
+// Row r (0..2) of K and of T = K S: K_r = (P_RR[r,:] H_R^T + P[r, Lo:Lo+2] H_Li^T) S^-1, Update.cpp:186
+__device__ __forceinline__ void old_robot_row(const OldHdr &h, const double *Prow, double p0, double p1, double &k0, double &k1,
+                                              double &t0, double &t1) {
+#pragma clang fp contract(off)
+    double u0 = 0, u1 = 0;
+    u0 += Prow[0] * (-h.c), u1 += Prow[0] * h.s;
+    u0 += Prow[1] * (-h.s), u1 += Prow[1] * (-h.c);
+    u0 += Prow[2] * h.h0, u1 += Prow[2] * h.h1;
+    double w0 = p0 * h.c + p1 * h.s, w1 = p0 * (-h.s) + p1 * h.c;  // H_Li^T = C
+    double s0 = u0 + w0, s1 = u1 + w1;
+    k0 = s0 * h.Si00 + s1 * h.Si01;
+    k1 = s0 * h.Si01 + s1 * h.Si11;
+    t0 = k0 * h.S00 + k1 * h.S01;
+    t1 = k0 * h.S01 + k1 * h.S11;
+}

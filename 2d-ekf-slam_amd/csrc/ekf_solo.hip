@@ -16,6 +16,17 @@
 //     records are double-buffered by measurement parity: a wave can be at most one measurement ahead of the slowest one;
 //   * New, Ignore and compass headers are computed by every thread as well: no header hand-off.
 // Everything else -- slots, the own-row cache, the hand-scheduled fold, the fragment-major P_LL reads -- is k_chain's.
+//
+// Where the arithmetic lives: the robot block of Propagate, the NEES sample, the association sweep, the Old header and the robot rows of the
+// gain, sym_u and LmState come from ekf_filter_math.h, the one copy both kernels call (ekf_kernels.hip includes it in front of k_chain, and
+// ekf_api.hip includes this file behind that one).  The gate, the New and compass branches and the Old landmark update are still written out
+// here, expression for expression k_chain's: k_solo<false>'s New branch is compiled with the cache stores of its two sides merged into one
+// pair, and each shared function tried inside the measurement loop (New header, new landmark, column rows, compass, Old landmark, Old robot
+// block; New, compass and the Old robot block also alone) moved one of the two stores back into the branches (ds_write_b128 36 -> 37 per
+// kernel) -- DESIGN.md section 7, row 10.  orient_old_inputs is also still a lambda in both kernels: shared, it leaves k_solo's text alone
+// but moves one s_waitcnt in k_chain<false, *>, and a device code that differs from the parent's in any instruction has to be timed against
+// it first.  From ekf_kernels.hip itself this file uses ChainKArgs, uni, lds_off, the FOLD_* macros and STAMP, and -- beyond those -- the
+// wave arg-min (wave_argmin), op_record and the double2_t typedef, which stay there with k_chain.
 #include "ekf_device.h"
 
 // Windows of up to twice what the own-row cache holds.  A map of 256 landmarks fits 16 slots of its window into LDS (131 KB), and
@@ -54,64 +65,6 @@ struct SoloRobot {  // the robot block as every thread holds it
     double c, s;
     double Prr[9];
 };
-
-// robot block of Propagate.cpp:15-75; rec = (v, w, dt, q00, q10, q01, q11) -- expression for expression k_chain's propagate_robot
-__device__ __forceinline__ void solo_propagate_robot(SoloRobot &rb, const double *rec) {
-    const double v = rec[0], w = rec[1], dt = rec[2];
-    const double so = rb.s, co = rb.c;
-    const double pa = -dt * v * so, pb = dt * v * co;  // Phi_R = [[1,0,pa],[0,1,pb],[0,0,1]], :42-44
-    double Q[4] = {rec[3], rec[5], rec[4], rec[6]};    // row-major from column-major
-    double Prr[9], pose[3];
-#pragma unroll
-    for (int i = 0; i < 9; i++) Prr[i] = rb.Prr[i];
-#pragma unroll
-    for (int i = 0; i < 3; i++) pose[i] = rb.pose[i];
-    rb.pose[0] = pose[0] + dt * (v * co);  // :33-38
-    rb.pose[1] = pose[1] + dt * (v * so);
-    rb.pose[2] = pose[2] + dt * w;
-    double Phi[9] = {1, 0, pa, 0, 1, pb, 0, 0, 1};
-    double Gm[6] = {-dt * co, 0, -dt * so, 0, 0, -dt};  // :46-48
-    double t1[9], t2[9], GQ[6], Pn[9];
-    // (Phi * P_RR) * Phi^T + (G * Q) * G^T, :53
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) t1[i * 3 + j] = Phi[i * 3] * Prr[j] + Phi[i * 3 + 1] * Prr[3 + j] + Phi[i * 3 + 2] * Prr[6 + j];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) t2[i * 3 + j] = t1[i * 3] * Phi[j * 3] + t1[i * 3 + 1] * Phi[j * 3 + 1] + t1[i * 3 + 2] * Phi[j * 3 + 2];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 2; j++) GQ[i * 2 + j] = Gm[i * 2] * Q[j] + Gm[i * 2 + 1] * Q[2 + j];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) Pn[i * 3 + j] = t2[i * 3 + j] + (GQ[i * 2] * Gm[j * 2] + GQ[i * 2 + 1] * Gm[j * 2 + 1]);
-    // 0.5 (P + P^T), :66-67 (a no-op outside this block: P enters bitwise symmetric)
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) rb.Prr[i * 3 + j] = 0.5 * (Pn[i * 3 + j] + Pn[j * 3 + i]);
-    sincos(rb.pose[2], &rb.s, &rb.c);
-}
-
-// NEES sample e^T P_RR^-1 e against rec = (x, y, phi) (thread 0)
-__device__ __forceinline__ void solo_nees_sample(const SoloRobot &R, const double *rec, ekf_stats &st) {
-    double e0 = R.pose[0] - rec[0], e1 = R.pose[1] - rec[1], e2 = R.pose[2] - rec[2];
-    e2 -= 6.283185307179586 * floor((e2 + 3.141592653589793) / 6.283185307179586);
-    double a = R.Prr[0], bb = R.Prr[1], c = R.Prr[2], d = R.Prr[4], e = R.Prr[5], f = R.Prr[8];
-    double A = d * f - e * e, Bc = c * e - bb * f, Cc = bb * e - c * d;
-    double det = a * A + bb * Bc + c * Cc;
-    double Dd = a * f - c * c, Ee = bb * c - a * e, Ff = a * d - bb * bb;
-    double q = e0 * (A * e0 + Bc * e1 + Cc * e2) + e1 * (Bc * e0 + Dd * e1 + Ee * e2) + e2 * (Cc * e0 + Ee * e1 + Ff * e2);
-    double nees = q / det;
-    if (det > 0.0 && nees >= 0.0 && nees < EKF_INF) {  // a fresh filter has P_RR = 0: no sample then
-        st.nees_sum += nees;
-        st.nees_count++;
-    }
-}
 
 // grid (1, filters of the launch), blockDim = 64 * ceil(capacity / 64) <= 256 threads; arguments as k_chain's (segments with
 // n_prev = 0, need_pass = 0, drop = 0: one slot set; a segment that fills its window folds it itself when ChainSeg::self_pass says so,
@@ -467,12 +420,15 @@ __global__ __launch_bounds__(256) void k_solo(EkfDev dv, const double *in, const
                         r0.rc[2 + e] = r0.rc[2 + e] + pb * r0.rc[4 + e];
                     }
                 }
-                solo_propagate_robot(rb, rec);
+                // (pa, pb are formed above and the call's own copies dropped: with the call first and its outputs used for the row, the four
+                // k_solo instantiations are no longer compiled to the parent's text -- integer and branch instructions move)
+                double pa_, pb_;
+                propagate_robot_block(rb, rb, rec, pa_, pb_);
                 continue;
             }
 
             if (type == OP_TRUTH) {
-                if (tid == 0) solo_nees_sample(rb, rec, L.st);
+                if (tid == 0) nees_sample(rb.pose, rb.Prr, rec, L.st);
                 continue;
             }
 

@@ -6,11 +6,20 @@
     (BB<n>_<k>, .Lfunc_end<n>) and inline-assembly labels, which follow the order of template instantiation and may move with host code;
   * resource_usage.txt, per kernel name: registers, spills, scratch, LDS and occupancy.
 
-usage: compare_kernel_asm.py PARENT/lib/asm PR/lib/asm      (exit status 0: identical)
-A change to the host side of ekf_api.hip must leave all of it unchanged."""
+usage: compare_kernel_asm.py [--allow-reordering] PARENT/lib/asm PR/lib/asm      (exit status 0: identical)
+A change to the host side of ekf_api.hip must leave all of it unchanged.
+
+For a kernel whose text differs, the per-kernel counts of the opcodes that differ are printed.  A change that moves device source without
+changing what is computed (the same expressions reached through a shared inline function) may come out of the compiler with other
+register names, another operand order of commutative instructions or another schedule.  --allow-reordering accepts that and nothing else:
+exit status 0 when every kernel descriptor and all resource usage is identical and, in every kernel whose text differs, no opcode that does
+floating-point arithmetic, touches memory or synchronises (SENSITIVE below) changes its count."""
+import collections
 import os
 import re
 import sys
+
+SENSITIVE = ("_f64", "mfma", "ds_", "global_", "buffer_", "flat_", "s_barrier", "s_load")
 
 
 def normalise(line):
@@ -51,6 +60,16 @@ def kernels(path):
     return {k: renumber(v) for k, v in text.items()}, desc
 
 
+def opcodes(lines):
+    """opcode -> count over the instruction lines of one kernel's text"""
+    count = collections.Counter()
+    for line in lines:
+        m = re.match(r"\s+([a-z]\w*)\b", line)  # (directives start with '.', labels in column 0, comments with ';')
+        if m:
+            count[m.group(1)] += 1
+    return count
+
+
 def resources(path):
     """kernel name -> {field: value}"""
     out, cur = {}, None
@@ -69,11 +88,13 @@ def resources(path):
 
 
 def main():
-    if len(sys.argv) != 3:
+    args = [v for v in sys.argv[1:] if v != "--allow-reordering"]
+    allow = len(args) != len(sys.argv) - 1
+    if len(args) != 2:
         print(__doc__)
         return 2
-    a, b = sys.argv[1], sys.argv[2]
-    bad = 0
+    a, b = args
+    bad = reordered = 0
     ta, da = kernels(os.path.join(a, "ekf_kernels.s"))
     tb, db = kernels(os.path.join(b, "ekf_kernels.s"))
     for what, x, y in (("kernel text", ta, tb), ("kernel descriptor", da, db)):
@@ -84,7 +105,19 @@ def main():
         for k in sorted(set(x) & set(y)):
             if x[k] != y[k]:
                 print("%s DIFFERS: %s (%d against %d lines)" % (what, k, len(x[k]), len(y[k])))
-                bad += 1
+                if x is not ta:
+                    bad += 1
+                    continue
+                ca, cb = opcodes(x[k]), opcodes(y[k])
+                diff = {op: (ca[op], cb[op]) for op in sorted(set(ca) | set(cb)) if ca[op] != cb[op]}
+                hard = [op for op in diff if any(w in op for w in SENSITIVE)]
+                print("    opcode counts that differ: %s" % (", ".join("%s %d -> %d" % (op, v[0], v[1]) for op, v in diff.items()) or "none"))
+                if hard:
+                    print("    of them floating-point, memory or synchronisation: %s" % ", ".join(hard))
+                if allow and not hard:
+                    reordered += 1
+                else:
+                    bad += 1
         print("%s: %d symbols in A, %d in B, %d identical (%d lines)" % (what, len(x), len(y), len(same), sum(len(x[k]) for k in same)))
     ra, rb = resources(os.path.join(a, "resource_usage.txt")), resources(os.path.join(b, "resource_usage.txt"))
     if sorted(ra) != sorted(rb):
@@ -95,7 +128,12 @@ def main():
             print("resource usage DIFFERS: %s: %s" % (k, {f: (ra[k].get(f), rb[k].get(f)) for f in set(ra[k]) | set(rb[k]) if ra[k].get(f) != rb[k].get(f)}))
             bad += 1
     print("resource usage: %d kernels in A, %d in B, %d identical" % (len(ra), len(rb), sum(1 for k in ra if rb.get(k) == ra[k])))
-    print("device code identical" if not bad else "device code DIFFERS (%d findings)" % bad)
+    if bad:
+        print("device code DIFFERS (%d findings)" % bad)
+    elif reordered:
+        print("device code reordered in %d kernels: descriptors, resource usage and the counts of every floating-point, memory and synchronisation opcode identical" % reordered)
+    else:
+        print("device code identical")
     return 1 if bad else 0
 
 
