@@ -1625,6 +1625,7 @@ static int sticky_status(ekf_batch *h, bool include_capacity) {
 //   ekf_reserve                                        QUIET_SETTLED  ST_NONE              refreshes the bounds AFTER the settle; only EKF_ERR_TIMEOUT ends it
 //   ekf_remove_landmarks, ekf_transform_frame,
 //   ekf_anchor_at_robot (and the batch forms)          QUIET_SETTLED  ST_INVALID_OR_FULL   the state stays as it is under either status
+//   ekf_join_map, ekf_batch_join_map                   QUIET_SETTLED  ST_INVALID_OR_FULL   BOTH handles, the source first (a join without room fails after the settle)
 // (ekf_get_landmark_covs and the mirror's readers go through refresh_bounds alone; ekf_flush / ekf_close_window through close_set.)
 enum QuietLevel { QUIET_STREAM, QUIET_SETTLED };
 enum StatusRule { ST_NONE, ST_INVALID, ST_INVALID_OR_FULL };
@@ -2117,6 +2118,65 @@ extern "C" int ekf_anchor_at_robot(ekf_handle h, int index) {
 extern "C" int ekf_batch_anchor_at_robot(ekf_handle h) {
     if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
     return reframe_impl(h, -1, nullptr);
+}
+
+// Map joining on the device (ekf_kernels.hip: k_join_tiles, k_join_vec, k_join_finish).  di < 0: the batch form, filter b of `s`
+// into filter b of `d`.  Both handles are brought to rest first (the source is only read afterwards, so its own quiescing is all
+// that ever happens to it), which also orders their streams: everything runs on the destination's chain stream while the source's
+// streams are idle, and the call waits for it.  Bm is rewritten in place in the destination's settled buffer in either pipeline
+// mode; the only transient allocation is the batch form's table of cos / sin (16 bytes per filter).
+static int join_impl(ekf_batch *d, int di, ekf_batch *s, int si) {
+    EKF_TRY(quiesce(s, QUIET_SETTLED, ST_INVALID_OR_FULL));
+    if (d != s) EKF_TRY(quiesce(d, QUIET_SETTLED, ST_INVALID_OR_FULL));
+    EkfDev &dv = d->dv;
+    const int bd0 = di < 0 ? 0 : di, bs0 = di < 0 ? 0 : si, nb = di < 0 ? dv.B : 1;
+    int nt = 0, nv = 0;
+    for (int k = 0; k < nb; k++) {
+        const int Ng = d->h_int[bd0 + k], Ns = s->h_int[bs0 + k];
+        if (Ng + Ns > dv.Ncap) {
+            char buf[200];
+            snprintf(buf, sizeof buf, "filter %d: %d + %d landmarks do not fit capacity_landmarks = %d (ekf_reserve, then join again)", bd0 + k, Ng, Ns, dv.Ncap);
+            return set_error(EKF_ERR_CAPACITY, buf);
+        }
+        const int t = join_tile_count(Ng, Ns);
+        nt = t > nt ? t : nt;
+        nv = Ng + Ns > nv ? Ng + Ns : nv;
+    }
+    DevTmp<double> rot_d;
+    JoinRot one = {1.0, 0.0};
+    // (the host mirror's heading is the device's x[2] bit for bit once the chain stream is idle: every writer of x[0..2] -- the chain
+    // kernels, k_set_meta, the finish kernels -- copies the pose into the mirror; a dense pass does not touch it)
+    if (nb == 1) {
+        one.c = cos(d->mirror_h[bd0].pose[2]), one.s = sin(d->mirror_h[bd0].pose[2]);
+    } else {
+        std::vector<double> rot((size_t)nb * 2);
+        for (int k = 0; k < nb; k++) rot[2 * k] = cos(d->mirror_h[bd0 + k].pose[2]), rot[2 * k + 1] = sin(d->mirror_h[bd0 + k].pose[2]);
+        HIP_TRY(rot_d.alloc(rot.size()));
+        HIP_TRY(hipMemcpy(rot_d.p, rot.data(), rot.size() * sizeof(double), hipMemcpyHostToDevice));  // (rot leaves scope: synchronous)
+    }
+    const EkfDev &sd = s->dv;
+    const JoinSrc sv = {sd.x, sd.R, sd.D, sd.Bm[s->buf_in], sd.n_lm, sd.xs, sd.dn, sd.T, sd.bm_stride};
+    const double *rotc = rot_d.p;
+    hipStream_t st = d->s_chain;
+    if (nt > 0) hipLaunchKernelGGL(k_join_tiles, dim3((unsigned)nt, (unsigned)nb), dim3(256), 0, st, dv, d->buf_in, sv, one, rotc, bd0, bs0);
+    if (nv > 0) hipLaunchKernelGGL(k_join_vec, dim3((unsigned)cdiv(nv, 256), (unsigned)nb), dim3(256), 0, st, dv, d->buf_in, sv, one, rotc, bd0, bs0);
+    hipLaunchKernelGGL(k_join_finish, dim3(nb), dim3(64), 0, st, dv, sv, one, rotc, bd0, bs0);
+    EKF_TRY(finish_rewrite(d, bd0, nb, /*rearm*/ true, nullptr, 0, /*flip_buf*/ false));
+    return di < 0 ? EKF_OK : d->h_int[bd0];
+}
+
+extern "C" int ekf_join_map(ekf_handle dst, int dst_index, ekf_handle src, int src_index) {
+    if (!dst || !src || dst_index < 0 || dst_index >= dst->dv.B || src_index < 0 || src_index >= src->dv.B) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    if (dst == src && dst_index == src_index) return set_error(EKF_ERR_BAD_ARG, "a filter cannot be joined to itself");
+    if (dst->device != src->device) return set_error(EKF_ERR_BAD_ARG, "the two handles live on different devices");
+    return join_impl(dst, dst_index, src, src_index);
+}
+
+extern "C" int ekf_batch_join_map(ekf_handle dst, ekf_handle src) {
+    if (!dst || !src || dst == src) return set_error(EKF_ERR_BAD_ARG, "bad argument (two different handles)");
+    if (dst->dv.B != src->dv.B) return set_error(EKF_ERR_BAD_ARG, "the two handles have different batch sizes");
+    if (dst->device != src->device) return set_error(EKF_ERR_BAD_ARG, "the two handles live on different devices");
+    return join_impl(dst, -1, src, 0);
 }
 
 extern "C" int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max) {

@@ -257,6 +257,52 @@ __host__ __device__ inline int bm_chain_offset(int rho, int c) {
     return (r >> 1) * 128 + (g * 16 + c) * 2 + (r & 1);
 }
 
+// Map joining (ekf_join_map) appends the Ns landmarks of a source filter behind the Ng landmarks of the destination: only the tile
+// COLUMNS from J0 = Ng / 32 on hold a new column, and one workgroup rewrites each of their tiles (I <= J), gathered by destination.
+// Tile t of that list (column after column) is (I, J); false behind the last column J1 - 1, J1 = tiles per side of the joined map.
+__host__ __device__ inline bool join_tile_ij(int t, int J0, int J1, int *I, int *J) {
+    int j = J0;
+    while (j < J1 && t >= j + 1) t -= j + 1, j++;
+    *I = t, *J = j;
+    return j < J1;
+}
+__host__ __device__ inline int join_tile_count(int Ng, int Ns) {
+    const int J0 = Ng >> 5, J1 = (2 * (Ng + Ns) + 63) >> 6;
+    return Ns > 0 ? J1 * (J1 + 1) / 2 - J0 * (J0 + 1) / 2 : 0;
+}
+
+// Where element (i', j') of the joined P_LL (landmark space, either order) comes from.  The SOURCE filter has a layout of its own
+// (Ts tiles per side, D stride dns: its capacity's, not the destination's).
+//   JM_OLD    both landmarks are the destination's: the element stays, bit for bit
+//   JM_ROBOT  one old, one new landmark: P_mR G_k^T, from the destination's robot rows alone (no source element)
+//   JM_BM     two different new landmarks: G_k P_RR G_l^T + (C P_s,kl C^T), the source block's upper-triangle home in the source's Bm;
+//             si, sj = the element's own rows in the source's landmark space (the rotation mixes it with the three others of its
+//             2x2 block, which lie at off(2k + e, 2l + f) = off(2k, 2l) + 32 e + 2 f: a landmark's two rows never leave a chain)
+//   JM_D      a new landmark's own block: the source's D (offset comp * dns + landmark)
+//   JM_ZERO   beyond the joined map
+enum { JM_ZERO = 0, JM_OLD = 1, JM_ROBOT = 2, JM_BM = 3, JM_D = 4 };
+struct JoinSource {
+    int where;
+    int si, sj;  // JM_BM / JM_D: rows of the source's landmark space, in the order asked for
+    size_t off;  // JM_BM: into the source filter's Bm, element (min, max); JM_D: into its D
+};
+__host__ __device__ inline JoinSource join_source(int Ng, int Ns, int Ts, int dns, int ip, int jp) {
+    JoinSource s;
+    s.where = JM_ZERO, s.si = s.sj = -1, s.off = 0;
+    const int li = ip >> 1, lj = jp >> 1;
+    if (li >= Ng + Ns || lj >= Ng + Ns) return s;
+    if (li < Ng && lj < Ng) {
+        s.where = JM_OLD;
+    } else if (li < Ng || lj < Ng) {
+        s.where = JM_ROBOT;
+    } else {
+        s.si = ip - 2 * Ng, s.sj = jp - 2 * Ng;
+        if (li == lj) s.where = JM_D, s.off = (size_t)((s.si & 1) + (s.sj & 1)) * dns + (s.si >> 1);
+        else s.where = JM_BM, s.off = s.si < s.sj ? bm_offset(Ts, s.si, s.sj) : bm_offset(Ts, s.sj, s.si);
+    }
+    return s;
+}
+
 // Offset (doubles) of row i' of slot PAIR p inside one (filter, set) of FA / FB: 4 doubles, slot 2p in
 // [0..1], slot 2p+1 in [2..3].
 __host__ __device__ inline size_t pair_offset(int rows, int ip, int p) {

@@ -2375,6 +2375,224 @@ __global__ void k_reframe_finish(EkfDev dv, ReframeFrame one, const double *fr, 
     for (int m = 0; m < 2 * dv.maxp; m++) dv.slot_active[(size_t)b * 2 * dv.maxp + m] = 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Map joining (ekf_join_map): the Ns landmarks of a source filter, expressed in the frame of the destination's estimated pose
+// p = (t, phi), appended behind the destination's Ng landmarks; the old pose is marginalised out, the source's pose becomes the
+// robot.  With C = Rot(phi), h_k = J C M_k (the third column of G_k = [I | C J M_k]) and g = J C u (of G_R):
+//   new landmark k:  M_k' = t + C M_k,   P' blocks as in include/ekfslam_c.h.
+// Per landmark-space row i' of the joined map the tile kernel needs four doubles, {w (3), h}: an old row's w = P_iR (its robot
+// columns); a new row's h = h_k[e] and w = (row e of G_k) P_RR = P_RR[e] + h P_RR[2].  Element (i', j'), j' new, is then
+// w_i[f] + w_i[2] h_j (f = j' & 1) -- plus, when i' is new too, the source's block rotated by C.
+// Launch order on the destination's chain stream, every slot of BOTH filters folded in and all their streams idle:
+//   k_join_tiles (the destination tiles that hold a new column; reads the old robot rows and the old P_RR)  ->  k_join_vec (x, D,
+//   robot rows of the new landmarks, own blocks of the diagonal tiles; the robot rows of the OLD landmarks in place)  ->
+//   k_join_finish (pose, P_RR, count, bookkeeping, host mirror).  Nothing is read after it was overwritten: the tile kernel
+//   writes Bm only, k_join_vec reads the pose and P_RR and leaves them alone.
+// The source is only read; its layout (strides of its own capacity) travels in JoinSrc.  cos / sin of the destination's heading are
+// taken on the host: in the kernel arguments (`one`) for a one-filter call, in a table `rot` = [filters of the launch][2] for the
+// batch form.  The launch covers destination filters bd0 + blockIdx.y and source filters bs0 + blockIdx.y.
+// ---------------------------------------------------------------------------------------------
+struct JoinSrc {
+    const double *x, *R, *D, *Bm;  // the source handle's arrays, Bm = its settled buffer
+    const int *n_lm;
+    int xs, dn, T;
+    size_t bm_stride;
+};
+struct JoinRot {
+    double c, s;  // C = [[c, -s], [s, c]]
+};
+__device__ inline JoinRot join_rot(const JoinRot &one, const double *rot, int by) {
+    JoinRot q = one;
+    if (rot) q.c = rot[2 * by], q.s = rot[2 * by + 1];
+    return q;
+}
+
+// {w0, w1, w2, h} of landmark-space row ip of the joined map (zeros beyond it), from the destination's OLD robot entries
+__device__ inline void join_operand(const EkfDev &dv, const JoinSrc &sv, int bd, int bs, JoinRot q, int Ng, int Ns, int ip, double op[4]) {
+    const double *R0 = dv.R + (size_t)bd * 3 * dv.xs;
+    const int l = ip >> 1, e = ip & 1;
+    op[0] = op[1] = op[2] = op[3] = 0.0;
+    if (l < Ng) {
+        for (int k = 0; k < 3; k++) op[k] = R0[(size_t)k * dv.xs + 3 + ip];
+    } else if (l < Ng + Ns) {
+        const double *m = sv.x + (size_t)bs * sv.xs + 3 + 2 * (l - Ng);
+        const double h = e ? q.c * m[0] - q.s * m[1] : -(q.s * m[0] + q.c * m[1]);
+        for (int k = 0; k < 3; k++) op[k] = R0[(size_t)e * dv.xs + k] + h * R0[2 * (size_t)dv.xs + k];
+        op[3] = h;
+    }
+}
+
+// One workgroup per destination tile that holds a new column (ekf_device.h: join_tile_ij) and filter pair, in place in Bm[buf].
+// The tile is walked in the frame changes' work items (reframe_item: a lane owns whole 2x2 blocks and stores 32-byte pieces, a
+// wave whole 256-byte runs); every block is classified by join_source.  Old x old blocks of a straddling tile are loaded and
+// stored back unchanged, stale places included; in a diagonal tile the places below the diagonal get the transposed upper value
+// (the same expression, so the same bits) as k_import stores them, and a new landmark's own block is left to k_join_vec.
+__global__ __launch_bounds__(256) void k_join_tiles(EkfDev dv, int buf, JoinSrc sv, JoinRot one, const double *rot, int bd0, int bs0) {
+    __shared__ double ops[128][4];  // [tile row | 64 + tile column]{w0, w1, w2, h}
+    const int bd = bd0 + blockIdx.y, bs = bs0 + blockIdx.y;
+    const int Ng = dv.n_lm[bd], Ns = sv.n_lm[bs];
+    if (Ns <= 0) return;
+    int I, J;
+    if (!join_tile_ij(blockIdx.x, Ng >> 5, (2 * (Ng + Ns) + 63) >> 6, &I, &J)) return;
+    const int tid = threadIdx.x;
+    const JoinRot q = join_rot(one, rot, blockIdx.y);
+    if (tid < 128) {
+        double op[4];
+        join_operand(dv, sv, bd, bs, q, Ng, Ns, 64 * (tid < 64 ? I : J) + (tid & 63), op);
+        *(double4_t *)&ops[tid][0] = (double4_t){op[0], op[1], op[2], op[3]};
+    }
+    __syncthreads();
+    const Rot2 cq = {q.c, -q.s};
+    double *tp = dv.Bm[buf] + (size_t)bd * dv.bm_stride + ((size_t)I * dv.T - ((size_t)I * (I - 1)) / 2 + (size_t)(J - I)) * 4096;
+    const double *sb = sv.Bm + (size_t)bs * sv.bm_stride;
+    ReframeItem it[2];
+    double o[2][2][4];  // [item][block]{(0,0), (0,1), (1,0), (1,1)}
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        it[r] = reframe_item(r * 256 + tid);
+        const int lc = 32 * J + (it[r].col >> 1);
+        JoinSource src[2];
+        bool swap[2];
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            const int lr = 32 * I + (it[r].row[k] >> 1);
+            swap[k] = lr > lc;  // (a diagonal tile's places below the diagonal)
+            src[k] = join_source(Ng, Ns, sv.T, sv.dn, 2 * (swap[k] ? lc : lr), 2 * (swap[k] ? lr : lc));
+        }
+        double4_t v0 = {0.0, 0.0, 0.0, 0.0}, v1 = {0.0, 0.0, 0.0, 0.0};
+        if (src[0].where == JM_OLD || src[1].where == JM_OLD) {
+            v0 = *(const double4_t *)(tp + it[r].off);
+            v1 = *(const double4_t *)(tp + it[r].off + 32);
+        }
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            double *ob = o[r][k];
+            ob[0] = ob[1] = ob[2] = ob[3] = 0.0;  // beyond the joined map; a new landmark's own block (k_join_vec)
+            if (src[k].where == JM_OLD) {  // value v of piece s is element (row[v & 1] + s, col + (v >> 1))
+                ob[0] = v0[k], ob[1] = v0[2 + k], ob[2] = v1[k], ob[3] = v1[2 + k];
+            } else if (src[k].where == JM_ROBOT || src[k].where == JM_BM) {
+                const int ri = swap[k] ? 64 + it[r].col : it[r].row[k], ci = swap[k] ? it[r].row[k] : 64 + it[r].col;
+                double g[2][2];
+                for (int e = 0; e < 2; e++)
+                    for (int f = 0; f < 2; f++) g[e][f] = ops[ri + e][f] + ops[ri + e][2] * ops[ci + f][3];
+                if (src[k].where == JM_BM) {
+                    const double *m = sb + src[k].off;
+                    double rb[4];
+                    rot_block(cq, m[0], m[2], m[32], m[34], rb);
+                    g[0][0] += rb[0], g[0][1] += rb[1], g[1][0] += rb[2], g[1][1] += rb[3];
+                }
+                ob[0] = g[0][0], ob[3] = g[1][1];
+                ob[1] = swap[k] ? g[1][0] : g[0][1], ob[2] = swap[k] ? g[0][1] : g[1][0];
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        __builtin_nontemporal_store(((double4_t){o[r][0][0], o[r][1][0], o[r][0][1], o[r][1][1]}), (double4_t *)(tp + it[r].off));
+        __builtin_nontemporal_store(((double4_t){o[r][0][2], o[r][1][2], o[r][0][3], o[r][1][3]}), (double4_t *)(tp + it[r].off + 32));
+    }
+}
+
+// One thread per landmark of the joined map.  An old landmark: its robot rows P_mR G_R^T, in place.  New landmark k: position, own
+// block (into D and into its stale place of the diagonal tile, as k_import stores it) and robot rows
+// G_k P_RR G_R^T + C P_s,kR C3^T.  Reads the destination's pose and P_RR and the source, writes neither.
+__global__ __launch_bounds__(256) void k_join_vec(EkfDev dv, int buf, JoinSrc sv, JoinRot one, const double *rot, int bd0, int bs0) {
+    const int bd = bd0 + blockIdx.y, bs = bs0 + blockIdx.y;
+    const int Ng = dv.n_lm[bd], Ns = sv.n_lm[bs];
+    const int l = blockIdx.x * 256 + threadIdx.x;
+    if (l >= Ng + Ns) return;
+    const JoinRot q = join_rot(one, rot, blockIdx.y);
+    double *x = dv.x + (size_t)bd * dv.xs;
+    double *R0 = dv.R + (size_t)bd * 3 * dv.xs;
+    const double *sx = sv.x + (size_t)bs * sv.xs;
+    const double *sR = sv.R + (size_t)bs * 3 * sv.xs;
+    const double g0 = -(q.s * sx[0] + q.c * sx[1]), g1 = q.c * sx[0] - q.s * sx[1];  // C J u
+    if (l < Ng) {
+        for (int e = 0; e < 2; e++) {
+            const size_t c = 3 + 2 * (size_t)l + e;
+            const double r0 = R0[c], r1 = R0[dv.xs + c], r2 = R0[2 * (size_t)dv.xs + c];
+            R0[c] = r0 + r2 * g0, R0[dv.xs + c] = r1 + r2 * g1;
+        }
+        return;
+    }
+    const int k = l - Ng;
+    const double mx = sx[3 + 2 * k], my = sx[4 + 2 * k];
+    const double cx = q.c * mx - q.s * my, cy = q.s * mx + q.c * my;
+    const double h[2] = {-cy, cx};
+    double w[2][3];
+    for (int e = 0; e < 2; e++)
+        for (int j = 0; j < 3; j++) w[e][j] = R0[(size_t)e * dv.xs + j] + h[e] * R0[2 * (size_t)dv.xs + j];
+    const Rot2 cq = {q.c, -q.s};
+    const double *sD = sv.D + (size_t)bs * 3 * sv.dn;
+    const double sxy = sD[sv.dn + k];
+    double d[4];
+    rot_block(cq, sD[k], sxy, sxy, sD[2 * (size_t)sv.dn + k], d);
+    const double dxx = (w[0][0] + w[0][2] * h[0]) + d[0], dxy = (w[0][1] + w[0][2] * h[1]) + d[1], dyy = (w[1][1] + w[1][2] * h[1]) + d[3];
+    double p[3][2];  // P_s,Rk
+    for (int j = 0; j < 3; j++) p[j][0] = sR[(size_t)j * sv.xs + 3 + 2 * k], p[j][1] = sR[(size_t)j * sv.xs + 4 + 2 * k];
+    double rr[3][2];
+    for (int e = 0; e < 2; e++) {
+        double cp[3];  // row e of C P_s,kR
+        for (int j = 0; j < 3; j++) cp[j] = e ? q.s * p[j][0] + q.c * p[j][1] : q.c * p[j][0] - q.s * p[j][1];
+        rr[0][e] = (w[e][0] + w[e][2] * g0) + (cp[0] * q.c - cp[1] * q.s);
+        rr[1][e] = (w[e][1] + w[e][2] * g1) + (cp[0] * q.s + cp[1] * q.c);
+        rr[2][e] = w[e][2] + cp[2];
+    }
+    x[3 + 2 * l] = x[0] + cx, x[4 + 2 * l] = x[1] + cy;
+    for (int j = 0; j < 3; j++) R0[(size_t)j * dv.xs + 3 + 2 * l] = rr[j][0], R0[(size_t)j * dv.xs + 4 + 2 * l] = rr[j][1];
+    double *Dx = dv.D + (size_t)bd * 3 * dv.dn;
+    Dx[l] = dxx, Dx[dv.dn + l] = dxy, Dx[2 * (size_t)dv.dn + l] = dyy;
+    double *own = dv.Bm[buf] + (size_t)bd * dv.bm_stride + bm_offset(dv.T, 2 * l, 2 * l);
+    own[0] = dxx, own[2] = dxy, own[32] = dxy, own[34] = dyy;
+}
+
+// Thread 0 of block blockIdx.x: the robot entries t' = t + C u, phi' = phi + psi, P_RR' = G_R P_RR G_R^T + C3 P_s,RR C3^T (the
+// upper triangle, mirrored), the new landmark count and k_set_meta's bookkeeping and host mirror.
+__global__ void k_join_finish(EkfDev dv, JoinSrc sv, JoinRot one, const double *rot, int bd0, int bs0) {
+    if (threadIdx.x != 0) return;
+    const int bd = bd0 + blockIdx.x, bs = bs0 + blockIdx.x;
+    const JoinRot q = join_rot(one, rot, blockIdx.x);
+    double *x = dv.x + (size_t)bd * dv.xs;
+    double *R0 = dv.R + (size_t)bd * 3 * dv.xs;
+    const double *sx = sv.x + (size_t)bs * sv.xs;
+    const double *sR = sv.R + (size_t)bs * 3 * sv.xs;
+    const double ux = sx[0], uy = sx[1];
+    const double g[2] = {-(q.s * ux + q.c * uy), q.c * ux - q.s * uy};
+    double P[3][3], S[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = i; j < 3; j++) P[i][j] = P[j][i] = R0[(size_t)i * dv.xs + j], S[i][j] = S[j][i] = sR[(size_t)i * sv.xs + j];
+    double A[3][3];  // G_R P
+    for (int j = 0; j < 3; j++) A[0][j] = P[0][j] + g[0] * P[2][j], A[1][j] = P[1][j] + g[1] * P[2][j], A[2][j] = P[2][j];
+    const Rot2 cq = {q.c, -q.s};
+    double d[4];
+    rot_block(cq, S[0][0], S[0][1], S[0][1], S[1][1], d);
+    double p[3][3];
+    p[0][0] = (A[0][0] + A[0][2] * g[0]) + d[0];
+    p[0][1] = p[1][0] = (A[0][1] + A[0][2] * g[1]) + d[1];
+    p[1][1] = (A[1][1] + A[1][2] * g[1]) + d[3];
+    p[0][2] = p[2][0] = A[0][2] + (q.c * S[0][2] - q.s * S[1][2]);
+    p[1][2] = p[2][1] = A[1][2] + (q.s * S[0][2] + q.c * S[1][2]);
+    p[2][2] = A[2][2] + S[2][2];
+    const double tx = x[0] + (q.c * ux - q.s * uy), ty = x[1] + (q.s * ux + q.c * uy);
+    x[0] = tx, x[1] = ty, x[2] = x[2] + sx[2];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) R0[(size_t)i * dv.xs + j] = p[i][j];
+    const int n_lm = dv.n_lm[bd] + sv.n_lm[bs];
+    dv.n_lm[bd] = n_lm;
+    dv.n_lm_sweep[bd] = n_lm;
+    dv.n_lm_flush[(size_t)bd * 2] = n_lm;
+    dv.n_lm_flush[(size_t)bd * 2 + 1] = n_lm;
+    dv.status[bd] = 0;
+    EkfMirror *mr = dv.mirror + bd;
+    for (int i = 0; i < 3; i++) mr->pose[i] = x[i];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) mr->Prr[i * 3 + j] = p[i][j];
+    mr->n_lm = n_lm;
+    mr->status = 0;
+    mr->log_count = dv.log_count[bd];
+    for (int m = 0; m < 2 * dv.maxp; m++) dv.slot_active[(size_t)bd * 2 * dv.maxp + m] = 0;
+}
+
 // Probe pair for ekf_api's concurrency check: the waiter spins (bounded, about 2 ms) until the setter, launched on ANOTHER
 // stream after it, has run; out[0] = 1 when it saw the flag.  Under tools that serialise kernel execution it times out.
 __global__ void k_probe_wait(int *flag, int *out) {

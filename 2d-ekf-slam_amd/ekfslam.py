@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "ekf_reset_stats", "ekf_stats_means_device", "ekf_record_truth", "ekf_stream", "ekf_device_bytes", "ekf_debug_windows", "ekf_debug_stream", "ekf_debug_stream_ring",
     "ekf_remove_landmarks", "ekf_batch_remove_landmarks", "ekf_get_landmark_covs",
     "ekf_transform_frame", "ekf_batch_transform_frame", "ekf_anchor_at_robot", "ekf_batch_anchor_at_robot",
+    "ekf_join_map", "ekf_batch_join_map",
 ]
 
 
@@ -104,6 +105,8 @@ def load():
     L.ekf_batch_transform_frame.argtypes = [_H, _dp]
     L.ekf_anchor_at_robot.argtypes = [_H, ctypes.c_int]
     L.ekf_batch_anchor_at_robot.argtypes = [_H]
+    L.ekf_join_map.argtypes = [_H, ctypes.c_int, _H, ctypes.c_int]
+    L.ekf_batch_join_map.argtypes = [_H, _H]
     L.ekf_script_load.argtypes = [_H, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _up, _dp]
     L.ekf_script_run.argtypes = [_H, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.ekf_sync.argtypes = [_H]
@@ -303,6 +306,16 @@ class FilterBatch:
             _chk(self.L.ekf_batch_anchor_at_robot(self.h))
         else:
             _chk(self.L.ekf_anchor_at_robot(self.h, int(index)))
+
+    def join_map(self, src, index=0, src_index=0):
+        """Append the landmarks of filter src_index of `src` (a FilterBatch; may be this one when the indices differ) behind those of
+        filter `index` on the device (ekf_join_map).  src's frame origin must be this filter's current estimated pose and the two
+        estimates independent; duplicates are not fused.  Returns the new landmark count; `src` is only read."""
+        return _chk(self.L.ekf_join_map(self.h, int(index), src.h, int(src_index)))
+
+    def batch_join_map(self, src):
+        """Filter b of `src` into filter b of this batch for every b (ekf_batch_join_map; equal batch sizes, another handle)."""
+        _chk(self.L.ekf_batch_join_map(self.h, src.h))
 
     def script_load(self, ctrl, z, R, valid=None, truth=None):
         """ctrl (steps, batch, 3); z (steps, M, batch, 2); R (steps, M, batch, 4) column-major blocks;

@@ -208,6 +208,38 @@ int ekf_batch_transform_frame(ekf_handle h, const double *frames /*[batch][3]*/)
 int ekf_anchor_at_robot(ekf_handle h, int index);
 int ekf_batch_anchor_at_robot(ekf_handle h);
 
+/* Map joining on the device: the landmarks of filter src_index of `src` (a local submap) are appended behind the landmarks of
+ * filter dst_index of `dst`, without a trip through ekf_get_state / ekf_set_state.
+ * CONTRACT, the caller's responsibility: (1) frame -- the origin of src's frame is dst's CURRENT ESTIMATED robot pose, which is
+ * what a caller gets who starts the local filter fresh (x = 0_3, P = 0) or anchors it at the moment the previous join ended;
+ * (2) independence -- the two estimates share no information (no measurement went into both).
+ * With dst = (pose p = (t, phi), landmarks L_0..L_{Ng-1}, P_g), src = (pose q = (u, psi), landmarks M_0..M_{Ns-1}, P_s),
+ * C = Rot(phi), J = [[0,-1],[1,0]]:  the old landmarks stay bit for bit, M_k' = t + C M_k becomes landmark Ng + k (order kept),
+ * the robot becomes src's robot, t' = t + C u, phi' = phi + psi (not wrapped), and dst's old pose is marginalised out:
+ * P' = J_g P_g J_g^T + J_s P_s J_s^T.  With G_k = [I | C J M_k], G_R = [[I, C J u], [0 0 1]], C3 = diag(C, 1):
+ *   old m x old l  unchanged bit for bit        old m x new k  P_mR G_k^T        new k x new l  G_k P_RR G_l^T + C P_s,kl C^T
+ *   old m x robot  P_mR G_R^T                   new k x robot  G_k P_RR G_R^T + C P_s,kR C3^T
+ *   robot x robot  G_R P_RR G_R^T + C3 P_s,RR C3^T
+ * cos(phi) and sin(phi) are taken once on the host (libm).  Joining into a fresh filter reproduces src's state exactly; joining a
+ * fresh src leaves dst exactly as it was.  Landmarks that both maps hold are NOT recognised or fused: they stay two landmarks.
+ * A NEES sample (ekf_record_truth) needs the caller's truth to be a pose in dst's frame, as before the join.
+ * src may be the same handle as dst when the indices differ, or a handle of another capacity, kernel family and pipeline mode on
+ * the same device (another device: EKF_ERR_BAD_ARG).  src is only read: its state, counters, decision log and loaded script stay
+ * bitwise what they were, and its immediate-mode calls stream again afterwards.  Both filters' deferred slots are folded first
+ * (at most one window each, none on a settled handle), streaming launches are stopped, the call orders the two handles' streams
+ * itself and synchronises.  Returns the new landmark count Ng + Ns or a negative status.
+ * Ng + Ns > ekf_capacity(dst): EKF_ERR_CAPACITY with both filters' exported states untouched (their deferred slots have been
+ * folded and streaming launches stopped nonetheless); it is NOT sticky (no join kernel ran): call ekf_reserve and join again.
+ * Other bad arguments (NULL, an index out of range, src == dst with equal indices) return EKF_ERR_BAD_ARG and leave both
+ * handles untouched; a sticky EKF_ERR_TIMEOUT / EKF_ERR_CAPACITY of either handle is returned unchanged with nothing modified.
+ * dst afterwards: counters and decision log unchanged, the host mirror shows the new pose, P_RR and landmark count, and every
+ * device buffer ends as ekf_set_state of the joined state would leave it (a loaded script stays loaded, ekf_reserve works before
+ * and after).
+ * ekf_batch_join_map: filter b of src into filter b of dst for every b in one launch sequence; equal batch sizes, src != dst.
+ * Returns EKF_OK or a negative status; one filter without room fails the whole call with nothing modified. */
+int ekf_join_map(ekf_handle dst, int dst_index, ekf_handle src, int src_index);
+int ekf_batch_join_map(ekf_handle dst, ekf_handle src);
+
 /* ---- device-resident step scripts (benchmarks, Monte-Carlo runs) ------------------------------
  * A script is `steps` steps; step s of filter b is
  *     Propagate(ctrl[s][b] = v, w, dt)  with Q from params as ekf_propagate does,
