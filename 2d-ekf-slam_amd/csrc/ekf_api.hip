@@ -22,6 +22,7 @@
 // single translation unit: the kernels are compiled together with their launch sites
 #include "ekf_kernels.hip"
 #include "ekf_solo.hip"
+#include "ekf_rewrite.hip"
 
 static thread_local std::string g_last_error;
 
@@ -2010,7 +2011,7 @@ static int remove_impl(ekf_batch *h, const unsigned char *keep, int ld_keep, int
             if (!k || l >= ld_keep || k[l]) map[n_new++] = l;  // (landmarks without an entry are kept)
         rm[2 * b] = n_old, rm[2 * b + 1] = n_new;
         any = any || n_new != n_old;
-        const int to = (2 * n_old + 63) / 64, tn = (2 * n_new + 63) / 64;
+        const int to = lm_tiles(n_old), tn = lm_tiles(n_new);
         nTo = to > nTo ? to : nTo;
         nTn = tn > nTn ? tn : nTn;
         if (n_out) n_out[b] = n_new;
@@ -2050,7 +2051,20 @@ extern "C" int ekf_batch_remove_landmarks(ekf_handle h, const unsigned char *kee
     return remove_impl(h, keep, ld_keep, -1, n_out);
 }
 
-// Frame changes on the device (ekf_kernels.hip: k_reframe_vec, k_reframe_tiles, k_reframe_finish), the order of steps as in
+// The per-filter argument of a rewrite launch over nb filters (ekf_rewrite.hip: arg_value), vals = [nb][doubles of A]: a one-filter
+// call carries it in the kernel arguments (*one), a batch call in a transient table (copied synchronously: vals may leave scope).
+template <typename A>
+static int rewrite_arg(const std::vector<double> &vals, int nb, A *one, DevTmp<double> *tab) {
+    if (nb == 1) {
+        memcpy(one, vals.data(), sizeof(A));
+        return EKF_OK;
+    }
+    HIP_TRY(tab->alloc(vals.size()));
+    HIP_TRY(hipMemcpy(tab->p, vals.data(), vals.size() * sizeof(double), hipMemcpyHostToDevice));
+    return EKF_OK;
+}
+
+// Frame changes on the device (ekf_rewrite.hip: k_reframe_vec, k_reframe_tiles, k_reframe_finish), the order of steps as in
 // remove_impl.  frames == nullptr: anchor at the robot; else one (t_x, t_y, theta) per filter of the launch.  index < 0: every
 // filter, one launch sequence with the grid over the filters.  Bm is rewritten in place in the settled buffer (either pipeline
 // mode: no second buffer, no scratch); the only transient allocation is the BATCH rigid call's frame table (48 bytes per filter; a
@@ -2064,7 +2078,7 @@ static int reframe_impl(ekf_batch *h, int index, const double *frames) {
     const int b_off = index < 0 ? 0 : index, nb = index < 0 ? dv.B : 1;
     int nT = 0;
     for (int b = b_off; b < b_off + nb; b++) {
-        const int t = (2 * h->h_int[b] + 63) / 64;
+        const int t = lm_tiles(h->h_int[b]);
         nT = t > nT ? t : nT;
     }
     hipStream_t s = h->s_chain;
@@ -2076,12 +2090,7 @@ static int reframe_impl(ekf_batch *h, int index, const double *frames) {
             const double *f = frames + 3 * (size_t)k;
             fr[6 * k] = f[0], fr[6 * k + 1] = f[1], fr[6 * k + 2] = cos(f[2]), fr[6 * k + 3] = sin(f[2]), fr[6 * k + 4] = f[2];
         }
-        if (nb == 1) {
-            for (int k = 0; k < 6; k++) one.v[k] = fr[k];
-        } else {
-            HIP_TRY(fr_d.alloc(fr.size()));
-            HIP_TRY(hipMemcpy(fr_d.p, fr.data(), fr.size() * sizeof(double), hipMemcpyHostToDevice));  // (fr leaves scope: synchronous)
-        }
+        EKF_TRY(rewrite_arg(fr, nb, &one, &fr_d));
     }
     const double *frc = fr_d.p;
     const auto k_vec = frames ? k_reframe_vec<false> : k_reframe_vec<true>;  // <ANCHOR>
@@ -2120,7 +2129,7 @@ extern "C" int ekf_batch_anchor_at_robot(ekf_handle h) {
     return reframe_impl(h, -1, nullptr);
 }
 
-// Map joining on the device (ekf_kernels.hip: k_join_tiles, k_join_vec, k_join_finish).  di < 0: the batch form, filter b of `s`
+// Map joining on the device (ekf_rewrite.hip: k_join_tiles, k_join_vec, k_join_finish).  di < 0: the batch form, filter b of `s`
 // into filter b of `d`.  Both handles are brought to rest first (the source is only read afterwards, so its own quiescing is all
 // that ever happens to it), which also orders their streams: everything runs on the destination's chain stream while the source's
 // streams are idle, and the call waits for it.  Bm is rewritten in place in the destination's settled buffer in either pipeline
@@ -2143,17 +2152,12 @@ static int join_impl(ekf_batch *d, int di, ekf_batch *s, int si) {
         nv = Ng + Ns > nv ? Ng + Ns : nv;
     }
     DevTmp<double> rot_d;
-    JoinRot one = {1.0, 0.0};
+    Rot2 one = {1.0, 0.0};
     // (the host mirror's heading is the device's x[2] bit for bit once the chain stream is idle: every writer of x[0..2] -- the chain
     // kernels, k_set_meta, the finish kernels -- copies the pose into the mirror; a dense pass does not touch it)
-    if (nb == 1) {
-        one.c = cos(d->mirror_h[bd0].pose[2]), one.s = sin(d->mirror_h[bd0].pose[2]);
-    } else {
-        std::vector<double> rot((size_t)nb * 2);
-        for (int k = 0; k < nb; k++) rot[2 * k] = cos(d->mirror_h[bd0 + k].pose[2]), rot[2 * k + 1] = sin(d->mirror_h[bd0 + k].pose[2]);
-        HIP_TRY(rot_d.alloc(rot.size()));
-        HIP_TRY(hipMemcpy(rot_d.p, rot.data(), rot.size() * sizeof(double), hipMemcpyHostToDevice));  // (rot leaves scope: synchronous)
-    }
+    std::vector<double> rot((size_t)nb * 2);
+    for (int k = 0; k < nb; k++) rot[2 * k] = cos(d->mirror_h[bd0 + k].pose[2]), rot[2 * k + 1] = sin(d->mirror_h[bd0 + k].pose[2]);
+    EKF_TRY(rewrite_arg(rot, nb, &one, &rot_d));
     const EkfDev &sd = s->dv;
     const JoinSrc sv = {sd.x, sd.R, sd.D, sd.Bm[s->buf_in], sd.n_lm, sd.xs, sd.dn, sd.T, sd.bm_stride};
     const double *rotc = rot_d.p;

@@ -184,16 +184,22 @@ struct EkfDev {
 // (I*T - I(I-1)/2 + J - I)-th 4096-double tile.  Inside a tile, 16 chains (row16-block rc, col16-
 // block cc) of 256 doubles; a chain is the C/D operand of v_mfma_f64_16x16x4_f64 stored as two
 // wave-contiguous 1 KiB pieces: piece h holds registers 2h, 2h+1 of every lane, lane = 16*(row&3)
-// + col, register = row>>2.
+// + col, register = row>>2.  bm_tile_base: the offset of stored tile (I, J), I <= J < T, alone.
+__host__ __device__ inline size_t bm_tile_base(int T, int I, int J) {
+    return ((size_t)I * T - ((size_t)I * (I - 1)) / 2 + (size_t)(J - I)) * 4096;
+}
 __host__ __device__ inline size_t bm_offset(int T, int ip, int jp) {
     int I = ip >> 6, J = jp >> 6;
-    size_t t = (size_t)I * T - ((size_t)I * (I - 1)) / 2 + (size_t)(J - I);
+    size_t t = (size_t)I * T - ((size_t)I * (I - 1)) / 2 + (size_t)(J - I);  // (= bm_tile_base / 4096, kept in its own words: the hot kernels' code follows them)
     int il = ip & 63, jl = jp & 63;
     int chain = (il >> 4) * 4 + (jl >> 4);
     int rho = il & 15, c = jl & 15;
     int r = rho >> 2, g = rho & 3;
     return t * 4096 + (size_t)chain * 256 + (size_t)(r >> 1) * 128 + (size_t)(g * 16 + c) * 2 + (r & 1);
 }
+
+// Tiles per side of the P_LL of n landmarks: the tile of the last landmark row, 2n - 1, plus one.
+__host__ __device__ inline int lm_tiles(int n) { return (2 * n + 63) >> 6; }
 
 // The inverse of bm_offset inside one tile: tile-local offset o (0..4095) -> tile-local row il, column jl.
 __host__ __device__ inline void bm_tile_coords(int o, int *il, int *jl) {
@@ -257,6 +263,14 @@ __host__ __device__ inline int bm_chain_offset(int rho, int c) {
     return (r >> 1) * 128 + (g * 16 + c) * 2 + (r & 1);
 }
 
+// (I, J) of stored tile t of a triangle with side nT, in storage order (t = I*nT - I(I-1)/2 + J - I): the grid of the kernels that
+// take one workgroup per tile (removal, frame changes)
+__host__ __device__ inline void tri_tile_ij(int t, int nT, int *I, int *J) {
+    int i = 0;
+    while (t >= nT - i) t -= nT - i, i++;
+    *I = i, *J = i + t;
+}
+
 // Map joining (ekf_join_map) appends the Ns landmarks of a source filter behind the Ng landmarks of the destination: only the tile
 // COLUMNS from J0 = Ng / 32 on hold a new column, and one workgroup rewrites each of their tiles (I <= J), gathered by destination.
 // Tile t of that list (column after column) is (I, J); false behind the last column J1 - 1, J1 = tiles per side of the joined map.
@@ -267,7 +281,7 @@ __host__ __device__ inline bool join_tile_ij(int t, int J0, int J1, int *I, int 
     return j < J1;
 }
 __host__ __device__ inline int join_tile_count(int Ng, int Ns) {
-    const int J0 = Ng >> 5, J1 = (2 * (Ng + Ns) + 63) >> 6;
+    const int J0 = Ng >> 5, J1 = lm_tiles(Ng + Ns);
     return Ns > 0 ? J1 * (J1 + 1) / 2 - J0 * (J0 + 1) / 2 : 0;
 }
 

@@ -25,6 +25,7 @@ SENSITIVE = ("_f64", "mfma", "ds_", "global_", "buffer_", "flat_", "s_barrier", 
 def normalise(line):
     line = re.sub(r"BB\d+_", "BB_", line)  # (labels .LBB<n>_<k> and the loop comments that name them)
     line = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", line)
+    line = re.sub(r"^(\.LBB_\d+:)\s+;", r"\1 ;", line)  # (the comment's column moves with the number of digits of <n>)
     return line.rstrip()
 
 

@@ -1,6 +1,7 @@
 // Host-only check of the HBM index maps in ekf_device.h: bm_offset must be a bijection from the
 // stored (i', j') pairs onto [0, tiles*4096) and agree with the MFMA C/D fragment order the dense
 // pass assumes; pair_offset must be a bijection onto the slot array with one landmark per 64-byte line.
+// The tile-level helpers the rewrite kernels share (tri_tile_ij, bm_tile_base, lm_tiles) must agree with bm_offset's numbering.
 #include <cstdio>
 #include <vector>
 
@@ -44,6 +45,22 @@ int main() {
     for (int p = 0; p < pairs; p++)
         for (int i = 0; i < n; i += 2)
             if (pair_offset(rows, i + 1, p) - pair_offset(rows, i, p) != 4 || (pair_offset(rows, i, p) % 8) != 0) return printf("landmark line mismatch\n"), 1;
+    for (int Tt = 1; Tt <= 9; Tt++) {
+        int t = 0;
+        for (int I = 0; I < Tt; I++)
+            for (int J = I; J < Tt; J++, t++) {  // storage order: every (I, J), I <= J < Tt, exactly once
+                int gi, gj;
+                tri_tile_ij(t, Tt, &gi, &gj);
+                if (gi != I || gj != J) return printf("tri_tile_ij(%d, %d) = (%d, %d), want (%d, %d)\n", t, Tt, gi, gj, I, J), 1;
+                if (bm_tile_base(Tt, I, J) != bm_offset(Tt, 64 * I, 64 * J)) return printf("bm_tile_base(%d, %d, %d) is not bm_offset's tile\n", Tt, I, J), 1;
+                if (bm_tile_base(Tt, I, J) != (size_t)t * 4096) return printf("bm_tile_base(%d, %d, %d) is not tile %d\n", Tt, I, J, t), 1;
+            }
+        if (t != Tt * (Tt + 1) / 2) return printf("triangle of side %d has %d tiles\n", Tt, t), 1;
+        if (bm_tile_base(Tt, Tt - 1, Tt - 1) + 4096 != (size_t)Tt * (Tt + 1) / 2 * 4096) return printf("last tile of side %d\n", Tt), 1;
+    }
+    if (lm_tiles(0) != 0) return printf("lm_tiles(0) = %d\n", lm_tiles(0)), 1;
+    for (int nl = 1; nl <= 300; nl++)  // the last landmark row is 2 nl - 1
+        if (lm_tiles(nl) != ((2 * nl - 1) >> 6) + 1) return printf("lm_tiles(%d) = %d\n", nl, lm_tiles(nl)), 1;
     printf("layout ok\n");
     return 0;
 }

@@ -1,4 +1,6 @@
-"""Shared test helpers: the parity tolerance of BASELINE.json's north_star, made well-defined."""
+"""Shared test helpers: the parity tolerance of BASELINE.json's north_star, made well-defined, and the scaffolding of the GPU tests of
+the map operations (removal, frame change, joining): injected filters, immediate-call scripts, window and stream probes."""
+import ctypes
 import functools
 import subprocess
 import sys
@@ -65,6 +67,92 @@ def correlated_state(pkg, oc, copies=16, rho=0.8, seed=20260011, n_landmarks=64,
             P[a:a + 2 * Ns, b:b + 2 * Ns] = (1.0 if c == d else rho) * Ps[3:, 3:]
     P = 0.5 * (P + P.T)
     return x, P
+
+
+def assert_bitwise(a, b, what=""):
+    """Two exported states (x, P), equal bit for bit."""
+    assert a[0].shape == b[0].shape and a[1].shape == b[1].shape, (what, a[0].shape, b[0].shape)
+    assert np.array_equal(a[0], b[0]), "%s: x differs" % what
+    dP = a[1] != b[1]
+    assert not dP.any(), "%s: P differs at %d elements, first %s" % (what, int(dP.sum()), np.argwhere(dP)[:3].tolist())
+
+
+def windows_closed(f):
+    f.L.ekf_debug_windows.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int)]
+    a, b = ctypes.c_longlong(), ctypes.c_int()
+    assert f.L.ekf_debug_windows(f.h, ctypes.byref(a), ctypes.byref(b)) == 0
+    return a.value
+
+
+def stream_starts(f):
+    f.L.ekf_debug_stream.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
+    a, b = ctypes.c_longlong(), ctypes.c_longlong()
+    on = f.L.ekf_debug_stream(f.h, ctypes.byref(a), ctypes.byref(b))
+    return on, a.value
+
+
+def far_feature(pkg, k):
+    """A feature well away from every landmark of the injected maps and from the other far features: a New landmark."""
+    return pkg.scenarios.measurement_from_feature_mm(70000.0 + 9000.0 * (k % 7), -40000.0 + 11000.0 * (k // 7))
+
+
+def run_steps(pkg, f, sc, s0, steps, M, new_every=0, k_new=0, oracle=None, oc=None):
+    """Immediate calls on a one-filter handle: propagate, M Old-type measurements of the script, every `new_every`-th step a far
+    feature (New).  Returns the decisions with their distances (and advances `oracle`, an oc.Session, the same way, asserting
+    identical decisions)."""
+    decs = []
+    for s in range(s0, s0 + steps):
+        v, w, dt = sc["ctrl"][s]
+        f.propagate(v, w, dt)
+        if oracle is not None:
+            oracle.propagate(v, w, oc.make_Q(v), dt)
+        meas = [(sc["z"][s, m], sc["R"][s, m].reshape(2, 2, order="F")) for m in range(M)]
+        if new_every and s % new_every == 0:
+            meas.append(far_feature(pkg, k_new))
+            k_new += 1
+        for z, R in meas:
+            d = f.update(z.reshape(1, 1, 2), R.reshape(1, 1, 2, 2))[0][0]
+            decs.append(d)
+            if oracle is not None:
+                od, om, _ = oracle.update(z.reshape(2, 1), R)
+                assert (d[0], d[1]) == (od[0], om[0]), (s, d, od, om)
+    return decs, k_new
+
+
+def make_filter(pkg, N, cap, seed, extent=None, max_pending=16):
+    """A one-filter handle loaded with the fixed-seed injected state of N landmarks."""
+    x0, P0 = pkg.scenarios.injected_state(N, seed=seed, extent=extent or 12.0 * (N / 64.0) ** 0.5 + 8.0)
+    f = pkg.FilterBatch(1, cap, max_pending=max_pending, log_capacity=4096)
+    f.set_state(x0, P0)
+    return f, x0, P0
+
+
+def open_window_pair(pkg, N, cap, seed, steps, extent=None, M=2, max_pending=16):
+    """Handles A and B after the same immediate calls (window open, streaming launch live on both) and their script; B is the witness
+    whose export, counters and decisions say what A held in front of the call under test."""
+    a, x0, _ = make_filter(pkg, N, cap, seed, extent, max_pending)
+    b, _, _ = make_filter(pkg, N, cap, seed, extent, max_pending)
+    sc = pkg.scenarios.steady_script(x0, steps=steps, M=M, seed=seed + 1, min_separation=1.0)
+    da, _ = run_steps(pkg, a, sc, 0, steps, M)
+    db, _ = run_steps(pkg, b, sc, 0, steps, M)
+    assert da == db
+    return a, b, sc
+
+
+def batch_script(pkg, B, steps, M):
+    """A script for B filters: measurement 0 near the robot (Old or New as it falls), the others far features (New)."""
+    ctrl = np.tile(np.array([0.3, 0.05, 0.05]), (steps, B, 1))
+    z = np.empty((steps, M, B, 2))
+    R = np.empty((steps, M, B, 4))
+    for s in range(steps):
+        for m in range(M):
+            for b in range(B):
+                if m == 0:
+                    zz, RR = pkg.scenarios.measurement_from_feature_mm(3000.0 + 37.0 * ((b + s) % 11), 800.0 - 53.0 * ((b * 3 + s) % 7))
+                else:
+                    zz, RR = far_feature(pkg, s + 3 * b % 5)
+                z[s, m, b], R[s, m, b] = zz, RR.ravel(order="F")
+    return ctrl, z, R
 
 
 @functools.lru_cache(maxsize=None)

@@ -13,26 +13,12 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import join_ref as jr  # noqa: E402
-from helpers import assert_bitwise_symmetric, assert_state_close  # noqa: E402
+from helpers import assert_bitwise, assert_bitwise_symmetric, assert_state_close, open_window_pair  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SIZES = [(200, 320), (100, 200)]
 NS, CAP_S = 70, 96
-
-
-def assert_bitwise(a, b, what=""):
-    assert a[0].shape == b[0].shape and a[1].shape == b[1].shape, (what, a[0].shape, b[0].shape)
-    assert np.array_equal(a[0], b[0]), "%s: x differs" % what
-    dP = a[1] != b[1]
-    assert not dP.any(), "%s: P differs at %d elements, first %s" % (what, int(dP.sum()), np.argwhere(dP)[:3].tolist())
-
-
-def make_filter(pkg, N, cap, seed, extent=None, max_pending=16):
-    x0, P0 = pkg.scenarios.injected_state(N, seed=seed, extent=extent or 12.0 * (N / 64.0) ** 0.5 + 8.0)
-    f = pkg.FilterBatch(1, cap, max_pending=max_pending, log_capacity=4096)
-    f.set_state(x0, P0)
-    return f, x0, P0
 
 
 def run_script(f, sc, steps, M):
@@ -43,16 +29,6 @@ def run_script(f, sc, steps, M):
         for m in range(M):
             decs.append(f.update(sc["z"][s, m].reshape(1, 1, 2), sc["R"][s, m].reshape(2, 2, order="F").reshape(1, 1, 2, 2))[0][0])
     return decs
-
-
-def open_window_pair(pkg, N, cap, seed, extent=None, steps=3, M=2, max_pending=16):
-    """Two handles after the same immediate calls (window open, streaming launch live on both); the second one is the witness whose
-    export, counters and decisions say what the first one held in front of the call."""
-    a, x0, _ = make_filter(pkg, N, cap, seed, extent, max_pending)
-    b, _, _ = make_filter(pkg, N, cap, seed, extent, max_pending)
-    sc = pkg.scenarios.steady_script(x0, steps=steps, M=M, seed=seed + 1, min_separation=1.0)
-    assert run_script(a, sc, steps, M) == run_script(b, sc, steps, M)
-    return a, b
 
 
 def measurement_of(pkg, x, l):
@@ -111,8 +87,8 @@ def continue_both(pkg, a, b, Ng, Ns):
 # ---- 1. parity with windows open on both filters ------------------------------------------------------
 @pytest.mark.parametrize("N,cap", SIZES)
 def test_parity_with_windows_open_on_both_filters(pkg, pipeline_mode, N, cap):
-    a, aw = open_window_pair(pkg, N, cap, seed=11)
-    s, sw = open_window_pair(pkg, NS, CAP_S, seed=15, extent=8.0)
+    a, aw, _ = open_window_pair(pkg, N, cap, seed=11, steps=3)
+    s, sw, _ = open_window_pair(pkg, NS, CAP_S, seed=15, extent=8.0, steps=3)
     xg, Pg = aw.get_state()
     xs, Ps = sw.get_state()
     st_a, dec_a, st_s, dec_s = aw.stats(), aw.decisions(), sw.stats(), sw.decisions()
@@ -139,7 +115,7 @@ def test_parity_with_windows_open_on_both_filters(pkg, pipeline_mode, N, cap):
 # ---- 2. exact cases ---------------------------------------------------------------------------------
 @pytest.mark.parametrize("cap", [320, 200])
 def test_join_into_a_fresh_filter_reproduces_the_source(pkg, pipeline_mode, cap):
-    s, sw = open_window_pair(pkg, NS, CAP_S, seed=25, extent=8.0)
+    s, sw, _ = open_window_pair(pkg, NS, CAP_S, seed=25, extent=8.0, steps=3)
     a = pkg.FilterBatch(1, cap, max_pending=16, log_capacity=4096)
     assert a.join_map(s) == NS
     xa, Pa = a.get_state()
@@ -151,7 +127,7 @@ def test_join_into_a_fresh_filter_reproduces_the_source(pkg, pipeline_mode, cap)
 
 @pytest.mark.parametrize("N,cap", SIZES)
 def test_join_of_a_fresh_source_leaves_the_destination_unchanged(pkg, pipeline_mode, N, cap):
-    a, aw = open_window_pair(pkg, N, cap, seed=31)
+    a, aw, _ = open_window_pair(pkg, N, cap, seed=31, steps=3)
     s = pkg.FilterBatch(1, CAP_S, max_pending=16, log_capacity=4096)
     assert a.join_map(s) == N
     xa, Pa = a.get_state()
@@ -166,8 +142,8 @@ def test_join_of_a_fresh_source_leaves_the_destination_unchanged(pkg, pipeline_m
 @pytest.mark.parametrize("reserve_first", [False, True])
 @pytest.mark.parametrize("N,cap", SIZES)
 def test_set_state_twin_goes_on_bit_for_bit(pkg, pipeline_mode, N, cap, reserve_first):
-    a, aw = open_window_pair(pkg, N, cap, seed=41, max_pending=8)
-    s, sw = open_window_pair(pkg, NS, CAP_S, seed=45, extent=8.0)
+    a, aw, _ = open_window_pair(pkg, N, cap, seed=41, max_pending=8, steps=3)
+    s, sw, _ = open_window_pair(pkg, NS, CAP_S, seed=45, extent=8.0, steps=3)
     aw.close(), sw.close()
     a.join_map(s)
     s.close()
@@ -230,8 +206,8 @@ def test_batch_form_equals_single_joins(pkg, pipeline_mode):
 
 # ---- 5. errors ------------------------------------------------------------------------------------------
 def test_errors_change_nothing_and_capacity_is_not_sticky(pkg, pipeline_mode):
-    a, aw = open_window_pair(pkg, 60, 64, seed=81)
-    s, sw = open_window_pair(pkg, 10, 32, seed=85, extent=8.0)
+    a, aw, _ = open_window_pair(pkg, 60, 64, seed=81, steps=3)
+    s, sw, _ = open_window_pair(pkg, 10, 32, seed=85, extent=8.0, steps=3)
     aw.close(), sw.close()
     held_a, held_s = a.get_state(), s.get_state()
     n_joined = (held_a[0].size - 3) // 2 + (held_s[0].size - 3) // 2
@@ -261,8 +237,8 @@ def test_errors_change_nothing_and_capacity_is_not_sticky(pkg, pipeline_mode):
 # ---- 6. join after removal --------------------------------------------------------------------------------
 @pytest.mark.parametrize("N,cap", SIZES)
 def test_join_after_removal_reuses_the_freed_rows(pkg, pipeline_mode, N, cap):
-    a, aw = open_window_pair(pkg, N, cap, seed=91, max_pending=8)
-    s, sw = open_window_pair(pkg, NS, CAP_S, seed=95, extent=8.0)
+    a, aw, _ = open_window_pair(pkg, N, cap, seed=91, max_pending=8, steps=3)
+    s, sw, _ = open_window_pair(pkg, NS, CAP_S, seed=95, extent=8.0, steps=3)
     keep = np.ones(N, dtype=bool)
     keep[1::3] = False  # spread over every tile
     n_kept = int(keep.sum())

@@ -12,75 +12,13 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import reframe_ref as rr  # noqa: E402
-from helpers import ABS_X, REL_TOL, assert_bitwise_symmetric, assert_state_close  # noqa: E402
+from helpers import (ABS_X, REL_TOL, assert_bitwise, assert_bitwise_symmetric, assert_state_close, batch_script,  # noqa: E402
+                     make_filter, open_window_pair, run_steps, stream_starts, windows_closed)
 
 pytestmark = pytest.mark.gpu
 
 FRAME = (3.0, -2.0, 0.7)
 SIZES = [(280, 320), (180, 200)]  # (capacity > 256: the several-workgroup chain kernel; <= 256: the one-workgroup kernel)
-pkg_scen = None
-
-
-@pytest.fixture(autouse=True)
-def _scen(pkg):
-    global pkg_scen
-    pkg_scen = pkg.scenarios
-
-
-def assert_bitwise(a, b, what=""):
-    assert a[0].shape == b[0].shape and a[1].shape == b[1].shape, (what, a[0].shape, b[0].shape)
-    assert np.array_equal(a[0], b[0]), "%s: x differs" % what
-    dP = a[1] != b[1]
-    assert not dP.any(), "%s: P differs at %d elements, first %s" % (what, int(dP.sum()), np.argwhere(dP)[:3].tolist())
-
-
-def windows_closed(f):
-    f.L.ekf_debug_windows.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int)]
-    a, b = ctypes.c_longlong(), ctypes.c_int()
-    assert f.L.ekf_debug_windows(f.h, ctypes.byref(a), ctypes.byref(b)) == 0
-    return a.value
-
-
-def stream_starts(f):
-    f.L.ekf_debug_stream.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
-    a, b = ctypes.c_longlong(), ctypes.c_longlong()
-    on = f.L.ekf_debug_stream(f.h, ctypes.byref(a), ctypes.byref(b))
-    return on, a.value
-
-
-def far_feature(k):
-    """A feature well away from every landmark of the injected maps and from the other far features: a New landmark."""
-    return pkg_scen.measurement_from_feature_mm(70000.0 + 9000.0 * (k % 7), -40000.0 + 11000.0 * (k // 7))
-
-
-def run_steps(f, sc, s0, steps, M, new_every=0, k_new=0, oracle=None, oc=None):
-    """Immediate calls on a one-filter handle: propagate, M Old-type measurements of the script, every `new_every`-th step a far
-    feature (New).  Returns the decisions with their distances (and advances `oracle`, an oc.Session, the same way, asserting
-    identical decisions)."""
-    decs = []
-    for s in range(s0, s0 + steps):
-        v, w, dt = sc["ctrl"][s]
-        f.propagate(v, w, dt)
-        if oracle is not None:
-            oracle.propagate(v, w, oc.make_Q(v), dt)
-        meas = [(sc["z"][s, m], sc["R"][s, m].reshape(2, 2, order="F")) for m in range(M)]
-        if new_every and s % new_every == 0:
-            meas.append(far_feature(k_new))
-            k_new += 1
-        for z, R in meas:
-            d = f.update(z.reshape(1, 1, 2), R.reshape(1, 1, 2, 2))[0][0]
-            decs.append(d)
-            if oracle is not None:
-                od, om, _ = oracle.update(z.reshape(2, 1), R)
-                assert (d[0], d[1]) == (od[0], om[0]), (s, d, od, om)
-    return decs, k_new
-
-
-def make_filter(pkg, N, cap, seed, max_pending=16):
-    x0, P0 = pkg.scenarios.injected_state(N, seed=seed, extent=12.0 * (N / 64.0) ** 0.5 + 8.0)
-    f = pkg.FilterBatch(1, cap, max_pending=max_pending, log_capacity=4096)
-    f.set_state(x0, P0)
-    return f, x0, P0
 
 
 def apply_call(f, call, frame=FRAME, index=0):
@@ -94,22 +32,11 @@ def reference(call, x, P, frame=FRAME):
     return rr.rigid(x, P, frame) if call == "rigid" else rr.anchor(x, P)
 
 
-def open_window_pair(pkg, N, cap, seed, steps=5, M=2, max_pending=16):
-    """Handles A and B after the same immediate calls (window open, streaming launch live); B's export is the state in front of the call."""
-    a, x0, P0 = make_filter(pkg, N, cap, seed, max_pending)
-    b, _, _ = make_filter(pkg, N, cap, seed, max_pending)
-    sc = pkg.scenarios.steady_script(x0, steps=steps, M=M, seed=seed + 1, min_separation=1.0)
-    da, _ = run_steps(a, sc, 0, steps, M)
-    db, _ = run_steps(b, sc, 0, steps, M)
-    assert da == db
-    return a, b, sc
-
-
 # ---- 1. parity with a window open ------------------------------------------------------------------
 @pytest.mark.parametrize("call", ["rigid", "anchor"])
 @pytest.mark.parametrize("N,cap", SIZES)
 def test_parity_with_a_window_open(pkg, pipeline_mode, N, cap, call):
-    a, b, _ = open_window_pair(pkg, N, cap, seed=11)
+    a, b, _ = open_window_pair(pkg, N, cap, seed=11, steps=5)
     before = b.get_state()
     st_b, dec_b = b.stats(), b.decisions()
     apply_call(a, call)
@@ -128,7 +55,7 @@ def test_parity_with_a_window_open(pkg, pipeline_mode, N, cap, call):
 # ---- 2. pure translation is exact ---------------------------------------------------------------------
 @pytest.mark.parametrize("N,cap", SIZES)
 def test_pure_translation_is_exact(pkg, pipeline_mode, N, cap):
-    a, b, _ = open_window_pair(pkg, N, cap, seed=21)
+    a, b, _ = open_window_pair(pkg, N, cap, seed=21, steps=5)
     x, P = b.get_state()
     a.transform_frame((3.0, -2.0, 0.0), index=0)
     xa, Pa = a.get_state()
@@ -143,7 +70,7 @@ def test_pure_translation_is_exact(pkg, pipeline_mode, N, cap):
 # ---- 3. anchor exactness ------------------------------------------------------------------------------
 @pytest.mark.parametrize("N,cap", SIZES)
 def test_anchor_is_exact_at_the_robot(pkg, pipeline_mode, N, cap):
-    a, b, _ = open_window_pair(pkg, N, cap, seed=31)
+    a, b, _ = open_window_pair(pkg, N, cap, seed=31, steps=5)
     a.anchor_at_robot(index=0)
     assert np.array_equal(a.poses()[0], np.zeros(3))
     assert np.array_equal(a.robot_cov(), np.zeros((3, 3)))
@@ -169,8 +96,8 @@ def test_continuation_twin_and_oracle(pkg, oc, pipeline_mode, N, cap, call):
     xr, Pr = reference(call, *before)
     S = oc.Session(xr, Pr, capacity_landmarks=cap)
     sc2 = pkg.scenarios.steady_script(xr, steps=12, M=2, seed=44, min_separation=1.0)
-    da, ka = run_steps(a, sc2, 0, 12, 2, new_every=2, oracle=S, oc=oc)
-    db, kb = run_steps(b, sc2, 0, 12, 2, new_every=2)
+    da, ka = run_steps(pkg, a, sc2, 0, 12, 2, new_every=2, oracle=S, oc=oc)
+    db, kb = run_steps(pkg, b, sc2, 0, 12, 2, new_every=2)
     assert da == db and ka == kb == 6
     assert sum(1 for d in da if d[0] == pkg.ekfslam.NEW) >= 6 and int(a.num_landmarks()[0]) >= N + 6
     sa, sb = a.get_state(), b.get_state()
@@ -186,10 +113,10 @@ def test_filter_is_equivariant_under_a_rigid_transform(pkg, pipeline_mode, N, ca
     a, x0, P0 = make_filter(pkg, N, cap, seed=11)
     b, _, _ = make_filter(pkg, N, cap, seed=11)
     sc = pkg.scenarios.steady_script(x0, steps=6, M=3, seed=12, min_separation=1.0)
-    da, _ = run_steps(a, sc, 0, 6, 3)
+    da, _ = run_steps(pkg, a, sc, 0, 6, 3)
     a.transform_frame(FRAME, index=0)
     b.transform_frame(FRAME, index=0)
-    db, _ = run_steps(b, sc, 0, 6, 3)
+    db, _ = run_steps(pkg, b, sc, 0, 6, 3)
     assert [(d[0], d[1]) for d in da] == [(d[0], d[1]) for d in db]
     assert all(d[0] == pkg.ekfslam.OLD for d in da)
     sa, sb = a.get_state(), b.get_state()
@@ -201,7 +128,7 @@ def test_filter_is_equivariant_under_a_rigid_transform(pkg, pipeline_mode, N, ca
 # ---- 6. anchored blocks are innovation covariances ------------------------------------------------------
 @pytest.mark.parametrize("N,cap", SIZES)
 def test_anchored_blocks_are_innovation_covariances(pkg, pipeline_mode, N, cap):
-    a, b, sc = open_window_pair(pkg, N, cap, seed=61)
+    a, b, sc = open_window_pair(pkg, N, cap, seed=61, steps=5)
     b.close()
     a.anchor_at_robot(index=0)
     for s in range(3):  # (each update moves the state: read it again, still without a propagation in between)
@@ -235,21 +162,6 @@ def test_full_size(pkg, pipeline_mode, call):
     a.close()
 
 
-def _batch_script(B, steps, M):
-    ctrl = np.tile(np.array([0.3, 0.05, 0.05]), (steps, B, 1))
-    z = np.empty((steps, M, B, 2))
-    R = np.empty((steps, M, B, 4))
-    for s in range(steps):
-        for m in range(M):
-            for b in range(B):
-                if m == 0:
-                    zz, RR = pkg_scen.measurement_from_feature_mm(3000.0 + 37.0 * ((b + s) % 11), 800.0 - 53.0 * ((b * 3 + s) % 7))
-                else:
-                    zz, RR = far_feature(s + 3 * b % 5)
-                z[s, m, b], R[s, m, b] = zz, RR.ravel(order="F")
-    return ctrl, z, R
-
-
 def test_batch_every_filter_its_own_frame(pkg, pipeline_mode):
     """256 filters x 256 landmarks: a different frame per filter in one call, each filter against its own reference; then the batch
     anchor the same way; then a scripted continuation against a twin batch loaded with set_state: bitwise."""
@@ -258,7 +170,7 @@ def test_batch_every_filter_its_own_frame(pkg, pipeline_mode):
     f = pkg.FilterBatch(B, cap)
     for b in range(B):
         f.set_state(*states[b % 4], index=b)
-    ctrl, z, R = _batch_script(B, 6, 2)
+    ctrl, z, R = batch_script(pkg, B, 6, 2)
     f.script_load(ctrl[:3], z[:3], R[:3])
     f.script_run(0, 3)
     before = [f.get_state(b) for b in range(B)]
@@ -299,7 +211,7 @@ def test_batch_every_filter_its_own_frame(pkg, pipeline_mode):
 def test_bad_arguments_and_sticky_status_change_nothing(pkg, pipeline_mode):
     f, x0, P0 = make_filter(pkg, 60, 64, seed=91)
     sc = pkg.scenarios.steady_script(x0, steps=4, M=2, seed=92, min_separation=1.0)
-    run_steps(f, sc, 0, 4, 2)
+    run_steps(pkg, f, sc, 0, 4, 2)
     st = f.get_state()
     L, BAD = f.L, pkg.ekfslam.ERR_BAD_ARG
     dp = ctypes.POINTER(ctypes.c_double)
@@ -339,7 +251,7 @@ def test_no_dense_pass_of_its_own_and_streaming_resumes(pkg, pipeline_mode, N, c
     streams again afterwards, and goes on exactly as a twin loaded with set_state."""
     a, x0, P0 = make_filter(pkg, N, cap, seed=101)
     sc = pkg.scenarios.steady_script(x0, steps=12, M=2, seed=102, min_separation=1.0)
-    run_steps(a, sc, 0, 3, 2)  # 6 slots of a 16-slot window: open
+    run_steps(pkg, a, sc, 0, 3, 2)  # 6 slots of a 16-slot window: open
     w0 = windows_closed(a)
     apply_call(a, call)
     w1 = windows_closed(a)
@@ -354,8 +266,8 @@ def test_no_dense_pass_of_its_own_and_streaming_resumes(pkg, pipeline_mode, N, c
     b = pkg.FilterBatch(1, cap, max_pending=16, log_capacity=4096)
     b.set_state(*st)
     sc2 = pkg.scenarios.steady_script(st[0], steps=6, M=2, seed=104, min_separation=1.0)
-    da, _ = run_steps(a, sc2, 0, 6, 2)
-    db, _ = run_steps(b, sc2, 0, 6, 2)
+    da, _ = run_steps(pkg, a, sc2, 0, 6, 2)
+    db, _ = run_steps(pkg, b, sc2, 0, 6, 2)
     on1, starts1 = stream_starts(a)
     if on:
         assert starts1 > starts0

@@ -7,7 +7,8 @@ import ctypes
 import numpy as np
 import pytest
 
-from helpers import assert_bitwise_symmetric, assert_state_close
+from helpers import (assert_bitwise, assert_bitwise_symmetric, assert_state_close, batch_script, make_filter, run_steps, stream_starts,
+                     windows_closed)
 
 pytestmark = pytest.mark.gpu
 
@@ -19,68 +20,9 @@ def reduce_state(x, P, keep):
     return x[rows].copy(), P[np.ix_(rows, rows)].copy()
 
 
-def assert_bitwise(a, b, what=""):
-    assert a[0].shape == b[0].shape and a[1].shape == b[1].shape, (what, a[0].shape, b[0].shape)
-    assert np.array_equal(a[0], b[0]), "%s: x differs" % what
-    dP = a[1] != b[1]
-    assert not dP.any(), "%s: P differs at %d elements, first %s" % (what, int(dP.sum()), np.argwhere(dP)[:3].tolist())
-
-
-def windows_closed(f):
-    f.L.ekf_debug_windows.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_int)]
-    a, b = ctypes.c_longlong(), ctypes.c_int()
-    assert f.L.ekf_debug_windows(f.h, ctypes.byref(a), ctypes.byref(b)) == 0
-    return a.value
-
-
-def stream_starts(f):
-    f.L.ekf_debug_stream.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong), ctypes.POINTER(ctypes.c_longlong)]
-    a, b = ctypes.c_longlong(), ctypes.c_longlong()
-    on = f.L.ekf_debug_stream(f.h, ctypes.byref(a), ctypes.byref(b))
-    return on, a.value
-
-
-def far_feature(k):
-    """A feature well away from every landmark of the injected maps and from the other far features: a New landmark."""
-    return pkg_scen.measurement_from_feature_mm(70000.0 + 9000.0 * (k % 7), -40000.0 + 11000.0 * (k // 7))
-
-
-pkg_scen = None
-
-
-@pytest.fixture(autouse=True)
-def _scen(pkg):
-    global pkg_scen
-    pkg_scen = pkg.scenarios
-
-
-def run_steps(f, sc, s0, steps, M, new_every=0, k_new=0, oracle=None, oc=None):
-    """Immediate calls on a one-filter handle: propagate, M Old-type measurements of the script, every `new_every`-th step a
-    far feature (New).  Returns the decisions (and advances `oracle`, an oc.Session, the same way)."""
-    decs = []
-    for s in range(s0, s0 + steps):
-        v, w, dt = sc["ctrl"][s]
-        f.propagate(v, w, dt)
-        if oracle is not None:
-            oracle.propagate(v, w, oc.make_Q(v), dt)
-        meas = [(sc["z"][s, m], sc["R"][s, m].reshape(2, 2, order="F")) for m in range(M)]
-        if new_every and s % new_every == 0:
-            meas.append(far_feature(k_new))
-            k_new += 1
-        for z, R in meas:
-            d = f.update(z.reshape(1, 1, 2), R.reshape(1, 1, 2, 2))[0][0]
-            decs.append((d[0], d[1]))
-            if oracle is not None:
-                od, om, _ = oracle.update(z.reshape(2, 1), R)
-                assert (d[0], d[1]) == (od[0], om[0]), (s, d, od, om)
-    return decs, k_new
-
-
-def make_filter(pkg, N, cap, seed, max_pending=16):
-    x0, P0 = pkg.scenarios.injected_state(N, seed=seed, extent=12.0 * (N / 64.0) ** 0.5 + 8.0)
-    f = pkg.FilterBatch(1, cap, max_pending=max_pending, log_capacity=4096)
-    f.set_state(x0, P0)
-    return f, x0, P0
+def kinds(decs):
+    """(decision, matched index) of run_steps' decisions: what the removal tests compare."""
+    return [(d[0], d[1]) for d in decs]
 
 
 # (capacity > 256: the several-workgroup chain kernel; <= 256: the one-workgroup kernel)
@@ -92,9 +34,9 @@ def test_removal_is_np_delete_bit_for_bit_with_a_window_open(pkg, pipeline_mode,
     a, x0, P0 = make_filter(pkg, N, cap, seed=11)
     b, _, _ = make_filter(pkg, N, cap, seed=11)
     sc = pkg.scenarios.steady_script(x0, steps=5, M=2, seed=12, min_separation=1.0)
-    da, _ = run_steps(a, sc, 0, 5, 2)
-    db, _ = run_steps(b, sc, 0, 5, 2)
-    assert da == db
+    da, _ = run_steps(pkg, a, sc, 0, 5, 2)
+    db, _ = run_steps(pkg, b, sc, 0, 5, 2)
+    assert kinds(da) == kinds(db)
     before = b.get_state()
     pose_b, rcov_b, st_b = b.poses()[0].copy(), b.robot_cov(), b.stats()
     keep = np.random.default_rng(13).random(N) > 0.3
@@ -120,8 +62,8 @@ def test_continuation_twin_reuses_the_freed_rows(pkg, oc, pipeline_mode, N, cap,
     a, x0, P0 = make_filter(pkg, N, cap, seed=21, max_pending=8)
     ref, _, _ = make_filter(pkg, N, cap, seed=21, max_pending=8)
     sc = pkg.scenarios.steady_script(x0, steps=40, M=2, seed=22, min_separation=1.0)
-    run_steps(a, sc, 0, 3, 2)
-    run_steps(ref, sc, 0, 3, 2)
+    run_steps(pkg, a, sc, 0, 3, 2)
+    run_steps(pkg, ref, sc, 0, 3, 2)
     xs, Ps = ref.get_state()
     ref.close()
     rng = np.random.default_rng(23)
@@ -135,9 +77,9 @@ def test_continuation_twin_reuses_the_freed_rows(pkg, oc, pipeline_mode, N, cap,
     sc2 = pkg.scenarios.steady_script(xr, steps=40, M=2, seed=24, min_separation=1.0)
     n_new_needed = n_remove + 6
     steps = n_new_needed  # one New per step
-    da, ka = run_steps(a, sc2, 0, steps, 2, new_every=1, oracle=S, oc=oc)
-    db, kb = run_steps(b, sc2, 0, steps, 2, new_every=1)
-    assert da == db and ka == kb == n_new_needed
+    da, ka = run_steps(pkg, a, sc2, 0, steps, 2, new_every=1, oracle=S, oc=oc)
+    db, kb = run_steps(pkg, b, sc2, 0, steps, 2, new_every=1)
+    assert kinds(da) == kinds(db) and ka == kb == n_new_needed
     assert sum(1 for d in da if d[0] == pkg.ekfslam.NEW) >= n_new_needed
     assert int(a.num_landmarks()[0]) > N  # grown past the old size: freed rows reused
     sa, sb = a.get_state(), b.get_state()
@@ -152,7 +94,7 @@ def test_full_size_removals(pkg, pipeline_mode):
     N = 4096
     f, x0, P0 = make_filter(pkg, N, N + 8, seed=31)
     sc = pkg.scenarios.steady_script(x0, steps=3, M=3, seed=32, min_separation=1.0)
-    run_steps(f, sc, 0, 3, 3)
+    run_steps(pkg, f, sc, 0, 3, 3)
     rng = np.random.default_rng(33)
     st = f.get_state()
     for case in ("first", "last", "block64", "spread1pct"):
@@ -174,21 +116,6 @@ def test_full_size_removals(pkg, pipeline_mode):
     f.close()
 
 
-def _batch_script(B, steps, M):
-    ctrl = np.tile(np.array([0.3, 0.05, 0.05]), (steps, B, 1))
-    z = np.empty((steps, M, B, 2))
-    R = np.empty((steps, M, B, 4))
-    for s in range(steps):
-        for m in range(M):
-            for b in range(B):
-                if m == 0:
-                    zz, RR = pkg_scen.measurement_from_feature_mm(3000.0 + 37.0 * ((b + s) % 11), 800.0 - 53.0 * ((b * 3 + s) % 7))
-                else:
-                    zz, RR = far_feature(s + 3 * b % 5)
-                z[s, m, b], R[s, m, b] = zz, RR.ravel(order="F")
-    return ctrl, z, R
-
-
 def test_batch_removal_every_filter_its_own_mask(pkg, pipeline_mode):
     """256 filters x 256 landmarks (the fused one-workgroup pass): each filter a different mask, one keeping all and one keeping
     none.  Every filter bitwise against np.delete; then a scripted continuation against a twin batch loaded with set_state per
@@ -198,7 +125,7 @@ def test_batch_removal_every_filter_its_own_mask(pkg, pipeline_mode):
     f = pkg.FilterBatch(B, cap)
     for b in range(B):
         f.set_state(*states[b % 4], index=b)
-    ctrl, z, R = _batch_script(B, 6, 2)
+    ctrl, z, R = batch_script(pkg, B, 6, 2)
     f.script_load(ctrl[:3], z[:3], R[:3])
     f.script_run(0, 3)
     before = [f.get_state(b) for b in range(B)]
@@ -240,7 +167,7 @@ def test_edges(pkg, pipeline_mode):
     N, cap = 60, 64
     f, x0, P0 = make_filter(pkg, N, cap, seed=51)
     sc = pkg.scenarios.steady_script(x0, steps=4, M=2, seed=52, min_separation=1.0)
-    run_steps(f, sc, 0, 4, 2)
+    run_steps(pkg, f, sc, 0, 4, 2)
     st = f.get_state()
     assert f.remove_landmarks(np.ones(N, dtype=bool), index=0) == N
     assert_bitwise(f.get_state(), st, "all kept")
@@ -305,7 +232,7 @@ def test_a_one_filter_handle_streams_again_after_a_removal(pkg, pipeline_mode):
     N, cap = 280, 320
     a, x0, P0 = make_filter(pkg, N, cap, seed=61)
     sc = pkg.scenarios.steady_script(x0, steps=12, M=2, seed=62, min_separation=1.0)
-    run_steps(a, sc, 0, 3, 2)
+    run_steps(pkg, a, sc, 0, 3, 2)
     keep = np.random.default_rng(63).random(N) > 0.1
     st = a.get_state()
     a.remove_landmarks(keep, index=0)
@@ -313,12 +240,12 @@ def test_a_one_filter_handle_streams_again_after_a_removal(pkg, pipeline_mode):
     b = pkg.FilterBatch(1, cap, max_pending=16, log_capacity=4096)
     b.set_state(*reduce_state(*st, keep))
     sc2 = pkg.scenarios.steady_script(reduce_state(*st, keep)[0], steps=8, M=2, seed=64, min_separation=1.0)
-    da, _ = run_steps(a, sc2, 0, 8, 2)
-    db, _ = run_steps(b, sc2, 0, 8, 2)
+    da, _ = run_steps(pkg, a, sc2, 0, 8, 2)
+    db, _ = run_steps(pkg, b, sc2, 0, 8, 2)
     on1, starts1 = stream_starts(a)
     if on:
         assert starts1 > starts0
-    assert da == db
+    assert kinds(da) == kinds(db)
     assert_bitwise(a.get_state(), b.get_state(), "streamed continuation")
     a.close(), b.close()
 
@@ -327,7 +254,7 @@ def test_a_one_filter_handle_streams_again_after_a_removal(pkg, pipeline_mode):
 def test_landmark_covs_are_the_diagonal_blocks_and_force_no_pass(pkg, pipeline_mode, N, cap):
     f, x0, P0 = make_filter(pkg, N, cap, seed=71)
     sc = pkg.scenarios.steady_script(x0, steps=3, M=2, seed=72, min_separation=1.0)
-    run_steps(f, sc, 0, 3, 2)  # 6 slots of a 16-slot window: open
+    run_steps(pkg, f, sc, 0, 3, 2)  # 6 slots of a 16-slot window: open
     closed = windows_closed(f)
     covs = f.landmark_covs()
     assert windows_closed(f) == closed
