@@ -23,6 +23,7 @@
 #include "ekf_kernels.hip"
 #include "ekf_solo.hip"
 #include "ekf_rewrite.hip"
+#include "ekf_factor.hip"
 
 static thread_local std::string g_last_error;
 
@@ -169,6 +170,13 @@ struct ekf_batch {
     ekf_params params_requested;
     // scratch
     std::vector<int> h_int;
+    // map assessment (ekf_joint_consistency): the factorisation's scratch, one device allocation made at the first call and kept
+    FactorScratch fac = {};
+    void *fac_base = nullptr;
+    long long state_edits = 0;     // rewrites, broadcasts and scripted runs so far: with chain_seq and stream_ops, "has the state changed?"
+    long long fac_stamp[3] = {-1, -1, -1};  // those three when the scratch was last filled (ekf_debug_joint_factor)
+    int fac_b0 = 0;                // ... by a call over filters [fac_b0, fac_b0 + fac_n.size()) with fac_n landmarks each
+    std::vector<int> fac_n;
 };
 
 static int sticky_status(ekf_batch *h, bool include_capacity);
@@ -708,6 +716,7 @@ extern "C" int ekf_destroy(ekf_handle h) {
     for (int i = 0; i < 2; i++)
         if (h->ev_flush[i]) hipEventDestroy(h->ev_flush[i]);
     if (h->bm1_base) hipFree(h->bm1_base);
+    if (h->fac_base) hipFree(h->fac_base);
     for (auto &g : h->graphs) hipGraphExecDestroy(g.exec);
     for (const DevArray &a : device_arrays(h))
         if (*a.slot) hipFree(*a.slot);
@@ -1621,6 +1630,7 @@ static int sticky_status(ekf_batch *h, bool include_capacity) {
 //   ekf_reset_stats, ekf_timer_start, ekf_timer_stop   QUIET_STREAM   ST_NONE              own work on the chain stream, not waited for
 //   ekf_get_x                                          QUIET_STREAM   ST_INVALID           copy
 //   ekf_get_state                                      QUIET_STREAM   ST_INVALID           size only: returns; else settle(), export
+//   ekf_joint_consistency (and the batch form)         QUIET_STREAM   ST_INVALID           settle(), factor in the scratch; the state is only read
 //   ekf_set_state                                      QUIET_SETTLED  ST_NONE              (the way out of a timed-out handle: no status ends it)
 //   ekf_broadcast_state                                QUIET_SETTLED  ST_NONE
 //   ekf_reserve                                        QUIET_SETTLED  ST_NONE              refreshes the bounds AFTER the settle; only EKF_ERR_TIMEOUT ends it
@@ -1658,6 +1668,7 @@ static int finish_rewrite(ekf_batch *h, int b0, int nb, bool rearm, const int *c
     EKF_TRY(check_launch());
     if (flip_buf) h->buf_in ^= 1;
     h->mirror_by_chain = false;
+    h->state_edits++;
     return refresh_bounds(h);
 }
 
@@ -1868,6 +1879,7 @@ extern "C" int ekf_set_state(ekf_handle h, int index, const double *x, const dou
 // moves over on the device (k_export into a dense staging matrix, k_import from it: the tile numbering depends on the capacity),
 // the counters, the decision log and a loaded script move with it, and the handle keeps its address.
 static int reserve_move_state(ekf_batch *h, ekf_batch *nh, const std::vector<int> &n_lm);
+static int factor_reserve(ekf_batch *h);
 
 extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     if (!h || capacity_landmarks < 1 || capacity_landmarks > EKF_MAX_CAPACITY) return set_error(EKF_ERR_BAD_ARG, "bad handle / capacity (EKF_MAX_CAPACITY)");
@@ -1930,8 +1942,10 @@ extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     std::swap(nh->script_d, h->script_d);
     nh->script_steps = h->script_steps, nh->script_M = h->script_M, nh->script_has_truth = h->script_has_truth;
     h->script_steps = 0;
+    const bool had_factor_scratch = h->fac_base != nullptr;
     std::swap(*h, *nh);  // the caller's handle now owns the larger buffers ...
     ekf_destroy(nh);     // ... and the old ones go
+    if (had_factor_scratch) EKF_TRY(factor_reserve(h));  // (the scratch of ekf_joint_consistency follows the capacity)
     return refresh_bounds(h);
 }
 
@@ -1985,6 +1999,7 @@ extern "C" int ekf_broadcast_state(ekf_handle h) {
     HIP_TRY(stream_wait(s));
     for (int b = 1; b < dv.B; b++) hipLaunchKernelGGL(k_set_meta, dim3(1), dim3(64), 0, s, dv, b, h->mirror_h[0].n_lm);  // also refreshes the host mirror
     h->mirror_by_chain = false;
+    h->state_edits++;
     return refresh_bounds(h);
 }
 
@@ -2183,6 +2198,97 @@ extern "C" int ekf_batch_join_map(ekf_handle dst, ekf_handle src) {
     return join_impl(dst, -1, src, 0);
 }
 
+// ---- map assessment -------------------------------------------------------------------------------
+// The scratch of ekf_joint_consistency (ekf_factor.hip: FactorScratch), sized by the handle's capacity: one allocation at the first
+// call, counted in ekf_device_bytes, freed by ekf_destroy; ekf_reserve builds the larger one.
+static int factor_reserve(ekf_batch *h) {
+    if (h->fac_base) return EKF_OK;
+    const EkfDev &dv = h->dv;
+    const size_t B = (size_t)dv.B;
+    const size_t nS = B * dv.bm_stride, nrhs = B * (size_t)dv.rows * 4, nacc = B * FAC_ACC, nxt = B * (size_t)dv.xs;
+    const size_t bytes = (nS + nrhs + nacc + nxt) * sizeof(double) + B * sizeof(ekf_joint);
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, bytes));
+    hipError_t e = hipMemsetAsync(p, 0, bytes, h->s_chain);
+    if (e == hipSuccess) e = stream_wait(h->s_chain);
+    if (e != hipSuccess) {
+        hipFree(p);
+        return set_error(EKF_ERR_HIP, hipGetErrorString(e));
+    }
+    h->fac_base = p;
+    h->fac.S = (double *)p;
+    h->fac.rhs = h->fac.S + nS;
+    h->fac.acc = h->fac.rhs + nrhs;
+    h->fac.xt = h->fac.acc + nacc;
+    h->fac.out = (ekf_joint *)(h->fac.xt + nxt);
+    h->device_bytes += bytes;
+    h->fac_stamp[0] = -1;
+    return EKF_OK;
+}
+
+// Filters [b0, b0 + nb): the rule of ekf_get_state (the streaming launch leaves, every deferred slot is folded, both streams idle),
+// then the settled state is only read: stage, 3 launches per tile step with the grid over the filters, finish, one copy back.
+static int joint_impl(ekf_batch *h, int b0, int nb, const double *x_true, int ld_true, ekf_joint *out) {
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
+    int n_max = 0;
+    for (int k = 0; k < nb; k++) n_max = h->h_int[b0 + k] > n_max ? h->h_int[b0 + k] : n_max;
+    if (x_true && ld_true < 3 + 2 * n_max) return set_error(EKF_ERR_BAD_ARG, "x_true rows are shorter than the largest state of the call");
+    EKF_TRY(settle(h));
+    EKF_TRY(factor_reserve(h));
+    const EkfDev &dv = h->dv;
+    const FactorScratch fs = h->fac;
+    hipStream_t s = h->s_chain;
+    const int have_truth = x_true ? 1 : 0;
+    if (x_true)
+        HIP_TRY(hipMemcpy2DAsync(fs.xt + (size_t)b0 * dv.xs, (size_t)dv.xs * sizeof(double), x_true, (size_t)ld_true * sizeof(double),
+                                 (size_t)(3 + 2 * n_max) * sizeof(double), nb, hipMemcpyHostToDevice, s));
+    const int nT = lm_tiles(n_max);
+    if (nT > 0) hipLaunchKernelGGL(k_chol_stage, dim3((unsigned)(nT * (nT + 1) / 2), (unsigned)nb), dim3(256), 0, s, dv, fs, h->buf_in, b0, nT, have_truth);
+    for (int k = 0; k < nT; k++) {
+        hipLaunchKernelGGL(k_chol_diag, dim3((unsigned)nb), dim3(320), 0, s, dv, fs, k, b0);
+        if (k + 1 < nT) {
+            hipLaunchKernelGGL(k_chol_panel, dim3((unsigned)(nT - 1 - k), (unsigned)nb), dim3(64), 0, s, dv, fs, k, b0);
+            hipLaunchKernelGGL(k_chol_trail, dim3((unsigned)chol_trail_count(nT, k), (unsigned)nb), dim3(256), 0, s, dv, fs, k, b0, nT);
+        }
+    }
+    hipLaunchKernelGGL(k_chol_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0, have_truth);
+    HIP_TRY(hipMemcpyAsync(out, fs.out + b0, sizeof(ekf_joint) * (size_t)nb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));
+    EKF_TRY(check_launch());
+    h->fac_stamp[0] = h->chain_seq, h->fac_stamp[1] = h->stream_ops, h->fac_stamp[2] = h->state_edits;
+    h->fac_b0 = b0;
+    h->fac_n.assign(h->h_int.begin() + b0, h->h_int.begin() + b0 + nb);
+    return EKF_OK;
+}
+
+extern "C" int ekf_joint_consistency(ekf_handle h, int index, const double *x_true, ekf_joint *out) {
+    if (!h || index < 0 || index >= h->dv.B || !out) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return joint_impl(h, index, 1, x_true, x_true ? 3 + 2 * h->dv.Ncap : 0, out);
+}
+
+extern "C" int ekf_batch_joint_consistency(ekf_handle h, const double *x_true, int ld_true, ekf_joint *out) {
+    if (!h || !out || (x_true && ld_true < 3)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return joint_impl(h, 0, h->dv.B, x_true, ld_true, out);
+}
+
+extern "C" int ekf_debug_joint_factor(ekf_handle h, int index, double *U_out, int ld) {
+    if (!h || index < 0 || index >= h->dv.B) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    const bool current = h->fac_base && h->fac_stamp[0] == h->chain_seq && h->fac_stamp[1] == h->stream_ops && h->fac_stamp[2] == h->state_edits;
+    if (!current || index < h->fac_b0 || index >= h->fac_b0 + (int)h->fac_n.size())
+        return set_error(EKF_ERR_STATE, "no factor of this filter's current state: call ekf_joint_consistency first");
+    const int m = 2 * h->fac_n[index - h->fac_b0];
+    if (m == 0) return 0;
+    if (!U_out || ld < m) return set_error(EKF_ERR_BAD_ARG, "bad output buffer");
+    HIP_TRY(hipSetDevice(h->device));
+    DevTmp<double> stage;
+    HIP_TRY(stage.alloc((size_t)m * m));
+    hipLaunchKernelGGL(k_chol_export, dim3(cdiv(m, 256), m), dim3(256), 0, h->s_chain, h->dv, h->fac, index, m, stage.p, m);
+    HIP_TRY(hipMemcpy2DAsync(U_out, (size_t)ld * sizeof(double), stage.p, (size_t)m * sizeof(double), (size_t)m * sizeof(double), m, hipMemcpyDeviceToHost, h->s_chain));
+    HIP_TRY(stream_wait(h->s_chain));
+    EKF_TRY(check_launch());
+    return m;
+}
+
 extern "C" int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max) {
     if (!h || index < 0 || index >= h->dv.B || n_max < 0 || (!cov_out && n_max > 0)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
@@ -2276,6 +2382,7 @@ extern "C" int ekf_script_run(ekf_handle h, int first_step, int n_steps, int use
     if (!h || !h->script_d) return set_error(EKF_ERR_STATE, "no script loaded");
     if (first_step < 0 || n_steps < 0 || first_step + n_steps > h->script_steps) return set_error(EKF_ERR_BAD_ARG, "step range outside the script");
     HIP_TRY(hipSetDevice(h->device));
+    h->state_edits++;
     // (a resident streaming launch takes a short run itself -- launch_ops, OP_SCRIPT -- and leaves first for everything else)
     int ops = ops_per_step(h);
     int s = first_step, end = first_step + n_steps;

@@ -317,6 +317,23 @@ __host__ __device__ inline JoinSource join_source(int Ng, int Ns, int Ts, int dn
     return s;
 }
 
+// The tile-blocked Cholesky of P_LL (ekf_joint_consistency, ekf_factor.hip).  Step k updates the stored tiles (I, J) with
+// k < I <= J < nT: tile t of that list, in storage order of the triangle that is left, and their number.
+__host__ __device__ inline int chol_trail_count(int nT, int k) {
+    const int m = nT - 1 - k;
+    return m > 0 ? m * (m + 1) / 2 : 0;
+}
+__host__ __device__ inline void chol_trail_ij(int t, int nT, int k, int *I, int *J) {
+    tri_tile_ij(t, nT - 1 - k, I, J);
+    *I += k + 1, *J += k + 1;
+}
+// A stored chain is an operand of v_mfma_f64_16x16x4_f64 as it lies: in k-step s (0..15) of the product U_ki^T U_kj, lane l holds
+// element (row 4 s + (l >> 4), column 16 blk + (l & 15)) of a panel tile -- as A for output row block blk, as B for output column
+// block blk.  Its tile-local offset; s even: the lane's 16-byte piece at that offset carries k-steps s and s + 1.
+__host__ __device__ inline int chol_operand_offset(int s, int blk, int lane) {
+    return ((s >> 2) * 4 + blk) * 256 + ((s >> 1) & 1) * 128 + lane * 2 + (s & 1);
+}
+
 // Offset (doubles) of row i' of slot PAIR p inside one (filter, set) of FA / FB: 4 doubles, slot 2p in
 // [0..1], slot 2p+1 in [2..3].
 __host__ __device__ inline size_t pair_offset(int rows, int ip, int p) {

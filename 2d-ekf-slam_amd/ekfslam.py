@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "ekf_remove_landmarks", "ekf_batch_remove_landmarks", "ekf_get_landmark_covs",
     "ekf_transform_frame", "ekf_batch_transform_frame", "ekf_anchor_at_robot", "ekf_batch_anchor_at_robot",
     "ekf_join_map", "ekf_batch_join_map",
+    "ekf_joint_consistency", "ekf_batch_joint_consistency", "ekf_debug_joint_factor",
 ]
 
 
@@ -44,6 +45,16 @@ class EkfStats(ctypes.Structure):
                 ("nees_count", ctypes.c_longlong), ("n_new", ctypes.c_longlong), ("n_old", ctypes.c_longlong),
                 ("n_ignore", ctypes.c_longlong)]
 
+
+class EkfJoint(ctypes.Structure):
+    _fields_ = [("n_landmarks", ctypes.c_int), ("info", ctypes.c_int), ("nees_map", ctypes.c_double), ("nees_joint", ctypes.c_double),
+                ("logdet_map", ctypes.c_double), ("logdet_joint", ctypes.c_double), ("min_pivot", ctypes.c_double),
+                ("max_pivot", ctypes.c_double), ("cov_robot_given_map", ctypes.c_double * 9)]
+
+
+JOINT_DTYPE = np.dtype([("n_landmarks", "i4"), ("info", "i4"), ("nees_map", "f8"), ("nees_joint", "f8"), ("logdet_map", "f8"),
+                        ("logdet_joint", "f8"), ("min_pivot", "f8"), ("max_pivot", "f8"), ("cov_robot_given_map", "f8", (3, 3))])
+assert JOINT_DTYPE.itemsize == ctypes.sizeof(EkfJoint)
 
 _STATS_DTYPE = np.dtype([(n, "f8" if t is ctypes.c_double else "i8") for n, t in EkfStats._fields_])
 
@@ -107,6 +118,9 @@ def load():
     L.ekf_batch_anchor_at_robot.argtypes = [_H]
     L.ekf_join_map.argtypes = [_H, ctypes.c_int, _H, ctypes.c_int]
     L.ekf_batch_join_map.argtypes = [_H, _H]
+    L.ekf_joint_consistency.argtypes = [_H, ctypes.c_int, _dp, ctypes.POINTER(EkfJoint)]
+    L.ekf_batch_joint_consistency.argtypes = [_H, _dp, ctypes.c_int, ctypes.POINTER(EkfJoint)]
+    L.ekf_debug_joint_factor.argtypes = [_H, ctypes.c_int, _dp, ctypes.c_int]
     L.ekf_script_load.argtypes = [_H, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _up, _dp]
     L.ekf_script_run.argtypes = [_H, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.ekf_sync.argtypes = [_H]
@@ -317,6 +331,44 @@ class FilterBatch:
         """Filter b of `src` into filter b of this batch for every b (ekf_batch_join_map; equal batch sizes, another handle)."""
         _chk(self.L.ekf_batch_join_map(self.h, src.h))
 
+    # -- map assessment ------------------------------------------------------------------------
+    def joint_consistency(self, x_true=None, index=None):
+        """Whole-state consistency on the device (ekf_joint_consistency): joint and map NEES against x_true, log det P, the pivots
+        of the factorisation of P_LL and the pose covariance conditioned on the map, as a structured array (JOINT_DTYPE) with one row
+        per filter.  index=None: every filter in one launch sequence, x_true [batch][>= largest state] (or [n] for a batch of one);
+        with an index: that filter alone, x_true [n].  x_true=None: a health check, the NEES fields are NaN.  The filter is only
+        read; `info` != 0 is a result (see include/ekfslam_c.h), not an exception."""
+        if index is None:
+            buf = (EkfJoint * self.batch)()
+            xt, ld = None, 0
+            if x_true is not None:
+                t = _f64(x_true)
+                if t.ndim == 1 and self.batch == 1:
+                    t = t.reshape(1, -1)
+                if t.ndim != 2 or t.shape[0] != self.batch:
+                    raise ValueError("x_true must be [batch][n]")
+                xt, ld = _p(t), t.shape[1]
+            _chk(self.L.ekf_batch_joint_consistency(self.h, xt, ld, buf))
+            return np.frombuffer(buf, dtype=JOINT_DTYPE, count=self.batch)  # (the array keeps the buffer alive)
+        buf = (EkfJoint * 1)()
+        xt = None
+        if x_true is not None:
+            t = _f64(x_true).reshape(-1)
+            n = _chk(self.L.ekf_get_state(self.h, int(index), None, None, 0)) if 0 <= int(index) < self.batch else 0
+            if t.size < n:
+                raise ValueError("x_true is shorter than the filter's state (%d < %d)" % (t.size, n))
+            xt = _p(t)
+        _chk(self.L.ekf_joint_consistency(self.h, int(index), xt, buf))
+        return np.frombuffer(buf, dtype=JOINT_DTYPE, count=1)
+
+    def joint_factor(self, index=0):
+        """Diagnostic: the upper factor U (U^T U = P_LL) the last joint_consistency call left for filter `index`, dense (2N, 2N);
+        EkfError ERR_STATE when the state has changed since."""
+        n = max(2 * int(self.num_landmarks()[int(index)]), 1)
+        out = np.zeros((n, n))  # column-major with ld = n: out[j, i] = U[i, j]
+        m = _chk(self.L.ekf_debug_joint_factor(self.h, int(index), _p(out), n))
+        return np.ascontiguousarray(out[:m, :m].T)
+
     def script_load(self, ctrl, z, R, valid=None, truth=None):
         """ctrl (steps, batch, 3); z (steps, M, batch, 2); R (steps, M, batch, 4) column-major blocks;
         valid (steps, M, batch); truth (steps, batch, 3)."""
@@ -481,3 +533,7 @@ class KalmanFilter:
         """Re-express the map relative to the estimated pose: X = Y = Phi = 0 with zero robot covariance afterwards."""
         self._f.anchor_at_robot(0)
         self._mirror()
+
+    def joint_consistency(self, x_true=None):
+        """Joint / map NEES, log det P, pivots and the pose covariance given the map (FilterBatch.joint_consistency): one record."""
+        return self._f.joint_consistency(x_true, 0)[0]

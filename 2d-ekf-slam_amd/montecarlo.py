@@ -114,3 +114,27 @@ def consistency_report(summary, nis_samples_per_filter, nees_samples_per_filter,
         hi = chi2.ppf(1 - alpha / 2, total_dof) / (k * m)
         rep[name] = dict(mean=mean, dof=dof, filters=int(k), lower=float(lo), upper=float(hi), consistent=bool(lo <= mean <= hi))
     return rep
+
+
+def joint_consistency_report(rows, alpha=0.05):
+    """Chi-square consistency check of whole-state NEES records (FilterBatch.joint_consistency, one row per filter and sample): if
+    the filters are consistent, the sum of the joint NEES values is chi2 with the summed 3 + 2N degrees of freedom, the sum of the
+    map NEES values chi2 with the summed 2N.  Rows with info != 0 (P_LL or the conditioned pose block not positive definite) and
+    rows without a NEES value (no truth was given) are skipped and counted."""
+    from scipy.stats import chi2
+
+    rows = np.atleast_1d(rows)
+    ok = rows[rows["info"] == 0]
+    rep = {"skipped": int(rows.size - ok.size)}
+    for name, field, dofs in (("joint", "nees_joint", 3 + 2 * ok["n_landmarks"].astype(np.int64)), ("map", "nees_map", 2 * ok["n_landmarks"].astype(np.int64))):
+        vals = ok[field]
+        use = np.isfinite(vals) & (dofs > 0)
+        total_dof = int(dofs[use].sum())
+        if total_dof == 0:
+            rep[name] = None
+            continue
+        total = float(vals[use].sum())
+        lo, hi = float(chi2.ppf(alpha / 2, total_dof)), float(chi2.ppf(1 - alpha / 2, total_dof))
+        rep[name] = dict(sum=total, dof=total_dof, samples=int(use.sum()), mean_per_dof=total / total_dof, lower=lo, upper=hi,
+                         consistent=bool(lo <= total <= hi))
+    return rep

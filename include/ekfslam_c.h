@@ -90,8 +90,9 @@ void ekf_default_params(ekf_params *p);
 
 /* KalmanFilter::KalmanFilter, kalmanfilter.cpp:4-12: x = 0_3, P = 0_3x3, no landmarks.
  * capacity_landmarks bounds N; all device memory is allocated here, none later (except a transient
- * staging buffer inside ekf_get_state / ekf_set_state, and inside ekf_remove_landmarks / ekf_batch_remove_landmarks the
- * landmark maps and, in the in-place pipeline (ekf_overlap() == 0), a scratch copy of the reduced maps' tiles).
+ * staging buffer inside ekf_get_state / ekf_set_state, inside ekf_remove_landmarks / ekf_batch_remove_landmarks the
+ * landmark maps and, in the in-place pipeline (ekf_overlap() == 0), a scratch copy of the reduced maps' tiles -- and the
+ * factorisation scratch of ekf_joint_consistency, allocated at its first call and kept: one more P_LL buffer per filter).
  * The sequential part of a filter runs on a few workgroups that exchange their arg-min candidates while they
  * run, so all of them must be resident on the GPU at once: creation fails with EKF_ERR_STATE when this
  * handle's workgroups do not fit beside those of the handles already live on the device (in this process).
@@ -239,6 +240,43 @@ int ekf_batch_anchor_at_robot(ekf_handle h);
  * Returns EKF_OK or a negative status; one filter without room fails the whole call with nothing modified. */
 int ekf_join_map(ekf_handle dst, int dst_index, ekf_handle src, int src_index);
 int ekf_batch_join_map(ekf_handle dst, ekf_handle src);
+
+/* Map assessment on the device: is the whole state (pose AND map) consistent, and is P still a covariance?  A Cholesky
+ * factorisation P_LL = U^T U of the settled landmark covariance in a scratch copy (64-row tile steps over the tile layout; the
+ * filter itself is only read), the robot block last:
+ *     U^T [y | W] = [e_L | P_LR],   S_R = P_RR - W^T W,   r = e_R - W^T y,
+ *     nees_map = |y|^2,  nees_joint = |y|^2 + r^T S_R^-1 r,  logdet_map = 2 sum log U_ii,  logdet_joint = logdet_map + log det S_R.
+ * e = x - x_true with the heading component wrapped to [-pi, pi) as ekf_record_truth wraps it; x_true lists the landmarks in the
+ * filter's own order (the caller's contract).  x_true == NULL: the NEES fields are NaN, everything else is filled (a health check).
+ * info = k > 0: every NEES and log-det field and cov_robot_given_map are NaN, min_pivot holds the offending pivot; info = -1: the
+ * map fields and cov_robot_given_map are valid, the joint fields NaN.  N = 0: the map fields are 0, the joint fields come from P_RR.
+ * A pivot that is not positive is NOT an error status: the call returns EKF_OK with info set, and the filter works on as before.
+ * The filter's exported state, counters, decision log, loaded script and host mirror are bitwise what ekf_get_state at the same
+ * point would leave: deferred slots are folded first, a streaming launch is stopped and immediate-mode calls stream again
+ * afterwards.  The call synchronises.  A sticky EKF_ERR_TIMEOUT is returned unchanged; a sticky EKF_ERR_CAPACITY does not block
+ * the call.  Bad arguments (NULL out, index out of range, ld_true smaller than the largest state of the batch when x_true is given)
+ * return EKF_ERR_BAD_ARG.  No floating-point atomics, every sum in a fixed order: two calls on an unchanged state return the same
+ * bits, and filter b of the batch form returns the bits of the one-filter call on b.  The batch form factors every filter in the
+ * same launch sequence (3 launches per tile step, whatever the batch).
+ * The scratch -- one P_LL buffer per filter plus four right-hand-side columns -- is allocated at the first call, kept on the handle
+ * (ekf_device_bytes counts it, ekf_reserve re-sizes it) and freed by ekf_destroy. */
+typedef struct ekf_joint {
+    int n_landmarks;               /* N of the filter at the call */
+    int info;                      /* 0 ok; k > 0: the leading minor of order k of P_LL is not positive (pivot <= 0 or NaN at
+                                      landmark-space row k-1), LAPACK's potrf convention; -1: P_LL is fine, but the pose block
+                                      conditioned on the map is not positive definite (fresh or anchored filter: P_RR = 0) */
+    double nees_map;               /* e_L^T P_LL^-1 e_L, 2N dof  */
+    double nees_joint;             /* e^T P^-1 e, 3 + 2N dof     */
+    double logdet_map;             /* log det P_LL               */
+    double logdet_joint;           /* log det P                  */
+    double min_pivot, max_pivot;   /* smallest / largest U_ii^2 over the 2N landmark rows (conditional variances) */
+    double cov_robot_given_map[9]; /* S_R = P_RR - P_RL P_LL^-1 P_LR, row-major */
+} ekf_joint;
+int ekf_joint_consistency(ekf_handle h, int index, const double *x_true /*[n] or NULL*/, ekf_joint *out);
+int ekf_batch_joint_consistency(ekf_handle h, const double *x_true /*[batch][ld_true] or NULL*/, int ld_true, ekf_joint *out /*[batch]*/);
+/* Diagnostic: the upper factor U (U^T U = P_LL) of filter `index` from the LAST consistency call, dense 2N x 2N column-major,
+ * ld >= 2N; EKF_ERR_STATE when the state changed since (or no call covered the filter).  Returns 2N.  Synchronises. */
+int ekf_debug_joint_factor(ekf_handle h, int index, double *U_out, int ld);
 
 /* ---- device-resident step scripts (benchmarks, Monte-Carlo runs) ------------------------------
  * A script is `steps` steps; step s of filter b is
