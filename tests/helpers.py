@@ -2,6 +2,7 @@
 the map operations (removal, frame change, joining): injected filters, immediate-call scripts, window and stream probes."""
 import ctypes
 import functools
+import math
 import subprocess
 import sys
 
@@ -75,6 +76,37 @@ def assert_bitwise(a, b, what=""):
     assert np.array_equal(a[0], b[0]), "%s: x differs" % what
     dP = a[1] != b[1]
     assert not dP.any(), "%s: P differs at %d elements, first %s" % (what, int(dP.sum()), np.argwhere(dP)[:3].tolist())
+
+
+def check_joint(r, ref, P, what):
+    """Every field of a device record against a factor_ref result; returns the worst relative error seen."""
+    import factor_ref as fr  # (beside this file; SciPy is needed by the tests that get here only)
+    N = ref["n_landmarks"]
+    assert int(r["n_landmarks"]) == N and int(r["info"]) == ref["info"], (what, int(r["n_landmarks"]), int(r["info"]), ref["info"])
+    worst = 0.0
+    for k in fr.FIELDS:
+        got, want = float(r[k]), ref[k]
+        if math.isnan(want):
+            assert math.isnan(got), (what, k, got)
+            continue
+        if k.startswith("logdet"):
+            err = abs(got - want)
+            print("%s %s: |err| %.3e" % (what, k, err))
+            assert err <= 1e-6 * (3 + 2 * N), (what, k, got, want)
+            worst = max(worst, err / max(abs(want), 1.0))
+        else:
+            err = fr.rel_err(got, want) if want != 0.0 else abs(got)
+            print("%s %s: rel %.3e" % (what, k, err))
+            assert err <= REL_TOL, (what, k, got, want)
+            worst = max(worst, err)
+    S, Sr = r["cov_robot_given_map"], ref["cov_robot_given_map"]
+    if np.isnan(Sr).all():
+        assert np.isnan(S).all(), what
+    else:
+        dS = np.abs(S - Sr)
+        print("%s cov_robot_given_map: max |err| %.3e" % (what, dS.max()))
+        assert np.all(dS <= REL_TOL * np.abs(Sr) + ABS_P * np.abs(P).max()), (what, dS.max())
+    return worst
 
 
 def windows_closed(f):

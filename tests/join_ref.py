@@ -16,17 +16,18 @@ import numpy as np
 JM = np.array([[0.0, -1.0], [1.0, 0.0]])
 
 
-def _rot(phi):
-    c, s = math.cos(phi), math.sin(phi)
-    return np.array([[c, -s], [s, c]])
+def _rot(phi, dtype=np.float64):
+    c, s = math.cos(phi), math.sin(phi)  # (float64 in every dtype)
+    return np.array([[c, -s], [s, c]], dtype=dtype)
 
 
-def join_g(xg, xs):
+# (dtype=np.longdouble: the same expressions carried in extended precision -- the yardstick of the float64 results)
+def join_g(xg, xs, dtype=np.float64):
     """The map itself on the two state vectors."""
-    xg, xs = np.asarray(xg, dtype=np.float64), np.asarray(xs, dtype=np.float64)
-    C, t = _rot(xg[2]), xg[0:2]
+    xg, xs = np.asarray(xg, dtype=dtype), np.asarray(xs, dtype=dtype)
+    C, t = _rot(float(xg[2]), dtype), xg[0:2]
     Ng, Ns = (xg.size - 3) // 2, (xs.size - 3) // 2
-    out = np.empty(3 + 2 * (Ng + Ns))
+    out = np.empty(3 + 2 * (Ng + Ns), dtype=dtype)
     out[0:2] = t + C @ xs[0:2]
     out[2] = xg[2] + xs[2]
     out[3:3 + 2 * Ng] = xg[3:]
@@ -34,16 +35,17 @@ def join_g(xg, xs):
     return out
 
 
-def join_J(xg, xs):
+def join_J(xg, xs, dtype=np.float64):
     """d join_g / d [xg; xs]: (3 + 2 (Ng + Ns)) x (len(xg) + len(xs))."""
-    xg, xs = np.asarray(xg, dtype=np.float64), np.asarray(xs, dtype=np.float64)
+    xg, xs = np.asarray(xg, dtype=dtype), np.asarray(xs, dtype=dtype)
     ng, ns = xg.size, xs.size
     Ng, Ns = (ng - 3) // 2, (ns - 3) // 2
-    C = _rot(xg[2])
-    J = np.zeros((3 + 2 * (Ng + Ns), ng + ns))
+    C = _rot(float(xg[2]), dtype)
+    Jm = JM.astype(dtype)
+    J = np.zeros((3 + 2 * (Ng + Ns), ng + ns), dtype=dtype)
     # robot: t + C u, phi + psi
     J[0:2, 0:2] = np.eye(2)
-    J[0:2, 2] = C @ JM @ xs[0:2]
+    J[0:2, 2] = C @ Jm @ xs[0:2]
     J[0:2, ng:ng + 2] = C
     J[2, 2] = 1.0
     J[2, ng + 2] = 1.0
@@ -53,22 +55,22 @@ def join_J(xg, xs):
     for k in range(Ns):
         r = 3 + 2 * (Ng + k)
         J[r:r + 2, 0:2] = np.eye(2)
-        J[r:r + 2, 2] = C @ JM @ xs[3 + 2 * k:5 + 2 * k]
+        J[r:r + 2, 2] = C @ Jm @ xs[3 + 2 * k:5 + 2 * k]
         J[r:r + 2, ng + 3 + 2 * k:ng + 5 + 2 * k] = C
     return J
 
 
-def join(xg, Pg, xs, Ps):
+def join(xg, Pg, xs, Ps, dtype=np.float64):
     """(x', P') through the dense Jacobian."""
-    xg, xs = np.asarray(xg, dtype=np.float64), np.asarray(xs, dtype=np.float64)
-    Pg, Ps = np.asarray(Pg, dtype=np.float64), np.asarray(Ps, dtype=np.float64)
+    xg, xs = np.asarray(xg, dtype=dtype), np.asarray(xs, dtype=dtype)
+    Pg, Ps = np.asarray(Pg, dtype=dtype), np.asarray(Ps, dtype=dtype)
     ng, ns = xg.size, xs.size
-    big = np.zeros((ng + ns, ng + ns))
+    big = np.zeros((ng + ns, ng + ns), dtype=dtype)
     big[:ng, :ng] = Pg
     big[ng:, ng:] = Ps
-    J = join_J(xg, xs)
+    J = join_J(xg, xs, dtype)
     P = J @ big @ J.T
-    return join_g(xg, xs), 0.5 * (P + P.T)
+    return join_g(xg, xs, dtype), 0.5 * (P + P.T)
 
 
 def join_blocks(xg, Pg, xs, Ps):

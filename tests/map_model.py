@@ -1,0 +1,563 @@
+"""Host model of a filter handle and generator of random operation sequences that mix the map rewrites (landmark removal, frame
+change, anchoring, map joining, ekf_reserve, the joint-consistency probe) with live filter traffic.  No GPU and no library here: the
+filter steps go through the C oracle (oracle/oracle_c.py), the rewrites through the NumPy references beside this file.
+
+A sequence is a plain list of (kind, args) pairs with every argument spelled out; tests/test_map_sequences.py replays it on the
+library and on `ModelRunner` in lockstep, tests/test_map_model_cpu.py on the model alone.  The generator runs a ModelRunner of its own
+(estimated heading for the compass offset, landmark counts, capacity), so a sequence is a function of (seed, profile) only.
+
+Hidden world per filter: a true pose and world landmarks pairwise >= 1 m apart (no arg-min near a tie), both kept in the world frame
+for good: measurements are relative to the true pose, so they do not care about the filter's frame.  Compass readings do; the
+generator tracks the offset between the filter's heading and the true one (-theta after a rigid transform, -(estimated phi) after
+an anchor; a join keeps it)."""
+import math
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import factor_ref as fr  # noqa: E402
+import join_ref as jr  # noqa: E402
+import reframe_ref as rr  # noqa: E402
+
+PROFILES = ("solo", "chain", "chain_wgs", "batch")
+# (a seed whose replay on the model leaves a measurement within 1e-6 relative of a gate is replaced here, never skipped at run time;
+# tests/test_map_model_cpu.py checks every one of these)
+SEEDS = {"solo": [0, 1, 2, 3, 4, 5, 6, 7], "chain": [0, 1, 2, 3, 4, 5, 6, 7], "chain_wgs": [0, 1, 2, 3, 4, 5, 6, 7], "batch": [0, 1, 2, 3, 4, 5]}
+N_STEPS = 40
+GAMMA_MIN, GAMMA_MAX = 10.0, 50.0  # the gates (ekf_default_params; oracle_c.update's defaults)
+COMPASS_VAR = 0.0005
+SRC_CAPS = (40, 96, 300)
+WINDOWS = (1, 3, 8, 16, 24, 32)
+REWRITES = ("remove", "transform", "anchor", "reserve", "join", "joint", "covs", "read")
+KINDS = ("propagate", "update", "compass") + REWRITES
+
+
+def lm_tiles(n):
+    """64 x 64 tiles (32 landmarks) along one side of P_LL (ekf_device.h)."""
+    return (2 * n + 63) >> 6
+
+
+def _oc():
+    from oracle import oracle_c
+    oracle_c.build()
+    return oracle_c
+
+
+def reduce_state(x, P, keep):
+    """np.delete of the rows and columns of the landmarks whose keep[l] is false (landmarks beyond the mask are kept)."""
+    N = (x.size - 3) // 2
+    k = np.ones(N, dtype=bool)
+    m = min(N, len(keep))
+    k[:m] = np.asarray(keep, dtype=bool)[:m]
+    gone = np.flatnonzero(~k)
+    rows = np.concatenate([3 + 2 * gone, 4 + 2 * gone]).astype(np.int64)
+    return np.delete(x, rows), np.delete(np.delete(P, rows, axis=0), rows, axis=1)
+
+
+class MapModel:
+    """One filter as a dense (x, P) in float64, one method per library call."""
+
+    def __init__(self, x=None, P=None):
+        self.oc = _oc()
+        self.x = np.zeros(3) if x is None else np.array(x, dtype=np.float64)
+        self.P = np.zeros((3, 3)) if P is None else np.array(P, dtype=np.float64)
+
+    @property
+    def n_landmarks(self):
+        return (self.x.size - 3) // 2
+
+    def propagate(self, v, w, dt):
+        self.x, self.P = self.oc.propagate(self.x, self.P, float(v), float(w), self.oc.make_Q(float(v)), float(dt))
+
+    def update(self, z, R):
+        """z (n_z, 2), R (n_z, 2, 2): one chunk.  Returns [(decision, matched, mahal)]."""
+        z = np.asarray(z, dtype=np.float64).reshape(-1, 2)
+        R = np.asarray(R, dtype=np.float64).reshape(-1, 2, 2)
+        self.x, self.P, dec, mat, mah = self.oc.update(self.x, self.P, z.T, np.concatenate(list(R), axis=1))
+        return list(zip(dec, mat, mah))
+
+    def compass(self, z, R):
+        self.x, self.P = self.oc.compass(self.x, self.P, float(z), float(R))
+
+    def remove(self, keep):
+        self.x, self.P = reduce_state(self.x, self.P, keep)
+        return self.n_landmarks
+
+    def transform(self, frame):
+        self.x, self.P = rr.rigid(self.x, self.P, frame)
+
+    def anchor(self):
+        self.x, self.P = rr.anchor(self.x, self.P)
+
+    def join(self, src):
+        self.x, self.P = jr.join(self.x, self.P, src.x, src.P)
+        return self.n_landmarks
+
+    def reserve(self, capacity):
+        pass
+
+    def joint(self, x_true):
+        return fr.lapack(self.x, self.P, x_true)
+
+    def landmark_covs(self):
+        l = np.arange(self.n_landmarks)
+        return np.stack([self.P[3 + 2 * l, 3 + 2 * l], self.P[3 + 2 * l, 4 + 2 * l], self.P[4 + 2 * l, 4 + 2 * l]], axis=1).reshape(-1, 3)
+
+    def clearly_positive_definite(self):
+        """P well inside the positive definite cone (condition below 1e8): the joint quantities then have one answer to far
+        better than the tolerance they are compared with."""
+        if not np.all(np.isfinite(self.P)):
+            return False
+        ev = np.linalg.eigvalsh(self.P)
+        return bool(ev[0] > 1e-8 * ev[-1])
+
+
+class ModelRunner:
+    """The models of one sequence: the destination handle's filters and, during a join, the source handle's.  step(op) applies one
+    operation and returns what the library must answer (None where there is nothing to compare)."""
+
+    def __init__(self):
+        self.models, self.src = [], []
+        self.cap = self.src_cap = 0
+        self.margin = math.inf  # the smallest |mahal - gamma| / gamma seen at either gate
+
+    def _note(self, decs):
+        for _, _, mah in decs:
+            for g in (GAMMA_MIN, GAMMA_MAX):
+                self.margin = min(self.margin, abs(mah - g) / g)
+
+    def _update(self, models, a, cap):
+        out = []
+        for b, m in enumerate(models):
+            idx = np.flatnonzero(a["valid"][b])
+            decs = m.update(a["z"][b, idx], a["R"][b, idx]) if idx.size else []
+            self._note(decs)
+            out.append(decs)
+            assert m.n_landmarks <= cap  # (a sequence never runs a handle into its sticky EKF_ERR_CAPACITY)
+        return out
+
+    def step(self, op):
+        kind, a = op
+        M = self.models
+        which = lambda: range(len(M)) if a.get("index") is None else [a["index"]]  # noqa: E731
+        if kind == "create":
+            self.models, self.cap = [MapModel() for _ in range(a["B"])], a["cap"]
+        elif kind == "load":
+            M[a["index"]] = MapModel(a["x"], a["P"])
+        elif kind == "propagate":
+            for b, m in enumerate(M):
+                m.propagate(a["v"][b], a["w"][b], a["dt"][b])
+        elif kind == "compass":
+            for b, m in enumerate(M):
+                if a["valid"][b]:
+                    m.compass(a["z"][b], a["R"])
+        elif kind == "update":
+            return self._update(M, a, self.cap)
+        elif kind == "remove":
+            return [M[b].remove(a["keep"][b]) for b in which()]
+        elif kind == "transform":
+            for b in which():
+                M[b].transform(a["frames"][b])
+        elif kind == "anchor":
+            for b in which():
+                M[b].anchor()
+        elif kind == "reserve":
+            self.cap = a["cap"]
+        elif kind == "src_create":
+            self.src, self.src_cap = [MapModel() for _ in range(a["B"])], a["cap"]
+        elif kind == "src_propagate":
+            for b, m in enumerate(self.src):
+                m.propagate(a["v"][b], a["w"][b], a["dt"][b])
+        elif kind == "src_update":
+            return self._update(self.src, a, self.src_cap)
+        elif kind == "join":
+            pairs = [(b, b) for b in range(len(M))] if a["index"] is None else [(a["index"], a["src_index"])]
+            if a["expect"] == "capacity":
+                assert any(M[d].n_landmarks + self.src[s].n_landmarks > self.cap for d, s in pairs)
+                return None
+            assert all(M[d].n_landmarks + self.src[s].n_landmarks <= self.cap for d, s in pairs)
+            return [M[d].join(self.src[s]) for d, s in pairs]
+        elif kind == "src_close":
+            self.src = []
+        elif kind == "joint":
+            return [M[b].joint(a["x_true"][b]) for b in which()]
+        elif kind == "covs":
+            return M[a["index"]].landmark_covs()
+        elif kind in ("read", "twin_begin", "twin_end"):
+            pass
+        else:
+            raise ValueError(kind)
+        return None
+
+
+# ---- the generator ----------------------------------------------------------------------------------
+def _world(rng, n, extent):
+    pts = []
+    while len(pts) < n:
+        p = rng.uniform(-extent, extent, 2)
+        if all((p[0] - q[0]) ** 2 + (p[1] - q[1]) ** 2 >= 1.0 for q in pts) and math.hypot(p[0], p[1]) >= 1.0:
+            pts.append(p)
+    return np.array(pts)
+
+
+class _Sim:
+    """The hidden side of one filter: true pose, world, which world landmark every map landmark is (-1: a spurious one made by an
+    outlier), the compass offset."""
+
+    def __init__(self, rng, n_world, extent):
+        self.world = _world(rng, n_world, extent)
+        self.pose = np.zeros(3)
+        self.in_map = []
+        self.offset = 0.0
+
+    def move(self, v, w, dt):
+        self.pose = self.pose + dt * np.array([v * math.cos(self.pose[2]), v * math.sin(self.pose[2]), w])
+
+    def rel(self, k):
+        c, s = math.cos(self.pose[2]), math.sin(self.pose[2])
+        d = self.world[k] - self.pose[:2]
+        return np.array([c * d[0] + s * d[1], -s * d[0] + c * d[1]])
+
+    def unseen(self):
+        seen = set(self.in_map)
+        return [k for k in range(len(self.world)) if k not in seen]
+
+
+def _measurement(oc, z):
+    return oc.make_measurement(1000.0 * z[0], 1000.0 * z[1])[1]
+
+
+def _initial_state(rng, sim, n0):
+    """n0 world landmarks already mapped: the estimate within its own covariance of the truth, P = D + U U^T."""
+    n = 3 + 2 * n0
+    x = np.empty(n)
+    x[:3] = sim.pose
+    x[3:] = (sim.world[:n0] + rng.normal(0.0, 0.03, (n0, 2))).reshape(-1)
+    d = rng.uniform(0.002, 0.004, n)
+    d[:3] *= 0.05
+    U = rng.normal(0.0, 3e-3, (n, 6))
+    P = U @ U.T
+    P[np.diag_indices(n)] += d
+    sim.in_map = list(range(n0))
+    return x, 0.5 * (P + P.T)
+
+
+class _Gen:
+    def __init__(self, seed, profile):
+        assert profile in PROFILES
+        self.oc = _oc()
+        self.rng = rng = np.random.default_rng([PROFILES.index(profile), seed, 20261018])
+        self.profile = profile
+        self.ops = []
+        self.run = ModelRunner()
+        self.deck = []
+        self.n_open, self.behind_traffic, self.force_open = 0, False, False
+        wgs = None
+        if profile == "solo":
+            cap, window, n_world, extent = int(rng.integers(40, 257)), int(rng.choice(WINDOWS)), 170, 13.0
+            starts = [[0, 5, 30, 31, 33, 60, 64, 70][int(rng.integers(0, 8))]]
+            if rng.random() < 0.5:  # little room: a join will be refused first
+                cap = max(40, starts[0] + int(rng.integers(8, 24)))
+        elif profile == "chain":
+            cap, window, n_world, extent = int(rng.integers(257, 701)), int(rng.choice(WINDOWS)), 420, 20.0
+            starts = [[0, 31, 64, 95, 130, 225, 245, 250][int(rng.integers(0, 8))]]
+            if starts[0] >= 225:  # little room: a join will be refused first
+                cap = int(rng.integers(257, 275))
+        elif profile == "chain_wgs":
+            cap, window, n_world, extent = int(rng.integers(30, 121)), int(rng.choice((1, 2, 4, 8, 16))), 170, 13.0
+            wgs = int(rng.integers(2, 5))
+            starts = [[0, 5, 20, 31, 33, 64][int(rng.integers(0, 6))]]
+        else:
+            B = int(rng.integers(3, 6))
+            cap, window, n_world, extent = int(rng.integers(40, 121)), int(rng.choice((2, 4, 8, 16))), 130, 11.0
+            pool = [5, 20, 31, 32, 33, 64]
+            starts = [pool[int(k)] for k in rng.choice(len(pool), size=B, replace=False)]
+            starts[int(rng.integers(0, B))] = 0  # one filter starts empty
+            if rng.random() < 0.5:  # little room: a join will be refused first
+                cap = max(40, max(starts) + int(rng.integers(8, 24)))
+        starts = [min(n0, cap - 6) for n0 in starts]
+        self.B = len(starts)
+        self.sims = [_Sim(rng, n_world, extent) for _ in starts]
+        self.emit("create", B=self.B, cap=cap, window=window, wgs=wgs)
+        for b, n0 in enumerate(starts):
+            if n0:
+                x, P = _initial_state(rng, self.sims[b], n0)
+                self.emit("load", index=b, x=x, P=P)
+
+    # -- plumbing
+    def emit(self, kind, **a):
+        # (a rewrite straight behind filter traffic that does not export first meets an open window and a live streaming launch)
+        if kind in ("remove", "transform", "anchor", "join") and not a["settle"] and self.behind_traffic:
+            self.n_open += 1
+        self.behind_traffic = kind in ("propagate", "update", "compass", "src_propagate", "src_update")
+        op = (kind, a)
+        self.ops.append(op)
+        return self.run.step(op)
+
+    @property
+    def models(self):
+        return self.run.models
+
+    def counts(self):
+        return [m.n_landmarks for m in self.models]
+
+    def grow(self, need):
+        """Room for `need` landmarks in every filter: an ekf_reserve, now and then across 256 (the kernel family changes)."""
+        cap = self.run.cap
+        new = max(need, cap) + int(self.rng.integers(4, 40))
+        if cap <= 256 and self.profile != "batch" and self.rng.random() < 0.4:
+            new = max(new, int(self.rng.integers(257, 300)))
+        self.emit("reserve", cap=new)
+
+    def note_new(self, sim, decs, world_ids):
+        for (dec, _, _), k in zip(decs, world_ids):
+            if dec == self.oc.NEW:
+                sim.in_map.append(k)
+
+    # -- one step of filter traffic
+    def traffic(self):
+        rng, B = self.rng, self.B
+        still = rng.random() < 0.1
+        v = np.zeros(B) if still else rng.uniform(0.05, 0.6, B)
+        w, dt = rng.uniform(-0.4, 0.4, B), rng.uniform(0.02, 0.3, B)
+        for b, s in enumerate(self.sims):
+            s.move(v[b], w[b], dt[b])
+        self.emit("propagate", v=v, w=w, dt=dt)
+        if rng.random() < 0.2:
+            valid = np.ones(B, dtype=bool) if B == 1 else rng.random(B) < 0.6
+            z = np.array([(s.pose[2] + s.offset) % 6.283185307 + rng.normal(0.0, 0.02) for s in self.sims])
+            self.emit("compass", z=z, R=COMPASS_VAR, valid=valid)
+        n_z = int(rng.integers(0, 5)) if B == 1 else int(rng.integers(1, 4))
+        if not n_z:
+            return
+        if max(self.counts()) + n_z > self.run.cap:
+            self.grow(max(self.counts()) + n_z)
+        z, R = np.zeros((B, n_z, 2)), np.tile(np.eye(2), (B, n_z, 1, 1))
+        valid = np.ones((B, n_z), dtype=bool) if B == 1 else rng.random((B, n_z)) < 0.75
+        ids = [[] for _ in range(B)]
+        for b, s in enumerate(self.sims):
+            mapped = [k for k in s.in_map if k >= 0]
+            fresh = s.unseen()
+            used = set()
+            for j in range(n_z):
+                if not valid[b, j]:
+                    continue
+                r = rng.random()  # < 0.55: a re-observation, < 0.88: a first sighting, else an outlier of a mapped landmark
+                pool = [k for k in (mapped if ((r < 0.55 or r >= 0.88) and mapped) else fresh) if k not in used]
+                if not pool:
+                    valid[b, j] = False
+                    continue
+                near = sorted(pool, key=lambda k: float(np.hypot(*(s.world[k] - s.pose[:2]))))[:12]
+                k = int(near[int(rng.integers(0, len(near)))])
+                used.add(k)
+                zz = s.rel(k) + rng.normal(0.0, 0.03, 2)
+                tag = k
+                if r >= 0.88 and k in mapped:  # an outlier between the gates, steered there by a trial on the model
+                    m = self.models[b]
+                    for _ in range(4):
+                        a = rng.uniform(0.0, 2.0 * math.pi)
+                        cand = zz + rng.uniform(0.15, 0.5) * np.array([math.cos(a), math.sin(a)])
+                        trial = self.oc.update(m.x, m.P, cand.reshape(2, 1), _measurement(self.oc, cand))
+                        if trial[2][0] == self.oc.IGNORE:
+                            break
+                    else:  # no trial fell between the gates: no measurement (a New one would sit half a metre from a real landmark)
+                        valid[b, j] = False
+                        continue
+                    zz, tag = cand, -1
+                z[b, j], R[b, j] = zz, _measurement(self.oc, zz)
+                ids[b].append(tag)
+        if not valid.any():
+            return
+        decs = self.emit("update", z=z, R=R, valid=valid)
+        for b, s in enumerate(self.sims):
+            self.note_new(s, decs[b], ids[b])
+
+    # -- rewrites and probes
+    def removal_mask(self, b, variant=None):
+        rng, N = self.rng, self.counts()[b]
+        keep = np.ones(N, dtype=bool)
+        if N == 0:
+            return keep
+        v = variant or str(rng.choice(["subset", "subset", "first", "last", "tile", "all", "edge"]))
+        if v == "subset":
+            keep = rng.random(N) > rng.uniform(0.1, 0.6)
+        elif v == "first":
+            keep[0] = False
+        elif v == "last":
+            keep[-1] = False
+        elif v == "tile":  # a whole tile's worth of landmarks, from a random start
+            a = int(rng.integers(0, max(N - 32, 0) + 1))
+            keep[a:a + 32] = False
+        elif v == "all":
+            keep[:] = False
+        else:  # "edge": down to a whole number of tiles
+            drop = N % 32 if N % 32 and N > 32 else min(N, 32)
+            if drop < N or rng.random() < 0.3:
+                keep[rng.choice(N, size=drop, replace=False)] = False
+        return keep
+
+    def do_remove(self, index, variant=None):
+        which = range(self.B) if index is None else [index]
+        keep = {b: self.removal_mask(b, variant) for b in which}
+        if index is None:  # the batch form: one [B][ld] array, landmarks beyond a filter's own count ignored
+            ld = max(max(len(k) for k in keep.values()), 1)
+            arr = np.ones((self.B, ld), dtype=bool)
+            for b, k in keep.items():
+                arr[b, :len(k)] = k
+            keep = {b: arr[b] for b in which}
+        for b in which:
+            k = keep[b][:len(self.sims[b].in_map)]
+            self.sims[b].in_map = [w for w, kept in zip(self.sims[b].in_map, k) if kept]
+        self.emit("remove", index=index, keep=keep, settle=bool(index is not None and self.B > 1 or self.rng.random() < 0.5) and not self.force_open)
+
+    def do_join(self, index):
+        rng, B = self.rng, self.B
+        dst = list(range(B)) if index is None else [index]
+        if any(len(self.sims[b].unseen()) < 30 for b in dst):
+            return False
+        if rng.random() < 0.5:  # the destination on a tile edge: no straddling old x new tile
+            for b in dst:
+                if self.counts()[b] > 32 and self.counts()[b] % 32:
+                    self.do_remove(b if B > 1 else index, "edge")
+        src_B = len(dst)
+        mine = [[] for _ in dst]  # world landmarks of the source's map, in its order
+        pools = []
+        room = min(self.run.cap - self.counts()[b] for b in dst)
+        refuse = room <= 40 and rng.random() < 0.7  # more landmarks than there is room for: EKF_ERR_CAPACITY first
+        for b in dst:
+            s = self.sims[b]
+            fresh = sorted(s.unseen(), key=lambda k: float(np.hypot(*(s.world[k] - s.pose[:2]))))
+            pools.append(fresh[:room + int(rng.integers(1, 4)) if refuse else int(rng.integers(3, 14))])
+        src_cap = int(rng.choice([c for c in SRC_CAPS if c >= max(len(p) for p in pools)]))
+        self.emit("src_create", B=src_B, cap=src_cap, window=int(rng.choice(WINDOWS)))
+        idle = int(rng.integers(0, src_B)) if src_B > 1 and rng.random() < 0.5 else -1  # a source filter that stays fresh
+        for t in range(8 if refuse else int(rng.integers(3, 9))):
+            v, w, dt = rng.uniform(0.05, 0.6, src_B), rng.uniform(-0.4, 0.4, src_B), rng.uniform(0.02, 0.3, src_B)
+            for i, b in enumerate(dst):
+                self.sims[b].move(v[i], w[i], dt[i])
+            self.emit("src_propagate", v=v, w=w, dt=dt)
+            n_z = (room + 10) // 8 if refuse else int(rng.integers(1, 4))
+            z, R = np.zeros((src_B, n_z, 2)), np.tile(np.eye(2), (src_B, n_z, 1, 1))
+            valid = np.zeros((src_B, n_z), dtype=bool)
+            ids = [[] for _ in dst]
+            for i, b in enumerate(dst):
+                if i == idle:
+                    continue
+                pick = rng.choice(len(pools[i]), size=min(n_z, len(pools[i])), replace=False)
+                if refuse:  # the pool in order, so that all of it is mapped
+                    pick = sorted(set((n_z * t + j) % len(pools[i]) for j in range(n_z)))
+                for j, p in enumerate(pick):
+                    k = pools[i][int(p)]
+                    z[i, j] = self.sims[b].rel(k) + rng.normal(0.0, 0.03, 2)
+                    R[i, j] = _measurement(self.oc, z[i, j])
+                    valid[i, j] = True
+                    ids[i].append(k)
+            decs = self.emit("src_update", z=z, R=R, valid=valid)
+            for i in range(src_B):
+                for (dec, _, _), k in zip(decs[i], ids[i]):
+                    if dec == self.oc.NEW:
+                        mine[i].append(k)
+        need = max(self.counts()[b] + self.run.src[i].n_landmarks for i, b in enumerate(dst))
+        settle = bool(rng.random() < 0.5 or B > 1 and index is not None)
+        if need > self.run.cap:
+            self.emit("join", index=index, src_index=0, expect="capacity", settle=True)
+            self.emit("reserve", cap=need + int(rng.integers(0, 40)))
+        self.emit("join", index=index, src_index=0, expect="ok", settle=settle)
+        for i, b in enumerate(dst):
+            self.sims[b].in_map += mine[i]
+        self.emit("src_close")
+        return True
+
+    def do_joint(self, index):
+        which = range(self.B) if index is None else [index]
+        xt = {}
+        for b in which:
+            m = self.models[b]
+            if m.clearly_positive_definite():
+                t = fr.draw_truth(m.x, m.P, int(self.rng.integers(0, 2 ** 31)))
+                t[2] += 2.0 * math.pi  # a full turn away: the error's heading component is wrapped
+                xt[b] = t
+            elif index is None:
+                return False
+            else:
+                xt[b] = None
+                if not (m.P[:3, :3] == 0.0).all() or (m.n_landmarks and not MapModel(m.x[3:], m.P[3:, 3:]).clearly_positive_definite()):
+                    return False  # neither clearly definite nor the exact zero pose block of an anchor: `info` would be a coin toss
+        self.emit("joint", index=index, x_true=xt)
+        return True
+
+    def rewrite(self, state_changing=False):
+        rng, B = self.rng, self.B
+        if not self.deck:
+            self.deck = [str(k) for k in rng.permutation(REWRITES)]
+        kind = str(rng.choice(["remove", "transform", "anchor"])) if state_changing else self.deck.pop()
+        # the batch profile: the batch form, or a single-index call on a filter b > 0 (the others must not move)
+        index = 0 if B == 1 else (int(rng.integers(1, B)) if rng.random() < 0.4 and not self.force_open else None)
+        if kind == "remove":
+            self.do_remove(index)
+        elif kind == "transform":
+            frames = {}
+            for b in (range(B) if index is None else [index]):
+                th = 0.0 if rng.random() < 0.25 else float(rng.uniform(-3.0, 3.0))
+                frames[b] = np.array([rng.uniform(-5.0, 5.0), rng.uniform(-5.0, 5.0), th])
+                self.sims[b].offset -= th
+            self.emit("transform", index=index, frames=frames, settle=bool(index is not None and B > 1 or rng.random() < 0.5) and not self.force_open)
+        elif kind == "anchor":
+            for b in (range(B) if index is None else [index]):
+                self.sims[b].offset -= float(self.models[b].x[2])
+            self.emit("anchor", index=index, settle=bool(index is not None and B > 1))
+        elif kind == "reserve":
+            self.grow(self.run.cap)
+        elif kind == "join":
+            if not self.do_join(index):
+                self.emit("read", index=int(rng.integers(0, B)))
+        elif kind == "joint":
+            if not self.do_joint(index) and not (index is None and self.do_joint(int(rng.integers(0, B)))):
+                self.emit("covs", index=int(rng.integers(0, B)))
+        elif kind == "covs":
+            self.emit("covs", index=int(rng.integers(0, B)))
+        else:
+            self.emit("read", index=int(rng.integers(0, B)))
+        return kind
+
+    def build(self):
+        rng = self.rng
+        twins_left, twin_end = 2, -1
+        for step in range(N_STEPS):
+            self.traffic()
+            if step == twin_end:
+                self.emit("twin_end")
+            # two twins per sequence at random rewrite points; a rewrite is made for one at steps 20 / 30 if chance has not
+            due = twins_left == 2 and step == 20 or twins_left >= 1 and step == 30
+            # ... and one that meets an open window (no export in front of it), should none have come by step 25
+            self.force_open = self.n_open == 0 and step >= 25 and step != twin_end
+            if rng.random() < 0.2 or step in (3, 17) or due or self.force_open:
+                kind = self.rewrite(state_changing=due or self.force_open)
+                # a set_state twin behind a rewrite: it runs the next five steps beside the handle, bit for bit
+                if twins_left and step > twin_end and step + 6 < N_STEPS and kind in ("remove", "transform", "anchor", "reserve", "join") \
+                        and (due or rng.random() < 0.4 + 0.03 * step):
+                    self.emit("twin_begin")
+                    twins_left, twin_end = twins_left - 1, step + 5
+        for b in range(self.B):
+            self.emit("read", index=b)
+        return self.ops
+
+
+def make_sequence(seed, profile):
+    """The operations of (seed, profile) as a list of (kind, args): create, load, then N_STEPS steps of traffic with a rewrite or
+    a probe about every fifth, then a read of every filter.  Per-filter arguments of the rewrites are dicts keyed by filter index;
+    `index` None is the batch form."""
+    return _Gen(seed, profile).build()
+
+
+def ops_equal(a, b):
+    """Two sequences, equal value for value."""
+    def eq(u, v):
+        if isinstance(u, dict):
+            return isinstance(v, dict) and u.keys() == v.keys() and all(eq(u[k], v[k]) for k in u)
+        if isinstance(u, np.ndarray) or isinstance(v, np.ndarray):
+            return np.array_equal(np.asarray(u), np.asarray(v))
+        return u == v
+    return len(a) == len(b) and all(p[0] == q[0] and eq(p[1], q[1]) for p, q in zip(a, b))

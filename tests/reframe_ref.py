@@ -17,10 +17,10 @@ def rot(a):
     return np.array([[c, -s], [s, c]])
 
 
-def _q(a):
-    """Rot(-a) written with cos(a), sin(a): [[c, s], [-s, c]]."""
+def _q(a, dtype=np.float64):
+    """Rot(-a) written with cos(a), sin(a): [[c, s], [-s, c]] (the float64 values of math.cos / math.sin in every dtype)."""
     c, s = math.cos(a), math.sin(a)
-    return np.array([[c, s], [-s, c]])
+    return np.array([[c, s], [-s, c]], dtype=dtype)
 
 
 def inverse_frame(frame):
@@ -31,20 +31,22 @@ def inverse_frame(frame):
 
 
 # ---- dense forms ---------------------------------------------------------------------------------
-def rigid_g(x, frame):
-    x = np.asarray(x, dtype=np.float64)
-    Q, t = _q(frame[2]), np.array([frame[0], frame[1]])
+# (dtype=np.longdouble: the same expressions carried in extended precision -- the yardstick of the float64 results; cos / sin stay
+# the float64 values the library takes)
+def rigid_g(x, frame, dtype=np.float64):
+    x = np.asarray(x, dtype=dtype)
+    Q, t = _q(frame[2], dtype), np.array([frame[0], frame[1]], dtype=dtype)
     out = np.empty_like(x)
     out[0:2] = Q @ (x[0:2] - t)
-    out[2] = x[2] - frame[2]
+    out[2] = x[2] - dtype(frame[2])
     out[3:] = ((x[3:].reshape(-1, 2) - t) @ Q.T).reshape(-1)
     return out
 
 
-def rigid_J(x, frame):
+def rigid_J(x, frame, dtype=np.float64):
     n = len(x)
-    Q = _q(frame[2])
-    J = np.zeros((n, n))
+    Q = _q(frame[2], dtype)
+    J = np.zeros((n, n), dtype=dtype)
     J[0:2, 0:2] = Q
     J[2, 2] = 1.0
     for a in range(3, n, 2):
@@ -52,29 +54,33 @@ def rigid_J(x, frame):
     return J
 
 
-def anchor_g(x):
-    x = np.asarray(x, dtype=np.float64)
-    Q = _q(x[2])
+def anchor_g(x, dtype=np.float64):
+    x = np.asarray(x, dtype=dtype)
+    Q = _q(float(x[2]), dtype)
     out = np.zeros_like(x)
     out[3:] = ((x[3:].reshape(-1, 2) - x[0:2]) @ Q.T).reshape(-1)
     return out
 
 
-def anchor_J(x):
-    x = np.asarray(x, dtype=np.float64)
+def anchor_J(x, dtype=np.float64):
+    x = np.asarray(x, dtype=dtype)
     n = len(x)
-    Q = _q(x[2])
-    J = np.zeros((n, n))
+    Q = _q(float(x[2]), dtype)
+    J = np.zeros((n, n), dtype=dtype)
     for a in range(3, n, 2):
         d = x[a:a + 2] - x[0:2]
         J[a:a + 2, 0:2] = -Q
-        J[a:a + 2, 2] = -Q @ (S @ d)
+        J[a:a + 2, 2] = -Q @ (S.astype(dtype) @ d)
         J[a:a + 2, a:a + 2] = Q
     return J
 
 
-def apply_dense(x, P, g, J):
-    return g(x), J(x) @ P @ J(x).T
+def apply_dense(x, P, g, J, dtype=None):
+    """g(x), J(x) P J(x)^T; with a dtype, g and J are called with it and P is carried in it."""
+    if dtype is None:
+        return g(x), J(x) @ P @ J(x).T
+    Jx = J(x, dtype=dtype)
+    return g(x, dtype=dtype), Jx @ np.asarray(P, dtype=dtype) @ Jx.T
 
 
 def central_difference(g, x, h=1e-6):

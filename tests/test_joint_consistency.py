@@ -17,8 +17,8 @@ import scipy.linalg
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import factor_ref as fr  # noqa: E402
 import reframe_ref as rr  # noqa: E402
-from helpers import (ABS_P, REL_TOL, assert_bitwise, batch_script, correlated_state, far_feature, make_filter,  # noqa: E402
-                     open_window_pair, run_steps, stream_starts)
+from helpers import (ABS_P, REL_TOL, assert_bitwise, batch_script, check_joint as check, correlated_state, far_feature,  # noqa: E402
+                     make_filter, open_window_pair, run_steps, stream_starts)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,36 +26,6 @@ pytestmark = pytest.mark.gpu
 # tile; the several-workgroup and the one-workgroup chain kernel
 CASES = [(31, 64), (32, 64), (33, 64), (100, 128), (280, 320), (180, 200)]
 NAN_OK = ("nees_map", "nees_joint", "logdet_map", "logdet_joint")
-
-
-def check(r, ref, P, what):
-    """Every field of a device record against a factor_ref result; returns the worst relative error seen."""
-    N = ref["n_landmarks"]
-    assert int(r["n_landmarks"]) == N and int(r["info"]) == ref["info"], (what, int(r["n_landmarks"]), int(r["info"]), ref["info"])
-    worst = 0.0
-    for k in fr.FIELDS:
-        got, want = float(r[k]), ref[k]
-        if math.isnan(want):
-            assert math.isnan(got), (what, k, got)
-            continue
-        if k.startswith("logdet"):
-            err = abs(got - want)
-            print("%s %s: |err| %.3e" % (what, k, err))
-            assert err <= 1e-6 * (3 + 2 * N), (what, k, got, want)
-            worst = max(worst, err / max(abs(want), 1.0))
-        else:
-            err = fr.rel_err(got, want) if want != 0.0 else abs(got)
-            print("%s %s: rel %.3e" % (what, k, err))
-            assert err <= REL_TOL, (what, k, got, want)
-            worst = max(worst, err)
-    S, Sr = r["cov_robot_given_map"], ref["cov_robot_given_map"]
-    if np.isnan(Sr).all():
-        assert np.isnan(S).all(), what
-    else:
-        dS = np.abs(S - Sr)
-        print("%s cov_robot_given_map: max |err| %.3e" % (what, dS.max()))
-        assert np.all(dS <= REL_TOL * np.abs(Sr) + ABS_P * np.abs(P).max()), (what, dS.max())
-    return worst
 
 
 def truth_for(x, P, seed):

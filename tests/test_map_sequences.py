@@ -1,0 +1,332 @@
+"""Random operation sequences that mix the map rewrites with live filter traffic: landmark removal, rigid transform, anchoring, map
+joining (from a source handle of another capacity, so another tile layout and often the other kernel family), ekf_reserve (now and
+then across capacity 256, where the kernel family changes under the state) and the read-only probes (ekf_joint_consistency,
+ekf_get_landmark_covs, a full state read), between propagations, measurement chunks and compass updates.
+
+tests/map_model.py generates every sequence from (seed, profile) and holds the host model (C oracle for the filter steps, the NumPy
+references for the rewrites); this file replays the list on the library and on the model in lockstep.  No seed and no step is
+skipped: tests/test_map_model_cpu.py checks on the CPU that no measurement of a committed seed lies within REL_TOL of a gate.
+Tolerances are the project's own (helpers.assert_state_close, REL_TOL, ABS_P); the observed maxima are printed per sequence.
+
+About half of the rewrites are made behind an open window (`settle` false: only the model says what must come out); the others
+export the state first, which adds the bitwise contracts -- removal is np.delete, theta = 0 leaves P alone, a join leaves the
+old x old block and the source alone, a single-index call leaves the other filters of the handle alone.  Twice per sequence a twin
+handle is loaded with set_state(get_state()) behind a rewrite and replays the next five steps beside the handle: exports and
+decisions must be bitwise equal, which is the only check that sees what a rewrite leaves behind the map (the zeros new landmarks
+grow into).  It cannot see the places of a diagonal tile that are nobody's home (a landmark's own block, whose home is D, and the
+blocks below the diagonal): no kernel and no export reads them, the dense pass only updates each from itself.
+
+In the chain_wgs profile EKF_CHAIN_WGS is set for the whole test, which keeps the one-workgroup kernel out of every handle: sources
+and twins run the chain kernel there too; "a source of the other kernel family" happens in the solo and chain profiles."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import map_model as mm  # noqa: E402
+from helpers import (ABS_P, REL_TOL, assert_bitwise, assert_bitwise_symmetric, assert_state_close, check_joint,  # noqa: E402
+                     stream_starts, windows_closed)
+
+pytestmark = pytest.mark.gpu
+
+REWRITES = ("remove", "transform", "anchor", "join", "reserve")
+TRAFFIC = ("propagate", "update", "compass", "src_propagate", "src_update")
+WORST = {}  # profile -> the largest errors seen so far in this session (printed behind every sequence)
+
+
+def real_decisions(dec, valid):
+    """Per filter, the decisions of the measurements that were not masked out (they sit at the end of the filter's row)."""
+    out = []
+    for b, row in enumerate(dec):
+        k = int(np.sum(valid[b]))
+        out.append(row[len(row) - k:] if k else [])
+    return out
+
+
+def per_filter(d, B, width, fill):
+    arr = np.full((B, width), fill)
+    for b, v in d.items():
+        arr[b, :len(v)] = v
+    return arr
+
+
+def apply(pkg, h, src, op):
+    """One operation on handle h (the handle under test or its twin); returns what the library answered."""
+    kind, a = op
+    B = h.batch
+    if kind == "load":
+        h.set_state(a["x"], a["P"], index=a["index"])
+    elif kind == "propagate":
+        h.propagate(a["v"], a["w"], a["dt"])
+    elif kind == "compass":
+        h.update_compass(a["z"], a["R"], valid=None if np.all(a["valid"]) else a["valid"])
+    elif kind == "update":
+        return real_decisions(h.update(a["z"], a["R"], valid=None if np.all(a["valid"]) else a["valid"]), a["valid"])
+    elif kind == "remove":
+        if a["index"] is None:
+            return [int(n) for n in h.remove_landmarks(per_filter(a["keep"], B, max(len(k) for k in a["keep"].values()), True))]
+        return [h.remove_landmarks(a["keep"][a["index"]], index=a["index"])]
+    elif kind == "transform":
+        if a["index"] is None:
+            h.transform_frame(per_filter(a["frames"], B, 3, 0.0))
+        else:
+            h.transform_frame(a["frames"][a["index"]], index=a["index"])
+    elif kind == "anchor":
+        h.anchor_at_robot(index=a["index"])
+    elif kind == "reserve":
+        h.reserve(a["cap"])
+    elif kind == "join":
+        if a["expect"] == "capacity":
+            rc = h.L.ekf_batch_join_map(h.h, src.h) if a["index"] is None else h.L.ekf_join_map(h.h, a["index"], src.h, a["src_index"])
+            assert rc == pkg.ekfslam.ERR_CAPACITY, rc
+            h.sync(), src.sync()  # EKF_OK: nothing sticky
+            return None
+        if a["index"] is None:
+            h.batch_join_map(src)
+            return [int(n) for n in h.num_landmarks()]
+        return [h.join_map(src, index=a["index"], src_index=a["src_index"])]
+    elif kind == "joint":
+        if a["index"] is None:
+            return h.joint_consistency(per_filter(a["x_true"], B, max(len(t) for t in a["x_true"].values()), 0.0)).copy()
+        return h.joint_consistency(a["x_true"][a["index"]], a["index"]).copy()
+    elif kind == "covs":
+        return h.landmark_covs(a["index"])
+    elif kind == "read":
+        return h.get_state(a["index"])
+    else:
+        raise ValueError(kind)
+    return None
+
+
+class Replay:
+    def __init__(self, pkg, monkeypatch, ops):
+        self.pkg, self.ops = pkg, ops
+        c = ops[0][1]
+        assert ops[0][0] == "create"
+        if c["wgs"]:
+            monkeypatch.setenv("EKF_CHAIN_WGS", str(c["wgs"]))
+        else:
+            monkeypatch.delenv("EKF_CHAIN_WGS", raising=False)
+        self.B, self.window = c["B"], c["window"]
+        self.f = pkg.FilterBatch(self.B, c["cap"], max_pending=self.window, log_capacity=4096)
+        self.twin = self.src = None
+        self.twin_decs = ([], [])
+        self.run = mm.ModelRunner()
+        self.run.step(ops[0])
+        self.err = {"x": 0.0, "P": 0.0, "joint": 0.0, "covs": 0.0}
+        self.n_twins = self.n_bitwise = self.n_open = self.n_live = 0
+        self.want_log, self.want_src_log = [[] for _ in range(self.B)], []
+        self.last = None  # the kind of the last library call on the handle
+
+    def close(self):
+        for h in (self.f, self.twin, self.src):
+            if h is not None:
+                h.close()
+
+    def export(self, h=None):
+        h = h or self.f
+        return [h.get_state(b) for b in range(h.batch)]
+
+    def compare(self, b, what, state=None):
+        """Filter b of the handle against its model: the whole state, symmetry, the count and the host mirror."""
+        x, P = state or self.f.get_state(b)
+        m = self.run.models[b]
+        e = assert_state_close(x, P, m.x, m.P, what="%s, filter %d" % (what, b))
+        self.err["x"], self.err["P"] = max(self.err["x"], e[0]), max(self.err["P"], e[1])
+        assert_bitwise_symmetric(P)
+        assert int(self.f.num_landmarks()[b]) == m.n_landmarks == (x.size - 3) // 2
+        assert np.array_equal(self.f.poses()[b], x[:3]), what
+        if self.B == 1:  # (ekf_get_robot_cov is a one-filter call)
+            assert np.array_equal(self.f.robot_cov(), P[:3, :3]), what
+        return x, P
+
+    def logs(self, h):
+        return h.stats(), [h.decisions(b) for b in range(h.batch)]
+
+    def check_logs(self, h, want, what):
+        """Counters and decision log of every filter against the model's record of its measurements."""
+        st = h.stats()
+        for b, w in enumerate(want):
+            assert [(d[0], d[1]) for d in h.decisions(b)] == w, (what, b)
+            E = self.pkg.ekfslam
+            assert [st[b]["n_new"], st[b]["n_old"], st[b]["n_ignore"]] == [sum(1 for d in w if d[0] == k) for k in (E.NEW, E.OLD, E.IGNORE)], (what, b)
+
+    # -- one operation on the handle, its twin and the model
+    def step(self, i, op):
+        kind, a = op
+        pkg, f, B = self.pkg, self.f, self.B
+        what = "op %d (%s)" % (i, kind)
+        if kind in ("twin_begin", "twin_end"):
+            self.last = kind  # (both export the state)
+        if kind == "twin_begin":
+            states = self.export()
+            self.twin = pkg.FilterBatch(B, f.capacity, max_pending=self.window, log_capacity=4096)
+            for b in range(B):
+                self.twin.set_state(*states[b], index=b)
+            self.twin_decs = ([], [])
+            return
+        if kind == "twin_end":
+            sa, sb = self.export(), self.export(self.twin)
+            for b in range(B):
+                assert_bitwise(sa[b], sb[b], "%s: handle vs set_state twin, filter %d" % (what, b))
+            assert self.twin_decs[0] == self.twin_decs[1] and np.array_equal(f.poses(), self.twin.poses())
+            self.twin.close()
+            self.twin, self.n_twins = None, self.n_twins + 1
+            return
+        if kind == "src_create":
+            self.src = pkg.FilterBatch(a["B"], a["cap"], max_pending=a["window"], log_capacity=4096)
+            self.want_src_log = [[] for _ in range(a["B"])]
+            self.run.step(op)
+            return
+        if kind in ("src_propagate", "src_update"):
+            got = apply(pkg, self.src, None, (kind[4:], a))
+            want = self.run.step(op)
+            if kind == "src_update":
+                assert [[(d[0], d[1]) for d in row] for row in got] == [[(d[0], d[1]) for d in row] for row in want], what
+                for b, row in enumerate(want):
+                    self.want_src_log[b] += [(d[0], d[1]) for d in row]
+            self.last = kind
+            return
+        if kind == "src_close":
+            self.src.close()
+            self.src = None
+            self.run.step(op)
+            return
+
+        which = list(range(B)) if a.get("index") is None else [a["index"]]
+        rewrite = kind in REWRITES
+        settle = bool(a.get("settle")) or kind == "joint" or (kind == "reserve" and i % 2 == 0)
+        # a rewrite that is not `settle` meets the handle (and a join its source) as the last immediate call left it: the window open,
+        # the streaming launch of a one-filter handle live -- nothing is read in front of it, reading the counters would stop the launch
+        before = self.export() if settle else None
+        src_before = self.export(self.src) if (kind == "join" and settle) else None
+        if rewrite and settle:
+            logs0 = self.logs(f)
+            src_logs0 = self.logs(self.src) if kind == "join" else None
+        if rewrite and not settle and self.last in TRAFFIC:
+            self.n_open += 1
+            self.n_live += stream_starts(f)[0] > 0  # (host counters only: this handle streams its immediate calls)
+        if kind == "covs":
+            closed0 = windows_closed(f)
+        counts0 = [m.n_landmarks for m in self.run.models]
+
+        got = apply(pkg, f, self.src, op)
+        if self.twin is not None:
+            got_twin = apply(pkg, self.twin, self.src, op)
+            if kind == "update":
+                self.twin_decs[0].extend(got), self.twin_decs[1].extend(got_twin)
+        want = self.run.step(op)
+
+        if kind == "update":
+            assert [[(d[0], d[1]) for d in row] for row in got] == [[(d[0], d[1]) for d in row] for row in want], (what, got, want)
+            for b, row in enumerate(want):
+                self.want_log[b] += [(d[0], d[1]) for d in row]
+        elif kind == "read":
+            self.compare(a["index"], what, got)
+        elif kind == "covs":
+            assert windows_closed(f) == closed0, what  # no dense pass: the window stays open
+            P = self.run.models[a["index"]].P
+            assert got.shape == want.shape, what
+            if want.size:
+                d = np.abs(got - want)
+                assert np.all(d <= REL_TOL * np.abs(want) + ABS_P * np.abs(P).max()), (what, d.max())
+                self.err["covs"] = max(self.err["covs"], float(d.max() / np.abs(P).max()))
+        elif kind == "joint":
+            for k, b in enumerate(which):
+                self.err["joint"] = max(self.err["joint"], check_joint(got[k], want[k], self.run.models[b].P, "%s, filter %d" % (what, b)))
+            again = apply(pkg, f, self.src, op)
+            assert again.tobytes() == got.tobytes(), what  # an unchanged state: the same bits
+            for b in range(B):
+                assert_bitwise(f.get_state(b), before[b], "%s: the call only reads, filter %d" % (what, b))
+        self.last = kind
+        if not rewrite:
+            return
+
+        self.check_logs(f, self.want_log, what)  # counters and decision log do not move
+        if kind == "join":
+            self.check_logs(self.src, self.want_src_log, what + ", source")
+        if settle:
+            assert self.logs(f) == logs0, what
+        after = self.export()
+        if kind == "join" and a["expect"] == "capacity":
+            for b in range(B):
+                assert_bitwise(after[b], before[b], "%s: destination after EKF_ERR_CAPACITY, filter %d" % (what, b))
+            for b, s in enumerate(self.export(self.src)):
+                assert_bitwise(s, src_before[b], "%s: source after EKF_ERR_CAPACITY, filter %d" % (what, b))
+            assert self.logs(self.src) == src_logs0
+            return
+        if got is not None:
+            assert got == want, (what, got, want)  # the new landmark counts
+        for b in range(B):
+            self.compare(b, what, after[b])
+        if kind == "anchor":
+            for b in which:
+                assert not after[b][0][:3].any() and not after[b][1][:3, :].any() and not after[b][1][:, :3].any(), what
+            assert not f.poses()[which].any()
+        if kind == "join":
+            assert not settle or self.logs(self.src) == src_logs0, what
+            for b, s in enumerate(self.export(self.src)):  # the source is only read: bitwise where it was exported, else its own model
+                if settle:
+                    assert_bitwise(s, src_before[b], "%s: the source, filter %d" % (what, b))
+                m = self.run.src[b]
+                assert_state_close(s[0], s[1], m.x, m.P, what="%s: the source, filter %d" % (what, b))
+        if not settle:
+            return
+        self.n_bitwise += 1
+        for b in range(B):
+            if b not in which or kind == "reserve":
+                assert_bitwise(after[b], before[b], "%s: filter %d is not touched" % (what, b))
+        for b in which:
+            if kind == "remove":
+                assert_bitwise(after[b], mm.reduce_state(*before[b], a["keep"][b]), "%s: np.delete, filter %d" % (what, b))
+            elif kind == "transform" and a["frames"][b][2] == 0.0:
+                assert np.array_equal(after[b][1], before[b][1]), what
+            elif kind == "join":
+                e = 3 + 2 * counts0[b]
+                assert np.array_equal(after[b][1][3:e, 3:e], before[b][1][3:, 3:]) and np.array_equal(after[b][0][3:e], before[b][0][3:]), what
+
+
+def run_sequence(pkg, monkeypatch, profile, seed):
+    ops = mm.make_sequence(seed, profile)
+    r = Replay(pkg, monkeypatch, ops)
+    try:
+        for i, op in enumerate(ops[1:], 1):
+            r.step(i, op)
+        assert r.twin is None and r.src is None
+        assert r.n_twins == 2 and r.n_open >= 1
+    finally:
+        r.close()
+    print("%s seed %d: %d ops, %d twins, %d exported rewrites, %d behind open traffic (%d on a streaming handle); max |dx| %.3e, "
+          "max |dP| / max |P| %.3e, joint worst %.3e, covs %.3e"
+          % (profile, seed, len(ops), r.n_twins, r.n_bitwise, r.n_open, r.n_live, r.err["x"], r.err["P"], r.err["joint"], r.err["covs"]))
+    w = WORST.setdefault(profile, dict.fromkeys(r.err, 0.0))
+    for k in w:
+        w[k] = max(w[k], r.err[k])
+    print("%s, worst so far: max |dx| %.3e, max |dP| / max |P| %.3e, joint %.3e, covs %.3e" % (profile, w["x"], w["P"], w["joint"], w["covs"]))
+
+
+@pytest.mark.parametrize("seed", mm.SEEDS["solo"])
+def test_solo_sequences(pkg, monkeypatch, pipeline_mode, seed):
+    """One filter, capacity 40-256 (the one-workgroup kernel where the pipeline mode allows it), windows of 1 to 32."""
+    run_sequence(pkg, monkeypatch, "solo", seed)
+
+
+@pytest.mark.parametrize("seed", mm.SEEDS["chain"])
+def test_chain_sequences(pkg, monkeypatch, pipeline_mode, seed):
+    """One filter, capacity 257-700: the several-workgroup chain kernel."""
+    run_sequence(pkg, monkeypatch, "chain", seed)
+
+
+@pytest.mark.parametrize("seed", mm.SEEDS["chain_wgs"])
+def test_chain_wgs_sequences(pkg, monkeypatch, pipeline_mode, seed):
+    """A small capacity on two to four workgroups (EKF_CHAIN_WGS)."""
+    run_sequence(pkg, monkeypatch, "chain_wgs", seed)
+
+
+@pytest.mark.parametrize("seed", mm.SEEDS["batch"])
+def test_batch_sequences(pkg, monkeypatch, pipeline_mode, seed):
+    """Three to five filters of one handle, each with its own landmark count; the batch forms with masks, and single-index calls on a
+    filter b > 0 that must leave the others bit for bit."""
+    run_sequence(pkg, monkeypatch, "batch", seed)
