@@ -15,6 +15,7 @@
 #include <mutex>
 #include <functional>
 #include <vector>
+#include <algorithm>
 
 #include "ekf_device.h"
 #include "ekf_geometry.h"
@@ -24,6 +25,7 @@
 #include "ekf_solo.hip"
 #include "ekf_rewrite.hip"
 #include "ekf_factor.hip"
+#include "ekf_pairs.hip"
 
 static thread_local std::string g_last_error;
 
@@ -177,6 +179,10 @@ struct ekf_batch {
     long long fac_stamp[3] = {-1, -1, -1};  // those three when the scratch was last filled (ekf_debug_joint_factor)
     int fac_b0 = 0;                // ... by a call over filters [fac_b0, fac_b0 + fac_n.size()) with fac_n landmarks each
     std::vector<int> fac_n;
+    // duplicate search (ekf_find_duplicates): bounding boxes, counters and split table in one allocation made at the first call, the
+    // pair list in a second one that grows when a call finds more pairs than it holds; both kept and counted in device_bytes
+    DupScratch dup = {};
+    void *dup_base = nullptr;
 };
 
 static int sticky_status(ekf_batch *h, bool include_capacity);
@@ -717,6 +723,8 @@ extern "C" int ekf_destroy(ekf_handle h) {
         if (h->ev_flush[i]) hipEventDestroy(h->ev_flush[i]);
     if (h->bm1_base) hipFree(h->bm1_base);
     if (h->fac_base) hipFree(h->fac_base);
+    if (h->dup_base) hipFree(h->dup_base);
+    if (h->dup.list) hipFree(h->dup.list);
     for (auto &g : h->graphs) hipGraphExecDestroy(g.exec);
     for (const DevArray &a : device_arrays(h))
         if (*a.slot) hipFree(*a.slot);
@@ -1631,6 +1639,7 @@ static int sticky_status(ekf_batch *h, bool include_capacity) {
 //   ekf_get_x                                          QUIET_STREAM   ST_INVALID           copy
 //   ekf_get_state                                      QUIET_STREAM   ST_INVALID           size only: returns; else settle(), export
 //   ekf_joint_consistency (and the batch form)         QUIET_STREAM   ST_INVALID           settle(), factor in the scratch; the state is only read
+//   ekf_find_duplicates (and the batch form)           QUIET_STREAM   ST_INVALID           settle(), the pairwise gate over Bm; the state is only read
 //   ekf_set_state                                      QUIET_SETTLED  ST_NONE              (the way out of a timed-out handle: no status ends it)
 //   ekf_broadcast_state                                QUIET_SETTLED  ST_NONE
 //   ekf_reserve                                        QUIET_SETTLED  ST_NONE              refreshes the bounds AFTER the settle; only EKF_ERR_TIMEOUT ends it
@@ -1880,6 +1889,7 @@ extern "C" int ekf_set_state(ekf_handle h, int index, const double *x, const dou
 // the counters, the decision log and a loaded script move with it, and the handle keeps its address.
 static int reserve_move_state(ekf_batch *h, ekf_batch *nh, const std::vector<int> &n_lm);
 static int factor_reserve(ekf_batch *h);
+static int dup_reserve(ekf_batch *h, int cap);
 
 extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     if (!h || capacity_landmarks < 1 || capacity_landmarks > EKF_MAX_CAPACITY) return set_error(EKF_ERR_BAD_ARG, "bad handle / capacity (EKF_MAX_CAPACITY)");
@@ -1943,9 +1953,11 @@ extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     nh->script_steps = h->script_steps, nh->script_M = h->script_M, nh->script_has_truth = h->script_has_truth;
     h->script_steps = 0;
     const bool had_factor_scratch = h->fac_base != nullptr;
+    const int had_dup_cap = h->dup_base ? h->dup.cap : 0;
     std::swap(*h, *nh);  // the caller's handle now owns the larger buffers ...
     ekf_destroy(nh);     // ... and the old ones go
     if (had_factor_scratch) EKF_TRY(factor_reserve(h));  // (the scratch of ekf_joint_consistency follows the capacity)
+    if (had_dup_cap) EKF_TRY(dup_reserve(h, had_dup_cap));  // (... and so does that of ekf_find_duplicates)
     return refresh_bounds(h);
 }
 
@@ -2287,6 +2299,126 @@ extern "C" int ekf_debug_joint_factor(ekf_handle h, int index, double *U_out, in
     HIP_TRY(stream_wait(h->s_chain));
     EKF_TRY(check_launch());
     return m;
+}
+
+// ---- duplicate search -----------------------------------------------------------------------------
+// The scratch of ekf_find_duplicates (ekf_pairs.hip: DupScratch).  Boxes, counters and the split table are sized by the handle's
+// capacity and allocated once; the pair list holds `cap` pairs per filter and is replaced by a larger one when a call finds more
+// than it holds.  Both are counted in ekf_device_bytes, freed by ekf_destroy; ekf_reserve builds them again for the larger capacity.
+static int dup_reserve(ekf_batch *h, int cap) {
+    const EkfDev &dv = h->dv;
+    const size_t B = (size_t)dv.B;
+    if (!h->dup_base) {
+        const size_t nbox = B * (size_t)(dv.dn >> 5) * 4;
+        const size_t bytes = nbox * sizeof(double) + B * 3 * sizeof(int);
+        void *p = nullptr;
+        HIP_TRY(hipMalloc(&p, bytes));
+        hipError_t e = hipMemsetAsync(p, 0, bytes, h->s_chain);
+        if (e == hipSuccess) e = stream_wait(h->s_chain);
+        if (e != hipSuccess) {
+            hipFree(p);
+            return set_error(EKF_ERR_HIP, hipGetErrorString(e));
+        }
+        h->dup_base = p;
+        h->dup.box = (double *)p;
+        h->dup.cnt = (int *)(h->dup.box + nbox);
+        h->dup.split = h->dup.cnt + 2 * B;
+        h->device_bytes += bytes;
+    }
+    if (cap > h->dup.cap) {
+        void *p = nullptr;
+        HIP_TRY(hipMalloc(&p, B * (size_t)cap * sizeof(ekf_dup_pair)));
+        if (h->dup.list) {
+            hipFree(h->dup.list);
+            h->device_bytes -= B * (size_t)h->dup.cap * sizeof(ekf_dup_pair);
+        }
+        h->dup.list = (ekf_dup_pair *)p;
+        h->dup.cap = cap;
+        h->device_bytes += B * (size_t)cap * sizeof(ekf_dup_pair);
+    }
+    return EKF_OK;
+}
+
+static int dup_cap_for(long long pairs) {
+    long long cap = 256;
+    while (cap < pairs) cap *= 2;
+    return (int)cap;
+}
+
+// Filters [b0, b0 + nb): the rule of ekf_get_state (the streaming launch leaves, every deferred slot is folded, both streams idle),
+// then the settled state is only read: boxes (with a Euclidean bound), tiles, the counters back, the lists back.  A call that
+// finds more pairs than the device list holds and has to hand some out runs the two kernels once more with a list that fits (the
+// state has not moved: the same pairs).  The appended order is the hardware's; each filter's list is sorted by (i, j) here.
+static int dup_impl(ekf_batch *h, int b0, int nb, double gate, double max_dist, int split_one, const int *split, ekf_dup_pair *pairs_out, int max_pairs,
+                    int *n_found_out, int *n_degenerate_out) {
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
+    int n_max = 0, nt = 0;
+    for (int k = 0; k < nb; k++) {
+        const int n = h->h_int[b0 + k], sp = split ? split[k] : split_one;
+        if (sp < 0 || sp > n) {
+            char buf[160];
+            snprintf(buf, sizeof buf, "filter %d: split = %d is outside [0, %d landmarks]", b0 + k, sp, n);
+            return set_error(EKF_ERR_BAD_ARG, buf);
+        }
+        const int t = dup_tile_count(n, sp);
+        nt = t > nt ? t : nt;
+        n_max = n > n_max ? n : n_max;
+    }
+    EKF_TRY(settle(h));
+    EKF_TRY(dup_reserve(h, dup_cap_for(max_pairs < 4096 ? max_pairs : 4096)));  // (a call that finds more grows the list below)
+    const EkfDev &dv = h->dv;
+    hipStream_t s = h->s_chain;
+    DupArgs da;
+    da.gate = gate, da.md2 = max_dist > 0.0 ? max_dist * max_dist : -1.0, da.split_one = split_one, da.use_tab = split ? 1 : 0;
+    if (split) HIP_TRY(hipMemcpyAsync(h->dup.split + b0, split, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
+    std::vector<int> cnt((size_t)2 * nb, 0);
+    for (int round = 0; nt > 0; round++) {
+        const DupScratch ds = h->dup;
+        HIP_TRY(hipMemsetAsync(ds.cnt + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
+        if (da.md2 >= 0.0) hipLaunchKernelGGL(k_dup_boxes, dim3((unsigned)cdiv(lm_tiles(n_max), 64), (unsigned)nb), dim3(64), 0, s, dv, ds, b0);
+        hipLaunchKernelGGL(k_dup_tiles, dim3((unsigned)nt, (unsigned)nb), dim3(256), 0, s, dv, ds, da, h->buf_in, b0);
+        HIP_TRY(hipMemcpyAsync(cnt.data(), ds.cnt + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost, s));
+        HIP_TRY(stream_wait(s));
+        EKF_TRY(check_launch());
+        int most = 0;
+        for (int k = 0; k < nb; k++) most = cnt[2 * k] > most ? cnt[2 * k] : most;
+        if (most <= ds.cap || max_pairs == 0) break;
+        if (round > 0) return set_error(EKF_ERR_STATE, "the pair count changed between two passes over an unchanged state");
+        EKF_TRY(dup_reserve(h, dup_cap_for(most)));
+    }
+    std::vector<ekf_dup_pair> got;
+    std::vector<size_t> at((size_t)nb + 1, 0);
+    for (int k = 0; k < nb; k++) at[k + 1] = at[k] + (max_pairs > 0 ? (size_t)cnt[2 * k] : 0);
+    got.resize(at[nb]);
+    for (int k = 0; k < nb; k++)
+        if (at[k + 1] > at[k])
+            HIP_TRY(hipMemcpyAsync(got.data() + at[k], h->dup.list + (size_t)(b0 + k) * h->dup.cap, sizeof(ekf_dup_pair) * (at[k + 1] - at[k]), hipMemcpyDeviceToHost, s));
+    if (at[nb] > 0) HIP_TRY(stream_wait(s));
+    for (int k = 0; k < nb; k++) {
+        const int found = cnt[2 * k];
+        if (n_found_out) n_found_out[k] = found;
+        if (n_degenerate_out) n_degenerate_out[k] = cnt[2 * k + 1];
+        if (at[k + 1] == at[k]) continue;
+        std::sort(got.begin() + at[k], got.begin() + at[k + 1], [](const ekf_dup_pair &a, const ekf_dup_pair &b) { return a.i != b.i ? a.i < b.i : a.j < b.j; });
+        memcpy(pairs_out + (size_t)k * max_pairs, got.data() + at[k], sizeof(ekf_dup_pair) * (size_t)(found < max_pairs ? found : max_pairs));
+    }
+    return nb == 1 && !n_found_out ? cnt[0] : EKF_OK;
+}
+
+static bool dup_args_ok(double gate, double max_dist, const ekf_dup_pair *pairs_out, int max_pairs) {
+    return __builtin_isfinite(gate) && gate >= 0.0 && max_dist == max_dist && max_pairs >= 0 && (pairs_out || max_pairs == 0);
+}
+
+extern "C" int ekf_find_duplicates(ekf_handle h, int index, double gate, double max_dist, int split, ekf_dup_pair *pairs_out, int max_pairs,
+                                   int *n_degenerate_out) {
+    if (!h || index < 0 || index >= h->dv.B || split < 0 || !dup_args_ok(gate, max_dist, pairs_out, max_pairs)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return dup_impl(h, index, 1, gate, max_dist, split, nullptr, pairs_out, max_pairs, nullptr, n_degenerate_out);
+}
+
+extern "C" int ekf_batch_find_duplicates(ekf_handle h, double gate, double max_dist, const int *split, ekf_dup_pair *pairs_out, int max_pairs, int *n_found_out,
+                                         int *n_degenerate_out) {
+    if (!h || !n_found_out || !dup_args_ok(gate, max_dist, pairs_out, max_pairs)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return dup_impl(h, 0, h->dv.B, gate, max_dist, 0, split, pairs_out, max_pairs, n_found_out, n_degenerate_out);
 }
 
 extern "C" int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max) {

@@ -334,6 +334,58 @@ __host__ __device__ inline int chol_operand_offset(int s, int blk, int lane) {
     return ((s >> 2) * 4 + blk) * 256 + ((s >> 1) & 1) * 128 + lane * 2 + (s & 1);
 }
 
+// Duplicate search (ekf_find_duplicates, ekf_pairs.hip): the pairs of landmarks i < j < n a call considers, walked by stored tile
+// (32 x 32 landmarks), work item (reframe_item: two complete cross blocks P_ij) and block.  split = 0: every pair, i.e. the stored
+// triangle of side lm_tiles(n).  0 < split <= n: only i < split <= j, which live in the rectangle of tiles I <= (split - 1) / 32,
+// J >= split / 32 (I <= J there); the two straddling tile rows / columns are filtered per pair.
+__host__ __device__ inline int dup_tile_count(int n, int split) {
+    const int nT = lm_tiles(n);
+    if (n < 2 || split >= n) return 0;
+    if (split <= 0) return nT * (nT + 1) / 2;
+    return (((split - 1) >> 5) + 1) * (nT - (split >> 5));
+}
+// tile t of that list; false behind its end
+__host__ __device__ inline bool dup_tile_ij(int t, int n, int split, int *I, int *J) {
+    if (t < 0 || t >= dup_tile_count(n, split)) return false;
+    const int nT = lm_tiles(n);
+    if (split <= 0) {
+        tri_tile_ij(t, nT, I, J);
+    } else {
+        const int J0 = split >> 5, w = nT - J0;
+        *I = t / w, *J = J0 + t % w;
+    }
+    return true;
+}
+// block k (0, 1) of work item `it` of tile (I, J): the pair it holds, or false (beyond the map, not above the diagonal -- a
+// landmark's own block and the below-diagonal twins of a diagonal tile, which are nobody's home -- or on one side of the split)
+__host__ __device__ inline bool dup_pair(int n, int split, int I, int J, const ReframeItem &it, int k, int *i, int *j) {
+    const int li = 32 * I + (it.row[k] >> 1), lj = 32 * J + (it.col >> 1);
+    *i = li, *j = lj;
+    return li < lj && lj < n && (split <= 0 || (li < split && lj >= split));
+}
+// The Euclidean bound: squared distance in ONE written-out form (a fused multiply-add, on the host and on the device), used for
+// the pairs and for the gaps between two groups' bounding boxes alike.  Rounding is monotone, so a box gap that is no larger than
+// every |L_i - L_j| component of the tile gives a value no larger than any pair's: a culled tile holds no pair within the bound.
+__host__ __device__ inline double dup_dist2(double dx, double dy) { return __builtin_fma(dx, dx, dy * dy); }
+__host__ __device__ inline double dup_box_gap(double lo_a, double hi_a, double lo_b, double hi_b) {
+    const double g0 = lo_a - hi_b, g1 = lo_b - hi_a;
+    const double g = g0 > g1 ? g0 : g1;
+    return g > 0.0 ? g : 0.0;
+}
+// The gate of one pair (include/ekfslam_c.h): S = P_ii + P_jj - P_ij - P_ij^T as (a, b; b, c), d = L_i - L_j.  Returns 0 with
+// *d2 = d^T S^-1 d, or 1 when the pair is degenerate (S not positive definite, NaN included).  No contraction: the host reference
+// (tests/dup_ref.py) evaluates the same operations in the same order.
+__host__ __device__ inline int dup_gate(double dx, double dy, const double di[3], const double dj[3], const double pij[4], double *d2) {
+#pragma clang fp contract(off)
+    const double a = (di[0] + dj[0]) - 2.0 * pij[0];
+    const double b = ((di[1] + dj[1]) - pij[1]) - pij[2];
+    const double c = (di[2] + dj[2]) - 2.0 * pij[3];
+    const double det = a * c - b * b;
+    if (!(a > 0.0 && det > 0.0)) return 1;
+    *d2 = ((c * dx * dx - 2.0 * b * dx * dy) + a * dy * dy) / det;
+    return 0;
+}
+
 // Offset (doubles) of row i' of slot PAIR p inside one (filter, set) of FA / FB: 4 doubles, slot 2p in
 // [0..1], slot 2p+1 in [2..3].
 __host__ __device__ inline size_t pair_offset(int rows, int ip, int p) {

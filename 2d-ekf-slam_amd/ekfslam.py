@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "ekf_transform_frame", "ekf_batch_transform_frame", "ekf_anchor_at_robot", "ekf_batch_anchor_at_robot",
     "ekf_join_map", "ekf_batch_join_map",
     "ekf_joint_consistency", "ekf_batch_joint_consistency", "ekf_debug_joint_factor",
+    "ekf_find_duplicates", "ekf_batch_find_duplicates",
 ]
 
 
@@ -55,6 +56,15 @@ class EkfJoint(ctypes.Structure):
 JOINT_DTYPE = np.dtype([("n_landmarks", "i4"), ("info", "i4"), ("nees_map", "f8"), ("nees_joint", "f8"), ("logdet_map", "f8"),
                         ("logdet_joint", "f8"), ("min_pivot", "f8"), ("max_pivot", "f8"), ("cov_robot_given_map", "f8", (3, 3))])
 assert JOINT_DTYPE.itemsize == ctypes.sizeof(EkfJoint)
+
+
+
+class EkfDupPair(ctypes.Structure):
+    _fields_ = [("i", ctypes.c_int), ("j", ctypes.c_int), ("d2", ctypes.c_double)]
+
+
+DUP_DTYPE = np.dtype([("i", "i4"), ("j", "i4"), ("d2", "f8")])
+assert DUP_DTYPE.itemsize == ctypes.sizeof(EkfDupPair) == 16
 
 _STATS_DTYPE = np.dtype([(n, "f8" if t is ctypes.c_double else "i8") for n, t in EkfStats._fields_])
 
@@ -121,6 +131,8 @@ def load():
     L.ekf_joint_consistency.argtypes = [_H, ctypes.c_int, _dp, ctypes.POINTER(EkfJoint)]
     L.ekf_batch_joint_consistency.argtypes = [_H, _dp, ctypes.c_int, ctypes.POINTER(EkfJoint)]
     L.ekf_debug_joint_factor.argtypes = [_H, ctypes.c_int, _dp, ctypes.c_int]
+    L.ekf_find_duplicates.argtypes = [_H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.POINTER(EkfDupPair), ctypes.c_int, _ip]
+    L.ekf_batch_find_duplicates.argtypes = [_H, ctypes.c_double, ctypes.c_double, _ip, ctypes.POINTER(EkfDupPair), ctypes.c_int, _ip, _ip]
     L.ekf_script_load.argtypes = [_H, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _up, _dp]
     L.ekf_script_run.argtypes = [_H, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.ekf_sync.argtypes = [_H]
@@ -155,6 +167,25 @@ def _p(a):
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def duplicate_keep_mask(pairs, n_landmarks):
+    """A keep mask for remove_landmarks from a list of duplicate pairs (find_duplicates): greedy one-to-one matching by ascending d2,
+    ties by (i, j); a pair is accepted when neither of its landmarks is matched already, and the later landmark j of an accepted
+    pair goes (keep[j] = False).  In a chain i-j-k of mutual candidates only the closest link is accepted: search again after the
+    removal when several copies of one point are expected."""
+    pairs = np.asarray(pairs, dtype=DUP_DTYPE).reshape(-1)
+    keep = np.ones(int(n_landmarks), dtype=bool)
+    matched = np.zeros(int(n_landmarks), dtype=bool)
+    for k in np.lexsort((pairs["j"], pairs["i"], pairs["d2"])):
+        i, j = int(pairs["i"][k]), int(pairs["j"][k])
+        if not (0 <= i < j < keep.size):
+            raise ValueError("pair (%d, %d) does not name two landmarks i < j of %d" % (i, j, keep.size))
+        if matched[i] or matched[j]:
+            continue
+        matched[i] = matched[j] = True
+        keep[j] = False
+    return keep
 
 
 def default_params(**kw):
@@ -361,6 +392,32 @@ class FilterBatch:
         _chk(self.L.ekf_joint_consistency(self.h, int(index), xt, buf))
         return np.frombuffer(buf, dtype=JOINT_DTYPE, count=1)
 
+    def find_duplicates(self, gate=9.21, max_dist=None, split=0, index=0, max_pairs=4096):
+        """Duplicate landmarks on the device (ekf_find_duplicates): the pairs i < j whose difference passes the gate
+        d^T (P_ii + P_jj - P_ij - P_ij^T)^-1 d <= gate (9.21: 99 % of chi-square with 2 dof), cross covariance included.  max_dist: only
+        pairs at most that far apart (None: no bound); split = Ng: only pairs i < Ng <= j, old x new after a join_map that appended
+        behind Ng landmarks.  Returns (pairs, n_found, n_degenerate): a DUP_DTYPE array ordered by (i, j) with the first
+        min(n_found, max_pairs) pairs, the number of pairs that pass, and the number of considered pairs whose S is not positive
+        definite (never listed).  index=None: every filter in one launch sequence (ekf_batch_find_duplicates), split an int or
+        [batch]; returns a list of such triples, one per filter.  The filter is only read; duplicate_keep_mask turns the list into
+        the mask remove_landmarks takes."""
+        md = 0.0 if max_dist is None else float(max_dist)
+        max_pairs = int(max_pairs)
+        if max_pairs < 0:
+            raise ValueError("max_pairs must not be negative")
+        if index is None:
+            sp = np.ascontiguousarray(np.broadcast_to(np.asarray(split, dtype=np.int32), (self.batch,)))
+            buf = (EkfDupPair * max(self.batch * max_pairs, 1))()
+            found, degen = np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch, dtype=np.int32)
+            _chk(self.L.ekf_batch_find_duplicates(self.h, float(gate), md, sp.ctypes.data_as(_ip), buf if max_pairs else None, max_pairs,
+                                                  found.ctypes.data_as(_ip), degen.ctypes.data_as(_ip)))
+            rows = np.frombuffer(buf, dtype=DUP_DTYPE, count=self.batch * max_pairs).reshape(self.batch, max_pairs)
+            return [(rows[b, :min(int(found[b]), max_pairs)].copy(), int(found[b]), int(degen[b])) for b in range(self.batch)]
+        buf = (EkfDupPair * max(max_pairs, 1))()
+        degen = ctypes.c_int(0)
+        found = _chk(self.L.ekf_find_duplicates(self.h, int(index), float(gate), md, int(split), buf if max_pairs else None, max_pairs, ctypes.byref(degen)))
+        return np.frombuffer(buf, dtype=DUP_DTYPE, count=min(found, max_pairs)).copy(), found, degen.value
+
     def joint_factor(self, index=0):
         """Diagnostic: the upper factor U (U^T U = P_LL) the last joint_consistency call left for filter `index`, dense (2N, 2N);
         EkfError ERR_STATE when the state has changed since."""
@@ -537,3 +594,7 @@ class KalmanFilter:
     def joint_consistency(self, x_true=None):
         """Joint / map NEES, log det P, pivots and the pose covariance given the map (FilterBatch.joint_consistency): one record."""
         return self._f.joint_consistency(x_true, 0)[0]
+
+    def find_duplicates(self, gate=9.21, max_dist=None, split=0, max_pairs=4096):
+        """Pairs of landmarks that pass the duplicate gate (FilterBatch.find_duplicates): (pairs, n_found, n_degenerate)."""
+        return self._f.find_duplicates(gate, max_dist, split, 0, max_pairs)

@@ -92,7 +92,8 @@ void ekf_default_params(ekf_params *p);
  * capacity_landmarks bounds N; all device memory is allocated here, none later (except a transient
  * staging buffer inside ekf_get_state / ekf_set_state, inside ekf_remove_landmarks / ekf_batch_remove_landmarks the
  * landmark maps and, in the in-place pipeline (ekf_overlap() == 0), a scratch copy of the reduced maps' tiles -- and the
- * factorisation scratch of ekf_joint_consistency, allocated at its first call and kept: one more P_LL buffer per filter).
+ * factorisation scratch of ekf_joint_consistency, allocated at its first call and kept: one more P_LL buffer per filter -- and
+ * the scratch of ekf_find_duplicates, likewise: a box per 32 landmarks and a pair list that grows with what a call finds).
  * The sequential part of a filter runs on a few workgroups that exchange their arg-min candidates while they
  * run, so all of them must be resident on the GPU at once: creation fails with EKF_ERR_STATE when this
  * handle's workgroups do not fit beside those of the handles already live on the device (in this process).
@@ -277,6 +278,41 @@ int ekf_batch_joint_consistency(ekf_handle h, const double *x_true /*[batch][ld_
 /* Diagnostic: the upper factor U (U^T U = P_LL) of filter `index` from the LAST consistency call, dense 2N x 2N column-major,
  * ld >= 2N; EKF_ERR_STATE when the state changed since (or no call covered the filter).  Returns 2N.  Synchronises. */
 int ekf_debug_joint_factor(ekf_handle h, int index, double *U_out, int ld);
+
+/* Duplicate search on the device: which landmarks i < j of a filter are the same point?  The pairwise gate with the cross
+ * covariance, which after ekf_join_map is of the size of the landmarks' own blocks (leaving it out makes the gate meaningless):
+ *     d = L_i - L_j = (dx, dy),   S = P_ii + P_jj - P_ij - P_ij^T = (a b; b c),   det = a c - b^2,
+ *     a = P_ii.xx + P_jj.xx - 2 P_ij[0][0],  b = P_ii.xy + P_jj.xy - P_ij[0][1] - P_ij[1][0],  c = P_ii.yy + P_jj.yy - 2 P_ij[1][1],
+ *     degenerate: !(a > 0 && det > 0) (catches NaN);   else d2 = (c dx^2 - 2 b dx dy + a dy^2) / det.
+ * P_ij is read where it lives, in one streaming read of the settled upper triangle; the filter itself is only read.
+ * Considered pairs: max_dist > 0: only pairs with dx^2 + dy^2 <= max_dist^2 (groups of 32 landmarks whose bounding boxes are
+ * further apart are skipped unread, with the same result); max_dist <= 0: no Euclidean bound.  split = 0: all pairs; 0 < split <= N:
+ * only i < split <= j, the old x new pairs after an ekf_join_map that returned Ng + Ns, called with split = Ng.
+ * A considered pair is listed iff it is not degenerate and d2 <= gate; degenerate considered pairs are counted into
+ * n_degenerate_out (may be NULL) and never listed.  The list is ordered by (i, j); the first min(found, max_pairs) pairs are
+ * written.  ekf_find_duplicates returns `found`, which may exceed max_pairs, or a negative status; pairs_out == NULL with
+ * max_pairs == 0 is a count-only call.  ekf_batch_find_duplicates writes filter b's list at pairs_out + b * max_pairs and its count
+ * to n_found_out[b], takes one split per filter (NULL: all 0) and returns EKF_OK or a negative status.  N < 2 finds nothing.
+ * The filter's exported state, counters, decision log, loaded script and host mirror are bitwise what ekf_get_state at the same
+ * point would leave: deferred slots are folded first, a streaming launch is stopped and immediate-mode calls stream again
+ * afterwards.  The call synchronises.  A sticky EKF_ERR_TIMEOUT is returned unchanged; a sticky EKF_ERR_CAPACITY does not block
+ * the call.  Bad arguments (NULL outputs where not allowed, index out of range, gate not finite or negative, max_dist NaN,
+ * split < 0 or > N, max_pairs < 0) return EKF_ERR_BAD_ARG.  Pairs are appended through an integer counter and sorted on the host,
+ * no floating-point atomics: every count, index and the bits of every d2 are the same on every call on an unchanged state, and
+ * filter b of the batch form returns exactly what the one-filter call on b returns.
+ * The scratch -- a bounding box per 32 landmarks, counters, and a pair list that grows when a call finds more than it holds (the
+ * search then runs once more) -- is allocated at the first call, kept on the handle (ekf_device_bytes counts it, ekf_reserve
+ * re-sizes it) and freed by ekf_destroy.  Marginalising the duplicate out with ekf_remove_landmarks is the conservative way to
+ * use the list; fusing the two estimates is not done here. */
+typedef struct ekf_dup_pair {
+    int i, j;   /* landmark numbers, i < j */
+    double d2;  /* d^T S^-1 d */
+} ekf_dup_pair;
+int ekf_find_duplicates(ekf_handle h, int index, double gate, double max_dist, int split, ekf_dup_pair *pairs_out, int max_pairs,
+                        int *n_degenerate_out /* may be NULL */);
+int ekf_batch_find_duplicates(ekf_handle h, double gate, double max_dist, const int *split /*[batch] or NULL = all 0*/,
+                              ekf_dup_pair *pairs_out /*[batch][max_pairs]*/, int max_pairs, int *n_found_out /*[batch]*/,
+                              int *n_degenerate_out /*[batch] or NULL*/);
 
 /* ---- device-resident step scripts (benchmarks, Monte-Carlo runs) ------------------------------
  * A script is `steps` steps; step s of filter b is
