@@ -3,6 +3,7 @@ the map operations (removal, frame change, joining): injected filters, immediate
 import ctypes
 import functools
 import math
+import os
 import subprocess
 import sys
 
@@ -185,6 +186,14 @@ def batch_script(pkg, B, steps, M):
                     zz, RR = far_feature(pkg, s + 3 * b % 5)
                 z[s, m, b], R[s, m, b] = zz, RR.ravel(order="F")
     return ctrl, z, R
+
+
+def run_cpp_check(tmp_path, name):
+    """tests/cpp/<name>.cpp compiled for the host into tmp_path and run: the finished process, for the caller to assert on."""
+    exe = str(tmp_path / name)
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cpp", name + ".cpp")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-o", exe, src])
+    return subprocess.run([exe], capture_output=True, text=True, timeout=600)
 
 
 @functools.lru_cache(maxsize=None)

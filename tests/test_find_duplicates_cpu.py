@@ -5,7 +5,6 @@ against its own restatement in extended precision; the state builder plants pair
 a gate that ignores the cross blocks; duplicate_keep_mask on hand-made lists."""
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -13,6 +12,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dup_ref as dr  # noqa: E402
+from helpers import run_cpp_check  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = (23, 24, 25, 92, 172, 272)  # + 8 planted landmarks: the GPU tests' 31, 32, 33, 100, 180, 280
@@ -36,9 +36,7 @@ def test_header_declares_and_binding_lists_the_calls(pkg):
 
 
 def test_pair_enumeration_agrees_with_brute_force(tmp_path):
-    exe = str(tmp_path / "dup_map_check")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "cpp", "dup_map_check.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    out = run_cpp_check(tmp_path, "dup_map_check")
     # N in {1, 2, 31, 32, 33, 64, 65, 100} x the valid, distinct splits of {0, 1, 31, 32, 33, N - 1, N}
     assert out.returncode == 0 and "dup map ok (39 cases)" in out.stdout, out.stdout + out.stderr
 

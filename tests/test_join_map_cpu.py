@@ -5,13 +5,13 @@ central differences of the map, the block table of include/ekfslam_c.h against t
 and positive semidefiniteness."""
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import join_ref as jr  # noqa: E402
+from helpers import run_cpp_check  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -35,9 +35,7 @@ def test_header_declares_and_binding_lists_the_join_calls(pkg):
 
 
 def test_index_function_agrees_with_a_dense_model(tmp_path):
-    exe = str(tmp_path / "join_map_check")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "cpp", "join_map_check.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    out = run_cpp_check(tmp_path, "join_map_check")
     assert out.returncode == 0 and "join map ok (70 cases)" in out.stdout, out.stdout + out.stderr
 
 

@@ -5,7 +5,6 @@ references the GPU tests compare with (tests/factor_ref.py: LAPACK on the whole 
 montecarlo.joint_consistency_report is checked against scipy.stats.chi2 on drawn errors."""
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -14,7 +13,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import factor_ref as fr  # noqa: E402
 import reframe_ref as rr  # noqa: E402
-from helpers import correlated_state  # noqa: E402
+from helpers import correlated_state, run_cpp_check  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -38,9 +37,7 @@ def test_header_declares_and_binding_lists_the_calls(pkg):
 
 
 def test_index_functions_agree_with_brute_force(tmp_path):
-    exe = str(tmp_path / "factor_map_check")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "cpp", "factor_map_check.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    out = run_cpp_check(tmp_path, "factor_map_check")
     assert out.returncode == 0 and "factor map ok (105 grids)" in out.stdout, out.stdout + out.stderr
 
 

@@ -4,14 +4,13 @@ a tile once and groups whole 2x2 blocks; and the NumPy reference the GPU tests c
 checked -- its Jacobians against central differences, its blockwise form against the dense J P J^T."""
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import reframe_ref as rr  # noqa: E402
-from helpers import assert_state_close  # noqa: E402
+from helpers import assert_state_close, run_cpp_check  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_FUNCTIONS = ("ekf_transform_frame", "ekf_batch_transform_frame", "ekf_anchor_at_robot", "ekf_batch_anchor_at_robot")
@@ -30,9 +29,7 @@ def test_header_declares_and_binding_lists_the_frame_calls(pkg):
 
 
 def test_tile_mapping_visits_every_element_once_in_whole_blocks(tmp_path):
-    exe = str(tmp_path / "reframe_map_check")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "cpp", "reframe_map_check.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    out = run_cpp_check(tmp_path, "reframe_map_check")
     assert out.returncode == 0 and "reframe map ok" in out.stdout, out.stdout + out.stderr
 
 

@@ -3,7 +3,10 @@
 removal kernel runs (ekf_device.h) reproduce the tile packing of the reduced matrix exactly."""
 import os
 import re
-import subprocess
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from helpers import run_cpp_check  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_FUNCTIONS = ("ekf_remove_landmarks", "ekf_batch_remove_landmarks", "ekf_get_landmark_covs")
@@ -21,7 +24,5 @@ def test_header_declares_and_binding_lists_the_map_management_calls(pkg):
 
 
 def test_removal_gather_reproduces_the_packing_of_the_reduced_matrix(tmp_path):
-    exe = str(tmp_path / "remove_map_check")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "cpp", "remove_map_check.cpp")])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    out = run_cpp_check(tmp_path, "remove_map_check")
     assert out.returncode == 0 and "remove map ok" in out.stdout, out.stdout + out.stderr
