@@ -26,6 +26,7 @@
 #include "ekf_rewrite.hip"
 #include "ekf_factor.hip"
 #include "ekf_pairs.hip"
+#include "ekf_fuse.hip"
 
 static thread_local std::string g_last_error;
 
@@ -183,6 +184,10 @@ struct ekf_batch {
     // pair list in a second one that grows when a call finds more pairs than it holds; both kept and counted in device_bytes
     DupScratch dup = {};
     void *dup_base = nullptr;
+    // landmark fusion (ekf_fuse_landmarks): pair table, the round's factor and right-hand sides, progress record; one allocation made
+    // at the first call, kept and counted in device_bytes
+    FuseScratch fuse = {};
+    void *fuse_base = nullptr;
 };
 
 static int sticky_status(ekf_batch *h, bool include_capacity);
@@ -725,6 +730,7 @@ extern "C" int ekf_destroy(ekf_handle h) {
     if (h->fac_base) hipFree(h->fac_base);
     if (h->dup_base) hipFree(h->dup_base);
     if (h->dup.list) hipFree(h->dup.list);
+    if (h->fuse_base) hipFree(h->fuse_base);
     for (auto &g : h->graphs) hipGraphExecDestroy(g.exec);
     for (const DevArray &a : device_arrays(h))
         if (*a.slot) hipFree(*a.slot);
@@ -1646,6 +1652,7 @@ static int sticky_status(ekf_batch *h, bool include_capacity) {
 //   ekf_remove_landmarks, ekf_transform_frame,
 //   ekf_anchor_at_robot (and the batch forms)          QUIET_SETTLED  ST_INVALID_OR_FULL   the state stays as it is under either status
 //   ekf_join_map, ekf_batch_join_map                   QUIET_SETTLED  ST_INVALID_OR_FULL   BOTH handles, the source first (a join without room fails after the settle)
+//   ekf_fuse_landmarks (and the batch form)            QUIET_SETTLED  ST_INVALID_OR_FULL   the pair list is checked first, against the mirror's counts; no pair: returns
 // (ekf_get_landmark_covs and the mirror's readers go through refresh_bounds alone; ekf_flush / ekf_close_window through close_set.)
 enum QuietLevel { QUIET_STREAM, QUIET_SETTLED };
 enum StatusRule { ST_NONE, ST_INVALID, ST_INVALID_OR_FULL };
@@ -1890,6 +1897,7 @@ extern "C" int ekf_set_state(ekf_handle h, int index, const double *x, const dou
 static int reserve_move_state(ekf_batch *h, ekf_batch *nh, const std::vector<int> &n_lm);
 static int factor_reserve(ekf_batch *h);
 static int dup_reserve(ekf_batch *h, int cap);
+static int fuse_reserve(ekf_batch *h);
 
 extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     if (!h || capacity_landmarks < 1 || capacity_landmarks > EKF_MAX_CAPACITY) return set_error(EKF_ERR_BAD_ARG, "bad handle / capacity (EKF_MAX_CAPACITY)");
@@ -1954,10 +1962,12 @@ extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     h->script_steps = 0;
     const bool had_factor_scratch = h->fac_base != nullptr;
     const int had_dup_cap = h->dup_base ? h->dup.cap : 0;
+    const bool had_fuse_scratch = h->fuse_base != nullptr;
     std::swap(*h, *nh);  // the caller's handle now owns the larger buffers ...
     ekf_destroy(nh);     // ... and the old ones go
     if (had_factor_scratch) EKF_TRY(factor_reserve(h));  // (the scratch of ekf_joint_consistency follows the capacity)
     if (had_dup_cap) EKF_TRY(dup_reserve(h, had_dup_cap));  // (... and so does that of ekf_find_duplicates)
+    if (had_fuse_scratch) EKF_TRY(fuse_reserve(h));         // (... and the pair table of ekf_fuse_landmarks)
     return refresh_bounds(h);
 }
 
@@ -2020,10 +2030,17 @@ extern "C" int ekf_broadcast_state(ekf_handle h) {
 // buffer (then flipped, as settle() does behind a pass; the buffer read is cleared), in place through a transient scratch copied back
 // (k_rm_finish); x, R, D compacted by k_rm_vec.  Every buffer ends as ekf_set_state of the reduced state would leave it; the buffer
 // addresses do not change (captured graphs and streaming launches hold EkfDev by value).
+static int remove_settled(ekf_batch *h, const unsigned char *keep, int ld_keep, int index, int *n_out);
 static int remove_impl(ekf_batch *h, const unsigned char *keep, int ld_keep, int index, int *n_out) {
     // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
     // every deferred slot folded, both streams idle
     EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
+    return remove_settled(h, keep, ld_keep, index, n_out);
+}
+
+// The removal itself, on a handle that quiesce(QUIET_SETTLED) has brought to rest (h_int[] current): remove_impl, and the end of
+// ekf_fuse_landmarks behind its own kernels on the chain stream.
+static int remove_settled(ekf_batch *h, const unsigned char *keep, int ld_keep, int index, int *n_out) {
     EkfDev &dv = h->dv;
     const int B = dv.B, mstride = dv.Ncap > 0 ? dv.Ncap : 1;
     std::vector<int> rm((size_t)B * (2 + mstride), 0);
@@ -2419,6 +2436,143 @@ extern "C" int ekf_batch_find_duplicates(ekf_handle h, double gate, double max_d
                                          int *n_degenerate_out) {
     if (!h || !n_found_out || !dup_args_ok(gate, max_dist, pairs_out, max_pairs)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
     return dup_impl(h, 0, h->dv.B, gate, max_dist, 0, split, pairs_out, max_pairs, n_found_out, n_degenerate_out);
+}
+
+// ---- landmark fusion ------------------------------------------------------------------------------
+// The scratch of ekf_fuse_landmarks (ekf_fuse.hip: FuseScratch), sized by the handle's capacity (a landmark is in at most one pair
+// of a call: Ncap / 2 pairs per filter): one allocation at the first call, counted in ekf_device_bytes, freed by ekf_destroy;
+// ekf_reserve builds the larger one.
+static int fuse_reserve(ekf_batch *h) {
+    if (h->fuse_base) return EKF_OK;
+    const EkfDev &dv = h->dv;
+    const size_t B = (size_t)dv.B;
+    const int pcap = dv.Ncap / 2 + 1;
+    const size_t nwr = B * 4 * FUSE_MAX_COLS, nU = B * FUSE_MAX_COLS * FUSE_MAX_COLS, nint = B * ((size_t)pcap * 2 + 4);
+    const size_t bytes = (nwr + nU) * sizeof(double) + nint * sizeof(int);
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, bytes));
+    hipError_t e = hipMemsetAsync(p, 0, bytes, h->s_chain);
+    if (e == hipSuccess) e = stream_wait(h->s_chain);
+    if (e != hipSuccess) {
+        hipFree(p);
+        return set_error(EKF_ERR_HIP, hipGetErrorString(e));
+    }
+    h->fuse_base = p;
+    h->fuse.wr = (double *)p;
+    h->fuse.U = h->fuse.wr + nwr;
+    h->fuse.pairs = (int *)(h->fuse.U + nU);
+    h->fuse.cnt = h->fuse.pairs + B * (size_t)pcap * 2;
+    h->fuse.done = h->fuse.cnt + B;
+    h->fuse.m_round = h->fuse.done + 2 * B;
+    h->fuse.pcap = pcap;
+    h->device_bytes += bytes;
+    return EKF_OK;
+}
+
+// Filters [b0, b0 + nb), filter b0 + k with n_pairs[k] pairs at pairs + k * ld_pairs.  The list is checked against the mirror's
+// landmark counts before anything else happens to the handle; a call without a pair returns there.  Then: settle, the pair table
+// up, rounds of at most ekf_window() pairs (ekf_fuse.hip; one dense pass each, in place in the settled buffer in either pipeline
+// mode, also on handles whose chain kernel folds its own windows), the progress record back, and the removal of the fused pairs'
+// j through remove_settled, which ends the rewrite.  Nothing fused anywhere: the rewrite is ended here (slot rows cleared, the
+// pass sizes restored).
+static int fuse_impl(ekf_batch *h, int b0, int nb, const ekf_dup_pair *pairs, int ld_pairs, const int *n_pairs, double slack, int *n_fused_out, int *n_lm_out) {
+    HIP_TRY(hipSetDevice(h->device));
+    EKF_TRY(refresh_bounds(h, false));
+    int most = 0;
+    std::vector<unsigned char> seen;
+    for (int k = 0; k < nb; k++) {
+        const int N = h->h_int[b0 + k], np = n_pairs[k];
+        if (np < 0 || (np > 0 && (!pairs || np > ld_pairs))) return set_error(EKF_ERR_BAD_ARG, "bad pair count or list");
+        seen.assign((size_t)(N > 0 ? N : 1), 0);
+        for (int q = 0; q < np; q++) {
+            const ekf_dup_pair &pr = pairs[(size_t)k * ld_pairs + q];
+            char buf[200];
+            if (!(0 <= pr.i && pr.i < pr.j && pr.j < N)) {
+                snprintf(buf, sizeof buf, "filter %d, pair %d: (%d, %d) does not name two landmarks i < j of %d", b0 + k, q, pr.i, pr.j, N);
+                return set_error(EKF_ERR_BAD_ARG, buf);
+            }
+            if (seen[pr.i] || seen[pr.j]) {
+                snprintf(buf, sizeof buf, "filter %d, pair %d: landmark %d is in another pair of the call", b0 + k, q, seen[pr.i] ? pr.i : pr.j);
+                return set_error(EKF_ERR_BAD_ARG, buf);
+            }
+            seen[pr.i] = seen[pr.j] = 1;
+        }
+        most = np > most ? np : most;
+    }
+    if (most == 0) {  // nothing to do: the window stays open
+        for (int k = 0; k < nb; k++) {
+            if (n_fused_out) n_fused_out[k] = 0;
+            if (n_lm_out) n_lm_out[k] = h->h_int[b0 + k];
+        }
+        return nb == 1 && !n_lm_out ? h->h_int[b0] : EKF_OK;
+    }
+    // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
+    // every deferred slot folded, both streams idle
+    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
+    EKF_TRY(fuse_reserve(h));
+    EkfDev &dv = h->dv;
+    const FuseScratch fs = h->fuse;
+    hipStream_t s = h->s_chain;
+    int n_max = 0;
+    std::vector<int> tab((size_t)nb * fs.pcap * 2, 0), cnt(n_pairs, n_pairs + nb);
+    for (int k = 0; k < nb; k++) {
+        n_max = h->h_int[b0 + k] > n_max ? h->h_int[b0 + k] : n_max;
+        if (cnt[k] > fs.pcap) return set_error(EKF_ERR_STATE, "more pairs than the pair table holds");  // (each landmark once: cannot happen)
+        for (int q = 0; q < cnt[k]; q++) {
+            tab[((size_t)k * fs.pcap + q) * 2] = pairs[(size_t)k * ld_pairs + q].i;
+            tab[((size_t)k * fs.pcap + q) * 2 + 1] = pairs[(size_t)k * ld_pairs + q].j;
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(fs.pairs + (size_t)b0 * fs.pcap * 2, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(fs.cnt + b0, cnt.data(), sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(fs.done + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
+    HIP_TRY(hipMemsetAsync(fs.m_round + b0, 0, sizeof(int) * (size_t)nb, s));
+    const int nT = lm_tiles(n_max);
+    for (int round = 0; round * dv.maxp < most; round++) {
+        const int m_hi = most - round * dv.maxp < dv.maxp ? most - round * dv.maxp : dv.maxp;
+        hipLaunchKernelGGL(k_fuse_gather, dim3((unsigned)cdiv(n_max, 256), (unsigned)m_hi, (unsigned)nb), dim3(256), 0, s, dv, fs, h->buf_in, round, b0);
+        hipLaunchKernelGGL(k_fuse_factor, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, round, slack, b0);
+        hipLaunchKernelGGL(k_fuse_apply, dim3((unsigned)cdiv(64 * nT, 256), (unsigned)nb), dim3(256), 0, s, dv, fs, b0);
+        hipLaunchKernelGGL(k_fuse_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0);
+        launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->buf_in, h->buf_in, nullptr, /*rev*/ 0, b0, nb);
+    }
+    std::vector<int> done((size_t)2 * nb, 0);
+    HIP_TRY(hipMemcpyAsync(done.data(), fs.done + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));
+    EKF_TRY(check_launch());
+    // the fused pairs' j go, exactly as ekf_remove_landmarks with keep[j] = 0 removes them
+    const int ld_keep = n_max > 0 ? n_max : 1;
+    std::vector<unsigned char> keep((size_t)dv.B * ld_keep, 1);
+    bool any = false;
+    for (int k = 0; k < nb; k++) {
+        const int fused = done[2 * k];
+        if (n_fused_out) n_fused_out[k] = fused;
+        for (int q = 0; q < fused; q++) keep[(size_t)(b0 + k) * ld_keep + pairs[(size_t)k * ld_pairs + q].j] = 0;
+        any = any || fused > 0;
+    }
+    if (any) {
+        std::vector<int> n_new((size_t)dv.B, 0);
+        EKF_TRY(remove_settled(h, keep.data(), ld_keep, -1, n_new.data()));
+        for (int k = 0; k < nb; k++)
+            if (n_lm_out) n_lm_out[k] = n_new[b0 + k];
+        return nb == 1 && !n_lm_out ? n_new[b0] : EKF_OK;
+    }
+    EKF_TRY(finish_rewrite(h, b0, nb, /*rearm*/ true, &h->h_int[b0], 1, /*flip_buf*/ false));
+    for (int k = 0; k < nb; k++)
+        if (n_lm_out) n_lm_out[k] = h->h_int[b0 + k];
+    return nb == 1 && !n_lm_out ? h->h_int[b0] : EKF_OK;
+}
+
+extern "C" int ekf_fuse_landmarks(ekf_handle h, int index, const ekf_dup_pair *pairs, int n_pairs, double slack, int *n_fused_out) {
+    if (!h || index < 0 || index >= h->dv.B || n_pairs < 0 || (n_pairs > 0 && !pairs) || !(__builtin_isfinite(slack) && slack >= 0.0))
+        return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return fuse_impl(h, index, 1, pairs, n_pairs, &n_pairs, slack, n_fused_out, nullptr);
+}
+
+extern "C" int ekf_batch_fuse_landmarks(ekf_handle h, const ekf_dup_pair *pairs, int ld_pairs, const int *n_pairs, double slack, int *n_fused_out,
+                                        int *n_landmarks_out) {
+    if (!h || !n_pairs || ld_pairs < 0 || !n_landmarks_out || !(__builtin_isfinite(slack) && slack >= 0.0)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return fuse_impl(h, 0, h->dv.B, pairs, ld_pairs, n_pairs, slack, n_fused_out, n_landmarks_out);
 }
 
 extern "C" int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max) {

@@ -391,3 +391,25 @@ __host__ __device__ inline int dup_gate(double dx, double dy, const double di[3]
 __host__ __device__ inline size_t pair_offset(int rows, int ip, int p) {
     return ((size_t)p * rows + ip) * 4;
 }
+
+// Landmark fusion (ekf_fuse_landmarks, ekf_fuse.hip) gathers columns of P: where the 2x2 block (landmark l, landmark c) of P_LL
+// lives.  FW_D: l == c, the own block in D (component e + f at (e + f) * dn + l).  FW_BM: l < c, the stored block; `off` is its
+// element (0, 0) in the filter's Bm, element (e, f) at off + 32 e + 2 f.  FW_BM_T: l > c, the block is the transpose of the stored
+// (c, l): element (e, f) at off + 32 f + 2 e.  The two rows of a landmark never leave a chain, and a 32-byte piece holds rows rho and
+// rho + 4 of two columns: the block's aligned pieces start at off - (off & 1) and 32 doubles on, the block is half (off & 1) of them
+// (reframe_item: row[0] and row[1]).
+enum { FW_D = 0, FW_BM = 1, FW_BM_T = 2 };
+struct FuseSource {
+    int where;
+    size_t off;
+};
+__host__ __device__ inline FuseSource fuse_source(int T, int l, int c) {
+    FuseSource s;
+    if (l == c) s.where = FW_D, s.off = (size_t)l;
+    else if (l < c) s.where = FW_BM, s.off = bm_offset(T, 2 * l, 2 * c);
+    else s.where = FW_BM_T, s.off = bm_offset(T, 2 * c, 2 * l);
+    return s;
+}
+// Column q (0 .. 2m - 1) of a fusion round -- component q & 1 of pair q >> 1 -- is element q & 3 of slot pair q >> 2: the offset
+// (doubles) of W / V element (row i', column q) inside set 0 of FA / FB.
+__host__ __device__ inline size_t fuse_slot_offset(int rows, int ip, int q) { return pair_offset(rows, ip, q >> 2) + (size_t)(q & 3); }

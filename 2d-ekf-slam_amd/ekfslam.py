@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "ekf_join_map", "ekf_batch_join_map",
     "ekf_joint_consistency", "ekf_batch_joint_consistency", "ekf_debug_joint_factor",
     "ekf_find_duplicates", "ekf_batch_find_duplicates",
+    "ekf_fuse_landmarks", "ekf_batch_fuse_landmarks",
 ]
 
 
@@ -133,6 +134,8 @@ def load():
     L.ekf_debug_joint_factor.argtypes = [_H, ctypes.c_int, _dp, ctypes.c_int]
     L.ekf_find_duplicates.argtypes = [_H, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.POINTER(EkfDupPair), ctypes.c_int, _ip]
     L.ekf_batch_find_duplicates.argtypes = [_H, ctypes.c_double, ctypes.c_double, _ip, ctypes.POINTER(EkfDupPair), ctypes.c_int, _ip, _ip]
+    L.ekf_fuse_landmarks.argtypes = [_H, ctypes.c_int, ctypes.POINTER(EkfDupPair), ctypes.c_int, ctypes.c_double, _ip]
+    L.ekf_batch_fuse_landmarks.argtypes = [_H, ctypes.POINTER(EkfDupPair), ctypes.c_int, _ip, ctypes.c_double, _ip, _ip]
     L.ekf_script_load.argtypes = [_H, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _up, _dp]
     L.ekf_script_run.argtypes = [_H, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.ekf_sync.argtypes = [_H]
@@ -169,23 +172,53 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _greedy_matching(pairs, n_landmarks):
+    """The pairs (as DUP_DTYPE) and the positions of the accepted ones, in the order they were accepted: greedy one-to-one
+    matching by ascending d2, ties by (i, j)."""
+    pairs = np.asarray(pairs, dtype=DUP_DTYPE).reshape(-1)
+    n = int(n_landmarks)
+    matched = np.zeros(n, dtype=bool)
+    accepted = []
+    for k in np.lexsort((pairs["j"], pairs["i"], pairs["d2"])):
+        i, j = int(pairs["i"][k]), int(pairs["j"][k])
+        if not (0 <= i < j < n):
+            raise ValueError("pair (%d, %d) does not name two landmarks i < j of %d" % (i, j, n))
+        if matched[i] or matched[j]:
+            continue
+        matched[i] = matched[j] = True
+        accepted.append(int(k))
+    return pairs, np.asarray(accepted, dtype=np.intp)
+
+
 def duplicate_keep_mask(pairs, n_landmarks):
     """A keep mask for remove_landmarks from a list of duplicate pairs (find_duplicates): greedy one-to-one matching by ascending d2,
     ties by (i, j); a pair is accepted when neither of its landmarks is matched already, and the later landmark j of an accepted
     pair goes (keep[j] = False).  In a chain i-j-k of mutual candidates only the closest link is accepted: search again after the
     removal when several copies of one point are expected."""
-    pairs = np.asarray(pairs, dtype=DUP_DTYPE).reshape(-1)
+    pairs, accepted = _greedy_matching(pairs, n_landmarks)
     keep = np.ones(int(n_landmarks), dtype=bool)
-    matched = np.zeros(int(n_landmarks), dtype=bool)
-    for k in np.lexsort((pairs["j"], pairs["i"], pairs["d2"])):
-        i, j = int(pairs["i"][k]), int(pairs["j"][k])
-        if not (0 <= i < j < keep.size):
-            raise ValueError("pair (%d, %d) does not name two landmarks i < j of %d" % (i, j, keep.size))
-        if matched[i] or matched[j]:
-            continue
-        matched[i] = matched[j] = True
-        keep[j] = False
+    keep[pairs["j"][accepted]] = False
     return keep
+
+
+def duplicate_matching(pairs, n_landmarks):
+    """The accepted pairs of duplicate_keep_mask's greedy matching as a DUP_DTYPE array ordered by (i, j): every landmark in at most
+    one pair, which is what fuse_landmarks takes; its j are the landmarks duplicate_keep_mask drops."""
+    pairs, accepted = _greedy_matching(pairs, n_landmarks)
+    out = pairs[accepted].copy()
+    return out[np.lexsort((out["j"], out["i"]))]
+
+
+def _pair_buffer(pairs):
+    """A pair list (DUP_DTYPE array, or anything with rows (i, j)) as a contiguous DUP_DTYPE array."""
+    a = np.asarray(pairs)
+    if a.dtype != DUP_DTYPE:
+        ij = np.asarray(pairs, dtype=np.int64).reshape(-1, 2) if a.size else np.zeros((0, 2), dtype=np.int64)
+        if ij.size and (np.abs(ij) > 2**31 - 1).any():
+            raise ValueError("landmark numbers out of range")
+        a = np.zeros(ij.shape[0], dtype=DUP_DTYPE)
+        a["i"], a["j"] = ij[:, 0], ij[:, 1]
+    return np.ascontiguousarray(a.reshape(-1))
 
 
 def default_params(**kw):
@@ -355,7 +388,7 @@ class FilterBatch:
     def join_map(self, src, index=0, src_index=0):
         """Append the landmarks of filter src_index of `src` (a FilterBatch; may be this one when the indices differ) behind those of
         filter `index` on the device (ekf_join_map).  src's frame origin must be this filter's current estimated pose and the two
-        estimates independent; duplicates are not fused.  Returns the new landmark count; `src` is only read."""
+        estimates independent; duplicates are not fused here (find_duplicates, fuse_landmarks).  Returns the new landmark count; `src` is only read."""
         return _chk(self.L.ekf_join_map(self.h, int(index), src.h, int(src_index)))
 
     def batch_join_map(self, src):
@@ -417,6 +450,37 @@ class FilterBatch:
         degen = ctypes.c_int(0)
         found = _chk(self.L.ekf_find_duplicates(self.h, int(index), float(gate), md, int(split), buf if max_pairs else None, max_pairs, ctypes.byref(degen)))
         return np.frombuffer(buf, dtype=DUP_DTYPE, count=min(found, max_pairs)).copy(), found, degen.value
+
+    def fuse_landmarks(self, pairs, slack=0.0, index=0):
+        """Fuse duplicate landmarks on the device (ekf_fuse_landmarks): every pair (i, j), i < j, is declared the same point -- the
+        equality constraint L_i = L_j as one update of the whole state (slack: its isotropic variance, 0 = exact) -- and j is
+        removed, the kept landmarks renumbered as remove_landmarks does.  pairs: a DUP_DTYPE array (d2 is ignored; take
+        duplicate_matching of what find_duplicates returned) or rows (i, j); each landmark in at most one pair.  Returns
+        (n_landmarks, n_fused); n_fused < len(pairs) when a round's S was not positive definite (that round and the later ones
+        were not applied).  index=None: pairs is a list of one pair array per filter (ekf_batch_fuse_landmarks); returns two
+        (batch,) arrays."""
+        slack = float(slack)
+        if not (np.isfinite(slack) and slack >= 0.0):
+            raise ValueError("slack must be finite and not negative")
+        if index is None:
+            lists = [_pair_buffer(p) for p in pairs]
+            if len(lists) != self.batch:
+                raise ValueError("pairs must hold one pair array per filter")
+            ld = max([a.size for a in lists] + [1])
+            buf = np.zeros((self.batch, ld), dtype=DUP_DTYPE)
+            cnt = np.zeros(self.batch, dtype=np.int32)
+            for b, a in enumerate(lists):
+                buf[b, :a.size] = a
+                cnt[b] = a.size
+            fused, n_out = np.zeros(self.batch, dtype=np.int32), np.zeros(self.batch, dtype=np.int32)
+            _chk(self.L.ekf_batch_fuse_landmarks(self.h, buf.ctypes.data_as(ctypes.POINTER(EkfDupPair)), ld, cnt.ctypes.data_as(_ip), slack,
+                                                 fused.ctypes.data_as(_ip), n_out.ctypes.data_as(_ip)))
+            return n_out, fused
+        a = _pair_buffer(pairs)
+        fused = ctypes.c_int(0)
+        n = _chk(self.L.ekf_fuse_landmarks(self.h, int(index), a.ctypes.data_as(ctypes.POINTER(EkfDupPair)) if a.size else None, a.size, slack,
+                                           ctypes.byref(fused)))
+        return n, fused.value
 
     def joint_factor(self, index=0):
         """Diagnostic: the upper factor U (U^T U = P_LL) the last joint_consistency call left for filter `index`, dense (2N, 2N);
@@ -598,3 +662,10 @@ class KalmanFilter:
     def find_duplicates(self, gate=9.21, max_dist=None, split=0, max_pairs=4096):
         """Pairs of landmarks that pass the duplicate gate (FilterBatch.find_duplicates): (pairs, n_found, n_degenerate)."""
         return self._f.find_duplicates(gate, max_dist, split, 0, max_pairs)
+
+    def fuse_landmarks(self, pairs, slack=0.0):
+        """Fuse the pairs (i, j) of duplicate landmarks and remove every j (FilterBatch.fuse_landmarks): (n_landmarks, n_fused);
+        refreshes X, Y, Phi and Num_Landmarks."""
+        out = self._f.fuse_landmarks(pairs, slack, 0)
+        self._mirror()
+        return out

@@ -93,7 +93,8 @@ void ekf_default_params(ekf_params *p);
  * staging buffer inside ekf_get_state / ekf_set_state, inside ekf_remove_landmarks / ekf_batch_remove_landmarks the
  * landmark maps and, in the in-place pipeline (ekf_overlap() == 0), a scratch copy of the reduced maps' tiles -- and the
  * factorisation scratch of ekf_joint_consistency, allocated at its first call and kept: one more P_LL buffer per filter -- and
- * the scratch of ekf_find_duplicates, likewise: a box per 32 landmarks and a pair list that grows with what a call finds).
+ * the scratch of ekf_find_duplicates, likewise: a box per 32 landmarks and a pair list that grows with what a call finds -- and
+ * the scratch of ekf_fuse_landmarks, likewise: a pair table and one round's 64 x 64 factor per filter).
  * The sequential part of a filter runs on a few workgroups that exchange their arg-min candidates while they
  * run, so all of them must be resident on the GPU at once: creation fails with EKF_ERR_STATE when this
  * handle's workgroups do not fit beside those of the handles already live on the device (in this process).
@@ -223,7 +224,8 @@ int ekf_batch_anchor_at_robot(ekf_handle h);
  *   old m x robot  P_mR G_R^T                   new k x robot  G_k P_RR G_R^T + C P_s,kR C3^T
  *   robot x robot  G_R P_RR G_R^T + C3 P_s,RR C3^T
  * cos(phi) and sin(phi) are taken once on the host (libm).  Joining into a fresh filter reproduces src's state exactly; joining a
- * fresh src leaves dst exactly as it was.  Landmarks that both maps hold are NOT recognised or fused: they stay two landmarks.
+ * fresh src leaves dst exactly as it was.  Landmarks that both maps hold are NOT recognised or fused here: they stay two landmarks
+ * (ekf_find_duplicates lists them, ekf_fuse_landmarks fuses them).
  * A NEES sample (ekf_record_truth) needs the caller's truth to be a pose in dst's frame, as before the join.
  * src may be the same handle as dst when the indices differ, or a handle of another capacity, kernel family and pipeline mode on
  * the same device (another device: EKF_ERR_BAD_ARG).  src is only read: its state, counters, decision log and loaded script stay
@@ -303,7 +305,7 @@ int ekf_debug_joint_factor(ekf_handle h, int index, double *U_out, int ld);
  * The scratch -- a bounding box per 32 landmarks, counters, and a pair list that grows when a call finds more than it holds (the
  * search then runs once more) -- is allocated at the first call, kept on the handle (ekf_device_bytes counts it, ekf_reserve
  * re-sizes it) and freed by ekf_destroy.  Marginalising the duplicate out with ekf_remove_landmarks is the conservative way to
- * use the list; fusing the two estimates is not done here. */
+ * use the list; ekf_fuse_landmarks below fuses the two estimates instead. */
 typedef struct ekf_dup_pair {
     int i, j;   /* landmark numbers, i < j */
     double d2;  /* d^T S^-1 d */
@@ -313,6 +315,38 @@ int ekf_find_duplicates(ekf_handle h, int index, double gate, double max_dist, i
 int ekf_batch_find_duplicates(ekf_handle h, double gate, double max_dist, const int *split /*[batch] or NULL = all 0*/,
                               ekf_dup_pair *pairs_out /*[batch][max_pairs]*/, int max_pairs, int *n_found_out /*[batch]*/,
                               int *n_degenerate_out /*[batch] or NULL*/);
+
+/* Landmark fusion on the device: the pairs (i_k, j_k), k < n_pairs, of one filter are declared the same point.  The equality
+ * constraint L_i = L_j of all pairs as ONE update of the whole state, then the removal of every j_k:
+ *     H (2m x n): +I_2 at landmark i_k, -I_2 at landmark j_k;   d = H x;   W = P H^T (column pair k = P[:, i_k] - P[:, j_k]);
+ *     S = H W + slack I = U^T U;   V = W U^-1;   y = U^-T d;   x <- x - V y;   P <- P - V V^T;
+ * then rows and columns of every j_k go and the kept landmarks are renumbered, exactly as ekf_remove_landmarks with keep[j_k] = 0.
+ * What is subtracted from P is symmetric and positive semidefinite by construction.  slack >= 0 (m^2) is an isotropic variance on
+ * the constraint: 0 is the exact constraint (afterwards, before the removal, the rows of i and j coincide up to rounding), a
+ * positive value tolerates pairs that are not quite the same point.  Unlike marginalising j out (ekf_remove_landmarks alone) the
+ * second observation's information is kept.
+ * Only i and j of a pair are read (d2 is ignored: the list of ekf_find_duplicates, thinned to a one-to-one matching, can be passed
+ * on).  Every pair needs 0 <= i < j < N and a landmark may appear in at most one pair of the call; anything else, a negative or
+ * non-finite slack, a NULL list with n_pairs > 0 or an index out of range is EKF_ERR_BAD_ARG, found on the host before the handle
+ * is touched.  n_pairs = 0 is a no-op that leaves an open window open.
+ * Otherwise deferred slots are folded first, a streaming launch is stopped (immediate-mode calls stream again afterwards), and the
+ * list is processed in rounds of at most ekf_window(h) pairs in list order, each round a complete joint update of its pairs with
+ * one dense pass over P_LL (in place, in either pipeline mode); conditioning on the constraints round after round equals
+ * conditioning on all of them at once up to rounding.  If S of a round is not positive definite (a pivot <= 0 or NaN: e.g. j an
+ * exact copy of i with slack = 0), that round and all later ones are NOT applied: the state is that after the completed rounds
+ * with exactly their j removed, and *n_fused_out (may be NULL) < n_pairs says so.  This is a result, not an error.
+ * ekf_fuse_landmarks returns the new landmark count or a negative status.  ekf_batch_fuse_landmarks takes filter b's list at
+ * pairs + b * ld_pairs with n_pairs[b] <= ld_pairs pairs (0: the filter stays as it is), writes n_fused_out[b] (may be NULL) and
+ * n_landmarks_out[b], runs every filter in the same launch sequence and returns EKF_OK or a negative status.
+ * A sticky EKF_ERR_TIMEOUT / EKF_ERR_CAPACITY is returned unchanged with nothing modified.  Counters, decision log and a loaded
+ * script stay; the host mirror shows the new pose, P_RR and landmark count, and every device buffer ends as ekf_set_state of the
+ * fused, reduced state would leave it.  The call synchronises.  No atomics, one writer per value, every sum in a fixed order: the
+ * same call on the same state gives the same bits, and filter b of the batch form gets the bits of the one-filter call on b.
+ * The scratch -- the pair table, one round's factor (at most 64 x 64) and right-hand sides -- is allocated at the first call
+ * that has a pair, kept on the handle (ekf_device_bytes counts it, ekf_reserve re-sizes it) and freed by ekf_destroy. */
+int ekf_fuse_landmarks(ekf_handle h, int index, const ekf_dup_pair *pairs, int n_pairs, double slack, int *n_fused_out /* may be NULL */);
+int ekf_batch_fuse_landmarks(ekf_handle h, const ekf_dup_pair *pairs /*[batch][ld_pairs]*/, int ld_pairs, const int *n_pairs /*[batch]*/,
+                             double slack, int *n_fused_out /*[batch] or NULL*/, int *n_landmarks_out /*[batch]*/);
 
 /* ---- device-resident step scripts (benchmarks, Monte-Carlo runs) ------------------------------
  * A script is `steps` steps; step s of filter b is
