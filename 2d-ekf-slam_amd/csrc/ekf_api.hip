@@ -27,6 +27,7 @@
 #include "ekf_factor.hip"
 #include "ekf_pairs.hip"
 #include "ekf_fuse.hip"
+#include "ekf_extract.hip"
 
 static thread_local std::string g_last_error;
 
@@ -1653,6 +1654,9 @@ static int sticky_status(ekf_batch *h, bool include_capacity) {
 //   ekf_anchor_at_robot (and the batch forms)          QUIET_SETTLED  ST_INVALID_OR_FULL   the state stays as it is under either status
 //   ekf_join_map, ekf_batch_join_map                   QUIET_SETTLED  ST_INVALID_OR_FULL   BOTH handles, the source first (a join without room fails after the settle)
 //   ekf_fuse_landmarks (and the batch form)            QUIET_SETTLED  ST_INVALID_OR_FULL   the pair list is checked first, against the mirror's counts; no pair: returns
+//   ekf_extract_map, ekf_batch_extract_map             source: QUIET_STREAM, ST_INVALID, ids checked, settle(); then the destination:
+//                                                      QUIET_SETTLED  ST_NONE              as ekf_set_state (the source is only read)
+//   ekf_get_submap                                     QUIET_STREAM   ST_INVALID           ids checked; size only: returns; else settle(), the dense gather
 // (ekf_get_landmark_covs and the mirror's readers go through refresh_bounds alone; ekf_flush / ekf_close_window through close_set.)
 enum QuietLevel { QUIET_STREAM, QUIET_SETTLED };
 enum StatusRule { ST_NONE, ST_INVALID, ST_INVALID_OR_FULL };
@@ -1859,6 +1863,22 @@ extern "C" int ekf_get_state(ekf_handle h, int index, double *x_out, double *P_o
     return n;
 }
 
+// Both streams are idle here (quiesce(QUIET_SETTLED)).  A launch that gave up (EKF_ERR_TIMEOUT) leaves the segment counters ahead
+// of the host's bases (workgroups that had not aborted kept counting, open_gates raised the rest) and possibly a pass that never
+// reported: every later stream gate would open early, every later in-kernel wait would run out again.  Start both from zero / from
+// the host's own count, so that a handle is usable again after ekf_set_state (and ekf_extract_map into it), as the sticky status
+// promises.
+static int restart_waits(ekf_batch *h) {
+    EkfDev &dv = h->dv;
+    hipStream_t s = h->s_chain;
+    read_debug_hooks(h);
+    HIP_TRY(hipMemsetAsync(dv.seg_count, 0, sizeof(unsigned long long) * EKF_PLAN_MAX, s));
+    for (int q = 0; q < EKF_PLAN_MAX; q++) h->seg_count_base[q] = 0;
+    h->open_set_gate = 0;
+    if (h->overlap) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, s, dv.pass_flag, h->pass_seq);
+    return EKF_OK;
+}
+
 extern "C" int ekf_set_state(ekf_handle h, int index, const double *x, const double *P, int ld, int n) {
     if (!h || index < 0 || index >= h->dv.B || !x || !P || n < 3 || ((n - 3) & 1) || ld < n) return set_error(EKF_ERR_BAD_ARG, "bad argument");
     int N = (n - 3) / 2;
@@ -1866,15 +1886,7 @@ extern "C" int ekf_set_state(ekf_handle h, int index, const double *x, const dou
     EKF_TRY(quiesce(h, QUIET_SETTLED, ST_NONE));
     EkfDev &dv = h->dv;
     hipStream_t s = h->s_chain;
-    // Both streams are idle here.  A launch that gave up (EKF_ERR_TIMEOUT) leaves the segment counters ahead of the host's
-    // bases (workgroups that had not aborted kept counting, open_gates raised the rest) and possibly a pass that never reported:
-    // every later stream gate would open early, every later in-kernel wait would run out again.  Start both from zero / from the
-    // host's own count, so that a handle is usable again after ekf_set_state, as the sticky status promises.
-    read_debug_hooks(h);
-    HIP_TRY(hipMemsetAsync(dv.seg_count, 0, sizeof(unsigned long long) * EKF_PLAN_MAX, s));
-    for (int q = 0; q < EKF_PLAN_MAX; q++) h->seg_count_base[q] = 0;
-    h->open_set_gate = 0;
-    if (h->overlap) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, s, dv.pass_flag, h->pass_seq);
+    EKF_TRY(restart_waits(h));
     DevTmp<double> stage;
     HIP_TRY(stage.alloc((size_t)n * n + n));
     double *xd = stage.p + (size_t)n * n;
@@ -2225,6 +2237,149 @@ extern "C" int ekf_batch_join_map(ekf_handle dst, ekf_handle src) {
     if (dst->dv.B != src->dv.B) return set_error(EKF_ERR_BAD_ARG, "the two handles have different batch sizes");
     if (dst->device != src->device) return set_error(EKF_ERR_BAD_ARG, "the two handles live on different devices");
     return join_impl(dst, -1, src, 0);
+}
+
+// ---- submap extraction ----------------------------------------------------------------------------
+// The list of a call, checked on the host before any handle is touched: every id non-negative, no id twice.  (Against the source's
+// landmark count: ext_ids_in_range, once the source is at rest.)
+static int ext_ids_distinct(const int *ids, int count, int filter) {
+    std::vector<int> sorted(ids, ids + count);
+    std::sort(sorted.begin(), sorted.end());
+    char buf[160];
+    if (count > 0 && sorted[0] < 0) {
+        snprintf(buf, sizeof buf, "filter %d: landmark id %d is negative", filter, sorted[0]);
+        return set_error(EKF_ERR_BAD_ARG, buf);
+    }
+    for (int k = 1; k < count; k++)
+        if (sorted[k] == sorted[k - 1]) {
+            snprintf(buf, sizeof buf, "filter %d: landmark id %d is named twice", filter, sorted[k]);
+            return set_error(EKF_ERR_BAD_ARG, buf);
+        }
+    return EKF_OK;
+}
+static int ext_ids_in_range(const int *ids, int count, int N, int filter) {
+    for (int k = 0; k < count; k++)
+        if (ids[k] >= N) {
+            char buf[160];
+            snprintf(buf, sizeof buf, "filter %d: landmark id %d is not one of its %d landmarks", filter, ids[k], N);
+            return set_error(EKF_ERR_BAD_ARG, buf);
+        }
+    return EKF_OK;
+}
+static JoinSrc join_src_of(const ekf_batch *s) {
+    const EkfDev &sd = s->dv;
+    return {sd.x, sd.R, sd.D, sd.Bm[s->buf_in], sd.n_lm, sd.xs, sd.dn, sd.T, sd.bm_stride};
+}
+
+// Submap extraction on the device (ekf_extract.hip: k_ext_tiles, k_ext_vec).  di < 0: the batch form, filter b of `s` into filter b
+// of `d`.  ids == nullptr: every landmark of the source in order; else filter k's list is ids + k * ld_ids with count[k] entries.
+// The source comes to rest first and is only read afterwards (sticky EKF_ERR_TIMEOUT ends the call; a sticky EKF_ERR_CAPACITY does
+// not: the state is valid); the destination is then treated as ekf_set_state treats it, except that only the tiles and vector
+// entries up to the larger of its previous and its new map are written -- everything behind them is zeros already.  Everything runs
+// on the destination's chain stream while the source's streams are idle, and the call waits for it.  The only transient allocation
+// is the id table (4 bytes per extracted landmark).
+static int extract_impl(ekf_batch *d, int di, ekf_batch *s, int si, const int *ids, int ld_ids, const int *count, int *n_out) {
+    const int bd0 = di < 0 ? 0 : di, bs0 = di < 0 ? 0 : si, nb = di < 0 ? d->dv.B : 1;
+    if (ids)
+        for (int k = 0; k < nb; k++) {
+            if (count[k] < 0 || count[k] > ld_ids) return set_error(EKF_ERR_BAD_ARG, "bad landmark count");
+            EKF_TRY(ext_ids_distinct(ids + (size_t)k * ld_ids, count[k], bs0 + k));
+        }
+    EKF_TRY(quiesce(s, QUIET_STREAM, ST_INVALID));
+    int mstride = 1;
+    for (int k = 0; k < nb; k++) {
+        const int N = s->h_int[bs0 + k], cnt = ids ? count[k] : N;
+        if (ids) EKF_TRY(ext_ids_in_range(ids + (size_t)k * ld_ids, cnt, N, bs0 + k));
+        mstride = cnt > mstride ? cnt : mstride;
+    }
+    EKF_TRY(settle(s));
+    EkfDev &dv = d->dv;
+    std::vector<int> ex((size_t)nb * (2 + mstride), 0);
+    for (int k = 0; k < nb; k++) {
+        const int cnt = ids ? count[k] : s->h_int[bs0 + k];
+        if (cnt > dv.Ncap) {
+            char buf[200];
+            snprintf(buf, sizeof buf, "filter %d: %d landmarks do not fit capacity_landmarks = %d (ekf_reserve, then extract again)", bd0 + k, cnt, dv.Ncap);
+            return set_error(EKF_ERR_CAPACITY, buf);
+        }
+        ex[2 * k + 1] = cnt;
+        int *tab = ex.data() + 2 * nb + (size_t)k * mstride;
+        for (int q = 0; q < cnt; q++) tab[q] = ids ? ids[(size_t)k * ld_ids + q] : q;
+    }
+    if (d != s) EKF_TRY(quiesce(d, QUIET_SETTLED, ST_NONE));
+    {
+        // the destination's previous maps: what has to be overwritten.  A timed-out filter's count is not to be trusted: all of it.
+        const int rc = refresh_bounds(d);
+        if (rc && rc != EKF_ERR_TIMEOUT) return rc;
+    }
+    int nT = 0, n_hi = 0;
+    for (int k = 0; k < nb; k++) {
+        int n_old = d->mirror_h[bd0 + k].status == EKF_ERR_TIMEOUT ? dv.Ncap : d->h_int[bd0 + k];
+        if (n_old < 0 || n_old > dv.Ncap) n_old = dv.Ncap;
+        ex[2 * k] = n_old;
+        const int hi = n_old > ex[2 * k + 1] ? n_old : ex[2 * k + 1];
+        n_hi = hi > n_hi ? hi : n_hi;
+    }
+    nT = lm_tiles(n_hi);
+    hipStream_t st = d->s_chain;
+    EKF_TRY(restart_waits(d));
+    DevTmp<int> ex_d;
+    HIP_TRY(ex_d.alloc(ex.size()));
+    HIP_TRY(hipMemcpyAsync(ex_d.p, ex.data(), ex.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    const JoinSrc sv = join_src_of(s);
+    double *other = d->overlap ? dv.Bm[d->buf_in ^ 1] : nullptr;
+    if (nT > 0)
+        hipLaunchKernelGGL(k_ext_tiles, dim3((unsigned)(nT * (nT + 1) / 2), (unsigned)nb), dim3(256), 0, st, dv, d->buf_in, other, sv, (const int *)ex_d.p, mstride, nb, nT, bd0,
+                           bs0);
+    hipLaunchKernelGGL(k_ext_vec, dim3(7, (unsigned)nb), dim3(1024), 0, st, dv, sv, (const int *)ex_d.p, mstride, nb, bd0, bs0);
+    std::vector<int> n_new((size_t)nb);
+    for (int k = 0; k < nb; k++) n_new[k] = ex[2 * k + 1];
+    EKF_TRY(finish_rewrite(d, bd0, nb, /*rearm*/ true, n_new.data(), 1, /*flip_buf*/ false));
+    for (int k = 0; k < nb; k++)
+        if (n_out) n_out[k] = n_new[k];
+    return di < 0 ? EKF_OK : n_new[0];
+}
+
+extern "C" int ekf_extract_map(ekf_handle dst, int dst_index, ekf_handle src, int src_index, const int *ids, int count) {
+    if (!dst || !src || dst_index < 0 || dst_index >= dst->dv.B || src_index < 0 || src_index >= src->dv.B) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    if (ids && count < 0) return set_error(EKF_ERR_BAD_ARG, "negative landmark count");
+    if (dst == src && dst_index == src_index) return set_error(EKF_ERR_BAD_ARG, "a filter cannot be extracted into itself");
+    if (dst->device != src->device) return set_error(EKF_ERR_BAD_ARG, "the two handles live on different devices");
+    return extract_impl(dst, dst_index, src, src_index, ids, count, &count, nullptr);
+}
+
+extern "C" int ekf_batch_extract_map(ekf_handle dst, ekf_handle src, const int *ids, int ld_ids, const int *count, int *n_out) {
+    if (!dst || !src || dst == src) return set_error(EKF_ERR_BAD_ARG, "bad argument (two different handles)");
+    if (dst->dv.B != src->dv.B) return set_error(EKF_ERR_BAD_ARG, "the two handles have different batch sizes");
+    if (dst->device != src->device) return set_error(EKF_ERR_BAD_ARG, "the two handles live on different devices");
+    if (ids && (!count || ld_ids < 0)) return set_error(EKF_ERR_BAD_ARG, "a list of ids needs its counts");
+    return extract_impl(dst, -1, src, 0, ids, ld_ids, count, n_out);
+}
+
+// The same marginal to the host: ekf_get_state's rule (the streaming launch leaves; the size alone folds nothing), then the device
+// gathers straight into a transient dense staging matrix of (3 + 2 count)^2 and one copy follows.  The filter is only read.
+extern "C" int ekf_get_submap(ekf_handle h, int index, const int *ids, int count, double *x_out, double *P_out, int ld) {
+    if (!h || index < 0 || index >= h->dv.B || count < 0 || (count > 0 && !ids)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    EKF_TRY(ext_ids_distinct(ids, count, index));
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
+    EKF_TRY(ext_ids_in_range(ids, count, h->h_int[index], index));
+    const int n = 3 + 2 * count;
+    if (!x_out && !P_out) return n;  // (the size alone: nothing is folded)
+    if (!x_out || !P_out || ld < n) return set_error(EKF_ERR_BAD_ARG, "bad output buffers");
+    EKF_TRY(settle(h));
+    hipStream_t s = h->s_chain;
+    DevTmp<double> stage;  // transient staging: dense n x n + x
+    DevTmp<int> ids_d;
+    HIP_TRY(stage.alloc((size_t)n * n + n));
+    HIP_TRY(ids_d.alloc((size_t)(count > 0 ? count : 1)));
+    if (count > 0) HIP_TRY(hipMemcpyAsync(ids_d.p, ids, sizeof(int) * (size_t)count, hipMemcpyHostToDevice, s));
+    double *xd = stage.p + (size_t)n * n;
+    hipLaunchKernelGGL(k_ext_dense, dim3((unsigned)cdiv(n, 256), (unsigned)n), dim3(256), 0, s, join_src_of(h), index, (const int *)ids_d.p, count, xd, stage.p, n, n);
+    HIP_TRY(hipMemcpyAsync(x_out, xd, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpy2DAsync(P_out, (size_t)ld * sizeof(double), stage.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));
+    EKF_TRY(check_launch());
+    return n;
 }
 
 // ---- map assessment -------------------------------------------------------------------------------

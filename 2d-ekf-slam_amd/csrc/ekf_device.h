@@ -413,3 +413,25 @@ __host__ __device__ inline FuseSource fuse_source(int T, int l, int c) {
 // Column q (0 .. 2m - 1) of a fusion round -- component q & 1 of pair q >> 1 -- is element q & 3 of slot pair q >> 2: the offset
 // (doubles) of W / V element (row i', column q) inside set 0 of FA / FB.
 __host__ __device__ inline size_t fuse_slot_offset(int rows, int ip, int q) { return pair_offset(rows, ip, q >> 2) + (size_t)(q & 3); }
+
+// Submap extraction (ekf_extract_map, ekf_get_submap; ekf_extract.hip) gathers by destination, from a source filter with a layout
+// of its own (Ts tiles per side, D stride dns).  ids[k] = source landmark of destination landmark k, pairwise distinct, in ANY
+// order; `count` landmarks are extracted.  extract_landmark: the source landmark of destination landmark k, -1 beyond the new map.
+// extract_block: where the 2x2 block (destination landmarks k, m) = P(a, c) of the source lives, a = ids[k], c = ids[m] -- its own
+// block in D, the stored block, or the stored block (c, a) transposed (fuse_source: the order of the ids decides, not the order
+// of k and m, so a place below the diagonal of a diagonal tile gets what k_import stores there) --, EX_ZERO beyond the new map.
+// extract_element: the same for one element (i', j') of the destination's landmark space, for the dense read-out: the removal's
+// rule with ids in place of its increasing map (remove_source takes (min, max) of the source rows itself).
+enum { EX_ZERO = -1 };  // beside FW_D, FW_BM, FW_BM_T
+__host__ __device__ inline int extract_landmark(const int *ids, int count, int k) { return k < count ? ids[k] : -1; }
+__host__ __device__ inline FuseSource extract_block(int Ts, int a, int c) {
+    if (a < 0 || c < 0) {
+        FuseSource s;
+        s.where = EX_ZERO, s.off = 0;
+        return s;
+    }
+    return fuse_source(Ts, a, c);
+}
+__host__ __device__ inline RmSource extract_element(int Ts, int dns, const int *ids, int count, int ip, int jp) {
+    return remove_source(Ts, dns, remove_row(ids, count, ip), remove_row(ids, count, jp));
+}

@@ -40,8 +40,9 @@ __device__ __forceinline__ int fuse_round_pairs(const EkfDev &dv, const FuseScra
     return m < 0 ? 0 : m > dv.maxp ? dv.maxp : m;
 }
 
-// the block (landmark l, landmark c) of P as {(0,0), (0,1), (1,0), (1,1)}
-__device__ __forceinline__ void fuse_block(const EkfDev &dv, const double *bm, const double *Dx, int l, int c, double m[4]) {
+// the block (landmark l, landmark c) of P as {(0,0), (0,1), (1,0), (1,1)}; F = EkfDev or JoinSrc (ekf_extract.hip reads another handle)
+template <typename F>
+__device__ __forceinline__ void fuse_block(const F &dv, const double *bm, const double *Dx, int l, int c, double m[4]) {
     const FuseSource s = fuse_source(dv.T, l, c);
     if (s.where == FW_D) {
         const double xy = Dx[dv.dn + s.off];

@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "ekf_remove_landmarks", "ekf_batch_remove_landmarks", "ekf_get_landmark_covs",
     "ekf_transform_frame", "ekf_batch_transform_frame", "ekf_anchor_at_robot", "ekf_batch_anchor_at_robot",
     "ekf_join_map", "ekf_batch_join_map",
+    "ekf_extract_map", "ekf_batch_extract_map", "ekf_get_submap",
     "ekf_joint_consistency", "ekf_batch_joint_consistency", "ekf_debug_joint_factor",
     "ekf_find_duplicates", "ekf_batch_find_duplicates",
     "ekf_fuse_landmarks", "ekf_batch_fuse_landmarks",
@@ -129,6 +130,9 @@ def load():
     L.ekf_batch_anchor_at_robot.argtypes = [_H]
     L.ekf_join_map.argtypes = [_H, ctypes.c_int, _H, ctypes.c_int]
     L.ekf_batch_join_map.argtypes = [_H, _H]
+    L.ekf_extract_map.argtypes = [_H, ctypes.c_int, _H, ctypes.c_int, _ip, ctypes.c_int]
+    L.ekf_batch_extract_map.argtypes = [_H, _H, _ip, ctypes.c_int, _ip, _ip]
+    L.ekf_get_submap.argtypes = [_H, ctypes.c_int, _ip, ctypes.c_int, _dp, _dp, ctypes.c_int]
     L.ekf_joint_consistency.argtypes = [_H, ctypes.c_int, _dp, ctypes.POINTER(EkfJoint)]
     L.ekf_batch_joint_consistency.argtypes = [_H, _dp, ctypes.c_int, ctypes.POINTER(EkfJoint)]
     L.ekf_debug_joint_factor.argtypes = [_H, ctypes.c_int, _dp, ctypes.c_int]
@@ -395,6 +399,52 @@ class FilterBatch:
         """Filter b of `src` into filter b of this batch for every b (ekf_batch_join_map; equal batch sizes, another handle)."""
         _chk(self.L.ekf_batch_join_map(self.h, src.h))
 
+    # -- submap extraction ---------------------------------------------------------------------
+    def extract_map(self, src, ids=None, index=0, src_index=0):
+        """Replace filter `index` with the marginal of filter src_index of `src` (a FilterBatch; may be this one when the indices
+        differ) over the robot and the landmarks `ids`, on the device (ekf_extract_map): landmark k becomes src's landmark ids[k],
+        any order, no id twice; ids=None: every landmark, a copy or fork.  The bits of src.get_state() indexed by the selection.
+        Returns the new landmark count; `src` is only read.  The result is NOT independent of src: never join it back."""
+        if ids is None:
+            return _chk(self.L.ekf_extract_map(self.h, int(index), src.h, int(src_index), None, 0))
+        a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        return _chk(self.L.ekf_extract_map(self.h, int(index), src.h, int(src_index), a.ctypes.data_as(_ip), a.size))
+
+    def batch_extract_map(self, src, ids=None, counts=None):
+        """Filter b of `src` into filter b of this batch for every b (ekf_batch_extract_map; equal batch sizes, another handle).
+        ids: [batch][ld] landmark lists with counts[b] entries each (counts=None: all ld), or a sequence of per-filter lists, or
+        None: every landmark of every filter.  Returns the new landmark counts (batch,)."""
+        n_out = np.empty(self.batch, dtype=np.int32)
+        if ids is None:
+            _chk(self.L.ekf_batch_extract_map(self.h, src.h, None, 0, None, n_out.ctypes.data_as(_ip)))
+            return n_out
+        if counts is None and not isinstance(ids, np.ndarray):
+            rows = [np.asarray(r, dtype=np.int32).reshape(-1) for r in ids]
+            counts = [r.size for r in rows]
+            tab = np.zeros((len(rows), max(counts + [1])), dtype=np.int32)
+            for b, r in enumerate(rows):
+                tab[b, :r.size] = r
+            ids = tab
+        a = np.ascontiguousarray(ids, dtype=np.int32)
+        if a.ndim != 2 or a.shape[0] != self.batch:
+            raise ValueError("ids must be [batch][ld]")
+        c = np.full(self.batch, a.shape[1], dtype=np.int32) if counts is None else np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+        if c.size != self.batch:
+            raise ValueError("counts must be [batch]")
+        _chk(self.L.ekf_batch_extract_map(self.h, src.h, a.ctypes.data_as(_ip), a.shape[1], c.ctypes.data_as(_ip), n_out.ctypes.data_as(_ip)))
+        return n_out
+
+    def get_submap(self, ids, index=0):
+        """(x, P) of the robot and the landmarks `ids` of filter `index` (ekf_get_submap): get_state()[sel] bit for bit, gathered on
+        the device into a dense buffer of that size alone.  The filter is left as get_state leaves it."""
+        a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        ip = a.ctypes.data_as(_ip) if a.size else None
+        n = _chk(self.L.ekf_get_submap(self.h, int(index), ip, a.size, None, None, 0))
+        x = np.empty(n)
+        P = np.empty((n, n))
+        _chk(self.L.ekf_get_submap(self.h, int(index), ip, a.size, _p(x), _p(P), n))
+        return x, P
+
     # -- map assessment ------------------------------------------------------------------------
     def joint_consistency(self, x_true=None, index=None):
         """Whole-state consistency on the device (ekf_joint_consistency): joint and map NEES against x_true, log det P, the pivots
@@ -654,6 +704,10 @@ class KalmanFilter:
         """Re-express the map relative to the estimated pose: X = Y = Phi = 0 with zero robot covariance afterwards."""
         self._f.anchor_at_robot(0)
         self._mirror()
+
+    def get_submap(self, ids):
+        """(x, P) of the robot and the landmarks `ids` alone (FilterBatch.get_submap): state()[sel] without the dense export."""
+        return self._f.get_submap(ids, 0)
 
     def joint_consistency(self, x_true=None):
         """Joint / map NEES, log det P, pivots and the pose covariance given the map (FilterBatch.joint_consistency): one record."""

@@ -244,6 +244,43 @@ int ekf_batch_anchor_at_robot(ekf_handle h);
 int ekf_join_map(ekf_handle dst, int dst_index, ekf_handle src, int src_index);
 int ekf_batch_join_map(ekf_handle dst, ekf_handle src);
 
+/* Submap extraction on the device: the way OUT of a filter without the dense export.  ekf_extract_map replaces filter dst_index of
+ * `dst` with the marginal of filter src_index of `src` over the robot and the landmarks ids[0..count): landmark k of dst is
+ * landmark ids[k] of src.  The ids are 0-based, pairwise distinct, in [0, N_src), and may come in ANY order.
+ *     x' = x[sel],  P' = P[sel, sel],  sel = [0, 1, 2, 3 + 2 ids[0], 4 + 2 ids[0], 3 + 2 ids[1], ...]
+ * There is no arithmetic: the result is bitwise what ekf_get_state(src) returns at the same point, indexed by sel.
+ * ids == NULL selects every landmark in order (count is ignored): a device-side copy or fork, also between handles of different
+ * capacity, kernel family and pipeline mode.  count == 0 with ids != NULL selects the pose and P_RR alone.  The ids are the
+ * caller's choice (the landmarks near the robot, one side of a split, a handful for a joint-compatibility test): ekf_get_x is 16
+ * bytes per landmark to choose from.  Returns the new landmark count of dst or a negative status.
+ * NOT INDEPENDENT: an extracted map shares all its information with its source.  Joining it back with ekf_join_map breaks that
+ * call's contract (2) and counts the information twice.  Extraction is for read-outs, forks, checkpoints and hand-offs.
+ * src is only read, exactly as in ekf_join_map: its deferred slots are folded first (at most one window), a streaming launch is
+ * stopped and its immediate-mode calls stream again afterwards; its state, counters, decision log and loaded script stay bitwise
+ * the same.  A sticky EKF_ERR_TIMEOUT of src is returned unchanged with nothing modified; a sticky EKF_ERR_CAPACITY of src does not
+ * block the call (its state is valid and only read, as for ekf_find_duplicates).  src may be dst itself when the indices differ, or
+ * any handle on the same device.
+ * dst is treated as ekf_set_state treats it: every device buffer ends as ekf_set_state of the extracted state would leave it (the
+ * tiles and vector entries of a larger previous map are zeroed), sticky errors are cleared, counters and decision log stay, a
+ * loaded script stays loaded, the host mirror shows the new pose, P_RR and count, and immediate-mode calls stream again.
+ * count > ekf_capacity(dst): EKF_ERR_CAPACITY, NOT sticky, neither filter's exported state changes (src has been folded
+ * nonetheless): call ekf_reserve and extract again.  EKF_ERR_BAD_ARG: a NULL handle, an index out of range, count < 0, an id out
+ * of range or repeated, handles on different devices, dst == src with equal indices (in-place reordering is not offered).  The list
+ * is checked on the host before any handle is touched, and against src's landmark count once src is at rest, before any kernel of
+ * the call runs.
+ * ekf_batch_extract_map: filter b of src into filter b of dst for every b in one launch sequence; equal batch sizes, src != dst;
+ * filter b's list is ids[b * ld_ids .. + count[b]).  One filter without room fails the whole call with nothing modified; filter b
+ * gets the bits of the one-filter call on b.  Returns EKF_OK or a negative status, n_out[b] = new landmark count.
+ * ekf_get_submap: the same marginal to the host.  x_out[3 + 2 count], P_out column-major with ld >= 3 + 2 count, bitwise
+ * symmetric; the padding rows between 3 + 2 count and ld are not written.  x_out = P_out = NULL returns the size 3 + 2 count.
+ * Follows ekf_get_state's quiescing rule, synchronises and leaves the filter bitwise as ekf_get_state at the same point would.
+ * The device gathers straight into a transient dense staging buffer of (3 + 2 count)^2 doubles and one copy follows: the full P
+ * is never formed.  Returns 3 + 2 count or a negative status. */
+int ekf_extract_map(ekf_handle dst, int dst_index, ekf_handle src, int src_index, const int *ids, int count);
+int ekf_batch_extract_map(ekf_handle dst, ekf_handle src, const int *ids /*[batch][ld_ids] or NULL*/, int ld_ids,
+                          const int *count /*[batch]; ignored when ids == NULL*/, int *n_out /*[batch] or NULL*/);
+int ekf_get_submap(ekf_handle h, int index, const int *ids, int count, double *x_out, double *P_out, int ld);
+
 /* Map assessment on the device: is the whole state (pose AND map) consistent, and is P still a covariance?  A Cholesky
  * factorisation P_LL = U^T U of the settled landmark covariance in a scratch copy (64-row tile steps over the tile layout; the
  * filter itself is only read), the robot block last:
