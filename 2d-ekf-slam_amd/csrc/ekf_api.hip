@@ -4,6 +4,11 @@
 // (host-mapped pinned memory, so an API call is kernel launches only), device-resident step
 // scripts and their HIP-graph replay.  There is no CPU fallback: without a gfx950 device
 // ekf_create fails with EKF_ERR_NO_DEVICE.
+//
+// This file is the hot layer -- window and segment planner, streaming command ring, close_set, launch_ops, the graph path -- and the
+// accessors.  The map operations (removal, frame change, joining, extraction, consistency, duplicate search, fusion), which run once
+// per call on a handle at rest, are in ekf_map_api.hip, included below where they use this file's helpers; their list checks and
+// tables are pure code in ekf_map_plan.h.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -19,6 +24,7 @@
 
 #include "ekf_device.h"
 #include "ekf_geometry.h"
+#include "ekf_map_plan.h"
 
 // single translation unit: the kernels are compiled together with their launch sites
 #include "ekf_kernels.hip"
@@ -31,21 +37,22 @@
 
 static thread_local std::string g_last_error;
 
-static int set_error(int code, const char *what) {
-    g_last_error = what ? what : "";
+// (format_text: ekf_map_plan.h, whose checks format the same way without this file: the CPU check program includes that header alone)
+__attribute__((format(printf, 2, 3))) static int set_error(int code, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    g_last_error = format_text(fmt, ap);
+    va_end(ap);
     return code;
 }
+static int set_error(const PlanStatus &st) { return st.code ? set_error(st.code, "%s", st.text.c_str()) : EKF_OK; }  // (a check of ekf_map_plan.h)
 
-int ekf_set_last_error(int code, const char *what) { return set_error(code, what); }  // for the library's other translation units (feat_api.hip)
+int ekf_set_last_error(int code, const char *what) { return set_error(code, "%s", what ? what : ""); }  // for the library's other translation units (feat_api.hip)
 
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            char buf_[512];                                                                  \
-            snprintf(buf_, sizeof buf_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return set_error(EKF_ERR_HIP, buf_);                                             \
-        }                                                                                    \
+#define HIP_TRY(expr)                                                                                                                     \
+    do {                                                                                                                                  \
+        hipError_t e_ = (expr);                                                                                                           \
+        if (e_ != hipSuccess) return set_error(EKF_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);   \
     } while (0)
 
 // ... and for the library's own int status chains (the callee has set the error text)
@@ -66,7 +73,21 @@ struct DevTmp {
         if (p) hipFree(p);
     }
     hipError_t alloc(size_t count) { return hipMalloc((void **)&p, count * sizeof(T)); }
+    // ... of at least one element, filled with `count` of the host's: on stream s, or (async = false) by a synchronous copy
+    hipError_t upload(const T *src, size_t count, hipStream_t s, bool async = true) {
+        const hipError_t e = alloc(count > 0 ? count : 1);
+        if (e != hipSuccess || count == 0) return e;
+        return async ? hipMemcpyAsync(p, src, count * sizeof(T), hipMemcpyHostToDevice, s) : hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice);
+    }
 };
+
+// Device scratch that a handle keeps from the first call of an operation on (ekf_map_api.hip), counted in ekf_device_bytes while it
+// lives: block_alloc / block_release; ekf_destroy releases every block, ekf_reserve has those that existed built again.
+struct DevBlock {
+    void *p = nullptr;
+    size_t bytes = 0;
+};
+enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_COUNT };
 
 struct GraphEntry {
     int steps, M, has_truth;
@@ -176,7 +197,6 @@ struct ekf_batch {
     std::vector<int> h_int;
     // map assessment (ekf_joint_consistency): the factorisation's scratch, one device allocation made at the first call and kept
     FactorScratch fac = {};
-    void *fac_base = nullptr;
     long long state_edits = 0;     // rewrites, broadcasts and scripted runs so far: with chain_seq and stream_ops, "has the state changed?"
     long long fac_stamp[3] = {-1, -1, -1};  // those three when the scratch was last filled (ekf_debug_joint_factor)
     int fac_b0 = 0;                // ... by a call over filters [fac_b0, fac_b0 + fac_n.size()) with fac_n landmarks each
@@ -184,15 +204,15 @@ struct ekf_batch {
     // duplicate search (ekf_find_duplicates): bounding boxes, counters and split table in one allocation made at the first call, the
     // pair list in a second one that grows when a call finds more pairs than it holds; both kept and counted in device_bytes
     DupScratch dup = {};
-    void *dup_base = nullptr;
     // landmark fusion (ekf_fuse_landmarks): pair table, the round's factor and right-hand sides, progress record; one allocation made
     // at the first call, kept and counted in device_bytes
     FuseScratch fuse = {};
-    void *fuse_base = nullptr;
+    DevBlock kept[BLK_COUNT];  // the allocations behind fac, dup (boxes and counters; the pair list) and fuse
 };
 
 static int sticky_status(ekf_batch *h, bool include_capacity);
 static int stream_stop(ekf_batch *h);
+static bool filter_ok(const ekf_batch *h, int index) { return h && index >= 0 && index < h->dv.B; }  // a handle and one of its filters
 
 extern "C" const char *ekf_last_error(void) { return g_last_error.c_str(); }
 
@@ -482,9 +502,7 @@ extern "C" int ekf_batch_create(ekf_handle *out, int batch, int capacity_landmar
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, device_id));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        char buf[256];
-        snprintf(buf, sizeof buf, "device %d is %s; this library carries gfx950 code objects only", device_id, prop.gcnArchName);
-        return set_error(EKF_ERR_NO_DEVICE, buf);
+        return set_error(EKF_ERR_NO_DEVICE, "device %d is %s; this library carries gfx950 code objects only", device_id, prop.gcnArchName);
     }
     HIP_TRY(hipSetDevice(device_id));
     ekf_batch *h = new ekf_batch();  // value-initialised: every pointer null, every count zero
@@ -511,7 +529,7 @@ static int create_impl(ekf_batch *h, int batch, int capacity_landmarks, int devi
     h->tn = read_tunables();
     const Tunables &tn = h->tn;
     const ChainGeometry geo = plan_geometry(batch, capacity_landmarks, h->params, prop.sharedMemPerBlock, tn);
-    if (geo.error) return set_error(geo.error, geo.what);
+    if (geo.error) return set_error(geo.error, "%s", geo.what);
     h->params.max_pending = geo.max_pending;  // the effective window, see ekf_window()
     h->params.overlap = geo.overlap ? 1 : 0;
     h->overlap = geo.overlap;
@@ -550,12 +568,9 @@ static int create_impl(ekf_batch *h, int batch, int capacity_landmarks, int devi
         // (one-workgroup filters wait for nobody: they need no co-residency and claim nothing)
         const int need = h->solo ? 0 : (G * h->chain_filters + per_cu - 1) / per_cu;
         std::lock_guard<std::mutex> lk(g_res_mu);
-        if (g_cus_claimed[device_id] + need > prop.multiProcessorCount) {
-            char buf[256];
-            snprintf(buf, sizeof buf, "this handle's %d chain workgroups need %d CUs, %d of %d are claimed by live handles: they could not all be resident at once",
-                     G * h->chain_filters, need, g_cus_claimed[device_id], prop.multiProcessorCount);
-            return set_error(EKF_ERR_STATE, buf);
-        }
+        if (g_cus_claimed[device_id] + need > prop.multiProcessorCount)
+            return set_error(EKF_ERR_STATE, "this handle's %d chain workgroups need %d CUs, %d of %d are claimed by live handles: they could not all be resident at once",
+                             G * h->chain_filters, need, g_cus_claimed[device_id], prop.multiProcessorCount);
         g_cus_claimed[device_id] += need;
         h->claimed_cus = need;
         h->solo_cus = h->solo ? (h->chain_filters + per_cu - 1) / per_cu : 0;
@@ -728,10 +743,8 @@ extern "C" int ekf_destroy(ekf_handle h) {
     for (int i = 0; i < 2; i++)
         if (h->ev_flush[i]) hipEventDestroy(h->ev_flush[i]);
     if (h->bm1_base) hipFree(h->bm1_base);
-    if (h->fac_base) hipFree(h->fac_base);
-    if (h->dup_base) hipFree(h->dup_base);
-    if (h->dup.list) hipFree(h->dup.list);
-    if (h->fuse_base) hipFree(h->fuse_base);
+    for (DevBlock &blk : h->kept)
+        if (blk.p) hipFree(blk.p);
     for (auto &g : h->graphs) hipGraphExecDestroy(g.exec);
     for (const DevArray &a : device_arrays(h))
         if (*a.slot) hipFree(*a.slot);
@@ -817,12 +830,7 @@ static hipError_t event_wait(hipEvent_t ev) {
 
 static int check_launch() {
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        char buf[256];
-        snprintf(buf, sizeof buf, "kernel launch failed: %s", hipGetErrorString(e));
-        return set_error(EKF_ERR_HIP, buf);
-    }
-    return EKF_OK;
+    return e != hipSuccess ? set_error(EKF_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e)) : EKF_OK;
 }
 
 // Wave -> tile table of the row-block dense pass for nT live tile rows: workgroup w (4 waves) gets tiles of class
@@ -1044,7 +1052,7 @@ static int stream_op(ekf_batch *h, const double *rec, int n_slots) {
             rc = stream_start(h, seq, h->pending);
             for (auto &enq : pass) {
                 hipError_t e = enq();
-                if (e != hipSuccess && rc == EKF_OK) rc = set_error(EKF_ERR_HIP, hipGetErrorString(e));
+                if (e != hipSuccess && rc == EKF_OK) rc = set_error(EKF_ERR_HIP, "%s", hipGetErrorString(e));
             }
             return rc;
         }
@@ -1159,7 +1167,7 @@ static int close_set(ekf_batch *h, bool terminal = false, EnqueueList *defer = n
         return EKF_OK;
     }
     hipError_t e = enqueue();
-    if (e != hipSuccess) return set_error(EKF_ERR_HIP, hipGetErrorString(e));
+    if (e != hipSuccess) return set_error(EKF_ERR_HIP, "%s", hipGetErrorString(e));
     return EKF_OK;
 }
 
@@ -1281,7 +1289,7 @@ static int launch_ops(ekf_batch *h, const double *in, const int *cursor, int k0,
             hipError_t e = enq();
             if (e != hipSuccess) {
                 passes.clear();
-                return set_error(EKF_ERR_HIP, hipGetErrorString(e));
+                return set_error(EKF_ERR_HIP, "%s", hipGetErrorString(e));
             }
         }
         passes.clear();
@@ -1358,9 +1366,9 @@ static int launch_ops_grouped(ekf_batch *h, const double *in, int k0, const unsi
     const int ng = h->ngroups, B = h->dv.B, maxp = h->dv.maxp;
     const int per = (B + ng - 1) / ng;
     hipError_t e;
-    if ((e = hipEventRecord(h->ev_fork, h->s_chain)) != hipSuccess) return set_error(EKF_ERR_HIP, hipGetErrorString(e));
+    if ((e = hipEventRecord(h->ev_fork, h->s_chain)) != hipSuccess) return set_error(EKF_ERR_HIP, "%s", hipGetErrorString(e));
     for (int g = 1; g < ng; g++) {
-        if ((e = hipStreamWaitEvent(h->s_grp[g], h->ev_fork, 0)) != hipSuccess) return set_error(EKF_ERR_HIP, hipGetErrorString(e));  // (nothing has been launched on a group stream yet)
+        if ((e = hipStreamWaitEvent(h->s_grp[g], h->ev_fork, 0)) != hipSuccess) return set_error(EKF_ERR_HIP, "%s", hipGetErrorString(e));  // (nothing has been launched on a group stream yet)
         if (h->tn.solo_stagger_ticks > 0) hipLaunchKernelGGL(k_delay, dim3(1), dim3(64), 0, h->s_grp[g], (long long)g * h->tn.solo_stagger_ticks);
     }
     const bool interleave = h->tn.batch_interleave;
@@ -1411,7 +1419,7 @@ static int launch_ops_grouped(ekf_batch *h, const double *in, int k0, const unsi
         if ((e = hipEventRecord(h->ev_join[g], h->s_grp[g])) == hipSuccess) e = hipStreamWaitEvent(h->s_chain, h->ev_join[g], 0);
         if (e != hipSuccess) {
             (void)stream_wait(h->s_grp[g]);  // no event to order the streams with: drain this one here
-            if (rc_pending == EKF_OK) rc_pending = set_error(EKF_ERR_HIP, hipGetErrorString(e));
+            if (rc_pending == EKF_OK) rc_pending = set_error(EKF_ERR_HIP, "%s", hipGetErrorString(e));
         }
     }
     if (rc_pending != EKF_OK) return rc_pending;
@@ -1614,17 +1622,11 @@ extern "C" int ekf_record_truth(ekf_handle h, const double *truth) {
 static int sticky_status(ekf_batch *h, bool include_capacity) {
     for (int b = 0; b < h->dv.B; b++) {
         const int st = h->mirror_h[b].status;
-        if (st == EKF_ERR_TIMEOUT) {
-            char buf[320];
-            snprintf(buf, sizeof buf, "filter %d: a device-side wait ran out (the %d chain workgroups of a filter were not all resident -- another tenant on the GPU? -- "
-                                      "or the dense pass a launch depends on did not complete); the filter's state is invalid until ekf_set_state", b, h->chain_wgs);
-            return set_error(EKF_ERR_TIMEOUT, buf);
-        }
-        if (st == EKF_ERR_CAPACITY && include_capacity) {
-            char buf[160];
-            snprintf(buf, sizeof buf, "filter %d: a New landmark did not fit capacity_landmarks = %d (Update.cpp:152-178 would have grown the state)", b, h->dv.Ncap);
-            return set_error(EKF_ERR_CAPACITY, buf);
-        }
+        if (st == EKF_ERR_TIMEOUT)
+            return set_error(EKF_ERR_TIMEOUT, "filter %d: a device-side wait ran out (the %d chain workgroups of a filter were not all resident -- another tenant on the GPU? -- "
+                                              "or the dense pass a launch depends on did not complete); the filter's state is invalid until ekf_set_state", b, h->chain_wgs);
+        if (st == EKF_ERR_CAPACITY && include_capacity)
+            return set_error(EKF_ERR_CAPACITY, "filter %d: a New landmark did not fit capacity_landmarks = %d (Update.cpp:152-178 would have grown the state)", b, h->dv.Ncap);
         if (st != 0 && st != EKF_ERR_CAPACITY) return set_error(st, "a kernel reported an error status");
     }
     return EKF_OK;
@@ -1765,7 +1767,7 @@ extern "C" int ekf_get_robot_cov(ekf_handle h, double P_RR_out[9]) {
 }
 
 extern "C" int ekf_get_x(ekf_handle h, int index, double *x_out, int n_max) {
-    if (!h || index < 0 || index >= h->dv.B || !x_out || n_max < 0) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    if (!filter_ok(h, index) || !x_out || n_max < 0) return set_error(EKF_ERR_BAD_ARG, "bad argument");
     EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
     int n = 3 + 2 * h->h_int[index];
     int cnt = n < n_max ? n : n_max;
@@ -1796,7 +1798,7 @@ static int fetch_decisions(ekf_batch *h, int n_z, ekf_decision *out) {
 }
 
 extern "C" int ekf_get_decisions(ekf_handle h, int index, ekf_decision *out, int count) {
-    if (!h || !out || index < 0 || index >= h->dv.B || count < 0) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    if (!filter_ok(h, index) || !out || count < 0) return set_error(EKF_ERR_BAD_ARG, "bad argument");
     EKF_TRY(quiesce(h, QUIET_STREAM, ST_NONE));
     long long cnt;
     HIP_TRY(hipMemcpyAsync(&cnt, h->dv.log_count + index, sizeof cnt, hipMemcpyDeviceToHost, h->s_chain));
@@ -1846,8 +1848,18 @@ extern "C" int ekf_reset_stats(ekf_handle h) {
 }
 
 // ---- dense state injection / extraction -----------------------------------------------------------
+// The end of a staged dense read-back, behind the export kernel on the chain stream: stage = an n x n matrix and, behind it, n
+// entries of x.  x_out (null: there is no x) and P_out, with the caller's leading dimension, are filled and waited for.
+static int read_back_dense(ekf_batch *h, const double *stage, int n, double *x_out, double *P_out, int ld) {
+    hipStream_t s = h->s_chain;
+    if (x_out) HIP_TRY(hipMemcpyAsync(x_out, stage + (size_t)n * n, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpy2DAsync(P_out, (size_t)ld * sizeof(double), stage, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));
+    return EKF_OK;
+}
+
 extern "C" int ekf_get_state(ekf_handle h, int index, double *x_out, double *P_out, int ld) {
-    if (!h || index < 0 || index >= h->dv.B) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
     EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
     int n = 3 + 2 * h->h_int[index];
     if (!x_out && !P_out) return n;  // (the size alone: nothing is folded)
@@ -1855,12 +1867,9 @@ extern "C" int ekf_get_state(ekf_handle h, int index, double *x_out, double *P_o
     EKF_TRY(settle(h));
     DevTmp<double> stage;  // transient staging: dense n x n + x
     HIP_TRY(stage.alloc((size_t)n * n + n));
-    double *xd = stage.p + (size_t)n * n;
-    hipLaunchKernelGGL(k_export, dim3(cdiv(n, 256), n), dim3(256), 0, h->s_chain, h->dv, index, h->buf_in, xd, stage.p, n, n);
-    HIP_TRY(hipMemcpyAsync(x_out, xd, sizeof(double) * n, hipMemcpyDeviceToHost, h->s_chain));
-    HIP_TRY(hipMemcpy2DAsync(P_out, (size_t)ld * sizeof(double), stage.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost, h->s_chain));
-    HIP_TRY(stream_wait(h->s_chain));
-    return n;
+    hipLaunchKernelGGL(k_export, dim3(cdiv(n, 256), n), dim3(256), 0, h->s_chain, h->dv, index, h->buf_in, stage.p + (size_t)n * n, stage.p, n, n);
+    EKF_TRY(read_back_dense(h, stage.p, n, x_out, P_out, ld));
+    return n;  // (a failed launch of k_export is not looked for here, as it is in ekf_get_submap)
 }
 
 // Both streams are idle here (quiesce(QUIET_SETTLED)).  A launch that gave up (EKF_ERR_TIMEOUT) leaves the segment counters ahead
@@ -1880,7 +1889,7 @@ static int restart_waits(ekf_batch *h) {
 }
 
 extern "C" int ekf_set_state(ekf_handle h, int index, const double *x, const double *P, int ld, int n) {
-    if (!h || index < 0 || index >= h->dv.B || !x || !P || n < 3 || ((n - 3) & 1) || ld < n) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    if (!filter_ok(h, index) || !x || !P || n < 3 || ((n - 3) & 1) || ld < n) return set_error(EKF_ERR_BAD_ARG, "bad argument");
     int N = (n - 3) / 2;
     if (N > h->dv.Ncap) return set_error(EKF_ERR_CAPACITY, "state larger than capacity_landmarks");
     EKF_TRY(quiesce(h, QUIET_SETTLED, ST_NONE));
@@ -1907,9 +1916,7 @@ extern "C" int ekf_set_state(ekf_handle h, int index, const double *x, const dou
 // moves over on the device (k_export into a dense staging matrix, k_import from it: the tile numbering depends on the capacity),
 // the counters, the decision log and a loaded script move with it, and the handle keeps its address.
 static int reserve_move_state(ekf_batch *h, ekf_batch *nh, const std::vector<int> &n_lm);
-static int factor_reserve(ekf_batch *h);
-static int dup_reserve(ekf_batch *h, int cap);
-static int fuse_reserve(ekf_batch *h);
+static int map_scratch_reserve(ekf_batch *h, const bool want[BLK_COUNT], int dup_cap);  // (ekf_map_api.hip)
 
 extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     if (!h || capacity_landmarks < 1 || capacity_landmarks > EKF_MAX_CAPACITY) return set_error(EKF_ERR_BAD_ARG, "bad handle / capacity (EKF_MAX_CAPACITY)");
@@ -1972,14 +1979,12 @@ extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     std::swap(nh->script_d, h->script_d);
     nh->script_steps = h->script_steps, nh->script_M = h->script_M, nh->script_has_truth = h->script_has_truth;
     h->script_steps = 0;
-    const bool had_factor_scratch = h->fac_base != nullptr;
-    const int had_dup_cap = h->dup_base ? h->dup.cap : 0;
-    const bool had_fuse_scratch = h->fuse_base != nullptr;
+    bool had[BLK_COUNT];  // the scratch the map operations keep follows the capacity
+    for (int i = 0; i < BLK_COUNT; i++) had[i] = h->kept[i].p != nullptr;
+    const int had_dup_cap = h->dup.cap;
     std::swap(*h, *nh);  // the caller's handle now owns the larger buffers ...
     ekf_destroy(nh);     // ... and the old ones go
-    if (had_factor_scratch) EKF_TRY(factor_reserve(h));  // (the scratch of ekf_joint_consistency follows the capacity)
-    if (had_dup_cap) EKF_TRY(dup_reserve(h, had_dup_cap));  // (... and so does that of ekf_find_duplicates)
-    if (had_fuse_scratch) EKF_TRY(fuse_reserve(h));         // (... and the pair table of ekf_fuse_landmarks)
+    EKF_TRY(map_scratch_reserve(h, had, had_dup_cap));
     return refresh_bounds(h);
 }
 
@@ -2037,714 +2042,7 @@ extern "C" int ekf_broadcast_state(ekf_handle h) {
     return refresh_bounds(h);
 }
 
-// ---- map management -------------------------------------------------------------------------------
-// Marginalise landmarks out on the device: gather by destination over the tile layout (k_rm_gather), in overlap mode into the other Bm
-// buffer (then flipped, as settle() does behind a pass; the buffer read is cleared), in place through a transient scratch copied back
-// (k_rm_finish); x, R, D compacted by k_rm_vec.  Every buffer ends as ekf_set_state of the reduced state would leave it; the buffer
-// addresses do not change (captured graphs and streaming launches hold EkfDev by value).
-static int remove_settled(ekf_batch *h, const unsigned char *keep, int ld_keep, int index, int *n_out);
-static int remove_impl(ekf_batch *h, const unsigned char *keep, int ld_keep, int index, int *n_out) {
-    // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
-    // every deferred slot folded, both streams idle
-    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
-    return remove_settled(h, keep, ld_keep, index, n_out);
-}
-
-// The removal itself, on a handle that quiesce(QUIET_SETTLED) has brought to rest (h_int[] current): remove_impl, and the end of
-// ekf_fuse_landmarks behind its own kernels on the chain stream.
-static int remove_settled(ekf_batch *h, const unsigned char *keep, int ld_keep, int index, int *n_out) {
-    EkfDev &dv = h->dv;
-    const int B = dv.B, mstride = dv.Ncap > 0 ? dv.Ncap : 1;
-    std::vector<int> rm((size_t)B * (2 + mstride), 0);
-    int nTo = 0, nTn = 0;
-    bool any = false;
-    for (int b = 0; b < B; b++) {
-        const int n_old = h->h_int[b];
-        const unsigned char *k = index < 0 ? keep + (size_t)b * ld_keep : (b == index ? keep : nullptr);
-        int *map = rm.data() + 2 * B + (size_t)b * mstride;
-        int n_new = 0;
-        for (int l = 0; l < n_old; l++)
-            if (!k || l >= ld_keep || k[l]) map[n_new++] = l;  // (landmarks without an entry are kept)
-        rm[2 * b] = n_old, rm[2 * b + 1] = n_new;
-        any = any || n_new != n_old;
-        const int to = lm_tiles(n_old), tn = lm_tiles(n_new);
-        nTo = to > nTo ? to : nTo;
-        nTn = tn > nTn ? tn : nTn;
-        if (n_out) n_out[b] = n_new;
-    }
-    if (!any) return index < 0 ? EKF_OK : rm[2 * index + 1];
-    hipStream_t s = h->s_chain;
-    DevTmp<int> rm_d;
-    DevTmp<double> scratch;
-    const size_t scratch_stride = (size_t)nTn * (nTn + 1) / 2 * 4096;
-    HIP_TRY(rm_d.alloc(rm.size()));
-    if (!h->overlap && scratch_stride) HIP_TRY(scratch.alloc((size_t)B * scratch_stride));
-    HIP_TRY(hipMemcpyAsync(rm_d.p, rm.data(), rm.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    if (nTo > 0) {
-        const dim3 grid((unsigned)(nTo * (nTo + 1) / 2), (unsigned)B);
-        if (h->overlap) {
-            hipLaunchKernelGGL(k_rm_gather, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, mstride, nTo, dv.Bm[h->buf_in ^ 1], dv.T, dv.bm_stride, 0);
-            hipLaunchKernelGGL(k_rm_finish, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, nTo, (const double *)nullptr, 0, (size_t)0);
-        } else {
-            if (scratch.p)
-                hipLaunchKernelGGL(k_rm_gather, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, mstride, nTo, scratch.p, nTn, scratch_stride, 1);
-            hipLaunchKernelGGL(k_rm_finish, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, nTo, (const double *)scratch.p, nTn, scratch_stride);
-        }
-    }
-    // D is read by the gather (landmarks' own blocks): compacted behind it
-    hipLaunchKernelGGL(k_rm_vec, dim3(7, B), dim3(1024), 0, s, dv, (const int *)rm_d.p, mstride);
-    EKF_TRY(finish_rewrite(h, 0, B, /*rearm*/ true, &rm[1], 2, /*flip_buf: the gather's output*/ h->overlap && nTo > 0));
-    return index < 0 ? EKF_OK : rm[2 * index + 1];
-}
-
-extern "C" int ekf_remove_landmarks(ekf_handle h, int index, const unsigned char *keep, int count) {
-    if (!h || index < 0 || index >= h->dv.B || !keep || count < 0) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    return remove_impl(h, keep, count, index, nullptr);
-}
-
-extern "C" int ekf_batch_remove_landmarks(ekf_handle h, const unsigned char *keep, int ld_keep, int *n_out) {
-    if (!h || !keep || ld_keep < 0) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    return remove_impl(h, keep, ld_keep, -1, n_out);
-}
-
-// The per-filter argument of a rewrite launch over nb filters (ekf_rewrite.hip: arg_value), vals = [nb][doubles of A]: a one-filter
-// call carries it in the kernel arguments (*one), a batch call in a transient table (copied synchronously: vals may leave scope).
-template <typename A>
-static int rewrite_arg(const std::vector<double> &vals, int nb, A *one, DevTmp<double> *tab) {
-    if (nb == 1) {
-        memcpy(one, vals.data(), sizeof(A));
-        return EKF_OK;
-    }
-    HIP_TRY(tab->alloc(vals.size()));
-    HIP_TRY(hipMemcpy(tab->p, vals.data(), vals.size() * sizeof(double), hipMemcpyHostToDevice));
-    return EKF_OK;
-}
-
-// Frame changes on the device (ekf_rewrite.hip: k_reframe_vec, k_reframe_tiles, k_reframe_finish), the order of steps as in
-// remove_impl.  frames == nullptr: anchor at the robot; else one (t_x, t_y, theta) per filter of the launch.  index < 0: every
-// filter, one launch sequence with the grid over the filters.  Bm is rewritten in place in the settled buffer (either pipeline
-// mode: no second buffer, no scratch); the only transient allocation is the BATCH rigid call's frame table (48 bytes per filter; a
-// one-filter call carries its frame in the kernel arguments); the anchor's per-row operands use slot set 0 of FA / FB, which are
-// cleared afterwards as a removal clears them.
-static int reframe_impl(ekf_batch *h, int index, const double *frames) {
-    // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
-    // every deferred slot folded, both streams idle
-    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
-    EkfDev &dv = h->dv;
-    const int b_off = index < 0 ? 0 : index, nb = index < 0 ? dv.B : 1;
-    int nT = 0;
-    for (int b = b_off; b < b_off + nb; b++) {
-        const int t = lm_tiles(h->h_int[b]);
-        nT = t > nT ? t : nT;
-    }
-    hipStream_t s = h->s_chain;
-    DevTmp<double> fr_d;
-    ReframeFrame one = {{0.0, 0.0, 1.0, 0.0, 0.0, 0.0}};
-    if (frames) {
-        std::vector<double> fr((size_t)nb * 6, 0.0);
-        for (int k = 0; k < nb; k++) {
-            const double *f = frames + 3 * (size_t)k;
-            fr[6 * k] = f[0], fr[6 * k + 1] = f[1], fr[6 * k + 2] = cos(f[2]), fr[6 * k + 3] = sin(f[2]), fr[6 * k + 4] = f[2];
-        }
-        EKF_TRY(rewrite_arg(fr, nb, &one, &fr_d));
-    }
-    const double *frc = fr_d.p;
-    const auto k_vec = frames ? k_reframe_vec<false> : k_reframe_vec<true>;  // <ANCHOR>
-    const auto k_tiles = frames ? k_reframe_tiles<false> : k_reframe_tiles<true>;
-    const auto k_finish = frames ? k_reframe_finish<false> : k_reframe_finish<true>;
-    if (nT > 0) {
-        const dim3 gv((unsigned)cdiv(32 * nT, 256), (unsigned)nb), gt((unsigned)(nT * (nT + 1) / 2), (unsigned)nb);
-        hipLaunchKernelGGL(k_vec, gv, dim3(256), 0, s, dv, one, frc, b_off);
-        hipLaunchKernelGGL(k_tiles, gt, dim3(256), 0, s, dv, h->buf_in, one, frc, b_off, nT);
-    }
-    hipLaunchKernelGGL(k_finish, dim3(nb), dim3(64), 0, s, dv, one, frc, b_off);
-    return finish_rewrite(h, b_off, nb, /*rearm*/ true, nullptr, 0, /*flip_buf*/ false);
-}
-
-static bool finite3(const double *f) { return __builtin_isfinite(f[0]) && __builtin_isfinite(f[1]) && __builtin_isfinite(f[2]); }
-
-extern "C" int ekf_transform_frame(ekf_handle h, int index, const double frame[3]) {
-    if (!h || index < 0 || index >= h->dv.B || !frame || !finite3(frame)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    return reframe_impl(h, index, frame);
-}
-
-extern "C" int ekf_batch_transform_frame(ekf_handle h, const double *frames) {
-    if (!h || !frames) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    for (int b = 0; b < h->dv.B; b++)
-        if (!finite3(frames + 3 * (size_t)b)) return set_error(EKF_ERR_BAD_ARG, "a frame is not finite");
-    return reframe_impl(h, -1, frames);
-}
-
-extern "C" int ekf_anchor_at_robot(ekf_handle h, int index) {
-    if (!h || index < 0 || index >= h->dv.B) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    return reframe_impl(h, index, nullptr);
-}
-
-extern "C" int ekf_batch_anchor_at_robot(ekf_handle h) {
-    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
-    return reframe_impl(h, -1, nullptr);
-}
-
-// Map joining on the device (ekf_rewrite.hip: k_join_tiles, k_join_vec, k_join_finish).  di < 0: the batch form, filter b of `s`
-// into filter b of `d`.  Both handles are brought to rest first (the source is only read afterwards, so its own quiescing is all
-// that ever happens to it), which also orders their streams: everything runs on the destination's chain stream while the source's
-// streams are idle, and the call waits for it.  Bm is rewritten in place in the destination's settled buffer in either pipeline
-// mode; the only transient allocation is the batch form's table of cos / sin (16 bytes per filter).
-static int join_impl(ekf_batch *d, int di, ekf_batch *s, int si) {
-    EKF_TRY(quiesce(s, QUIET_SETTLED, ST_INVALID_OR_FULL));
-    if (d != s) EKF_TRY(quiesce(d, QUIET_SETTLED, ST_INVALID_OR_FULL));
-    EkfDev &dv = d->dv;
-    const int bd0 = di < 0 ? 0 : di, bs0 = di < 0 ? 0 : si, nb = di < 0 ? dv.B : 1;
-    int nt = 0, nv = 0;
-    for (int k = 0; k < nb; k++) {
-        const int Ng = d->h_int[bd0 + k], Ns = s->h_int[bs0 + k];
-        if (Ng + Ns > dv.Ncap) {
-            char buf[200];
-            snprintf(buf, sizeof buf, "filter %d: %d + %d landmarks do not fit capacity_landmarks = %d (ekf_reserve, then join again)", bd0 + k, Ng, Ns, dv.Ncap);
-            return set_error(EKF_ERR_CAPACITY, buf);
-        }
-        const int t = join_tile_count(Ng, Ns);
-        nt = t > nt ? t : nt;
-        nv = Ng + Ns > nv ? Ng + Ns : nv;
-    }
-    DevTmp<double> rot_d;
-    Rot2 one = {1.0, 0.0};
-    // (the host mirror's heading is the device's x[2] bit for bit once the chain stream is idle: every writer of x[0..2] -- the chain
-    // kernels, k_set_meta, the finish kernels -- copies the pose into the mirror; a dense pass does not touch it)
-    std::vector<double> rot((size_t)nb * 2);
-    for (int k = 0; k < nb; k++) rot[2 * k] = cos(d->mirror_h[bd0 + k].pose[2]), rot[2 * k + 1] = sin(d->mirror_h[bd0 + k].pose[2]);
-    EKF_TRY(rewrite_arg(rot, nb, &one, &rot_d));
-    const EkfDev &sd = s->dv;
-    const JoinSrc sv = {sd.x, sd.R, sd.D, sd.Bm[s->buf_in], sd.n_lm, sd.xs, sd.dn, sd.T, sd.bm_stride};
-    const double *rotc = rot_d.p;
-    hipStream_t st = d->s_chain;
-    if (nt > 0) hipLaunchKernelGGL(k_join_tiles, dim3((unsigned)nt, (unsigned)nb), dim3(256), 0, st, dv, d->buf_in, sv, one, rotc, bd0, bs0);
-    if (nv > 0) hipLaunchKernelGGL(k_join_vec, dim3((unsigned)cdiv(nv, 256), (unsigned)nb), dim3(256), 0, st, dv, d->buf_in, sv, one, rotc, bd0, bs0);
-    hipLaunchKernelGGL(k_join_finish, dim3(nb), dim3(64), 0, st, dv, sv, one, rotc, bd0, bs0);
-    EKF_TRY(finish_rewrite(d, bd0, nb, /*rearm*/ true, nullptr, 0, /*flip_buf*/ false));
-    return di < 0 ? EKF_OK : d->h_int[bd0];
-}
-
-extern "C" int ekf_join_map(ekf_handle dst, int dst_index, ekf_handle src, int src_index) {
-    if (!dst || !src || dst_index < 0 || dst_index >= dst->dv.B || src_index < 0 || src_index >= src->dv.B) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    if (dst == src && dst_index == src_index) return set_error(EKF_ERR_BAD_ARG, "a filter cannot be joined to itself");
-    if (dst->device != src->device) return set_error(EKF_ERR_BAD_ARG, "the two handles live on different devices");
-    return join_impl(dst, dst_index, src, src_index);
-}
-
-extern "C" int ekf_batch_join_map(ekf_handle dst, ekf_handle src) {
-    if (!dst || !src || dst == src) return set_error(EKF_ERR_BAD_ARG, "bad argument (two different handles)");
-    if (dst->dv.B != src->dv.B) return set_error(EKF_ERR_BAD_ARG, "the two handles have different batch sizes");
-    if (dst->device != src->device) return set_error(EKF_ERR_BAD_ARG, "the two handles live on different devices");
-    return join_impl(dst, -1, src, 0);
-}
-
-// ---- submap extraction ----------------------------------------------------------------------------
-// The list of a call, checked on the host before any handle is touched: every id non-negative, no id twice.  (Against the source's
-// landmark count: ext_ids_in_range, once the source is at rest.)
-static int ext_ids_distinct(const int *ids, int count, int filter) {
-    std::vector<int> sorted(ids, ids + count);
-    std::sort(sorted.begin(), sorted.end());
-    char buf[160];
-    if (count > 0 && sorted[0] < 0) {
-        snprintf(buf, sizeof buf, "filter %d: landmark id %d is negative", filter, sorted[0]);
-        return set_error(EKF_ERR_BAD_ARG, buf);
-    }
-    for (int k = 1; k < count; k++)
-        if (sorted[k] == sorted[k - 1]) {
-            snprintf(buf, sizeof buf, "filter %d: landmark id %d is named twice", filter, sorted[k]);
-            return set_error(EKF_ERR_BAD_ARG, buf);
-        }
-    return EKF_OK;
-}
-static int ext_ids_in_range(const int *ids, int count, int N, int filter) {
-    for (int k = 0; k < count; k++)
-        if (ids[k] >= N) {
-            char buf[160];
-            snprintf(buf, sizeof buf, "filter %d: landmark id %d is not one of its %d landmarks", filter, ids[k], N);
-            return set_error(EKF_ERR_BAD_ARG, buf);
-        }
-    return EKF_OK;
-}
-static JoinSrc join_src_of(const ekf_batch *s) {
-    const EkfDev &sd = s->dv;
-    return {sd.x, sd.R, sd.D, sd.Bm[s->buf_in], sd.n_lm, sd.xs, sd.dn, sd.T, sd.bm_stride};
-}
-
-// Submap extraction on the device (ekf_extract.hip: k_ext_tiles, k_ext_vec).  di < 0: the batch form, filter b of `s` into filter b
-// of `d`.  ids == nullptr: every landmark of the source in order; else filter k's list is ids + k * ld_ids with count[k] entries.
-// The source comes to rest first and is only read afterwards (sticky EKF_ERR_TIMEOUT ends the call; a sticky EKF_ERR_CAPACITY does
-// not: the state is valid); the destination is then treated as ekf_set_state treats it, except that only the tiles and vector
-// entries up to the larger of its previous and its new map are written -- everything behind them is zeros already.  Everything runs
-// on the destination's chain stream while the source's streams are idle, and the call waits for it.  The only transient allocation
-// is the id table (4 bytes per extracted landmark).
-static int extract_impl(ekf_batch *d, int di, ekf_batch *s, int si, const int *ids, int ld_ids, const int *count, int *n_out) {
-    const int bd0 = di < 0 ? 0 : di, bs0 = di < 0 ? 0 : si, nb = di < 0 ? d->dv.B : 1;
-    if (ids)
-        for (int k = 0; k < nb; k++) {
-            if (count[k] < 0 || count[k] > ld_ids) return set_error(EKF_ERR_BAD_ARG, "bad landmark count");
-            EKF_TRY(ext_ids_distinct(ids + (size_t)k * ld_ids, count[k], bs0 + k));
-        }
-    EKF_TRY(quiesce(s, QUIET_STREAM, ST_INVALID));
-    int mstride = 1;
-    for (int k = 0; k < nb; k++) {
-        const int N = s->h_int[bs0 + k], cnt = ids ? count[k] : N;
-        if (ids) EKF_TRY(ext_ids_in_range(ids + (size_t)k * ld_ids, cnt, N, bs0 + k));
-        mstride = cnt > mstride ? cnt : mstride;
-    }
-    EKF_TRY(settle(s));
-    EkfDev &dv = d->dv;
-    std::vector<int> ex((size_t)nb * (2 + mstride), 0);
-    for (int k = 0; k < nb; k++) {
-        const int cnt = ids ? count[k] : s->h_int[bs0 + k];
-        if (cnt > dv.Ncap) {
-            char buf[200];
-            snprintf(buf, sizeof buf, "filter %d: %d landmarks do not fit capacity_landmarks = %d (ekf_reserve, then extract again)", bd0 + k, cnt, dv.Ncap);
-            return set_error(EKF_ERR_CAPACITY, buf);
-        }
-        ex[2 * k + 1] = cnt;
-        int *tab = ex.data() + 2 * nb + (size_t)k * mstride;
-        for (int q = 0; q < cnt; q++) tab[q] = ids ? ids[(size_t)k * ld_ids + q] : q;
-    }
-    if (d != s) EKF_TRY(quiesce(d, QUIET_SETTLED, ST_NONE));
-    {
-        // the destination's previous maps: what has to be overwritten.  A timed-out filter's count is not to be trusted: all of it.
-        const int rc = refresh_bounds(d);
-        if (rc && rc != EKF_ERR_TIMEOUT) return rc;
-    }
-    int nT = 0, n_hi = 0;
-    for (int k = 0; k < nb; k++) {
-        int n_old = d->mirror_h[bd0 + k].status == EKF_ERR_TIMEOUT ? dv.Ncap : d->h_int[bd0 + k];
-        if (n_old < 0 || n_old > dv.Ncap) n_old = dv.Ncap;
-        ex[2 * k] = n_old;
-        const int hi = n_old > ex[2 * k + 1] ? n_old : ex[2 * k + 1];
-        n_hi = hi > n_hi ? hi : n_hi;
-    }
-    nT = lm_tiles(n_hi);
-    hipStream_t st = d->s_chain;
-    EKF_TRY(restart_waits(d));
-    DevTmp<int> ex_d;
-    HIP_TRY(ex_d.alloc(ex.size()));
-    HIP_TRY(hipMemcpyAsync(ex_d.p, ex.data(), ex.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    const JoinSrc sv = join_src_of(s);
-    double *other = d->overlap ? dv.Bm[d->buf_in ^ 1] : nullptr;
-    if (nT > 0)
-        hipLaunchKernelGGL(k_ext_tiles, dim3((unsigned)(nT * (nT + 1) / 2), (unsigned)nb), dim3(256), 0, st, dv, d->buf_in, other, sv, (const int *)ex_d.p, mstride, nb, nT, bd0,
-                           bs0);
-    hipLaunchKernelGGL(k_ext_vec, dim3(7, (unsigned)nb), dim3(1024), 0, st, dv, sv, (const int *)ex_d.p, mstride, nb, bd0, bs0);
-    std::vector<int> n_new((size_t)nb);
-    for (int k = 0; k < nb; k++) n_new[k] = ex[2 * k + 1];
-    EKF_TRY(finish_rewrite(d, bd0, nb, /*rearm*/ true, n_new.data(), 1, /*flip_buf*/ false));
-    for (int k = 0; k < nb; k++)
-        if (n_out) n_out[k] = n_new[k];
-    return di < 0 ? EKF_OK : n_new[0];
-}
-
-extern "C" int ekf_extract_map(ekf_handle dst, int dst_index, ekf_handle src, int src_index, const int *ids, int count) {
-    if (!dst || !src || dst_index < 0 || dst_index >= dst->dv.B || src_index < 0 || src_index >= src->dv.B) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    if (ids && count < 0) return set_error(EKF_ERR_BAD_ARG, "negative landmark count");
-    if (dst == src && dst_index == src_index) return set_error(EKF_ERR_BAD_ARG, "a filter cannot be extracted into itself");
-    if (dst->device != src->device) return set_error(EKF_ERR_BAD_ARG, "the two handles live on different devices");
-    return extract_impl(dst, dst_index, src, src_index, ids, count, &count, nullptr);
-}
-
-extern "C" int ekf_batch_extract_map(ekf_handle dst, ekf_handle src, const int *ids, int ld_ids, const int *count, int *n_out) {
-    if (!dst || !src || dst == src) return set_error(EKF_ERR_BAD_ARG, "bad argument (two different handles)");
-    if (dst->dv.B != src->dv.B) return set_error(EKF_ERR_BAD_ARG, "the two handles have different batch sizes");
-    if (dst->device != src->device) return set_error(EKF_ERR_BAD_ARG, "the two handles live on different devices");
-    if (ids && (!count || ld_ids < 0)) return set_error(EKF_ERR_BAD_ARG, "a list of ids needs its counts");
-    return extract_impl(dst, -1, src, 0, ids, ld_ids, count, n_out);
-}
-
-// The same marginal to the host: ekf_get_state's rule (the streaming launch leaves; the size alone folds nothing), then the device
-// gathers straight into a transient dense staging matrix of (3 + 2 count)^2 and one copy follows.  The filter is only read.
-extern "C" int ekf_get_submap(ekf_handle h, int index, const int *ids, int count, double *x_out, double *P_out, int ld) {
-    if (!h || index < 0 || index >= h->dv.B || count < 0 || (count > 0 && !ids)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    EKF_TRY(ext_ids_distinct(ids, count, index));
-    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
-    EKF_TRY(ext_ids_in_range(ids, count, h->h_int[index], index));
-    const int n = 3 + 2 * count;
-    if (!x_out && !P_out) return n;  // (the size alone: nothing is folded)
-    if (!x_out || !P_out || ld < n) return set_error(EKF_ERR_BAD_ARG, "bad output buffers");
-    EKF_TRY(settle(h));
-    hipStream_t s = h->s_chain;
-    DevTmp<double> stage;  // transient staging: dense n x n + x
-    DevTmp<int> ids_d;
-    HIP_TRY(stage.alloc((size_t)n * n + n));
-    HIP_TRY(ids_d.alloc((size_t)(count > 0 ? count : 1)));
-    if (count > 0) HIP_TRY(hipMemcpyAsync(ids_d.p, ids, sizeof(int) * (size_t)count, hipMemcpyHostToDevice, s));
-    double *xd = stage.p + (size_t)n * n;
-    hipLaunchKernelGGL(k_ext_dense, dim3((unsigned)cdiv(n, 256), (unsigned)n), dim3(256), 0, s, join_src_of(h), index, (const int *)ids_d.p, count, xd, stage.p, n, n);
-    HIP_TRY(hipMemcpyAsync(x_out, xd, sizeof(double) * n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpy2DAsync(P_out, (size_t)ld * sizeof(double), stage.p, (size_t)n * sizeof(double), (size_t)n * sizeof(double), n, hipMemcpyDeviceToHost, s));
-    HIP_TRY(stream_wait(s));
-    EKF_TRY(check_launch());
-    return n;
-}
-
-// ---- map assessment -------------------------------------------------------------------------------
-// The scratch of ekf_joint_consistency (ekf_factor.hip: FactorScratch), sized by the handle's capacity: one allocation at the first
-// call, counted in ekf_device_bytes, freed by ekf_destroy; ekf_reserve builds the larger one.
-static int factor_reserve(ekf_batch *h) {
-    if (h->fac_base) return EKF_OK;
-    const EkfDev &dv = h->dv;
-    const size_t B = (size_t)dv.B;
-    const size_t nS = B * dv.bm_stride, nrhs = B * (size_t)dv.rows * 4, nacc = B * FAC_ACC, nxt = B * (size_t)dv.xs;
-    const size_t bytes = (nS + nrhs + nacc + nxt) * sizeof(double) + B * sizeof(ekf_joint);
-    void *p = nullptr;
-    HIP_TRY(hipMalloc(&p, bytes));
-    hipError_t e = hipMemsetAsync(p, 0, bytes, h->s_chain);
-    if (e == hipSuccess) e = stream_wait(h->s_chain);
-    if (e != hipSuccess) {
-        hipFree(p);
-        return set_error(EKF_ERR_HIP, hipGetErrorString(e));
-    }
-    h->fac_base = p;
-    h->fac.S = (double *)p;
-    h->fac.rhs = h->fac.S + nS;
-    h->fac.acc = h->fac.rhs + nrhs;
-    h->fac.xt = h->fac.acc + nacc;
-    h->fac.out = (ekf_joint *)(h->fac.xt + nxt);
-    h->device_bytes += bytes;
-    h->fac_stamp[0] = -1;
-    return EKF_OK;
-}
-
-// Filters [b0, b0 + nb): the rule of ekf_get_state (the streaming launch leaves, every deferred slot is folded, both streams idle),
-// then the settled state is only read: stage, 3 launches per tile step with the grid over the filters, finish, one copy back.
-static int joint_impl(ekf_batch *h, int b0, int nb, const double *x_true, int ld_true, ekf_joint *out) {
-    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
-    int n_max = 0;
-    for (int k = 0; k < nb; k++) n_max = h->h_int[b0 + k] > n_max ? h->h_int[b0 + k] : n_max;
-    if (x_true && ld_true < 3 + 2 * n_max) return set_error(EKF_ERR_BAD_ARG, "x_true rows are shorter than the largest state of the call");
-    EKF_TRY(settle(h));
-    EKF_TRY(factor_reserve(h));
-    const EkfDev &dv = h->dv;
-    const FactorScratch fs = h->fac;
-    hipStream_t s = h->s_chain;
-    const int have_truth = x_true ? 1 : 0;
-    if (x_true)
-        HIP_TRY(hipMemcpy2DAsync(fs.xt + (size_t)b0 * dv.xs, (size_t)dv.xs * sizeof(double), x_true, (size_t)ld_true * sizeof(double),
-                                 (size_t)(3 + 2 * n_max) * sizeof(double), nb, hipMemcpyHostToDevice, s));
-    const int nT = lm_tiles(n_max);
-    if (nT > 0) hipLaunchKernelGGL(k_chol_stage, dim3((unsigned)(nT * (nT + 1) / 2), (unsigned)nb), dim3(256), 0, s, dv, fs, h->buf_in, b0, nT, have_truth);
-    for (int k = 0; k < nT; k++) {
-        hipLaunchKernelGGL(k_chol_diag, dim3((unsigned)nb), dim3(320), 0, s, dv, fs, k, b0);
-        if (k + 1 < nT) {
-            hipLaunchKernelGGL(k_chol_panel, dim3((unsigned)(nT - 1 - k), (unsigned)nb), dim3(64), 0, s, dv, fs, k, b0);
-            hipLaunchKernelGGL(k_chol_trail, dim3((unsigned)chol_trail_count(nT, k), (unsigned)nb), dim3(256), 0, s, dv, fs, k, b0, nT);
-        }
-    }
-    hipLaunchKernelGGL(k_chol_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0, have_truth);
-    HIP_TRY(hipMemcpyAsync(out, fs.out + b0, sizeof(ekf_joint) * (size_t)nb, hipMemcpyDeviceToHost, s));
-    HIP_TRY(stream_wait(s));
-    EKF_TRY(check_launch());
-    h->fac_stamp[0] = h->chain_seq, h->fac_stamp[1] = h->stream_ops, h->fac_stamp[2] = h->state_edits;
-    h->fac_b0 = b0;
-    h->fac_n.assign(h->h_int.begin() + b0, h->h_int.begin() + b0 + nb);
-    return EKF_OK;
-}
-
-extern "C" int ekf_joint_consistency(ekf_handle h, int index, const double *x_true, ekf_joint *out) {
-    if (!h || index < 0 || index >= h->dv.B || !out) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    return joint_impl(h, index, 1, x_true, x_true ? 3 + 2 * h->dv.Ncap : 0, out);
-}
-
-extern "C" int ekf_batch_joint_consistency(ekf_handle h, const double *x_true, int ld_true, ekf_joint *out) {
-    if (!h || !out || (x_true && ld_true < 3)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    return joint_impl(h, 0, h->dv.B, x_true, ld_true, out);
-}
-
-extern "C" int ekf_debug_joint_factor(ekf_handle h, int index, double *U_out, int ld) {
-    if (!h || index < 0 || index >= h->dv.B) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    const bool current = h->fac_base && h->fac_stamp[0] == h->chain_seq && h->fac_stamp[1] == h->stream_ops && h->fac_stamp[2] == h->state_edits;
-    if (!current || index < h->fac_b0 || index >= h->fac_b0 + (int)h->fac_n.size())
-        return set_error(EKF_ERR_STATE, "no factor of this filter's current state: call ekf_joint_consistency first");
-    const int m = 2 * h->fac_n[index - h->fac_b0];
-    if (m == 0) return 0;
-    if (!U_out || ld < m) return set_error(EKF_ERR_BAD_ARG, "bad output buffer");
-    HIP_TRY(hipSetDevice(h->device));
-    DevTmp<double> stage;
-    HIP_TRY(stage.alloc((size_t)m * m));
-    hipLaunchKernelGGL(k_chol_export, dim3(cdiv(m, 256), m), dim3(256), 0, h->s_chain, h->dv, h->fac, index, m, stage.p, m);
-    HIP_TRY(hipMemcpy2DAsync(U_out, (size_t)ld * sizeof(double), stage.p, (size_t)m * sizeof(double), (size_t)m * sizeof(double), m, hipMemcpyDeviceToHost, h->s_chain));
-    HIP_TRY(stream_wait(h->s_chain));
-    EKF_TRY(check_launch());
-    return m;
-}
-
-// ---- duplicate search -----------------------------------------------------------------------------
-// The scratch of ekf_find_duplicates (ekf_pairs.hip: DupScratch).  Boxes, counters and the split table are sized by the handle's
-// capacity and allocated once; the pair list holds `cap` pairs per filter and is replaced by a larger one when a call finds more
-// than it holds.  Both are counted in ekf_device_bytes, freed by ekf_destroy; ekf_reserve builds them again for the larger capacity.
-static int dup_reserve(ekf_batch *h, int cap) {
-    const EkfDev &dv = h->dv;
-    const size_t B = (size_t)dv.B;
-    if (!h->dup_base) {
-        const size_t nbox = B * (size_t)(dv.dn >> 5) * 4;
-        const size_t bytes = nbox * sizeof(double) + B * 3 * sizeof(int);
-        void *p = nullptr;
-        HIP_TRY(hipMalloc(&p, bytes));
-        hipError_t e = hipMemsetAsync(p, 0, bytes, h->s_chain);
-        if (e == hipSuccess) e = stream_wait(h->s_chain);
-        if (e != hipSuccess) {
-            hipFree(p);
-            return set_error(EKF_ERR_HIP, hipGetErrorString(e));
-        }
-        h->dup_base = p;
-        h->dup.box = (double *)p;
-        h->dup.cnt = (int *)(h->dup.box + nbox);
-        h->dup.split = h->dup.cnt + 2 * B;
-        h->device_bytes += bytes;
-    }
-    if (cap > h->dup.cap) {
-        void *p = nullptr;
-        HIP_TRY(hipMalloc(&p, B * (size_t)cap * sizeof(ekf_dup_pair)));
-        if (h->dup.list) {
-            hipFree(h->dup.list);
-            h->device_bytes -= B * (size_t)h->dup.cap * sizeof(ekf_dup_pair);
-        }
-        h->dup.list = (ekf_dup_pair *)p;
-        h->dup.cap = cap;
-        h->device_bytes += B * (size_t)cap * sizeof(ekf_dup_pair);
-    }
-    return EKF_OK;
-}
-
-static int dup_cap_for(long long pairs) {
-    long long cap = 256;
-    while (cap < pairs) cap *= 2;
-    return (int)cap;
-}
-
-// Filters [b0, b0 + nb): the rule of ekf_get_state (the streaming launch leaves, every deferred slot is folded, both streams idle),
-// then the settled state is only read: boxes (with a Euclidean bound), tiles, the counters back, the lists back.  A call that
-// finds more pairs than the device list holds and has to hand some out runs the two kernels once more with a list that fits (the
-// state has not moved: the same pairs).  The appended order is the hardware's; each filter's list is sorted by (i, j) here.
-static int dup_impl(ekf_batch *h, int b0, int nb, double gate, double max_dist, int split_one, const int *split, ekf_dup_pair *pairs_out, int max_pairs,
-                    int *n_found_out, int *n_degenerate_out) {
-    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
-    int n_max = 0, nt = 0;
-    for (int k = 0; k < nb; k++) {
-        const int n = h->h_int[b0 + k], sp = split ? split[k] : split_one;
-        if (sp < 0 || sp > n) {
-            char buf[160];
-            snprintf(buf, sizeof buf, "filter %d: split = %d is outside [0, %d landmarks]", b0 + k, sp, n);
-            return set_error(EKF_ERR_BAD_ARG, buf);
-        }
-        const int t = dup_tile_count(n, sp);
-        nt = t > nt ? t : nt;
-        n_max = n > n_max ? n : n_max;
-    }
-    EKF_TRY(settle(h));
-    EKF_TRY(dup_reserve(h, dup_cap_for(max_pairs < 4096 ? max_pairs : 4096)));  // (a call that finds more grows the list below)
-    const EkfDev &dv = h->dv;
-    hipStream_t s = h->s_chain;
-    DupArgs da;
-    da.gate = gate, da.md2 = max_dist > 0.0 ? max_dist * max_dist : -1.0, da.split_one = split_one, da.use_tab = split ? 1 : 0;
-    if (split) HIP_TRY(hipMemcpyAsync(h->dup.split + b0, split, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
-    std::vector<int> cnt((size_t)2 * nb, 0);
-    for (int round = 0; nt > 0; round++) {
-        const DupScratch ds = h->dup;
-        HIP_TRY(hipMemsetAsync(ds.cnt + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
-        if (da.md2 >= 0.0) hipLaunchKernelGGL(k_dup_boxes, dim3((unsigned)cdiv(lm_tiles(n_max), 64), (unsigned)nb), dim3(64), 0, s, dv, ds, b0);
-        hipLaunchKernelGGL(k_dup_tiles, dim3((unsigned)nt, (unsigned)nb), dim3(256), 0, s, dv, ds, da, h->buf_in, b0);
-        HIP_TRY(hipMemcpyAsync(cnt.data(), ds.cnt + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost, s));
-        HIP_TRY(stream_wait(s));
-        EKF_TRY(check_launch());
-        int most = 0;
-        for (int k = 0; k < nb; k++) most = cnt[2 * k] > most ? cnt[2 * k] : most;
-        if (most <= ds.cap || max_pairs == 0) break;
-        if (round > 0) return set_error(EKF_ERR_STATE, "the pair count changed between two passes over an unchanged state");
-        EKF_TRY(dup_reserve(h, dup_cap_for(most)));
-    }
-    std::vector<ekf_dup_pair> got;
-    std::vector<size_t> at((size_t)nb + 1, 0);
-    for (int k = 0; k < nb; k++) at[k + 1] = at[k] + (max_pairs > 0 ? (size_t)cnt[2 * k] : 0);
-    got.resize(at[nb]);
-    for (int k = 0; k < nb; k++)
-        if (at[k + 1] > at[k])
-            HIP_TRY(hipMemcpyAsync(got.data() + at[k], h->dup.list + (size_t)(b0 + k) * h->dup.cap, sizeof(ekf_dup_pair) * (at[k + 1] - at[k]), hipMemcpyDeviceToHost, s));
-    if (at[nb] > 0) HIP_TRY(stream_wait(s));
-    for (int k = 0; k < nb; k++) {
-        const int found = cnt[2 * k];
-        if (n_found_out) n_found_out[k] = found;
-        if (n_degenerate_out) n_degenerate_out[k] = cnt[2 * k + 1];
-        if (at[k + 1] == at[k]) continue;
-        std::sort(got.begin() + at[k], got.begin() + at[k + 1], [](const ekf_dup_pair &a, const ekf_dup_pair &b) { return a.i != b.i ? a.i < b.i : a.j < b.j; });
-        memcpy(pairs_out + (size_t)k * max_pairs, got.data() + at[k], sizeof(ekf_dup_pair) * (size_t)(found < max_pairs ? found : max_pairs));
-    }
-    return nb == 1 && !n_found_out ? cnt[0] : EKF_OK;
-}
-
-static bool dup_args_ok(double gate, double max_dist, const ekf_dup_pair *pairs_out, int max_pairs) {
-    return __builtin_isfinite(gate) && gate >= 0.0 && max_dist == max_dist && max_pairs >= 0 && (pairs_out || max_pairs == 0);
-}
-
-extern "C" int ekf_find_duplicates(ekf_handle h, int index, double gate, double max_dist, int split, ekf_dup_pair *pairs_out, int max_pairs,
-                                   int *n_degenerate_out) {
-    if (!h || index < 0 || index >= h->dv.B || split < 0 || !dup_args_ok(gate, max_dist, pairs_out, max_pairs)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    return dup_impl(h, index, 1, gate, max_dist, split, nullptr, pairs_out, max_pairs, nullptr, n_degenerate_out);
-}
-
-extern "C" int ekf_batch_find_duplicates(ekf_handle h, double gate, double max_dist, const int *split, ekf_dup_pair *pairs_out, int max_pairs, int *n_found_out,
-                                         int *n_degenerate_out) {
-    if (!h || !n_found_out || !dup_args_ok(gate, max_dist, pairs_out, max_pairs)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    return dup_impl(h, 0, h->dv.B, gate, max_dist, 0, split, pairs_out, max_pairs, n_found_out, n_degenerate_out);
-}
-
-// ---- landmark fusion ------------------------------------------------------------------------------
-// The scratch of ekf_fuse_landmarks (ekf_fuse.hip: FuseScratch), sized by the handle's capacity (a landmark is in at most one pair
-// of a call: Ncap / 2 pairs per filter): one allocation at the first call, counted in ekf_device_bytes, freed by ekf_destroy;
-// ekf_reserve builds the larger one.
-static int fuse_reserve(ekf_batch *h) {
-    if (h->fuse_base) return EKF_OK;
-    const EkfDev &dv = h->dv;
-    const size_t B = (size_t)dv.B;
-    const int pcap = dv.Ncap / 2 + 1;
-    const size_t nwr = B * 4 * FUSE_MAX_COLS, nU = B * FUSE_MAX_COLS * FUSE_MAX_COLS, nint = B * ((size_t)pcap * 2 + 4);
-    const size_t bytes = (nwr + nU) * sizeof(double) + nint * sizeof(int);
-    void *p = nullptr;
-    HIP_TRY(hipMalloc(&p, bytes));
-    hipError_t e = hipMemsetAsync(p, 0, bytes, h->s_chain);
-    if (e == hipSuccess) e = stream_wait(h->s_chain);
-    if (e != hipSuccess) {
-        hipFree(p);
-        return set_error(EKF_ERR_HIP, hipGetErrorString(e));
-    }
-    h->fuse_base = p;
-    h->fuse.wr = (double *)p;
-    h->fuse.U = h->fuse.wr + nwr;
-    h->fuse.pairs = (int *)(h->fuse.U + nU);
-    h->fuse.cnt = h->fuse.pairs + B * (size_t)pcap * 2;
-    h->fuse.done = h->fuse.cnt + B;
-    h->fuse.m_round = h->fuse.done + 2 * B;
-    h->fuse.pcap = pcap;
-    h->device_bytes += bytes;
-    return EKF_OK;
-}
-
-// Filters [b0, b0 + nb), filter b0 + k with n_pairs[k] pairs at pairs + k * ld_pairs.  The list is checked against the mirror's
-// landmark counts before anything else happens to the handle; a call without a pair returns there.  Then: settle, the pair table
-// up, rounds of at most ekf_window() pairs (ekf_fuse.hip; one dense pass each, in place in the settled buffer in either pipeline
-// mode, also on handles whose chain kernel folds its own windows), the progress record back, and the removal of the fused pairs'
-// j through remove_settled, which ends the rewrite.  Nothing fused anywhere: the rewrite is ended here (slot rows cleared, the
-// pass sizes restored).
-static int fuse_impl(ekf_batch *h, int b0, int nb, const ekf_dup_pair *pairs, int ld_pairs, const int *n_pairs, double slack, int *n_fused_out, int *n_lm_out) {
-    HIP_TRY(hipSetDevice(h->device));
-    EKF_TRY(refresh_bounds(h, false));
-    int most = 0;
-    std::vector<unsigned char> seen;
-    for (int k = 0; k < nb; k++) {
-        const int N = h->h_int[b0 + k], np = n_pairs[k];
-        if (np < 0 || (np > 0 && (!pairs || np > ld_pairs))) return set_error(EKF_ERR_BAD_ARG, "bad pair count or list");
-        seen.assign((size_t)(N > 0 ? N : 1), 0);
-        for (int q = 0; q < np; q++) {
-            const ekf_dup_pair &pr = pairs[(size_t)k * ld_pairs + q];
-            char buf[200];
-            if (!(0 <= pr.i && pr.i < pr.j && pr.j < N)) {
-                snprintf(buf, sizeof buf, "filter %d, pair %d: (%d, %d) does not name two landmarks i < j of %d", b0 + k, q, pr.i, pr.j, N);
-                return set_error(EKF_ERR_BAD_ARG, buf);
-            }
-            if (seen[pr.i] || seen[pr.j]) {
-                snprintf(buf, sizeof buf, "filter %d, pair %d: landmark %d is in another pair of the call", b0 + k, q, seen[pr.i] ? pr.i : pr.j);
-                return set_error(EKF_ERR_BAD_ARG, buf);
-            }
-            seen[pr.i] = seen[pr.j] = 1;
-        }
-        most = np > most ? np : most;
-    }
-    if (most == 0) {  // nothing to do: the window stays open
-        for (int k = 0; k < nb; k++) {
-            if (n_fused_out) n_fused_out[k] = 0;
-            if (n_lm_out) n_lm_out[k] = h->h_int[b0 + k];
-        }
-        return nb == 1 && !n_lm_out ? h->h_int[b0] : EKF_OK;
-    }
-    // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
-    // every deferred slot folded, both streams idle
-    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
-    EKF_TRY(fuse_reserve(h));
-    EkfDev &dv = h->dv;
-    const FuseScratch fs = h->fuse;
-    hipStream_t s = h->s_chain;
-    int n_max = 0;
-    std::vector<int> tab((size_t)nb * fs.pcap * 2, 0), cnt(n_pairs, n_pairs + nb);
-    for (int k = 0; k < nb; k++) {
-        n_max = h->h_int[b0 + k] > n_max ? h->h_int[b0 + k] : n_max;
-        if (cnt[k] > fs.pcap) return set_error(EKF_ERR_STATE, "more pairs than the pair table holds");  // (each landmark once: cannot happen)
-        for (int q = 0; q < cnt[k]; q++) {
-            tab[((size_t)k * fs.pcap + q) * 2] = pairs[(size_t)k * ld_pairs + q].i;
-            tab[((size_t)k * fs.pcap + q) * 2 + 1] = pairs[(size_t)k * ld_pairs + q].j;
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(fs.pairs + (size_t)b0 * fs.pcap * 2, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(fs.cnt + b0, cnt.data(), sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(fs.done + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
-    HIP_TRY(hipMemsetAsync(fs.m_round + b0, 0, sizeof(int) * (size_t)nb, s));
-    const int nT = lm_tiles(n_max);
-    for (int round = 0; round * dv.maxp < most; round++) {
-        const int m_hi = most - round * dv.maxp < dv.maxp ? most - round * dv.maxp : dv.maxp;
-        hipLaunchKernelGGL(k_fuse_gather, dim3((unsigned)cdiv(n_max, 256), (unsigned)m_hi, (unsigned)nb), dim3(256), 0, s, dv, fs, h->buf_in, round, b0);
-        hipLaunchKernelGGL(k_fuse_factor, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, round, slack, b0);
-        hipLaunchKernelGGL(k_fuse_apply, dim3((unsigned)cdiv(64 * nT, 256), (unsigned)nb), dim3(256), 0, s, dv, fs, b0);
-        hipLaunchKernelGGL(k_fuse_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0);
-        launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->buf_in, h->buf_in, nullptr, /*rev*/ 0, b0, nb);
-    }
-    std::vector<int> done((size_t)2 * nb, 0);
-    HIP_TRY(hipMemcpyAsync(done.data(), fs.done + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost, s));
-    HIP_TRY(stream_wait(s));
-    EKF_TRY(check_launch());
-    // the fused pairs' j go, exactly as ekf_remove_landmarks with keep[j] = 0 removes them
-    const int ld_keep = n_max > 0 ? n_max : 1;
-    std::vector<unsigned char> keep((size_t)dv.B * ld_keep, 1);
-    bool any = false;
-    for (int k = 0; k < nb; k++) {
-        const int fused = done[2 * k];
-        if (n_fused_out) n_fused_out[k] = fused;
-        for (int q = 0; q < fused; q++) keep[(size_t)(b0 + k) * ld_keep + pairs[(size_t)k * ld_pairs + q].j] = 0;
-        any = any || fused > 0;
-    }
-    if (any) {
-        std::vector<int> n_new((size_t)dv.B, 0);
-        EKF_TRY(remove_settled(h, keep.data(), ld_keep, -1, n_new.data()));
-        for (int k = 0; k < nb; k++)
-            if (n_lm_out) n_lm_out[k] = n_new[b0 + k];
-        return nb == 1 && !n_lm_out ? n_new[b0] : EKF_OK;
-    }
-    EKF_TRY(finish_rewrite(h, b0, nb, /*rearm*/ true, &h->h_int[b0], 1, /*flip_buf*/ false));
-    for (int k = 0; k < nb; k++)
-        if (n_lm_out) n_lm_out[k] = h->h_int[b0 + k];
-    return nb == 1 && !n_lm_out ? h->h_int[b0] : EKF_OK;
-}
-
-extern "C" int ekf_fuse_landmarks(ekf_handle h, int index, const ekf_dup_pair *pairs, int n_pairs, double slack, int *n_fused_out) {
-    if (!h || index < 0 || index >= h->dv.B || n_pairs < 0 || (n_pairs > 0 && !pairs) || !(__builtin_isfinite(slack) && slack >= 0.0))
-        return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    return fuse_impl(h, index, 1, pairs, n_pairs, &n_pairs, slack, n_fused_out, nullptr);
-}
-
-extern "C" int ekf_batch_fuse_landmarks(ekf_handle h, const ekf_dup_pair *pairs, int ld_pairs, const int *n_pairs, double slack, int *n_fused_out,
-                                        int *n_landmarks_out) {
-    if (!h || !n_pairs || ld_pairs < 0 || !n_landmarks_out || !(__builtin_isfinite(slack) && slack >= 0.0)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    return fuse_impl(h, 0, h->dv.B, pairs, ld_pairs, n_pairs, slack, n_fused_out, n_landmarks_out);
-}
-
-extern "C" int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max) {
-    if (!h || index < 0 || index >= h->dv.B || n_max < 0 || (!cov_out && n_max > 0)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    EKF_TRY(refresh_bounds(h));  // the chain stream idle (a resident streaming launch leaves first); no pass, the flush stream untouched
-    const int N = h->h_int[index];
-    const int cnt = N < n_max ? N : n_max;
-    if (cnt == 0) return N;
-    std::vector<double> comp((size_t)3 * cnt);  // the three components of the always-current diagonal blocks
-    HIP_TRY(hipMemcpy2DAsync(comp.data(), (size_t)cnt * sizeof(double), h->dv.D + (size_t)index * 3 * h->dv.dn, (size_t)h->dv.dn * sizeof(double),
-                             (size_t)cnt * sizeof(double), 3, hipMemcpyDeviceToHost, h->s_chain));
-    HIP_TRY(stream_wait(h->s_chain));
-    for (int l = 0; l < cnt; l++)
-        for (int c = 0; c < 3; c++) cov_out[3 * l + c] = comp[(size_t)c * cnt + l];
-    return N;
-}
+#include "ekf_map_api.hip"
 
 // ---- scripts --------------------------------------------------------------------------------------
 static inline int ops_per_step(const ekf_batch *h) { return 1 + h->script_M + (h->script_has_truth ? 1 : 0); }

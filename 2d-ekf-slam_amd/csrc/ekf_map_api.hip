@@ -1,0 +1,596 @@
+// ekf_map_api.hip -- host side of the map operations of include/ekfslam_c.h: removal, frame change and anchoring, joining, extraction
+// and ekf_get_submap, joint consistency, duplicate search, fusion, ekf_get_landmark_covs.  Included by ekf_api.hip (one translation
+// unit: ekf_batch, HIP_TRY / EKF_TRY, quiesce, finish_rewrite, DevTmp and the kept scratch blocks are that file's).  Every entry point
+// runs once per call on a handle it brings to rest and reads: check, quiesce, plan, upload, launch, finish.  The checks of the
+// caller's lists and the tables the kernels read are pure code in ekf_map_plan.h; the order of those checks relative to quiescing is
+// the table above quiesce().
+
+// The filters of a call, [b0, b0 + nb) of a handle: one filter, or (index < 0) the whole batch; and their landmark counts (h_int[]).
+struct Filters {
+    int b0, nb;
+};
+static Filters filters_of(const ekf_batch *h, int index) { return index < 0 ? Filters{0, h->dv.B} : Filters{index, 1}; }
+static const int *counts_of(const ekf_batch *h, int b0) { return h->h_int.data() + b0; }
+
+// A block of device scratch for the handle to keep (DevBlock), optionally zeroed on the chain stream and waited for; a failure
+// leaves *blk as it was.  A block that *blk held goes once the new one exists.
+static void block_release(ekf_batch *h, DevBlock *blk) {
+    if (!blk->p) return;
+    hipFree(blk->p);
+    h->device_bytes -= blk->bytes;
+    *blk = DevBlock();
+}
+static int block_alloc(ekf_batch *h, DevBlock *blk, size_t bytes, bool zero) {
+    void *p = nullptr;
+    HIP_TRY(hipMalloc(&p, bytes));
+    hipError_t e = zero ? hipMemsetAsync(p, 0, bytes, h->s_chain) : hipSuccess;
+    if (zero && e == hipSuccess) e = stream_wait(h->s_chain);
+    if (e != hipSuccess) {
+        hipFree(p);
+        return set_error(EKF_ERR_HIP, "%s", hipGetErrorString(e));
+    }
+    block_release(h, blk);
+    blk->p = p, blk->bytes = bytes;
+    h->device_bytes += bytes;
+    return EKF_OK;
+}
+
+// ---- map management -------------------------------------------------------------------------------
+// Marginalise landmarks out on the device: gather by destination over the tile layout (k_rm_gather), in overlap mode into the other Bm
+// buffer (then flipped, as settle() does behind a pass; the buffer read is cleared), in place through a transient scratch copied back
+// (k_rm_finish); x, R, D compacted by k_rm_vec.  Every buffer ends as ekf_set_state of the reduced state would leave it; the buffer
+// addresses do not change (captured graphs and streaming launches hold EkfDev by value).
+// The removal itself, on a handle that quiesce(QUIET_SETTLED) has brought to rest (h_int[] current): remove_impl, and the end of
+// ekf_fuse_landmarks behind its own kernels on the chain stream.  Filter f.b0 + k has the mask keep + k * ld_keep; its new count
+// goes to n_out[k] (n_out may be null).
+static int remove_settled(ekf_batch *h, Filters f, const unsigned char *keep, int ld_keep, int *n_out) {
+    EkfDev &dv = h->dv;
+    const int B = dv.B, mstride = dv.Ncap > 0 ? dv.Ncap : 1;
+    const RemovalPlan pl = plan_removal(counts_of(h, 0), B, mstride, keep, ld_keep, f.b0, f.nb);
+    for (int k = 0; n_out && k < f.nb; k++) n_out[k] = pl.n_new(f.b0 + k);
+    if (!pl.any) return EKF_OK;
+    const int nTo = pl.nTo, nTn = pl.nTn;
+    hipStream_t s = h->s_chain;
+    DevTmp<int> rm_d;
+    DevTmp<double> scratch;
+    const size_t scratch_stride = (size_t)nTn * (nTn + 1) / 2 * 4096;
+    if (!h->overlap && scratch_stride) HIP_TRY(scratch.alloc((size_t)B * scratch_stride));
+    HIP_TRY(rm_d.upload(pl.rm.data(), pl.rm.size(), s));
+    if (nTo > 0) {
+        const dim3 grid((unsigned)(nTo * (nTo + 1) / 2), (unsigned)B);
+        if (h->overlap) {
+            hipLaunchKernelGGL(k_rm_gather, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, mstride, nTo, dv.Bm[h->buf_in ^ 1], dv.T, dv.bm_stride, 0);
+            hipLaunchKernelGGL(k_rm_finish, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, nTo, (const double *)nullptr, 0, (size_t)0);
+        } else {
+            if (scratch.p)
+                hipLaunchKernelGGL(k_rm_gather, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, mstride, nTo, scratch.p, nTn, scratch_stride, 1);
+            hipLaunchKernelGGL(k_rm_finish, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, nTo, (const double *)scratch.p, nTn, scratch_stride);
+        }
+    }
+    // D is read by the gather (landmarks' own blocks): compacted behind it
+    hipLaunchKernelGGL(k_rm_vec, dim3(7, B), dim3(1024), 0, s, dv, (const int *)rm_d.p, mstride);
+    return finish_rewrite(h, 0, B, /*rearm*/ true, &pl.rm[1], 2, /*flip_buf: the gather's output*/ h->overlap && nTo > 0);
+}
+
+static int remove_impl(ekf_batch *h, Filters f, const unsigned char *keep, int ld_keep, int *n_out) {
+    // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
+    // every deferred slot folded, both streams idle
+    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
+    return remove_settled(h, f, keep, ld_keep, n_out);
+}
+
+extern "C" int ekf_remove_landmarks(ekf_handle h, int index, const unsigned char *keep, int count) {
+    if (!filter_ok(h, index) || !keep || count < 0) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    int n;
+    EKF_TRY(remove_impl(h, filters_of(h, index), keep, count, &n));
+    return n;
+}
+
+extern "C" int ekf_batch_remove_landmarks(ekf_handle h, const unsigned char *keep, int ld_keep, int *n_out) {
+    if (!h || !keep || ld_keep < 0) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return remove_impl(h, filters_of(h, -1), keep, ld_keep, n_out);
+}
+
+// The per-filter argument of a rewrite launch over nb filters (ekf_rewrite.hip: arg_value), vals = [nb][doubles of A]: a one-filter
+// call carries it in the kernel arguments (*one), a batch call in a transient table (copied synchronously: vals may leave scope).
+template <typename A>
+static int rewrite_arg(const std::vector<double> &vals, int nb, A *one, DevTmp<double> *tab) {
+    if (nb == 1) memcpy(one, vals.data(), sizeof(A));
+    else HIP_TRY(tab->upload(vals.data(), vals.size(), nullptr, /*async*/ false));
+    return EKF_OK;
+}
+
+// Frame changes on the device (ekf_rewrite.hip: k_reframe_vec, k_reframe_tiles, k_reframe_finish), the order of steps as in
+// remove_impl.  frames == nullptr: anchor at the robot; else one (t_x, t_y, theta) per filter of the launch, one launch sequence
+// with the grid over the filters.  Bm is rewritten in place in the settled buffer (either pipeline
+// mode: no second buffer, no scratch); the only transient allocation is the BATCH rigid call's frame table (48 bytes per filter; a
+// one-filter call carries its frame in the kernel arguments); the anchor's per-row operands use slot set 0 of FA / FB, which are
+// cleared afterwards as a removal clears them.
+static int reframe_impl(ekf_batch *h, Filters f, const double *frames) {
+    // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
+    // every deferred slot folded, both streams idle
+    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
+    EkfDev &dv = h->dv;
+    const int b_off = f.b0, nb = f.nb, nT = lm_tiles(most_landmarks(counts_of(h, b_off), nb));
+    hipStream_t s = h->s_chain;
+    DevTmp<double> fr_d;
+    ReframeFrame one = {{0.0, 0.0, 1.0, 0.0, 0.0, 0.0}};
+    if (frames) {
+        std::vector<double> fr((size_t)nb * 6, 0.0);
+        for (int k = 0; k < nb; k++) {
+            const double *fk = frames + 3 * (size_t)k;
+            fr[6 * k] = fk[0], fr[6 * k + 1] = fk[1], fr[6 * k + 2] = cos(fk[2]), fr[6 * k + 3] = sin(fk[2]), fr[6 * k + 4] = fk[2];
+        }
+        EKF_TRY(rewrite_arg(fr, nb, &one, &fr_d));
+    }
+    const double *frc = fr_d.p;
+    const auto k_vec = frames ? k_reframe_vec<false> : k_reframe_vec<true>;  // <ANCHOR>
+    const auto k_tiles = frames ? k_reframe_tiles<false> : k_reframe_tiles<true>;
+    const auto k_finish = frames ? k_reframe_finish<false> : k_reframe_finish<true>;
+    if (nT > 0) {
+        const dim3 gv((unsigned)cdiv(32 * nT, 256), (unsigned)nb), gt((unsigned)(nT * (nT + 1) / 2), (unsigned)nb);
+        hipLaunchKernelGGL(k_vec, gv, dim3(256), 0, s, dv, one, frc, b_off);
+        hipLaunchKernelGGL(k_tiles, gt, dim3(256), 0, s, dv, h->buf_in, one, frc, b_off, nT);
+    }
+    hipLaunchKernelGGL(k_finish, dim3(nb), dim3(64), 0, s, dv, one, frc, b_off);
+    return finish_rewrite(h, b_off, nb, /*rearm*/ true, nullptr, 0, /*flip_buf*/ false);
+}
+
+static bool finite3(const double *f) { return __builtin_isfinite(f[0]) && __builtin_isfinite(f[1]) && __builtin_isfinite(f[2]); }
+
+extern "C" int ekf_transform_frame(ekf_handle h, int index, const double frame[3]) {
+    if (!filter_ok(h, index) || !frame || !finite3(frame)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return reframe_impl(h, filters_of(h, index), frame);
+}
+
+extern "C" int ekf_batch_transform_frame(ekf_handle h, const double *frames) {
+    if (!h || !frames) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    for (int b = 0; b < h->dv.B; b++)
+        if (!finite3(frames + 3 * (size_t)b)) return set_error(EKF_ERR_BAD_ARG, "a frame is not finite");
+    return reframe_impl(h, filters_of(h, -1), frames);
+}
+
+extern "C" int ekf_anchor_at_robot(ekf_handle h, int index) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return reframe_impl(h, filters_of(h, index), nullptr);
+}
+
+extern "C" int ekf_batch_anchor_at_robot(ekf_handle h) {
+    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
+    return reframe_impl(h, filters_of(h, -1), nullptr);
+}
+
+// What the join and extraction kernels read of a source handle at rest.
+static JoinSrc join_src_of(const ekf_batch *s) {
+    const EkfDev &sd = s->dv;
+    return {sd.x, sd.R, sd.D, sd.Bm[s->buf_in], sd.n_lm, sd.xs, sd.dn, sd.T, sd.bm_stride};
+}
+
+// Map joining on the device (ekf_rewrite.hip: k_join_tiles, k_join_vec, k_join_finish): filter bs0 + k of `s` into filter
+// fd.b0 + k of `d`.  Both handles are brought to rest first (the source is only read afterwards, so its own quiescing is all
+// that ever happens to it), which also orders their streams: everything runs on the destination's chain stream while the source's
+// streams are idle, and the call waits for it.  Bm is rewritten in place in the destination's settled buffer in either pipeline
+// mode; the only transient allocation is the batch form's table of cos / sin (16 bytes per filter).
+static int join_impl(ekf_batch *d, Filters fd, ekf_batch *s, int bs0) {
+    EKF_TRY(quiesce(s, QUIET_SETTLED, ST_INVALID_OR_FULL));
+    if (d != s) EKF_TRY(quiesce(d, QUIET_SETTLED, ST_INVALID_OR_FULL));
+    EkfDev &dv = d->dv;
+    const int bd0 = fd.b0, nb = fd.nb;
+    int nt = 0, nv = 0;
+    for (int k = 0; k < nb; k++) {
+        const int Ng = d->h_int[bd0 + k], Ns = s->h_int[bs0 + k];
+        if (Ng + Ns > dv.Ncap) return set_error(plan_no_room(bd0 + k, Ng, Ns, dv.Ncap, "join"));
+        nt = std::max(nt, join_tile_count(Ng, Ns));
+        nv = std::max(nv, Ng + Ns);
+    }
+    DevTmp<double> rot_d;
+    Rot2 one = {1.0, 0.0};
+    // (the host mirror's heading is the device's x[2] bit for bit once the chain stream is idle: every writer of x[0..2] -- the chain
+    // kernels, k_set_meta, the finish kernels -- copies the pose into the mirror; a dense pass does not touch it)
+    std::vector<double> rot((size_t)nb * 2);
+    for (int k = 0; k < nb; k++) rot[2 * k] = cos(d->mirror_h[bd0 + k].pose[2]), rot[2 * k + 1] = sin(d->mirror_h[bd0 + k].pose[2]);
+    EKF_TRY(rewrite_arg(rot, nb, &one, &rot_d));
+    const JoinSrc sv = join_src_of(s);
+    const double *rotc = rot_d.p;
+    hipStream_t st = d->s_chain;
+    if (nt > 0) hipLaunchKernelGGL(k_join_tiles, dim3((unsigned)nt, (unsigned)nb), dim3(256), 0, st, dv, d->buf_in, sv, one, rotc, bd0, bs0);
+    if (nv > 0) hipLaunchKernelGGL(k_join_vec, dim3((unsigned)cdiv(nv, 256), (unsigned)nb), dim3(256), 0, st, dv, d->buf_in, sv, one, rotc, bd0, bs0);
+    hipLaunchKernelGGL(k_join_finish, dim3(nb), dim3(64), 0, st, dv, sv, one, rotc, bd0, bs0);
+    return finish_rewrite(d, bd0, nb, /*rearm*/ true, nullptr, 0, /*flip_buf*/ false);
+}
+
+extern "C" int ekf_join_map(ekf_handle dst, int dst_index, ekf_handle src, int src_index) {
+    if (!filter_ok(dst, dst_index) || !filter_ok(src, src_index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    if (dst == src && dst_index == src_index) return set_error(EKF_ERR_BAD_ARG, "a filter cannot be joined to itself");
+    if (dst->device != src->device) return set_error(EKF_ERR_BAD_ARG, "the two handles live on different devices");
+    EKF_TRY(join_impl(dst, filters_of(dst, dst_index), src, src_index));
+    return dst->h_int[dst_index];
+}
+
+extern "C" int ekf_batch_join_map(ekf_handle dst, ekf_handle src) {
+    if (!dst || !src || dst == src) return set_error(EKF_ERR_BAD_ARG, "bad argument (two different handles)");
+    if (dst->dv.B != src->dv.B) return set_error(EKF_ERR_BAD_ARG, "the two handles have different batch sizes");
+    if (dst->device != src->device) return set_error(EKF_ERR_BAD_ARG, "the two handles live on different devices");
+    return join_impl(dst, filters_of(dst, -1), src, 0);
+}
+
+// ---- submap extraction ----------------------------------------------------------------------------
+// Submap extraction on the device (ekf_extract.hip: k_ext_tiles, k_ext_vec): filter bs0 + k of `s` into filter fd.b0 + k of `d`,
+// its new count to n_out[k].  ids == nullptr: every landmark of the source in order; else filter k's list is ids + k * ld_ids with
+// count[k] entries, checked on the host before any handle is touched (every id non-negative, no id twice) and against the source's
+// landmark count once the source is at rest.
+// The source comes to rest first and is only read afterwards (sticky EKF_ERR_TIMEOUT ends the call; a sticky EKF_ERR_CAPACITY does
+// not: the state is valid); the destination is then treated as ekf_set_state treats it, except that only the tiles and vector
+// entries up to the larger of its previous and its new map are written -- everything behind them is zeros already.  Everything runs
+// on the destination's chain stream while the source's streams are idle, and the call waits for it.  The only transient allocation
+// is the id table (4 bytes per extracted landmark).
+static int extract_impl(ekf_batch *d, Filters fd, ekf_batch *s, int bs0, const int *ids, int ld_ids, const int *count, int *n_out) {
+    const int bd0 = fd.b0, nb = fd.nb;
+    EKF_TRY(set_error(plan_extract_lists(ids, ld_ids, count, bs0, nb)));
+    EKF_TRY(quiesce(s, QUIET_STREAM, ST_INVALID));
+    int mstride;
+    EKF_TRY(set_error(plan_extract_range(ids, ld_ids, count, counts_of(s, bs0), bs0, nb, &mstride)));
+    EKF_TRY(settle(s));
+    EkfDev &dv = d->dv;
+    std::vector<int> ex;
+    EKF_TRY(set_error(plan_extract_table(ids, ld_ids, count, counts_of(s, bs0), bd0, nb, mstride, dv.Ncap, &ex)));
+    if (d != s) EKF_TRY(quiesce(d, QUIET_SETTLED, ST_NONE));
+    {
+        // the destination's previous maps: what has to be overwritten.  A timed-out filter's count is not to be trusted: all of it.
+        const int rc = refresh_bounds(d);
+        if (rc && rc != EKF_ERR_TIMEOUT) return rc;
+    }
+    std::vector<int> n_dst((size_t)nb);
+    for (int k = 0; k < nb; k++) n_dst[k] = d->mirror_h[bd0 + k].status == EKF_ERR_TIMEOUT ? -1 : d->h_int[bd0 + k];
+    const int nT = lm_tiles(plan_extract_old_counts(&ex, n_dst.data(), nb, dv.Ncap));
+    hipStream_t st = d->s_chain;
+    EKF_TRY(restart_waits(d));
+    DevTmp<int> ex_d;
+    HIP_TRY(ex_d.upload(ex.data(), ex.size(), st));
+    const JoinSrc sv = join_src_of(s);
+    double *other = d->overlap ? dv.Bm[d->buf_in ^ 1] : nullptr;
+    if (nT > 0)
+        hipLaunchKernelGGL(k_ext_tiles, dim3((unsigned)(nT * (nT + 1) / 2), (unsigned)nb), dim3(256), 0, st, dv, d->buf_in, other, sv, (const int *)ex_d.p, mstride, nb, nT, bd0,
+                           bs0);
+    hipLaunchKernelGGL(k_ext_vec, dim3(7, (unsigned)nb), dim3(1024), 0, st, dv, sv, (const int *)ex_d.p, mstride, nb, bd0, bs0);
+    EKF_TRY(finish_rewrite(d, bd0, nb, /*rearm*/ true, &ex[1], 2, /*flip_buf*/ false));
+    for (int k = 0; n_out && k < nb; k++) n_out[k] = ex[2 * k + 1];
+    return EKF_OK;
+}
+
+extern "C" int ekf_extract_map(ekf_handle dst, int dst_index, ekf_handle src, int src_index, const int *ids, int count) {
+    if (!filter_ok(dst, dst_index) || !filter_ok(src, src_index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    if (ids && count < 0) return set_error(EKF_ERR_BAD_ARG, "negative landmark count");
+    if (dst == src && dst_index == src_index) return set_error(EKF_ERR_BAD_ARG, "a filter cannot be extracted into itself");
+    if (dst->device != src->device) return set_error(EKF_ERR_BAD_ARG, "the two handles live on different devices");
+    int n;
+    EKF_TRY(extract_impl(dst, filters_of(dst, dst_index), src, src_index, ids, count, &count, &n));
+    return n;
+}
+
+extern "C" int ekf_batch_extract_map(ekf_handle dst, ekf_handle src, const int *ids, int ld_ids, const int *count, int *n_out) {
+    if (!dst || !src || dst == src) return set_error(EKF_ERR_BAD_ARG, "bad argument (two different handles)");
+    if (dst->dv.B != src->dv.B) return set_error(EKF_ERR_BAD_ARG, "the two handles have different batch sizes");
+    if (dst->device != src->device) return set_error(EKF_ERR_BAD_ARG, "the two handles live on different devices");
+    if (ids && (!count || ld_ids < 0)) return set_error(EKF_ERR_BAD_ARG, "a list of ids needs its counts");
+    return extract_impl(dst, filters_of(dst, -1), src, 0, ids, ld_ids, count, n_out);
+}
+
+// The same marginal to the host: ekf_get_state's rule (the streaming launch leaves; the size alone folds nothing), then the device
+// gathers straight into a transient dense staging matrix of (3 + 2 count)^2 and one copy follows.  The filter is only read.
+extern "C" int ekf_get_submap(ekf_handle h, int index, const int *ids, int count, double *x_out, double *P_out, int ld) {
+    if (!filter_ok(h, index) || count < 0 || (count > 0 && !ids)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    EKF_TRY(set_error(plan_ids_distinct(ids, count, index)));
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
+    EKF_TRY(set_error(plan_ids_in_range(ids, count, h->h_int[index], index)));
+    const int n = 3 + 2 * count;
+    if (!x_out && !P_out) return n;  // (the size alone: nothing is folded)
+    if (!x_out || !P_out || ld < n) return set_error(EKF_ERR_BAD_ARG, "bad output buffers");
+    EKF_TRY(settle(h));
+    hipStream_t s = h->s_chain;
+    DevTmp<double> stage;  // transient staging: dense n x n + x
+    DevTmp<int> ids_d;
+    HIP_TRY(stage.alloc((size_t)n * n + n));
+    HIP_TRY(ids_d.upload(ids, (size_t)count, s));
+    hipLaunchKernelGGL(k_ext_dense, dim3((unsigned)cdiv(n, 256), (unsigned)n), dim3(256), 0, s, join_src_of(h), index, (const int *)ids_d.p, count, stage.p + (size_t)n * n,
+                       stage.p, n, n);
+    EKF_TRY(read_back_dense(h, stage.p, n, x_out, P_out, ld));
+    EKF_TRY(check_launch());
+    return n;
+}
+
+// ---- map assessment -------------------------------------------------------------------------------
+// The scratch of ekf_joint_consistency (ekf_factor.hip: FactorScratch), sized by the handle's capacity: one block at the first
+// call; ekf_reserve builds the larger one.
+static int factor_reserve(ekf_batch *h) {
+    DevBlock &blk = h->kept[BLK_FACTOR];
+    if (blk.p) return EKF_OK;
+    const EkfDev &dv = h->dv;
+    const size_t B = (size_t)dv.B;
+    const size_t nS = B * dv.bm_stride, nrhs = B * (size_t)dv.rows * 4, nacc = B * FAC_ACC, nxt = B * (size_t)dv.xs;
+    EKF_TRY(block_alloc(h, &blk, (nS + nrhs + nacc + nxt) * sizeof(double) + B * sizeof(ekf_joint), /*zero*/ true));
+    h->fac.S = (double *)blk.p;
+    h->fac.rhs = h->fac.S + nS;
+    h->fac.acc = h->fac.rhs + nrhs;
+    h->fac.xt = h->fac.acc + nacc;
+    h->fac.out = (ekf_joint *)(h->fac.xt + nxt);
+    h->fac_stamp[0] = -1;
+    return EKF_OK;
+}
+
+// The filters f: the rule of ekf_get_state (the streaming launch leaves, every deferred slot is folded, both streams idle),
+// then the settled state is only read: stage, 3 launches per tile step with the grid over the filters, finish, one copy back.
+static int joint_impl(ekf_batch *h, Filters f, const double *x_true, int ld_true, ekf_joint *out) {
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
+    const int b0 = f.b0, nb = f.nb, n_max = most_landmarks(counts_of(h, b0), nb);
+    if (x_true && ld_true < 3 + 2 * n_max) return set_error(EKF_ERR_BAD_ARG, "x_true rows are shorter than the largest state of the call");
+    EKF_TRY(settle(h));
+    EKF_TRY(factor_reserve(h));
+    const EkfDev &dv = h->dv;
+    const FactorScratch fs = h->fac;
+    hipStream_t s = h->s_chain;
+    const int have_truth = x_true ? 1 : 0;
+    if (x_true)
+        HIP_TRY(hipMemcpy2DAsync(fs.xt + (size_t)b0 * dv.xs, (size_t)dv.xs * sizeof(double), x_true, (size_t)ld_true * sizeof(double),
+                                 (size_t)(3 + 2 * n_max) * sizeof(double), nb, hipMemcpyHostToDevice, s));
+    const int nT = lm_tiles(n_max);
+    if (nT > 0) hipLaunchKernelGGL(k_chol_stage, dim3((unsigned)(nT * (nT + 1) / 2), (unsigned)nb), dim3(256), 0, s, dv, fs, h->buf_in, b0, nT, have_truth);
+    for (int k = 0; k < nT; k++) {
+        hipLaunchKernelGGL(k_chol_diag, dim3((unsigned)nb), dim3(320), 0, s, dv, fs, k, b0);
+        if (k + 1 < nT) {
+            hipLaunchKernelGGL(k_chol_panel, dim3((unsigned)(nT - 1 - k), (unsigned)nb), dim3(64), 0, s, dv, fs, k, b0);
+            hipLaunchKernelGGL(k_chol_trail, dim3((unsigned)chol_trail_count(nT, k), (unsigned)nb), dim3(256), 0, s, dv, fs, k, b0, nT);
+        }
+    }
+    hipLaunchKernelGGL(k_chol_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0, have_truth);
+    HIP_TRY(hipMemcpyAsync(out, fs.out + b0, sizeof(ekf_joint) * (size_t)nb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));
+    EKF_TRY(check_launch());
+    h->fac_stamp[0] = h->chain_seq, h->fac_stamp[1] = h->stream_ops, h->fac_stamp[2] = h->state_edits;
+    h->fac_b0 = b0;
+    h->fac_n.assign(h->h_int.begin() + b0, h->h_int.begin() + b0 + nb);
+    return EKF_OK;
+}
+
+extern "C" int ekf_joint_consistency(ekf_handle h, int index, const double *x_true, ekf_joint *out) {
+    if (!filter_ok(h, index) || !out) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return joint_impl(h, filters_of(h, index), x_true, x_true ? 3 + 2 * h->dv.Ncap : 0, out);
+}
+
+extern "C" int ekf_batch_joint_consistency(ekf_handle h, const double *x_true, int ld_true, ekf_joint *out) {
+    if (!h || !out || (x_true && ld_true < 3)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return joint_impl(h, filters_of(h, -1), x_true, ld_true, out);
+}
+
+extern "C" int ekf_debug_joint_factor(ekf_handle h, int index, double *U_out, int ld) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    const bool current = h->kept[BLK_FACTOR].p && h->fac_stamp[0] == h->chain_seq && h->fac_stamp[1] == h->stream_ops && h->fac_stamp[2] == h->state_edits;
+    if (!current || index < h->fac_b0 || index >= h->fac_b0 + (int)h->fac_n.size())
+        return set_error(EKF_ERR_STATE, "no factor of this filter's current state: call ekf_joint_consistency first");
+    const int m = 2 * h->fac_n[index - h->fac_b0];
+    if (m == 0) return 0;
+    if (!U_out || ld < m) return set_error(EKF_ERR_BAD_ARG, "bad output buffer");
+    HIP_TRY(hipSetDevice(h->device));
+    DevTmp<double> stage;
+    HIP_TRY(stage.alloc((size_t)m * m));
+    hipLaunchKernelGGL(k_chol_export, dim3(cdiv(m, 256), m), dim3(256), 0, h->s_chain, h->dv, h->fac, index, m, stage.p, m);
+    EKF_TRY(read_back_dense(h, stage.p, m, nullptr, U_out, ld));
+    EKF_TRY(check_launch());
+    return m;
+}
+
+// ---- duplicate search -----------------------------------------------------------------------------
+// The scratch of ekf_find_duplicates (ekf_pairs.hip: DupScratch).  Boxes, counters and the split table are sized by the handle's
+// capacity: one block at the first call; the pair list, a block of its own that is not zeroed, holds `cap` pairs per filter and is
+// replaced by a larger one when a call finds more than it holds.  ekf_reserve builds both again for the larger capacity.
+static int dup_reserve(ekf_batch *h, int cap) {
+    const EkfDev &dv = h->dv;
+    const size_t B = (size_t)dv.B;
+    if (!h->kept[BLK_DUP].p) {
+        const size_t nbox = B * (size_t)(dv.dn >> 5) * 4;
+        EKF_TRY(block_alloc(h, &h->kept[BLK_DUP], nbox * sizeof(double) + B * 3 * sizeof(int), /*zero*/ true));
+        h->dup.box = (double *)h->kept[BLK_DUP].p;
+        h->dup.cnt = (int *)(h->dup.box + nbox);
+        h->dup.split = h->dup.cnt + 2 * B;
+    }
+    if (cap > h->dup.cap) {
+        EKF_TRY(block_alloc(h, &h->kept[BLK_DUP_LIST], B * (size_t)cap * sizeof(ekf_dup_pair), /*zero*/ false));
+        h->dup.list = (ekf_dup_pair *)h->kept[BLK_DUP_LIST].p;
+        h->dup.cap = cap;
+    }
+    return EKF_OK;
+}
+
+static int dup_cap_for(long long pairs) {
+    long long cap = 256;
+    while (cap < pairs) cap *= 2;
+    return (int)cap;
+}
+
+// The filters f: the rule of ekf_get_state (the streaming launch leaves, every deferred slot is folded, both streams idle),
+// then the settled state is only read: boxes (with a Euclidean bound), tiles, the counters back, the lists back.  A call that
+// finds more pairs than the device list holds and has to hand some out runs the two kernels once more with a list that fits (the
+// state has not moved: the same pairs).  The appended order is the hardware's; each filter's list is sorted by (i, j) here.
+static int dup_impl(ekf_batch *h, Filters f, double gate, double max_dist, int split_one, const int *split, ekf_dup_pair *pairs_out, int max_pairs, int *n_found_out,
+                    int *n_degenerate_out) {
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
+    const int b0 = f.b0, nb = f.nb, n_max = most_landmarks(counts_of(h, b0), nb);
+    int nt;
+    EKF_TRY(set_error(plan_dup_tiles(counts_of(h, b0), b0, nb, split_one, split, &nt)));
+    EKF_TRY(settle(h));
+    EKF_TRY(dup_reserve(h, dup_cap_for(max_pairs < 4096 ? max_pairs : 4096)));  // (a call that finds more grows the list below)
+    const EkfDev &dv = h->dv;
+    hipStream_t s = h->s_chain;
+    DupArgs da;
+    da.gate = gate, da.md2 = max_dist > 0.0 ? max_dist * max_dist : -1.0, da.split_one = split_one, da.use_tab = split ? 1 : 0;
+    if (split) HIP_TRY(hipMemcpyAsync(h->dup.split + b0, split, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
+    std::vector<int> cnt((size_t)2 * nb, 0);
+    for (int round = 0; nt > 0; round++) {
+        const DupScratch ds = h->dup;
+        HIP_TRY(hipMemsetAsync(ds.cnt + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
+        if (da.md2 >= 0.0) hipLaunchKernelGGL(k_dup_boxes, dim3((unsigned)cdiv(lm_tiles(n_max), 64), (unsigned)nb), dim3(64), 0, s, dv, ds, b0);
+        hipLaunchKernelGGL(k_dup_tiles, dim3((unsigned)nt, (unsigned)nb), dim3(256), 0, s, dv, ds, da, h->buf_in, b0);
+        HIP_TRY(hipMemcpyAsync(cnt.data(), ds.cnt + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost, s));
+        HIP_TRY(stream_wait(s));
+        EKF_TRY(check_launch());
+        int most = 0;
+        for (int k = 0; k < nb; k++) most = cnt[2 * k] > most ? cnt[2 * k] : most;
+        if (most <= ds.cap || max_pairs == 0) break;
+        if (round > 0) return set_error(EKF_ERR_STATE, "the pair count changed between two passes over an unchanged state");
+        EKF_TRY(dup_reserve(h, dup_cap_for(most)));
+    }
+    std::vector<ekf_dup_pair> got;
+    std::vector<size_t> at((size_t)nb + 1, 0);
+    for (int k = 0; k < nb; k++) at[k + 1] = at[k] + (max_pairs > 0 ? (size_t)cnt[2 * k] : 0);
+    got.resize(at[nb]);
+    for (int k = 0; k < nb; k++)
+        if (at[k + 1] > at[k])
+            HIP_TRY(hipMemcpyAsync(got.data() + at[k], h->dup.list + (size_t)(b0 + k) * h->dup.cap, sizeof(ekf_dup_pair) * (at[k + 1] - at[k]), hipMemcpyDeviceToHost, s));
+    if (at[nb] > 0) HIP_TRY(stream_wait(s));
+    for (int k = 0; k < nb; k++) {
+        const int found = cnt[2 * k];
+        if (n_found_out) n_found_out[k] = found;
+        if (n_degenerate_out) n_degenerate_out[k] = cnt[2 * k + 1];
+        if (at[k + 1] == at[k]) continue;
+        std::sort(got.begin() + at[k], got.begin() + at[k + 1], [](const ekf_dup_pair &a, const ekf_dup_pair &b) { return a.i != b.i ? a.i < b.i : a.j < b.j; });
+        memcpy(pairs_out + (size_t)k * max_pairs, got.data() + at[k], sizeof(ekf_dup_pair) * (size_t)(found < max_pairs ? found : max_pairs));
+    }
+    return nb == 1 && !n_found_out ? cnt[0] : EKF_OK;
+}
+
+static bool dup_args_ok(double gate, double max_dist, const ekf_dup_pair *pairs_out, int max_pairs) {
+    return __builtin_isfinite(gate) && gate >= 0.0 && max_dist == max_dist && max_pairs >= 0 && (pairs_out || max_pairs == 0);
+}
+
+extern "C" int ekf_find_duplicates(ekf_handle h, int index, double gate, double max_dist, int split, ekf_dup_pair *pairs_out, int max_pairs,
+                                   int *n_degenerate_out) {
+    if (!filter_ok(h, index) || split < 0 || !dup_args_ok(gate, max_dist, pairs_out, max_pairs)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return dup_impl(h, filters_of(h, index), gate, max_dist, split, nullptr, pairs_out, max_pairs, nullptr, n_degenerate_out);
+}
+
+extern "C" int ekf_batch_find_duplicates(ekf_handle h, double gate, double max_dist, const int *split, ekf_dup_pair *pairs_out, int max_pairs, int *n_found_out,
+                                         int *n_degenerate_out) {
+    if (!h || !n_found_out || !dup_args_ok(gate, max_dist, pairs_out, max_pairs)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return dup_impl(h, filters_of(h, -1), gate, max_dist, 0, split, pairs_out, max_pairs, n_found_out, n_degenerate_out);
+}
+
+// ---- landmark fusion ------------------------------------------------------------------------------
+// The scratch of ekf_fuse_landmarks (ekf_fuse.hip: FuseScratch), sized by the handle's capacity (a landmark is in at most one pair
+// of a call: Ncap / 2 pairs per filter): one block at the first call; ekf_reserve builds the larger one.
+static int fuse_reserve(ekf_batch *h) {
+    DevBlock &blk = h->kept[BLK_FUSE];
+    if (blk.p) return EKF_OK;
+    const EkfDev &dv = h->dv;
+    const size_t B = (size_t)dv.B;
+    const int pcap = dv.Ncap / 2 + 1;
+    const size_t nwr = B * 4 * FUSE_MAX_COLS, nU = B * FUSE_MAX_COLS * FUSE_MAX_COLS, nint = B * ((size_t)pcap * 2 + 4);
+    EKF_TRY(block_alloc(h, &blk, (nwr + nU) * sizeof(double) + nint * sizeof(int), /*zero*/ true));
+    h->fuse.wr = (double *)blk.p;
+    h->fuse.U = h->fuse.wr + nwr;
+    h->fuse.pairs = (int *)(h->fuse.U + nU);
+    h->fuse.cnt = h->fuse.pairs + B * (size_t)pcap * 2;
+    h->fuse.done = h->fuse.cnt + B;
+    h->fuse.m_round = h->fuse.done + 2 * B;
+    h->fuse.pcap = pcap;
+    return EKF_OK;
+}
+
+// ekf_reserve: the blocks the old buffers had (want[]; the pair list with dup_cap pairs per filter), built for the new capacity.
+// want[BLK_DUP] is not read: dup_reserve builds base and list together, and a base whose list never got allocated is not rebuilt.
+static int map_scratch_reserve(ekf_batch *h, const bool want[BLK_COUNT], int dup_cap) {
+    if (want[BLK_FACTOR]) EKF_TRY(factor_reserve(h));
+    if (want[BLK_DUP_LIST]) EKF_TRY(dup_reserve(h, dup_cap));
+    if (want[BLK_FUSE]) EKF_TRY(fuse_reserve(h));
+    return EKF_OK;
+}
+
+// The filters f, filter f.b0 + k with n_pairs[k] pairs at pairs + k * ld_pairs.  The list is checked against the mirror's
+// landmark counts before anything else happens to the handle; a call without a pair returns there.  Then: settle, the pair table
+// up, rounds of at most ekf_window() pairs (ekf_fuse.hip; one dense pass each, in place in the settled buffer in either pipeline
+// mode, also on handles whose chain kernel folds its own windows), the progress record back, and the removal of the fused pairs'
+// j through remove_settled, which ends the rewrite.  Nothing fused anywhere: the rewrite is ended here (slot rows cleared, the
+// pass sizes restored).
+static int fuse_impl(ekf_batch *h, Filters f, const ekf_dup_pair *pairs, int ld_pairs, const int *n_pairs, double slack, int *n_fused_out, int *n_lm_out) {
+    const int b0 = f.b0, nb = f.nb;
+    // the one way out: n_lm[k] landmarks in filter b0 + k now, done[2 k] of its pairs fused (done == nullptr: none anywhere)
+    const auto leave = [=](const int *n_lm, const int *done) {
+        for (int k = 0; k < nb; k++) {
+            if (n_fused_out) n_fused_out[k] = done ? done[2 * k] : 0;
+            if (n_lm_out) n_lm_out[k] = n_lm[k];
+        }
+        return nb == 1 && !n_lm_out ? n_lm[0] : EKF_OK;
+    };
+    HIP_TRY(hipSetDevice(h->device));
+    EKF_TRY(refresh_bounds(h, false));
+    int most;
+    EKF_TRY(set_error(plan_fuse_pairs(pairs, ld_pairs, n_pairs, counts_of(h, b0), b0, nb, &most)));
+    if (most == 0) return leave(counts_of(h, b0), nullptr);  // nothing to do: the window stays open
+    // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
+    // every deferred slot folded, both streams idle
+    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
+    EKF_TRY(fuse_reserve(h));
+    EkfDev &dv = h->dv;
+    const FuseScratch fs = h->fuse;
+    hipStream_t s = h->s_chain;
+    const int n_max = most_landmarks(counts_of(h, b0), nb);
+    std::vector<int> tab;
+    EKF_TRY(set_error(plan_fuse_table(pairs, ld_pairs, n_pairs, nb, fs.pcap, &tab)));
+    HIP_TRY(hipMemcpyAsync(fs.pairs + (size_t)b0 * fs.pcap * 2, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(fs.cnt + b0, n_pairs, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(fs.done + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
+    HIP_TRY(hipMemsetAsync(fs.m_round + b0, 0, sizeof(int) * (size_t)nb, s));
+    const int nT = lm_tiles(n_max);
+    for (int round = 0; round * dv.maxp < most; round++) {
+        const int m_hi = most - round * dv.maxp < dv.maxp ? most - round * dv.maxp : dv.maxp;
+        hipLaunchKernelGGL(k_fuse_gather, dim3((unsigned)cdiv(n_max, 256), (unsigned)m_hi, (unsigned)nb), dim3(256), 0, s, dv, fs, h->buf_in, round, b0);
+        hipLaunchKernelGGL(k_fuse_factor, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, round, slack, b0);
+        hipLaunchKernelGGL(k_fuse_apply, dim3((unsigned)cdiv(64 * nT, 256), (unsigned)nb), dim3(256), 0, s, dv, fs, b0);
+        hipLaunchKernelGGL(k_fuse_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0);
+        launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->buf_in, h->buf_in, nullptr, /*rev*/ 0, b0, nb);
+    }
+    std::vector<int> done((size_t)2 * nb, 0);
+    HIP_TRY(hipMemcpyAsync(done.data(), fs.done + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));
+    EKF_TRY(check_launch());
+    // the fused pairs' j go, exactly as ekf_remove_landmarks with keep[j] = 0 removes them
+    const int ld_keep = n_max > 0 ? n_max : 1;
+    std::vector<unsigned char> keep((size_t)nb * ld_keep, 1);
+    bool any = false;
+    for (int k = 0; k < nb; k++) {
+        if (n_fused_out) n_fused_out[k] = done[2 * k];  // (filled even where the removal below fails)
+        for (int q = 0; q < done[2 * k]; q++) keep[(size_t)k * ld_keep + pairs[(size_t)k * ld_pairs + q].j] = 0;
+        any = any || done[2 * k] > 0;
+    }
+    std::vector<int> n_new(counts_of(h, b0), counts_of(h, b0) + nb);
+    if (any) EKF_TRY(remove_settled(h, f, keep.data(), ld_keep, n_new.data()));
+    else EKF_TRY(finish_rewrite(h, b0, nb, /*rearm*/ true, n_new.data(), 1, /*flip_buf*/ false));
+    return leave(n_new.data(), done.data());
+}
+
+extern "C" int ekf_fuse_landmarks(ekf_handle h, int index, const ekf_dup_pair *pairs, int n_pairs, double slack, int *n_fused_out) {
+    if (!filter_ok(h, index) || n_pairs < 0 || (n_pairs > 0 && !pairs) || !(__builtin_isfinite(slack) && slack >= 0.0))
+        return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return fuse_impl(h, filters_of(h, index), pairs, n_pairs, &n_pairs, slack, n_fused_out, nullptr);
+}
+
+extern "C" int ekf_batch_fuse_landmarks(ekf_handle h, const ekf_dup_pair *pairs, int ld_pairs, const int *n_pairs, double slack, int *n_fused_out,
+                                        int *n_landmarks_out) {
+    if (!h || !n_pairs || ld_pairs < 0 || !n_landmarks_out || !(__builtin_isfinite(slack) && slack >= 0.0)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return fuse_impl(h, filters_of(h, -1), pairs, ld_pairs, n_pairs, slack, n_fused_out, n_landmarks_out);
+}
+
+extern "C" int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max) {
+    if (!filter_ok(h, index) || n_max < 0 || (!cov_out && n_max > 0)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    EKF_TRY(refresh_bounds(h));  // the chain stream idle (a resident streaming launch leaves first); no pass, the flush stream untouched
+    const int N = h->h_int[index];
+    const int cnt = N < n_max ? N : n_max;
+    if (cnt == 0) return N;
+    std::vector<double> comp((size_t)3 * cnt);  // the three components of the always-current diagonal blocks
+    HIP_TRY(hipMemcpy2DAsync(comp.data(), (size_t)cnt * sizeof(double), h->dv.D + (size_t)index * 3 * h->dv.dn, (size_t)h->dv.dn * sizeof(double),
+                             (size_t)cnt * sizeof(double), 3, hipMemcpyDeviceToHost, h->s_chain));
+    HIP_TRY(stream_wait(h->s_chain));
+    for (int l = 0; l < cnt; l++)
+        for (int c = 0; c < 3; c++) cov_out[3 * l + c] = comp[(size_t)c * cnt + l];
+    return N;
+}

@@ -1,0 +1,188 @@
+// ekf_map_plan.h -- the host-side planning of the map operations (ekf_map_api.hip) as pure code: the checks of the lists a caller
+// hands in and the tables the kernels of ekf_rewrite.hip, ekf_extract.hip, ekf_pairs.hip and ekf_fuse.hip read.  No HIP call and no
+// handle in here: landmark counts come in as plain arrays, n_lm[k] = landmarks of the k-th filter of the call, whose number in its
+// handle is b0 + k (error texts name that number).  A check reports a status and a text; the caller hands both to set_error.
+// tests/cpp/map_plan_check.cpp runs all of it on the CPU.
+#pragma once
+#include <stdarg.h>
+#include <stdio.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "ekf_device.h"
+
+// printf into a string: the library's one formatter of error texts (set_error in ekf_api.hip, plan_fail here)
+inline std::string format_text(const char *fmt, va_list ap) {
+    std::string s(256, '\0');
+    for (;;) {
+        va_list again;
+        va_copy(again, ap);
+        const int n = vsnprintf(&s[0], s.size(), fmt, again);
+        va_end(again);
+        const bool fits = n < (int)s.size();
+        s.resize(fits ? (size_t)(n > 0 ? n : 0) : (size_t)n + 1);
+        if (fits) return s;
+    }
+}
+
+struct PlanStatus {
+    int code = EKF_OK;
+    std::string text;
+};
+
+__attribute__((format(printf, 2, 3))) inline PlanStatus plan_fail(int code, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    PlanStatus st = {code, format_text(fmt, ap)};
+    va_end(ap);
+    return st;
+}
+
+inline int most_landmarks(const int *n_lm, int nb) { return nb > 0 ? std::max(0, *std::max_element(n_lm, n_lm + nb)) : 0; }
+
+// A map of n landmarks (and joined: more behind them) that a handle of capacity Ncap cannot hold; joined < 0: n alone.
+inline PlanStatus plan_no_room(int filter, int n, int joined, int Ncap, const char *verb) {
+    if (joined < 0) return plan_fail(EKF_ERR_CAPACITY, "filter %d: %d landmarks do not fit capacity_landmarks = %d (ekf_reserve, then %s again)", filter, n, Ncap, verb);
+    return plan_fail(EKF_ERR_CAPACITY, "filter %d: %d + %d landmarks do not fit capacity_landmarks = %d (ekf_reserve, then %s again)", filter, n, joined, Ncap, verb);
+}
+
+// ---- id lists (ekf_extract_map, ekf_get_submap) ---------------------------------------------------------------------------------
+// Every id non-negative, no id twice: checked before any handle is touched.
+inline PlanStatus plan_ids_distinct(const int *ids, int count, int filter) {
+    std::vector<int> sorted(ids, ids + count);
+    std::sort(sorted.begin(), sorted.end());
+    if (count > 0 && sorted[0] < 0) return plan_fail(EKF_ERR_BAD_ARG, "filter %d: landmark id %d is negative", filter, sorted[0]);
+    for (int k = 1; k < count; k++)
+        if (sorted[k] == sorted[k - 1]) return plan_fail(EKF_ERR_BAD_ARG, "filter %d: landmark id %d is named twice", filter, sorted[k]);
+    return {};
+}
+// ... and against the source's landmark count, once the source is at rest.
+inline PlanStatus plan_ids_in_range(const int *ids, int count, int N, int filter) {
+    for (int k = 0; k < count; k++)
+        if (ids[k] >= N) return plan_fail(EKF_ERR_BAD_ARG, "filter %d: landmark id %d is not one of its %d landmarks", filter, ids[k], N);
+    return {};
+}
+
+// The lists of an extraction over nb filters, filter k's at ids + k * ld_ids with count[k] entries (ids == nullptr: every landmark
+// of the source in order): the counts and plan_ids_distinct of each.
+inline PlanStatus plan_extract_lists(const int *ids, int ld_ids, const int *count, int bs0, int nb) {
+    for (int k = 0; ids && k < nb; k++) {
+        if (count[k] < 0 || count[k] > ld_ids) return plan_fail(EKF_ERR_BAD_ARG, "bad landmark count");
+        const PlanStatus st = plan_ids_distinct(ids + (size_t)k * ld_ids, count[k], bs0 + k);
+        if (st.code) return st;
+    }
+    return {};
+}
+// ... plan_ids_in_range of each against the source's counts n_src[k]; *mstride = the longest list, at least 1.
+inline PlanStatus plan_extract_range(const int *ids, int ld_ids, const int *count, const int *n_src, int bs0, int nb, int *mstride) {
+    *mstride = 1;
+    for (int k = 0; k < nb; k++) {
+        const int cnt = ids ? count[k] : n_src[k];
+        if (ids) {
+            const PlanStatus st = plan_ids_in_range(ids + (size_t)k * ld_ids, cnt, n_src[k], bs0 + k);
+            if (st.code) return st;
+        }
+        *mstride = std::max(*mstride, cnt);
+    }
+    return {};
+}
+// The table k_ext_tiles and k_ext_vec read: ex[2 k] = previous landmark count of destination filter k (plan_extract_old_counts
+// fills it), ex[2 k + 1] = its new one, then nb lists of mstride ids.  A list longer than the destination's capacity ends it.
+inline PlanStatus plan_extract_table(const int *ids, int ld_ids, const int *count, const int *n_src, int bd0, int nb, int mstride, int Ncap, std::vector<int> *ex) {
+    ex->assign((size_t)nb * (2 + mstride), 0);
+    for (int k = 0; k < nb; k++) {
+        const int cnt = ids ? count[k] : n_src[k];
+        if (cnt > Ncap) return plan_no_room(bd0 + k, cnt, -1, Ncap, "extract");
+        (*ex)[2 * k + 1] = cnt;
+        int *tab = ex->data() + 2 * nb + (size_t)k * mstride;
+        for (int q = 0; q < cnt; q++) tab[q] = ids ? ids[(size_t)k * ld_ids + q] : q;
+    }
+    return {};
+}
+// The destination's previous maps, what has to be overwritten: n_dst[k], or the whole capacity where the count is not to be
+// trusted (the caller passes -1 for a timed-out filter).  Returns the largest of the old and new counts of the call.
+inline int plan_extract_old_counts(std::vector<int> *ex, const int *n_dst, int nb, int Ncap) {
+    int n_hi = 0;
+    for (int k = 0; k < nb; k++) {
+        const int n_old = n_dst[k] < 0 || n_dst[k] > Ncap ? Ncap : n_dst[k];
+        (*ex)[2 * k] = n_old;
+        n_hi = std::max(n_hi, std::max(n_old, (*ex)[2 * k + 1]));
+    }
+    return n_hi;
+}
+
+// ---- removal (ekf_remove_landmarks, the end of ekf_fuse_landmarks) ----------------------------------------------------------------
+// The table k_rm_gather, k_rm_finish and k_rm_vec read, over ALL B filters of the handle: rm[2 b] = old count, rm[2 b + 1] = new
+// count, then B maps of mstride entries, map[new] = old.  Filter b0 + k of the call's nb has the keep mask keep + k * ld_keep (a
+// landmark without an entry is kept); the other filters keep everything.  nTo / nTn: the most tiles per side before / after.
+struct RemovalPlan {
+    std::vector<int> rm;
+    int nTo = 0, nTn = 0;
+    bool any = false;  // some landmark goes
+    int n_new(int b) const { return rm[2 * b + 1]; }
+};
+inline RemovalPlan plan_removal(const int *n_lm, int B, int mstride, const unsigned char *keep, int ld_keep, int b0, int nb) {
+    RemovalPlan p;
+    p.rm.assign((size_t)B * (2 + mstride), 0);
+    for (int b = 0; b < B; b++) {
+        const int n_old = n_lm[b];
+        const unsigned char *k = b >= b0 && b < b0 + nb ? keep + (size_t)(b - b0) * ld_keep : nullptr;
+        int *map = p.rm.data() + 2 * B + (size_t)b * mstride;
+        int n_new = 0;
+        for (int l = 0; l < n_old; l++)
+            if (!k || l >= ld_keep || k[l]) map[n_new++] = l;
+        p.rm[2 * b] = n_old, p.rm[2 * b + 1] = n_new;
+        p.any = p.any || n_new != n_old;
+        p.nTo = std::max(p.nTo, lm_tiles(n_old)), p.nTn = std::max(p.nTn, lm_tiles(n_new));
+    }
+    return p;
+}
+
+// ---- duplicate search ---------------------------------------------------------------------------------------------------------------
+// split[k] (or split_one for every filter) within [0, n_lm[k]]; *nt = the most tiles of a filter's search (dup_tile_count).
+inline PlanStatus plan_dup_tiles(const int *n_lm, int b0, int nb, int split_one, const int *split, int *nt) {
+    *nt = 0;
+    for (int k = 0; k < nb; k++) {
+        const int n = n_lm[k], sp = split ? split[k] : split_one;
+        if (sp < 0 || sp > n) return plan_fail(EKF_ERR_BAD_ARG, "filter %d: split = %d is outside [0, %d landmarks]", b0 + k, sp, n);
+        *nt = std::max(*nt, dup_tile_count(n, sp));
+    }
+    return {};
+}
+
+// ---- fusion -------------------------------------------------------------------------------------------------------------------------
+// Filter k's n_pairs[k] pairs at pairs + k * ld_pairs: 0 <= i < j < n_lm[k], every landmark in at most one pair.  *most = the
+// longest list.
+inline PlanStatus plan_fuse_pairs(const ekf_dup_pair *pairs, int ld_pairs, const int *n_pairs, const int *n_lm, int b0, int nb, int *most) {
+    *most = 0;
+    std::vector<unsigned char> seen;
+    for (int k = 0; k < nb; k++) {
+        const int N = n_lm[k], np = n_pairs[k];
+        if (np < 0 || (np > 0 && (!pairs || np > ld_pairs))) return plan_fail(EKF_ERR_BAD_ARG, "bad pair count or list");
+        seen.assign((size_t)(N > 0 ? N : 1), 0);
+        for (int q = 0; q < np; q++) {
+            const ekf_dup_pair &pr = pairs[(size_t)k * ld_pairs + q];
+            if (!(0 <= pr.i && pr.i < pr.j && pr.j < N))
+                return plan_fail(EKF_ERR_BAD_ARG, "filter %d, pair %d: (%d, %d) does not name two landmarks i < j of %d", b0 + k, q, pr.i, pr.j, N);
+            if (seen[pr.i] || seen[pr.j])
+                return plan_fail(EKF_ERR_BAD_ARG, "filter %d, pair %d: landmark %d is in another pair of the call", b0 + k, q, seen[pr.i] ? pr.i : pr.j);
+            seen[pr.i] = seen[pr.j] = 1;
+        }
+        *most = std::max(*most, np);
+    }
+    return {};
+}
+// The pair table k_fuse_gather reads (FuseScratch::pairs of the call's filters): nb lists of pcap (i, j).
+inline PlanStatus plan_fuse_table(const ekf_dup_pair *pairs, int ld_pairs, const int *n_pairs, int nb, int pcap, std::vector<int> *tab) {
+    tab->assign((size_t)nb * pcap * 2, 0);
+    for (int k = 0; k < nb; k++) {
+        if (n_pairs[k] > pcap) return plan_fail(EKF_ERR_STATE, "more pairs than the pair table holds");  // (each landmark once: cannot happen)
+        for (int q = 0; q < n_pairs[k]; q++) {
+            (*tab)[((size_t)k * pcap + q) * 2] = pairs[(size_t)k * ld_pairs + q].i;
+            (*tab)[((size_t)k * pcap + q) * 2 + 1] = pairs[(size_t)k * ld_pairs + q].j;
+        }
+    }
+    return {};
+}

@@ -40,6 +40,13 @@ def test_extraction_gather_reproduces_the_packing_of_the_selected_matrix(tmp_pat
     assert out.returncode == 0 and "extract map ok" in out.stdout, out.stdout + out.stderr
 
 
+def test_map_plan_checks_and_tables(tmp_path):
+    """csrc/ekf_map_plan.h called directly (tests/cpp/map_plan_check.cpp): the refusals of the map calls' lists with the library's
+    codes and texts, and the removal, extraction and pair tables against a restatement, at landmark counts around the tile edges."""
+    out = run_cpp_check(tmp_path, "map_plan_check")
+    assert out.returncode == 0 and "map plan ok" in out.stdout, out.stdout + out.stderr
+
+
 def test_bench_case_table_and_byte_model():
     assert b_ext.CASES == list(b_ext.TABLE)
     c = {case: b_ext.parse(case) for case in b_ext.CASES}

@@ -183,3 +183,87 @@ def test_reserve_keeps_the_stream_an_open_timer_and_the_pass_profile(pkg):
     assert launches >= (steps * M) // 8 and 0.0 < total_ms < ms, (launches, total_ms, ms)   # passes from BOTH sides of the growth
     assert all(d[0] == pkg.ekfslam.OLD for d in f.decisions(0, steps * M))
     f.close()
+
+
+# ---- the scratch the map operations keep, as a whole ------------------------------------------------------
+def _joint_as_ref(r):
+    """A device record in the shape helpers.check_joint takes for its reference."""
+    ref = dict((k, float(r[k])) for k in ("nees_map", "nees_joint", "logdet_map", "logdet_joint", "min_pivot", "max_pivot"))
+    ref.update(n_landmarks=int(r["n_landmarks"]), info=int(r["info"]), cov_robot_given_map=np.array(r["cov_robot_given_map"]))
+    return ref
+
+
+def test_scratch_of_joint_find_and_fuse_follows_a_reserve_together(pkg, pipeline_mode):
+    """ekf_joint_consistency, ekf_find_duplicates and ekf_fuse_landmarks each keep device scratch in the handle, and ekf_reserve
+    rebuilds all three for the larger capacity.  One handle (two filters of 40 landmarks, three of them exact copies of others, in
+    capacity 64) runs the three calls, grows to 96 -- a third tile -- and runs them again.  Every call's results equal those of a
+    twin created at capacity 96 that holds the same state (ekf_set_state of the handle's export) and makes that call as its first
+    of the kind, with no scratch yet: bit for bit for the duplicate search (tests/test_find_duplicates.py asserts the same bits
+    across a reserve) and wherever the twin has the handle's capacity; where the capacities differ (64 against 96), within the
+    tolerances of tests/test_joint_consistency.py and tests/test_fuse_landmarks.py.  ekf_device_bytes rises at the first call of
+    each operation, rises with the reserve and is the same figure after each call behind it."""
+    import fuse_ref as fr
+    from helpers import assert_bitwise, check_joint
+
+    B, CAP0, CAP1 = 2, 64, 96
+    a = pkg.FilterBatch(B, CAP0, max_pending=8, log_capacity=4096)
+    for b in range(B):
+        x, P = pkg.scenarios.injected_state(37, seed=300 + b, extent=15.0)
+        for i in (5, 17, 29):  # landmarks 37, 38, 39 are 5, 17, 29 again
+            x, P = fr.with_exact_copy(x, P, i)
+        a.set_state(x, P, index=b)
+    assert [int(n) for n in a.num_landmarks()] == [40, 40]
+
+    def twin():
+        t = pkg.FilterBatch(B, CAP1, max_pending=8, log_capacity=4096)
+        for b in range(B):
+            t.set_state(*a.get_state(b), index=b)
+        return t
+
+    def round_of_calls(pairs, same_capacity, rises):
+        # joint consistency
+        states = [a.get_state(b) for b in range(B)]
+        xt = np.stack([s[0] + 0.01 for s in states])
+        t, before = twin(), a.device_bytes()
+        ra, rt = a.joint_consistency(xt), t.joint_consistency(xt)
+        if same_capacity:
+            assert ra.tobytes() == rt.tobytes()
+        else:
+            for b in range(B):
+                check_joint(ra[b], _joint_as_ref(rt[b]), states[b][1], "joint consistency, filter %d" % b)
+        assert (a.device_bytes() > before) if rises else (a.device_bytes() == before), ("joint consistency", before, a.device_bytes())
+        t.close()
+        # duplicate search
+        t, before = twin(), a.device_bytes()
+        da, dt = a.find_duplicates(gate=1e3, index=None), t.find_duplicates(gate=1e3, index=None)
+        for b in range(B):
+            print("filter %d: %d pairs pass, %d degenerate" % (b, da[b][1], da[b][2]))
+            assert da[b][0].tobytes() == dt[b][0].tobytes() and da[b][1:] == dt[b][1:], b
+            assert da[b][1] > 0 and da[b][2] >= 1  # (pairs to compare; the exact copies are counted, not listed)
+        assert (a.device_bytes() > before) if rises else (a.device_bytes() == before), ("find duplicates", before, a.device_bytes())
+        t.close()
+        # fusion
+        t, before = twin(), a.device_bytes()
+        lists = [fr.as_pairs(pairs)] * B
+        (na, fa), (nt, ft) = a.fuse_landmarks(lists, slack=1e-4, index=None), t.fuse_landmarks(lists, slack=1e-4, index=None)
+        assert list(na) == list(nt) and list(fa) == list(ft) == [len(pairs)] * B
+        for b in range(B):
+            sa, st = a.get_state(b), t.get_state(b)
+            if same_capacity:
+                assert_bitwise(sa, st, "fused filter %d" % b)
+            else:
+                assert_state_close(sa[0], sa[1], st[0], st[1], what="fused filter %d" % b)
+            assert_bitwise_symmetric(sa[1])
+        assert (a.device_bytes() > before) if rises else (a.device_bytes() == before), ("fuse landmarks", before, a.device_bytes())
+        t.close()
+
+    round_of_calls([(5, 37), (2, 20)], same_capacity=False, rises=True)   # 37 and 20 go: the copies 38, 39 become 36, 37
+    assert [int(n) for n in a.num_landmarks()] == [38, 38]
+    held, before = [a.get_state(b) for b in range(B)], a.device_bytes()
+    a.reserve(CAP1)
+    assert a.capacity == CAP1 and a.device_bytes() > before
+    for b in range(B):
+        assert_bitwise(a.get_state(b), held[b], "filter %d across the reserve" % b)
+    round_of_calls([(17, 36), (1, 30)], same_capacity=True, rises=False)
+    assert [int(n) for n in a.num_landmarks()] == [36, 36]
+    a.close()
