@@ -28,7 +28,9 @@ def terms(x, P, dtype=np.float64):
 def find(x, P, gate=GATE, max_dist=None, split=0, dtype=np.float64, with_terms=False):
     N = (len(x) - 3) // 2
     if N < 2:
-        return np.zeros(0, dtype=DUP_DTYPE), 0
+        none = np.zeros(0, dtype=bool)
+        terms_of_nothing = dict(i=np.zeros(0, dtype=int), j=np.zeros(0, dtype=int), d2=np.zeros(0), r2=np.zeros(0), considered=none, ok=none)
+        return (np.zeros(0, dtype=DUP_DTYPE), 0) + ((terms_of_nothing,) if with_terms else ())
     dx, dy, a, b, c, det = terms(x, P, dtype)
     i, j = np.triu_indices(N, 1)
     if split > 0:

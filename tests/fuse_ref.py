@@ -1,4 +1,5 @@
-"""NumPy statement of ekf_fuse_landmarks (include/ekfslam_c.h) on a dense export, and the builder of joined maps with duplicates.
+"""NumPy statement of ekf_fuse_landmarks (include/ekfslam_c.h) on a dense export, and the builders of joined maps with duplicates and
+of maps whose chosen landmarks are noisy copies of others (with_noisy_copies: any pair list, S well conditioned).
 
 fuse(x, P, pairs, slack, round_size) -> (x, P, n_fused): for the pairs (i_k, j_k) of a round,
     W = P[:, i] - P[:, j] (column pairs),  d = x_i - x_j,  S = W[i] - W[j] + slack I = U^T U,  V = W U^-1,  y = U^-T d,
@@ -145,3 +146,24 @@ def with_exact_copy(x, P, i):
     n = len(x)
     src = np.concatenate([np.arange(n), [3 + 2 * i, 4 + 2 * i]]).astype(int)
     return x[src].copy(), P[np.ix_(src, src)].copy()
+
+
+def with_noisy_copies(x, P, pairs, seed, target=2.0):
+    """The state with landmark j of every pair (i, j) made a noisy copy of landmark i, as dup_ref.with_duplicates plants one: every
+    cross covariance of j copied from i, P_jj = P_ii + R and L_j = L_i + e with R a random SPD matrix of size 1e-3 and
+    e^T R^-1 e = target.  S of the pair list is then exactly blockdiag(R): well conditioned whatever the list."""
+    rng = np.random.default_rng(seed)
+    ij = as_ij(pairs)
+    src = np.arange(len(x))
+    for i, j in ij:
+        src[3 + 2 * j:5 + 2 * j] = (3 + 2 * i, 4 + 2 * i)
+    x1, P1 = np.array(x, dtype=np.float64)[src], np.array(P, dtype=np.float64)[np.ix_(src, src)]
+    for i, j in ij:
+        A = rng.normal(size=(2, 2))
+        R = 1e-3 * (A @ A.T + 0.5 * np.eye(2))
+        R = 0.5 * (R + R.T)
+        th = rng.uniform(0.0, 2.0 * np.pi)
+        x1[3 + 2 * j:5 + 2 * j] += np.linalg.cholesky(R) @ np.array([np.cos(th), np.sin(th)]) * np.sqrt(target)
+        P1[3 + 2 * j:5 + 2 * j, 3 + 2 * j:5 + 2 * j] += R
+    assert np.array_equal(P1, P1.T)
+    return x1, P1

@@ -1,5 +1,6 @@
 """Shared test helpers: the parity tolerance of BASELINE.json's north_star, made well-defined, and the scaffolding of the GPU tests of
-the map operations (removal, frame change, joining): injected filters, immediate-call scripts, window and stream probes."""
+the map operations (removal, frame change, joining, duplicate search, fusion, extraction): injected filters, immediate-call scripts,
+window and stream probes, the reference of the submap extraction (NumPy indexing) and the contract of a duplicate list."""
 import ctypes
 import functools
 import math
@@ -204,3 +205,51 @@ def gpu_present():
     out = subprocess.run([sys.executable, "-c", "import torch; print(int(torch.cuda.is_available()))"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     return out.stdout.split()[-1] == "1"
+
+
+# ---- submap extraction: the reference is indexing --------------------------------------------------------
+def sel_of(ids):
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    return np.concatenate([np.arange(3), np.stack([3 + 2 * ids, 4 + 2 * ids], axis=1).reshape(-1)]).astype(np.int64)
+
+
+def index_state(state, ids):
+    """The reference of ekf_extract_map / ekf_get_submap: rows and columns of an exported state (ids None: every landmark)."""
+    x, P = state
+    s = np.arange(x.size) if ids is None else sel_of(ids)
+    return x[s].copy(), P[np.ix_(s, s)].copy()
+
+
+def shuffled_ids(N, count, seed):
+    """`count` distinct landmarks of N in shuffled order, the tile edges 0, 31, 32, 63, 64 and the last landmark among them."""
+    rng = np.random.default_rng(seed)
+    must = sorted({l for l in (0, 31, 32, 63, 64, N - 1) if 0 <= l < N})[:count]
+    rest = [l for l in rng.permutation(N) if l not in must][:count - len(must)]
+    ids = np.array(must + rest, dtype=np.int32)
+    rng.shuffle(ids)
+    assert ids.size == count and np.unique(ids).size == count
+    return ids
+
+
+# ---- duplicate search: the contract of a list against tests/dup_ref.py -------------------------------------
+MARGIN = 1e-3  # no pair of a compared list within this (relative) of the gate or of max_dist
+
+
+def ij(pairs):
+    return list(zip(pairs["i"].tolist(), pairs["j"].tolist()))
+
+
+def check_duplicates(got, x, P, gate=9.21, max_dist=None, split=0, what=""):
+    """A device result (pairs, n_found, n_degenerate) against the reference on the export (x, P); returns the worst d2 error."""
+    import dup_ref as dr  # (beside this file)
+    pairs, found, degen = got
+    m_gate, m_dist = dr.margins(x, P, gate, max_dist, split)
+    assert m_gate > MARGIN and m_dist > MARGIN, (what, "the reference has a pair on the edge: another seed", m_gate, m_dist)
+    ref, ref_degen = dr.find(x, P, gate, max_dist, split)
+    assert found == len(ref) and degen == ref_degen, (what, found, len(ref), degen, ref_degen)
+    assert ij(pairs) == ij(ref)[:len(pairs)], (what, ij(pairs), ij(ref))
+    if len(pairs) == 0:
+        return 0.0
+    err = np.abs(pairs["d2"] - ref["d2"][:len(pairs)])
+    assert np.all(err <= REL_TOL * np.abs(ref["d2"][:len(pairs)]) + 1e-9), (what, err.max())
+    return float((err / np.maximum(np.abs(ref["d2"][:len(pairs)]), 1e-9)).max())

@@ -1,6 +1,8 @@
 """Host model of a filter handle and generator of random operation sequences that mix the map rewrites (landmark removal, frame
-change, anchoring, map joining, ekf_reserve, the joint-consistency probe) with live filter traffic.  No GPU and no library here: the
-filter steps go through the C oracle (oracle/oracle_c.py), the rewrites through the NumPy references beside this file.
+change, anchoring, map joining, ekf_reserve, the joint-consistency probe; in the *_maps profiles also the duplicate search, the join
+-> find -> match -> fuse workflow and submap extraction as a probe and as a rewrite of the handle) with live filter traffic.  No GPU
+and no library here: the filter steps go through the C oracle (oracle/oracle_c.py), the rewrites through the NumPy references
+beside this file (the package is imported for its pure-Python duplicate_matching only).
 
 A sequence is a plain list of (kind, args) pairs with every argument spelled out; tests/test_map_sequences.py replays it on the
 library and on `ModelRunner` in lockstep, tests/test_map_model_cpu.py on the model alone.  The generator runs a ModelRunner of its own
@@ -9,7 +11,25 @@ library and on `ModelRunner` in lockstep, tests/test_map_model_cpu.py on the mod
 Hidden world per filter: a true pose and world landmarks pairwise >= 1 m apart (no arg-min near a tie), both kept in the world frame
 for good: measurements are relative to the true pose, so they do not care about the filter's frame.  Compass readings do; the
 generator tracks the offset between the filter's heading and the true one (-theta after a rigid transform, -(estimated phi) after
-an anchor; a join keeps it)."""
+an anchor; a join keeps it).
+
+The *_maps profiles (appended, so that the four older profiles keep their place in the rng seed and their sequences value for value):
+  dups     ekf_find_duplicates as a read-only probe.  The gate is the first of DUP_GATES for which the model's state keeps every pair
+           DUP_MARGIN (relative) away from the gate and from max_dist and no pair of the split is near-degenerate
+           (dups_precondition); the library's list is then the model's list.  No gate qualifies: a `covs` op instead.
+  fuse     the workflow on a map the filter built: a source handle re-observes world landmarks the destination has mapped (the
+           isolated ones nearest the robot), join, dups with split = old count (the op carries the one-to-one matching of the
+           model's list, which the device's own list must reproduce), perhaps propagations and a compass update -- no measurement:
+           the world's 1 m separation does not hold while duplicates exist --, fuse with slack 0 or 1e-4 in rounds of the handle's
+           window, then the removal of a planted duplicate the gate did not match.  Now and then a fuse of no pair (a no-op).
+  extract  a scratch handle of another tile count (created and closed inside the op): a probe (ekf_extract_map into the scratch and
+           ekf_get_submap, both NumPy indexing of the export, bit for bit), or a rewrite: the handle replaced by its own shuffled
+           marginal through the scratch (one-filter profiles, and the batch form in batch_maps), or filter b replaced by a fork of
+           its sibling c (batch_maps; b's hidden world becomes a copy of c's).
+The round size of a fuse is the handle's effective window (ekf_window): ekf_batch_create may shorten max_pending to what fits the
+LDS and ekf_reserve plans the geometry again (ekf_geometry.h: plan_geometry), so the generator checks with a restatement of that
+plan (planned_window) that the window of every capacity the handle takes is the max_pending it was created with, in either pipeline
+mode; the op carries it and the replay asserts it."""
 import math
 import os
 import sys
@@ -17,14 +37,21 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dup_ref as dr  # noqa: E402
 import factor_ref as fr  # noqa: E402
+import fuse_ref as fu  # noqa: E402
 import join_ref as jr  # noqa: E402
 import reframe_ref as rr  # noqa: E402
+from helpers import index_state, shuffled_ids  # noqa: E402
 
-PROFILES = ("solo", "chain", "chain_wgs", "batch")
+PROFILES = ("solo", "chain", "chain_wgs", "batch", "solo_maps", "chain_maps", "batch_maps")
+MAP_PROFILES = PROFILES[4:]
 # (a seed whose replay on the model leaves a measurement within 1e-6 relative of a gate is replaced here, never skipped at run time;
-# tests/test_map_model_cpu.py checks every one of these)
-SEEDS = {"solo": [0, 1, 2, 3, 4, 5, 6, 7], "chain": [0, 1, 2, 3, 4, 5, 6, 7], "chain_wgs": [0, 1, 2, 3, 4, 5, 6, 7], "batch": [0, 1, 2, 3, 4, 5]}
+# tests/test_map_model_cpu.py checks every one of these.  The *_maps lists: the first six seeds that the generator's own assertions
+# -- every source landmark mapped, every matched pair a planted one, every pair fused, S clearly definite -- and the coverage
+# the CPU tests ask of a profile let through)
+SEEDS = {"solo": [0, 1, 2, 3, 4, 5, 6, 7], "chain": [0, 1, 2, 3, 4, 5, 6, 7], "chain_wgs": [0, 1, 2, 3, 4, 5, 6, 7], "batch": [0, 1, 2, 3, 4, 5],
+         "solo_maps": [0, 1, 2, 3, 4, 5], "chain_maps": [0, 1, 2, 3, 6, 10], "batch_maps": [3, 4, 5, 6, 7, 13]}
 N_STEPS = 40
 GAMMA_MIN, GAMMA_MAX = 10.0, 50.0  # the gates (ekf_default_params; oracle_c.update's defaults)
 COMPASS_VAR = 0.0005
@@ -32,6 +59,14 @@ SRC_CAPS = (40, 96, 300)
 WINDOWS = (1, 3, 8, 16, 24, 32)
 REWRITES = ("remove", "transform", "anchor", "reserve", "join", "joint", "covs", "read")
 KINDS = ("propagate", "update", "compass") + REWRITES
+MAP_REWRITES = REWRITES + ("dups", "fuse", "extract")  # the deck of the *_maps profiles
+MAP_KINDS = KINDS + ("dups", "fuse", "extract")
+DUP_GATES = (9.21, 7.0, 12.0, 5.0, 16.0)
+DUP_MARGIN = 1e-3   # tests/helpers.py: MARGIN
+DUP_MIN_REL = 1e-6  # a pair's S = (a b; b c): a > DUP_MIN_REL (P_ii.xx + P_jj.xx) and det > DUP_MIN_REL a c
+FUSE_MIN_EIG = 1e-6  # every round's S: smallest eigenvalue > FUSE_MIN_EIG x the largest
+SCRATCH_CAPS = (8, 40, 96, 130, 200, 300, 400)
+LDS_PER_BLOCK = 163840  # hipDeviceProp_t::sharedMemPerBlock of the MI355X
 
 
 def lm_tiles(n):
@@ -43,6 +78,81 @@ def _oc():
     from oracle import oracle_c
     oracle_c.build()
     return oracle_c
+
+
+def duplicate_matching(pairs, n_landmarks):
+    """The package's greedy one-to-one matching (pure Python; importing the package loads no library)."""
+    import __graft_entry__ as ge
+    return ge.load_package().ekfslam.duplicate_matching(pairs, n_landmarks)
+
+
+def planned_window(batch, cap, max_pending, overlap, wgs=None):
+    """ekf_window() of a handle as plan_geometry (csrc/ekf_geometry.h) plans it with EKF_OVERLAP forced to `overlap`, the other
+    tunables at their defaults (EKF_CHAIN_WGS = wgs), on a device with LDS_PER_BLOCK bytes of LDS per workgroup."""
+    maxp = min(max(int(max_pending), 1), 32)
+    budget = LDS_PER_BLOCK - 16384
+    sets = 2 if overlap else 1
+    ceil64 = lambda v: (v + 63) // 64 * 64  # noqa: E731
+    G = max((cap + 191) // 192, (ceil64(cap) * maxp * sets * 32 + budget - 1) // budget, min((cap + 63) // 64, 32))
+    G = max(min(G, 64, max(256 // batch, 1)), 1)
+    g_cap = 1 if batch >= 256 else min(64, 256 // batch)
+    while G < g_cap and ceil64((cap + G - 1) // G) * maxp * sets * 32 > budget:
+        G += 1
+    want_solo = not overlap and wgs is None
+    if want_solo and cap <= 256 and ceil64(cap) * (maxp if maxp <= 16 else 16) * 32 <= budget:
+        G = 1
+    if wgs:
+        G = wgs
+    G = min(G, 64)
+    if G * batch > 256:
+        G = max(256 // batch, 1)
+    solo_kernel = not overlap and G == 1 and want_solo and cap <= 256
+    lpw64 = ceil64((cap + G - 1) // G)
+    if lpw64 * maxp * sets * 32 > budget:
+        if solo_kernel and budget // (lpw64 * 32) >= 16:
+            maxp = min(maxp, 32)
+        else:
+            maxp = budget // (lpw64 * sets * 32)
+            if maxp > 1:
+                maxp &= ~1
+    return maxp
+
+
+def dups_precondition(x, P, gate, max_dist, split):
+    """What makes the LIST of a duplicate search comparable between the model and the library (which agree to about 1e-12): every
+    pair DUP_MARGIN (relative) away from the gate and from max_dist (dup_ref.margins), and no pair of the split near-degenerate,
+    S = (a b; b c) with a > DUP_MIN_REL (P_ii.xx + P_jj.xx) and det > DUP_MIN_REL a c."""
+    N = (len(x) - 3) // 2
+    if N < 2:
+        return True
+    m_gate, m_dist = dr.margins(x, P, gate, max_dist, split)
+    if not (m_gate > DUP_MARGIN and m_dist > DUP_MARGIN):
+        return False
+    _, _, a, _, c, det = dr.terms(x, P)
+    i, j = np.triu_indices(N, 1)
+    if split > 0:
+        m = (i < split) & (j >= split)
+        i, j = i[m], j[m]
+    xx = np.diag(P)[3::2]
+    a, c, det = a[i, j], c[i, j], det[i, j]
+    return bool(np.all(a > DUP_MIN_REL * (xx[i] + xx[j])) and np.all(det > DUP_MIN_REL * a * c))
+
+
+def fuse_rounds_definite(x, P, ij, slack, window):
+    """Every round's S = H W + slack I of fuse_ref.fuse(x, P, ij, slack, window) clearly positive definite: its smallest eigenvalue
+    above FUSE_MIN_EIG times its largest."""
+    x, P = np.array(x, dtype=np.float64), np.array(P, dtype=np.float64)
+    ij = np.asarray(ij, dtype=np.int64).reshape(-1, 2)
+    for r0 in range(0, len(ij), window):
+        r = ij[r0:r0 + window]
+        ci = np.stack([3 + 2 * r[:, 0], 4 + 2 * r[:, 0]], axis=1).reshape(-1)
+        cj = np.stack([3 + 2 * r[:, 1], 4 + 2 * r[:, 1]], axis=1).reshape(-1)
+        W = P[:, ci] - P[:, cj]
+        ev = np.linalg.eigvalsh(W[ci] - W[cj] + slack * np.eye(len(ci)))
+        if not ev[0] > FUSE_MIN_EIG * ev[-1]:
+            return False
+        x, P = fu.update(x, P, r, slack)
+    return True
 
 
 def reduce_state(x, P, keep):
@@ -97,6 +207,20 @@ class MapModel:
 
     def reserve(self, capacity):
         pass
+
+    def find_duplicates(self, gate, max_dist, split):
+        """((i, j) list, n_found, n_degenerate)."""
+        pairs, degen = dr.find(self.x, self.P, gate, max_dist, split)
+        return list(zip(pairs["i"].tolist(), pairs["j"].tolist())), len(pairs), degen
+
+    def fuse(self, ij, slack, window):
+        """(n_landmarks, n_fused) in rounds of `window` pairs, as the handle takes them."""
+        self.x, self.P, fused = fu.fuse(self.x, self.P, np.asarray(ij, dtype=np.int64).reshape(-1, 2), slack, window)
+        return self.n_landmarks, fused
+
+    def extract(self, src, ids):
+        self.x, self.P = index_state((src.x, src.P), ids)
+        return self.n_landmarks
 
     def joint(self, x_true):
         return fr.lapack(self.x, self.P, x_true)
@@ -185,6 +309,14 @@ class ModelRunner:
             return [M[b].joint(a["x_true"][b]) for b in which()]
         elif kind == "covs":
             return M[a["index"]].landmark_covs()
+        elif kind == "dups":
+            return [M[b].find_duplicates(a["gate"], a["max_dist"], a["split"][b]) for b in which()]
+        elif kind == "fuse":
+            return [M[b].fuse(a["pairs"][b], a["slack"], a["window"]) for b in which()]
+        elif kind == "extract":
+            if a["mode"] == "probe":
+                return None
+            return [M[b].extract(M[a["src_index"] if a["mode"] == "fork" else b], a["ids"][b]) for b in which()]
         elif kind in ("read", "twin_begin", "twin_end"):
             pass
         else:
@@ -250,6 +382,8 @@ class _Gen:
         self.oc = _oc()
         self.rng = rng = np.random.default_rng([PROFILES.index(profile), seed, 20261018])
         self.profile = profile
+        self.maps = profile in MAP_PROFILES
+        profile = profile[:-5] if self.maps else profile  # (the parameters of the profile it extends)
         self.ops = []
         self.run = ModelRunner()
         self.deck = []
@@ -279,6 +413,8 @@ class _Gen:
                 cap = max(40, max(starts) + int(rng.integers(8, 24)))
         starts = [min(n0, cap - 6) for n0 in starts]
         self.B = len(starts)
+        self.base, self.window, self.wgs = profile, window, wgs
+        self.twin_wish, self.twin_kind = None, None
         self.sims = [_Sim(rng, n_world, extent) for _ in starts]
         self.emit("create", B=self.B, cap=cap, window=window, wgs=wgs)
         for b, n0 in enumerate(starts):
@@ -289,8 +425,11 @@ class _Gen:
     # -- plumbing
     def emit(self, kind, **a):
         # (a rewrite straight behind filter traffic that does not export first meets an open window and a live streaming launch)
-        if kind in ("remove", "transform", "anchor", "join") and not a["settle"] and self.behind_traffic:
+        if (kind in ("remove", "transform", "anchor", "join", "fuse") or kind == "extract" and a["mode"] != "probe") and not a["settle"] \
+                and self.behind_traffic:
             self.n_open += 1
+        if self.maps and kind in ("create", "reserve"):  # the effective window stays the one asked for, whatever the capacity
+            assert all(planned_window(self.B, a["cap"], self.window, ov, self.wgs) == self.window for ov in (False, True)), a["cap"]
         self.behind_traffic = kind in ("propagate", "update", "compass", "src_propagate", "src_update")
         op = (kind, a)
         self.ops.append(op)
@@ -307,7 +446,7 @@ class _Gen:
         """Room for `need` landmarks in every filter: an ekf_reserve, now and then across 256 (the kernel family changes)."""
         cap = self.run.cap
         new = max(need, cap) + int(self.rng.integers(4, 40))
-        if cap <= 256 and self.profile != "batch" and self.rng.random() < 0.4:
+        if cap <= 256 and self.base != "batch" and self.rng.random() < 0.4:
             new = max(new, int(self.rng.integers(257, 300)))
         self.emit("reserve", cap=new)
 
@@ -522,8 +661,248 @@ class _Gen:
             self.emit("read", index=int(rng.integers(0, B)))
         return kind
 
+    # -- the *_maps profiles: duplicate search, fusion, extraction
+    def twin_point(self, kind):
+        """Behind a state-changing op: a twin starts here if build_maps wished for one and this kind may carry it."""
+        if self.twin_wish == "any" or self.twin_wish == "new" and kind in ("fuse", "extract"):
+            self.emit("twin_begin")
+            self.twin_wish, self.twin_kind = None, kind
+
+    def do_dups(self, index, splits=None, max_dist=None, matched=False):
+        """A duplicate search whose list the model can vouch for (a `covs` op where no gate of DUP_GATES qualifies).  Returns the
+        gate, or None."""
+        rng, B = self.rng, self.B
+        which = list(range(B)) if index is None else [index]
+        if splits is None:
+            splits = {b: int(rng.integers(1, self.counts()[b] + 1)) if self.counts()[b] and rng.random() < 0.5 else 0 for b in which}
+            max_dist = float(rng.choice([0.5, 1.5, 4.0])) if rng.random() < 0.5 else None
+        settle = bool(index is not None and B > 1 or rng.random() < 0.5)
+        for gate in DUP_GATES:
+            if all(dups_precondition(self.models[b].x, self.models[b].P, gate, max_dist, splits[b]) for b in which):
+                match = None
+                if matched:  # the one-to-one matching of the model's list: what the fuse behind this search is given
+                    match = {}
+                    for b in which:
+                        m = self.models[b]
+                        found, _ = dr.find(m.x, m.P, gate, max_dist, splits[b])
+                        match[b] = fu.as_ij(duplicate_matching(found, m.n_landmarks))
+                self.emit("dups", index=index, gate=gate, max_dist=max_dist, split=splits, matched=match, settle=settle)
+                return gate
+        self.emit("covs", index=int(rng.integers(0, B)))
+        return None
+
+    def between(self):
+        """Traffic that is no measurement, on every filter: a propagation, now and then a compass update behind it."""
+        rng, B = self.rng, self.B
+        v, w, dt = rng.uniform(0.05, 0.6, B), rng.uniform(-0.4, 0.4, B), rng.uniform(0.02, 0.3, B)
+        for b, s in enumerate(self.sims):
+            s.move(v[b], w[b], dt[b])
+        self.emit("propagate", v=v, w=w, dt=dt)
+        if rng.random() < 0.4:
+            valid = np.ones(B, dtype=bool) if B == 1 else rng.random(B) < 0.6
+            z = np.array([(s.pose[2] + s.offset) % 6.283185307 + rng.normal(0.0, 0.02) for s in self.sims])
+            self.emit("compass", z=z, R=COMPASS_VAR, valid=valid)
+
+    def do_fuse(self, index):
+        """join -> find -> match -> fuse on the map the filter built.  False (nothing emitted but perhaps a removal down to a tile
+        edge) where there is nothing to re-observe."""
+        rng, B = self.rng, self.B
+        dst = list(range(B)) if index is None else [index]
+        if any(len(self.sims[b].unseen()) < 30 for b in dst):
+            return False
+        if rng.random() < 0.5:  # the destination on a tile edge
+            for b in dst:
+                if self.counts()[b] > 32 and self.counts()[b] % 32:
+                    self.do_remove(b if B > 1 else index, "edge")
+        many = self.window <= 8 and rng.random() < 0.7  # more pairs than a round takes
+        only_dups = rng.random() < 0.3  # a source that maps nothing new: the fuse gives back every row of the join
+        pools, seen = [], []
+        for b in dst:
+            s, m = self.sims[b], self.models[b]
+            L = m.x[3:].reshape(-1, 2)
+            # re-observed: landmarks no other ESTIMATE of the map comes within 1 m of (a spurious one made by an outlier would
+            # be a second candidate at the gate), nearest the robot first
+            # ... and 2 m from the robot at least: the source drives up to a metre and a half meanwhile
+            cand = [l for l, k in enumerate(s.in_map) if k >= 0 and (len(L) == 1 or np.sort(np.hypot(*(L - L[l]).T))[1] >= 1.0)
+                    and np.hypot(*(s.world[k] - s.pose[:2])) >= 2.0]
+            cand.sort(key=lambda l: float(np.hypot(*(s.world[s.in_map[l]] - s.pose[:2]))))
+            cand = cand[:int(rng.integers(9, 12)) if many else int(rng.integers(1, 5))]
+            fresh = sorted(s.unseen(), key=lambda k: float(np.hypot(*(s.world[k] - s.pose[:2]))))
+            seen.append(cand)
+            pools.append([s.in_map[l] for l in cand] + ([] if only_dups and cand else fresh[:int(rng.integers(1, 8))]))
+        if not any(seen):
+            return False
+        old = self.counts()
+        src_B, T = len(dst), 8
+        n_z = -(-max(len(p) for p in pools) // 6)  # the whole pool is mapped by step 6, the first of it seen again behind that
+        self.emit("src_create", B=src_B, cap=int(rng.choice([c for c in SRC_CAPS if c >= max(len(p) for p in pools)])), window=int(rng.choice(WINDOWS)))
+        mine = [[] for _ in dst]
+        for t in range(T):
+            v, w, dt = rng.uniform(0.05, 0.6, src_B), rng.uniform(-0.4, 0.4, src_B), rng.uniform(0.02, 0.3, src_B)
+            for i, b in enumerate(dst):
+                self.sims[b].move(v[i], w[i], dt[i])
+            self.emit("src_propagate", v=v, w=w, dt=dt)
+            z, R = np.zeros((src_B, n_z, 2)), np.tile(np.eye(2), (src_B, n_z, 1, 1))
+            valid = np.zeros((src_B, n_z), dtype=bool)
+            ids = [[] for _ in dst]
+            for i, b in enumerate(dst):
+                for j, p in enumerate(sorted(set((n_z * t + j) % len(pools[i]) for j in range(n_z)))):
+                    k = pools[i][p]
+                    z[i, j] = self.sims[b].rel(k) + rng.normal(0.0, 0.03, 2)
+                    R[i, j] = _measurement(self.oc, z[i, j])
+                    valid[i, j] = True
+                    ids[i].append(k)
+            decs = self.emit("src_update", z=z, R=R, valid=valid)
+            for i in range(src_B):
+                for (dec, _, _), k in zip(decs[i], ids[i]):
+                    if dec == self.oc.NEW:
+                        mine[i].append(k)
+        need = max(old[b] + self.run.src[i].n_landmarks for i, b in enumerate(dst))
+        if need > self.run.cap:
+            self.emit("reserve", cap=need + int(rng.integers(0, 40)))
+        self.emit("join", index=index, src_index=0, expect="ok", settle=bool(rng.random() < 0.5 or B > 1 and index is not None))
+        for i, b in enumerate(dst):
+            self.sims[b].in_map += mine[i]
+        self.emit("src_close")
+        # the planted pairs (old landmark, its re-observation), per destination filter
+        planted = {}
+        for i, b in enumerate(dst):
+            assert sorted(mine[i]) == sorted(pools[i]), "a source landmark was not mapped"
+            planted[b] = sorted((l, old[b] + mine[i].index(self.sims[b].in_map[l])) for l in seen[i])
+        gate = self.do_dups(index, splits={b: old[b] for b in dst}, matched=True)
+        assert gate is not None, "no gate keeps the joined map's pairs off its edge"
+        pairs = self.ops[-1][1]["matched"]
+        for b in dst:
+            assert set(map(tuple, pairs[b].tolist())) <= set(planted[b]), "a matched pair that was not planted"
+        open_fuse = rng.random() < 0.6
+        if open_fuse:  # the fuse meets an open window
+            for _ in range(int(rng.integers(1, 3))):
+                self.between()
+        slack = float(rng.choice([0.0, 1e-4]))
+        for b in dst:
+            fu.check_pairs(pairs[b], self.counts()[b])
+            assert fuse_rounds_definite(self.models[b].x, self.models[b].P, pairs[b], slack, self.window), "S of a round is not clearly definite"
+        res = self.emit("fuse", index=index, pairs=pairs, slack=slack, window=self.window,
+                        settle=bool(index is not None and B > 1 or not open_fuse and rng.random() < 0.5))
+        assert [r[1] for r in res] == [len(pairs[b]) for b in dst], "the reference did not fuse every pair"
+        left = {}
+        for b in dst:
+            gone = set(pairs[b][:, 1].tolist())
+            alive = [l for l in range(len(self.sims[b].in_map)) if l not in gone]
+            self.sims[b].in_map = [self.sims[b].in_map[l] for l in alive]
+            left[b] = [alive.index(j) for _, j in planted[b] if j not in gone]  # planted, but not matched: it must not meet traffic
+        if any(len(p) for p in pairs.values()):
+            self.twin_point("fuse")
+        if any(left.values()):
+            keep = {b: np.ones(max(max(self.counts()), 1) if index is None else self.counts()[b], dtype=bool) for b in dst}
+            for b in dst:
+                keep[b][left[b]] = False
+                k = keep[b][:len(self.sims[b].in_map)]
+                self.sims[b].in_map = [w for w, kept in zip(self.sims[b].in_map, k) if kept]
+            self.emit("remove", index=index, keep=keep, settle=bool(index is not None and B > 1 or rng.random() < 0.5))
+        return True
+
+    def draw_ids(self, N, rewrite):
+        rng = self.rng
+        r = rng.random()
+        if r < 0.15:
+            return None  # every landmark in order: a copy
+        if r < (0.22 if rewrite else 0.3) or N == 0:
+            return np.zeros(0, dtype=np.int32)  # the pose and P_RR alone
+        count = int(rng.integers(max(1, N - 8), N + 1)) if rewrite and rng.random() < 0.7 else int(rng.integers(1, N + 1))
+        return shuffled_ids(N, count, seed=int(rng.integers(0, 2 ** 31)))
+
+    def do_extract(self, index, rewrite):
+        """Submap extraction through a scratch handle of another tile count: a probe of one filter, or a rewrite -- the handle
+        replaced by its own marginal (one filter, or the batch form), or filter `index` by a fork of a sibling."""
+        rng, B = self.rng, self.B
+        counts = self.counts()
+        src_index = None
+        if not rewrite:
+            mode, index = "probe", int(rng.integers(0, B)) if index is None else index
+        elif B == 1:
+            mode = "self"
+        elif index is None:
+            mode = "batch"
+        else:
+            mode, src_index = "fork", int(rng.choice([c for c in range(B) if c != index]))
+        which = list(range(B)) if index is None else [index]
+        ids = {b: self.draw_ids(counts[src_index if mode == "fork" else b], rewrite) for b in which}
+        size = lambda b: counts[src_index if mode == "fork" else b] if ids[b] is None else len(ids[b])  # noqa: E731
+        caps = [c for c in SCRATCH_CAPS if c >= max(max(size(b) for b in which), 1) and lm_tiles(c) != lm_tiles(self.run.cap)]
+        if rewrite:
+            for b in which:
+                s = self.sims[src_index] if mode == "fork" else self.sims[b]
+                sel = list(range(len(s.in_map))) if ids[b] is None else ids[b].tolist()
+                if mode == "fork":  # b's hidden world becomes a copy of its sibling's
+                    t = _Sim.__new__(_Sim)
+                    t.world, t.pose, t.offset = s.world, s.pose.copy(), s.offset
+                    self.sims[b] = t
+                self.sims[b].in_map = [s.in_map[l] for l in sel]
+        self.emit("extract", mode=mode, index=index, src_index=src_index, ids=ids, scratch_cap=int(rng.choice(caps)) if mode != "fork" else None,
+                  settle=bool(index is not None and B > 1 or rng.random() < 0.5) and not self.force_open)
+        if rewrite:
+            self.twin_point("extract")
+
+    def rewrite_maps(self, forced=None):
+        """One rewrite or probe of the *_maps deck; forced "state": a state-changing one, "new": a fuse or an extraction."""
+        rng, B = self.rng, self.B
+        if not self.deck:
+            self.deck = [str(k) for k in rng.permutation(MAP_REWRITES + MAP_REWRITES[-3:])]  # (the three newer kinds twice)
+        if forced == "new":
+            kind = str(rng.choice(["fuse", "extract"]))
+        elif forced == "state":
+            kind = str(rng.choice(["remove", "transform", "anchor", "extract"]))
+        else:
+            kind = self.deck.pop()
+        index = 0 if B == 1 else (int(rng.integers(1, B)) if rng.random() < 0.4 and not self.force_open else None)
+        if kind == "dups":
+            self.do_dups(index)
+        elif kind == "fuse":
+            if (forced or rng.random() < 0.75) and self.do_fuse(index):
+                pass
+            elif forced:
+                self.do_extract(index, True)
+            else:  # a fuse of no pair: a no-op, whatever the window holds
+                which = range(B) if index is None else [index]
+                self.emit("fuse", index=index, pairs={b: np.zeros((0, 2), dtype=np.int64) for b in which}, slack=0.0, window=self.window,
+                          settle=bool(index is not None and B > 1 or rng.random() < 0.5))
+        elif kind == "extract":
+            self.do_extract(index, bool(forced or rng.random() < 0.6))
+        else:
+            self.deck.append(kind)
+            n = len(self.ops)
+            self.rewrite()  # (pops it again)
+            if kind in ("remove", "transform", "anchor", "reserve", "join") and any(k == kind for k, _ in self.ops[n:]):
+                self.twin_point(kind)
+        return kind
+
+    def build_maps(self):
+        rng = self.rng
+        twins_left, twin_end, twin_new = 2, -1, False
+        for step in range(N_STEPS):
+            self.traffic()
+            if step == twin_end:
+                self.emit("twin_end")
+            due = twins_left == 2 and step == 20 or twins_left >= 1 and step == 30
+            self.force_open = self.n_open == 0 and step >= 25 and step != twin_end
+            if rng.random() < 0.35 or step in (3, 17) or due or self.force_open:
+                # two twins per sequence, one of them at least behind a fuse or an extraction (the second, if the first was not)
+                self.twin_wish, self.twin_kind = None, None
+                if twins_left and step > twin_end and step + 6 < N_STEPS and (due or rng.random() < 0.4 + 0.03 * step):
+                    self.twin_wish = "any" if twin_new or twins_left == 2 and not due else "new"
+                self.rewrite_maps("new" if due and self.twin_wish == "new" else "state" if due or self.force_open else None)
+                self.twin_wish = None
+                if self.twin_kind:
+                    twins_left, twin_end, twin_new = twins_left - 1, step + 5, twin_new or self.twin_kind in ("fuse", "extract")
+        for b in range(self.B):
+            self.emit("read", index=b)
+        return self.ops
+
     def build(self):
         rng = self.rng
+        if self.maps:
+            return self.build_maps()
         twins_left, twin_end = 2, -1
         for step in range(N_STEPS):
             self.traffic()
@@ -548,7 +927,7 @@ class _Gen:
 def make_sequence(seed, profile):
     """The operations of (seed, profile) as a list of (kind, args): create, load, then N_STEPS steps of traffic with a rewrite or
     a probe about every fifth, then a read of every filter.  Per-filter arguments of the rewrites are dicts keyed by filter index;
-    `index` None is the batch form."""
+    `index` None is the batch form.  The *_maps profiles draw from a deck that holds dups, fuse and extract as well (the module docstring)."""
     return _Gen(seed, profile).build()
 
 

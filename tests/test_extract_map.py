@@ -17,36 +17,14 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from helpers import assert_bitwise, assert_bitwise_symmetric, make_filter, open_window_pair, run_steps, stream_starts  # noqa: E402
+from helpers import (assert_bitwise, assert_bitwise_symmetric, index_state, make_filter, open_window_pair, run_steps, shuffled_ids,  # noqa: E402
+                     stream_starts)
 
 pytestmark = pytest.mark.gpu
 
 SOURCES = [(200, 320), (100, 200)]
 _IP = ctypes.POINTER(ctypes.c_int)
 _DP = ctypes.POINTER(ctypes.c_double)
-
-
-def sel_of(ids):
-    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
-    return np.concatenate([np.arange(3), np.stack([3 + 2 * ids, 4 + 2 * ids], axis=1).reshape(-1)]).astype(np.int64)
-
-
-def index_state(state, ids):
-    """The reference: rows and columns of an exported state."""
-    x, P = state
-    s = sel_of(ids)
-    return x[s].copy(), P[np.ix_(s, s)].copy()
-
-
-def shuffled_ids(N, count, seed):
-    """`count` distinct landmarks of N in shuffled order, the tile edges 0, 31, 32, 63, 64 and the last landmark among them."""
-    rng = np.random.default_rng(seed)
-    must = sorted({l for l in (0, 31, 32, 63, 64, N - 1) if l < N})[:count]
-    rest = [l for l in rng.permutation(N) if l not in must][:count - len(must)]
-    ids = np.array(must + rest, dtype=np.int32)
-    rng.shuffle(ids)
-    assert ids.size == count and np.unique(ids).size == count
-    return ids
 
 
 def fresh(pkg, cap, max_pending=16):

@@ -20,12 +20,12 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import dup_ref as dr  # noqa: E402
 import join_ref as jr  # noqa: E402
-from helpers import REL_TOL, assert_bitwise, assert_state_close, make_filter, run_steps, stream_starts  # noqa: E402
+from helpers import assert_bitwise, assert_state_close, ij, make_filter, run_steps, stream_starts  # noqa: E402
+from helpers import check_duplicates as check  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 CASES = [(31, 64), (32, 64), (33, 64), (100, 128), (180, 200), (280, 320)]
-MARGIN = 1e-3
 
 
 @functools.lru_cache(maxsize=None)
@@ -55,25 +55,6 @@ def open_window_pair(pkg, N, cap, seed, steps):
     db, _ = run_steps(pkg, b, sc, 0, steps, 2)
     assert da == db
     return a, b, planted
-
-
-def ij(pairs):
-    return list(zip(pairs["i"].tolist(), pairs["j"].tolist()))
-
-
-def check(got, x, P, gate=dr.GATE, max_dist=None, split=0, what=""):
-    """A device result (pairs, n_found, n_degenerate) against the reference on the export (x, P); returns the worst d2 error."""
-    pairs, found, degen = got
-    m_gate, m_dist = dr.margins(x, P, gate, max_dist, split)
-    assert m_gate > MARGIN and m_dist > MARGIN, (what, "the reference has a pair on the edge: another seed", m_gate, m_dist)
-    ref, ref_degen = dr.find(x, P, gate, max_dist, split)
-    assert found == len(ref) and degen == ref_degen, (what, found, len(ref), degen, ref_degen)
-    assert ij(pairs) == ij(ref)[:len(pairs)], (what, ij(pairs), ij(ref))
-    if len(pairs) == 0:
-        return 0.0
-    err = np.abs(pairs["d2"] - ref["d2"][:len(pairs)])
-    assert np.all(err <= REL_TOL * np.abs(ref["d2"][:len(pairs)]) + 1e-9), (what, err.max())
-    return float((err / np.maximum(np.abs(ref["d2"][:len(pairs)]), 1e-9)).max())
 
 
 # ---- 1. parity with a window open ---------------------------------------------------------------------

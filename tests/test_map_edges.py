@@ -8,7 +8,16 @@ Every case: a window is left open by a few immediate steps, a witness handle tha
 test held; parity against the NumPy reference (tests/reframe_ref.py, tests/join_ref.py, tests/factor_ref.py; helpers' tolerances) or
 bit for bit where the contract says so (np.delete, theta = 0, the old x old block); bitwise symmetry; and a set_state twin that goes
 on for three steps with a far New landmark, bit for bit -- the check that sees the zeros behind the map (not the places of a
-diagonal tile that are nobody's home, a landmark's own block and the blocks below the diagonal: nothing reads those).  A map that fills its capacity is given room by ekf_reserve first (which must not change a bit)."""
+diagonal tile that are nobody's home, a landmark's own block and the blocks below the diagonal: nothing reads those).  A map that fills its capacity is given room by ekf_reserve first (which must not change a bit).
+
+The same for the three newer map operations.  Fusion (tests/fuse_ref.py, rounds of the handle's window): a pair whose j is alone in
+the last tile, 32 pairs over four rounds that give a whole tile back, and maps of 511 / 512 / 513 landmarks, whose columns of
+3 + 2 N = 1025 / 1027 / 1029 elements end either side of the 1024-element chunk.  Duplicate search (tests/dup_ref.py, the contract
+of tests/test_find_duplicates.py): 0, 1, 2, 63, 64, 65 landmarks and a map that fills its capacity, one planted pair whose later
+landmark is the map's last.  Extraction (NumPy indexing, bit for bit): sources of 0 / 1 / 31 / 32 / 33 / 65 landmarks into a
+destination of another tile count, a destination that held 65 and receives 1, selections of 511 / 512 / 513 landmarks.  And each of
+the three straight behind a window in which a far New landmark has just started a second tile (32 -> 33): they read the settled
+tile layout and must close that window themselves."""
 import os
 import sys
 
@@ -17,12 +26,14 @@ import pytest
 import scipy.linalg
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dup_ref as dr  # noqa: E402
 import factor_ref as fr  # noqa: E402
+import fuse_ref as fu  # noqa: E402
 import join_ref as jr  # noqa: E402
 import map_model as mm  # noqa: E402
 import reframe_ref as rr  # noqa: E402
-from helpers import (ABS_P, REL_TOL, assert_bitwise, assert_bitwise_symmetric, assert_state_close, batch_script, check_joint,  # noqa: E402
-                     open_window_pair, run_steps)
+from helpers import (ABS_P, REL_TOL, assert_bitwise, assert_bitwise_symmetric, assert_state_close, batch_script, check_duplicates,  # noqa: E402
+                     check_joint, ij, index_state, open_window_pair, run_steps, windows_closed)
 
 pytestmark = pytest.mark.gpu
 
@@ -300,4 +311,218 @@ def test_joint_consistency(pkg, pipeline_mode, N, cap):
     assert not np.tril(U, -1).any()
     assert_bitwise(a.get_state(), (x, P), "the call only reads")
     twin_goes_on(pkg, a, "joint consistency N=%d" % N)
+    a.close()
+
+
+# ---- duplicate search, fusion, extraction ------------------------------------------------------------------------
+def witnessed_state(pkg, x, P, cap, seed, new_every=0):
+    """witnessed() for a state of the caller's: two handles loaded with (x, P), the same two immediate steps on both (two Old-type
+    measurements each; new_every: a far New landmark as well), the witness exported and closed."""
+    N = (x.size - 3) // 2
+    M = min(2, N)
+    pair = [pkg.FilterBatch(1, cap, max_pending=WINDOW, log_capacity=4096) for _ in range(2)]
+    sc = pkg.scenarios.steady_script(x, steps=2, M=M, seed=seed, min_separation=1.0)
+    decs = []
+    for f in pair:
+        f.set_state(x, P)
+        decs.append(run_steps(pkg, f, sc, 0, 2, M, new_every=new_every))
+    assert decs[0] == decs[1]
+    a, w = pair
+    before, logs = w.get_state(), (w.stats(), w.decisions())
+    w.close()
+    return a, before, logs
+
+
+def k_pairs(N):
+    return [(0, N - 1), (255, 256)]
+
+
+FUSES = {
+    "33, pair (0, 32): the map loses a tile": (33, 64, [(0, 32)]),
+    "64, the 32 pairs (k, k + 32): four rounds, a whole tile goes": (64, 64, [(k, k + 32) for k in range(32)]),
+    "65, pair (31, 64)": (65, 96, [(31, 64)]),
+    "511: columns of 1025": (511, 520, k_pairs(511)),
+    "512: columns of 1027": (512, 520, k_pairs(512)),
+    "513: columns of 1029": (513, 520, k_pairs(513)),
+}
+
+
+@pytest.mark.parametrize("slack", [0.0, 1e-4])
+@pytest.mark.parametrize("case", list(FUSES))
+def test_fuse(pkg, pipeline_mode, case, slack):
+    N, cap, rows = FUSES[case]
+    pairs = fu.as_pairs(rows)
+    x0, P0 = pkg.scenarios.injected_state(N, seed=800 + N, extent=12.0 * (N / 64.0) ** 0.5 + 8.0)
+    a, before, logs = witnessed_state(pkg, *fu.with_noisy_copies(x0, P0, pairs, seed=801 + N), cap, seed=802 + N)
+    assert a.window == WINDOW
+    closed0 = windows_closed(a)
+    got = a.fuse_landmarks(pairs, slack=slack)
+    assert windows_closed(a) - closed0 <= 1  # the open window; the rounds' passes are the call's own
+    ref = fu.fuse(*before, pairs, slack, WINDOW)
+    assert got == (N - len(rows), len(rows)) and ref[2] == len(rows), (got, ref[2])
+    after = a.get_state()
+    err = assert_state_close(after[0], after[1], ref[0], ref[1], what=case)
+    print("fuse %s, slack %g: %d rounds, max |dx| %.3e, max |dP| / max |P| %.3e" % (case, slack, -(-len(rows) // WINDOW), err[0], err[1]))
+    settled_checks(a, after, logs, N - len(rows))
+    twin_goes_on(pkg, a, case)
+    a.close()
+
+
+def planted_at_the_end(pkg, N, seed):
+    """N landmarks, the last one a planted duplicate (d2 = 3) of a landmark of an earlier tile where there is one: the pair lies
+    across the last tile edge.  dup_ref.with_duplicates without the renumbering; the seed moves on until the copied landmark is one
+    of an earlier tile (a property of the builder's draw alone)."""
+    while True:
+        x, P = pkg.scenarios.injected_state(N - 1, seed=seed, extent=12.0 * (N / 64.0) ** 0.5 + 8.0)
+        x, P, planted = dr.with_duplicates(x, P, targets=(3.0,), seed=seed + 1, permute=False)
+        (i, j, _), = planted
+        assert j == N - 1
+        if i // 32 < j // 32 or j < 33:
+            return x, P, (i, j)
+        seed += 2
+
+
+@pytest.mark.parametrize("N,cap", [(0, 8), (1, 8), (2, 8), (63, 64), (64, 64), (65, 96)])
+def test_find_duplicates(pkg, pipeline_mode, N, cap):
+    """(64, 64) is the map that fills its capacity."""
+    if N >= 2:
+        x, P, pair = planted_at_the_end(pkg, N, seed=900 + N)
+        a, before, logs = witnessed_state(pkg, x, P, cap, seed=950 + N)
+    else:
+        a, before, logs = witnessed(pkg, N, cap, seed=900 + N)
+        pair = None
+    got = a.find_duplicates()
+    worst = check_duplicates(got, *before, what="N=%d" % N)
+    assert len(got[0]) == got[1] and (pair is None and got[1] == 0 or pair in ij(got[0])), (pair, ij(got[0]))
+    again = a.find_duplicates()
+    assert again[0].tobytes() == got[0].tobytes() and again[1:] == got[1:]
+    for split, max_dist in ((max(N - 1, 0), None), (0, 1.0), (N, 0.05)):  # old x last, a Euclidean bound, a split that considers nothing
+        r = a.find_duplicates(split=split, max_dist=max_dist)
+        worst = max(worst, check_duplicates(r, *before, split=split, max_dist=max_dist, what="N=%d split=%d max_dist=%s" % (N, split, max_dist)))
+        if pair is not None and split == N - 1:
+            assert pair in ij(r[0])
+    if pair is not None:  # a gate that ignores P_ij answers something else: another list, or another distance for the planted pair
+        blind, _ = dr.find(before[0], dr.without_cross_blocks(before[1]))
+        d2 = dict(zip(ij(got[0]), got[0]["d2"].tolist()))[pair]
+        assert ij(blind) != ij(got[0]) or abs(dict(zip(ij(blind), blind["d2"].tolist()))[pair] / d2 - 1.0) > 0.1
+    print("find N=%d: %d pairs, worst error of d2 %.3e (relative, floor 1e-9)" % (N, got[1], worst))
+    after = a.get_state()
+    assert_bitwise(after, before, "the call only reads")
+    settled_checks(a, after, logs, N)
+    twin_goes_on(pkg, a, "find N=%d" % N)
+    a.close()
+
+
+def id_lists(N):
+    return {"None": None, "[]": np.zeros(0, dtype=np.int32), "the last only": np.array([N - 1] if N else [], dtype=np.int32),
+            "all reversed": np.arange(N, dtype=np.int32)[::-1].copy()}
+
+
+def extraction_checks(pkg, s, held, logs_s, d, logs_d, ids, what):
+    """d.extract_map(s, ids) and s.get_submap(ids) against NumPy indexing of what the source's witness exported; the source only read."""
+    want = index_state(held, ids)
+    n = (want[0].size - 3) // 2
+    assert d.extract_map(s, ids) == n, what
+    got = d.get_state()
+    assert_bitwise(got, want, "%s: ekf_extract_map" % what)
+    assert_bitwise(s.get_submap(np.arange((held[0].size - 3) // 2, dtype=np.int32) if ids is None else ids), want, "%s: ekf_get_submap" % what)
+    settled_checks(d, got, logs_d, n)
+    after_s = s.get_state()
+    assert_bitwise(after_s, held, "%s: the source" % what)
+    settled_checks(s, after_s, logs_s, (held[0].size - 3) // 2)
+
+
+@pytest.mark.parametrize("which", ["None", "[]", "the last only", "all reversed"])
+@pytest.mark.parametrize("N,cap,cap_d", [(0, 8, 40), (1, 8, 40), (31, 32, 64), (32, 32, 96), (33, 64, 96), (65, 96, 200)])
+def test_extract(pkg, pipeline_mode, N, cap, cap_d, which):
+    """A source with its window open into a fresh destination of another tile count."""
+    assert mm.lm_tiles(cap) != mm.lm_tiles(cap_d)
+    ids = id_lists(N)[which]
+    s, held, logs_s = witnessed(pkg, N, cap, seed=1000 + N)
+    d = pkg.FilterBatch(1, cap_d, max_pending=WINDOW, log_capacity=4096)
+    extraction_checks(pkg, s, held, logs_s, d, (d.stats(), d.decisions()), ids, "N=%d ids %s" % (N, which))
+    s.close()
+    twin_goes_on(pkg, d, "extract N=%d ids %s" % (N, which))
+    d.close()
+
+
+@pytest.mark.parametrize("Ns,ids", [(33, [32]), (1, [0]), (65, [64]), (33, None)])
+def test_extract_into_a_destination_that_held_65(pkg, pipeline_mode, Ns, ids):
+    """Three tile rows, a window open on them, replaced by one landmark (or by 33): the tiles of the larger map are zeroed."""
+    d, _, logs_d = witnessed(pkg, 65, 96, seed=1100)
+    s, held, logs_s = witnessed(pkg, Ns, 64 if Ns <= 33 else 128, seed=1101 + Ns)
+    extraction_checks(pkg, s, held, logs_s, d, logs_d, None if ids is None else np.array(ids, dtype=np.int32), "65 <- %s of %d" % (ids, Ns))
+    s.close()
+    twin_goes_on(pkg, d, "65 <- %s of %d" % (ids, Ns))
+    d.close()
+
+
+@pytest.mark.parametrize("Ns,count", [(512, 511), (512, 512), (513, 513)])
+def test_extract_across_the_chunk(pkg, pipeline_mode, Ns, count):
+    """Selections of 511 / 512 / 513 landmarks: 3 + 2 count = 1025 / 1027 / 1029 (a source of 512 has no 513 to give: that one is
+    taken from 513), shuffled, into a destination of another tile count."""
+    s, held, logs_s = witnessed(pkg, Ns, 520, seed=1200 + Ns)
+    ids = np.random.default_rng(1201 + count).permutation(Ns).astype(np.int32)[:count]
+    d = pkg.FilterBatch(1, 600, max_pending=WINDOW, log_capacity=4096)
+    extraction_checks(pkg, s, held, logs_s, d, (d.stats(), d.decisions()), ids, "%d of %d" % (count, Ns))
+    s.close()
+    twin_goes_on(pkg, d, "%d of %d" % (count, Ns))
+    d.close()
+
+
+# ---- behind a window in which the map grew into a new tile ---------------------------------------------------------
+def grown(pkg):
+    """A handle of 32 landmarks (capacity 64) whose open window holds a far New landmark: 33 landmarks, the 33rd in a tile row that the
+    settled layout does not have yet.  Nothing is read from the handle; its witness says what it holds."""
+    x, P = pkg.scenarios.injected_state(32, seed=1300, extent=12.0 * 0.5 ** 0.5 + 8.0)
+    a, before, logs = witnessed_state(pkg, x, P, 64, seed=1301, new_every=2)
+    assert before[0].size == 3 + 2 * 33 and logs[0][0]["n_new"] == 1
+    assert windows_closed(a) == 0  # (a host counter: five slots of eight, the New landmark among them, still deferred)
+    return a, before, logs
+
+
+def test_find_duplicates_behind_a_grown_window(pkg, pipeline_mode):
+    a, before, logs = grown(pkg)
+    got = a.find_duplicates(gate=1e12)  # every pair passes: the 32 pairs of the new landmark are in the list
+    check_duplicates(got, *before, gate=1e12, what="grown window")
+    assert got[1] == 33 * 32 // 2 and ij(got[0])[-1] == (31, 32)
+    check_duplicates(a.find_duplicates(split=32), *before, split=32, what="grown window, old x new")
+    after = a.get_state()
+    assert_bitwise(after, before, "the call only reads")
+    settled_checks(a, after, logs, 33)
+    twin_goes_on(pkg, a, "find behind a grown window")
+    a.close()
+
+
+def test_fuse_behind_a_grown_window(pkg, pipeline_mode):
+    a, before, logs = grown(pkg)
+    pairs = fu.as_pairs([(31, 32), (0, 5)])
+    got = a.fuse_landmarks(pairs, slack=1e-4)
+    ref = fu.fuse(*before, pairs, 1e-4, WINDOW)
+    assert got == (31, 2) and ref[2] == 2
+    after = a.get_state()
+    err = assert_state_close(after[0], after[1], ref[0], ref[1], what="grown window")
+    print("fuse behind a grown window: max |dx| %.3e, max |dP| / max |P| %.3e" % err)
+    settled_checks(a, after, logs, 31)
+    twin_goes_on(pkg, a, "fuse behind a grown window")
+    a.close()
+
+
+def test_extract_behind_a_grown_window(pkg, pipeline_mode):
+    a, before, logs = grown(pkg)
+    ids = np.arange(33, dtype=np.int32)[::-1].copy()
+    d = pkg.FilterBatch(1, 96, max_pending=WINDOW, log_capacity=4096)
+    logs_d = (d.stats(), d.decisions())
+    assert d.extract_map(a, ids) == 33  # the first call on the handle: it closes the window itself
+    got = d.get_state()
+    assert_bitwise(got, index_state(before, ids), "ekf_extract_map behind a grown window")
+    settled_checks(d, got, logs_d, 33)
+    d.close()
+    a.close()
+    a, before, logs = grown(pkg)
+    assert_bitwise(a.get_submap(ids), index_state(before, ids), "ekf_get_submap behind a grown window")
+    after = a.get_state()
+    assert_bitwise(after, before, "the call only reads")
+    settled_checks(a, after, logs, 33)
+    twin_goes_on(pkg, a, "get_submap behind a grown window")
     a.close()

@@ -1,7 +1,12 @@
 """The sequence generator and the host model of tests/map_model.py, without a GPU: what tests/test_map_sequences.py relies on when
 it replays every committed seed without skipping a seed or a step.  Determinism, coverage of the operations and of the tile-edge
 branches, decision margins (no measurement within REL_TOL of a gate, so the library and the model, which agree to about 1e-12, cannot
-decide differently), and the error of the float64 references themselves against the same expressions in np.longdouble."""
+decide differently), and the error of the float64 references themselves against the same expressions in np.longdouble.
+For the *_maps profiles also: what they must cover of the duplicate search, the fusion and the extraction; that every `dups` op meets
+the precondition under which its LIST may be compared (margins to the gate and to max_dist, no near-degenerate pair) and every `fuse`
+op's list is one the library accepts, with every round's S clearly positive definite; fuse_ref.fuse against its np.longdouble
+restatement.  The four older profiles generate what they generated before the *_maps profiles were appended (compared once against the
+previous tests/map_model.py, value for value)."""
 import os
 import sys
 
@@ -9,12 +14,15 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fuse_ref as fu  # noqa: E402
 import join_ref as jr  # noqa: E402
 import map_model as mm  # noqa: E402
 import reframe_ref as rr  # noqa: E402
 from helpers import REL_TOL, assert_state_close  # noqa: E402
 
 ALL = [(p, s) for p in mm.PROFILES for s in mm.SEEDS[p]]
+OLD_PROFILES = mm.PROFILES[:4]
+TRAFFIC = ("propagate", "update", "compass", "src_propagate", "src_update")
 
 
 @pytest.fixture(scope="module")
@@ -31,7 +39,8 @@ def replay(ops):
 
 
 def test_seed_lists():
-    assert [len(mm.SEEDS[p]) for p in mm.PROFILES] == [8, 8, 8, 6]
+    assert mm.PROFILES[:4] == ("solo", "chain", "chain_wgs", "batch") and mm.MAP_PROFILES == ("solo_maps", "chain_maps", "batch_maps")
+    assert [len(mm.SEEDS[p]) for p in mm.PROFILES] == [8, 8, 8, 6, 6, 6, 6]
     assert all(len(set(s)) == len(s) for s in mm.SEEDS.values())
 
 
@@ -48,22 +57,32 @@ def test_profile_parameters(sequences, profile):
         ops = sequences[profile, seed]
         c = ops[0][1]
         assert ops[0][0] == "create"
-        if profile == "solo":
+        maps, base = profile in mm.MAP_PROFILES, profile.replace("_maps", "")
+        if base == "solo":
             assert 40 <= c["cap"] <= 256 and c["window"] in mm.WINDOWS and c["B"] == 1 and c["wgs"] is None
-        elif profile == "chain":
+        elif base == "chain":
             assert 257 <= c["cap"] <= 700 and c["B"] == 1 and c["wgs"] is None
-        elif profile == "chain_wgs":
+        elif base == "chain_wgs":
             assert c["cap"] <= 120 and 2 <= c["wgs"] <= 4 and c["B"] == 1
         else:
             assert 3 <= c["B"] <= 5
             loaded = {a["index"]: (a["x"].size - 3) // 2 for k, a in ops if k == "load"}
             assert len(loaded) == c["B"] - 1 and len(set(loaded.values())) == len(loaded)  # one starts empty, each its own count
-        assert sum(1 for k, _ in ops if k == "propagate") == mm.N_STEPS
+        if maps:  # (a fuse may have propagations of its own in front of it)
+            assert sum(1 for k, _ in ops if k == "propagate") >= mm.N_STEPS
+            assert all(a["window"] == c["window"] for k, a in ops if k == "fuse")
+            assert all(a["scratch_cap"] in mm.SCRATCH_CAPS for k, a in ops if k == "extract" and a["mode"] != "fork")
+            behind = [ops[i - 1] for i, (k, _) in enumerate(ops) if k == "twin_begin"]
+            assert all(k != "extract" or a["mode"] != "probe" for k, a in behind)
+            assert any(k in ("fuse", "extract") for k, _ in behind), seed  # one twin at least goes on behind a fuse or an extraction
+        else:
+            assert sum(1 for k, _ in ops if k == "propagate") == mm.N_STEPS
+            assert not any(k in ("dups", "fuse", "extract") for k, _ in ops)
         assert sum(1 for k, _ in ops if k == "twin_begin") == sum(1 for k, _ in ops if k == "twin_end") == 2
         assert all(a["cap"] in mm.SRC_CAPS for k, a in ops if k == "src_create")
 
 
-@pytest.mark.parametrize("profile", mm.PROFILES)
+@pytest.mark.parametrize("profile", OLD_PROFILES)
 def test_coverage(sequences, profile):
     count = dict.fromkeys(mm.KINDS + ("join_refused", "twin", "theta_0", "across_256", "single_index", "open"), 0)
     aligned_joins = tile_drops = removed_all = 0
@@ -109,6 +128,112 @@ def test_coverage(sequences, profile):
         assert count["single_index"] >= 5
 
 
+@pytest.mark.parametrize("profile", mm.MAP_PROFILES)
+def test_coverage_of_the_map_profiles(sequences, profile):
+    count = dict.fromkeys(mm.MAP_KINDS + ("twin", "open", "single_index", "multi_round", "nine_in_window_8", "fuse_open", "extract_open", "fuse_tile_drop",
+                                          "fuse_empty", "dups_split", "dups_max_dist", "dups_matched", "ids_empty", "ids_none", "extract_rewrite", "across_256"), 0)
+    scratch, modes = set(), set()
+    for seed in mm.SEEDS[profile]:
+        last, open_here = None, 0
+        for (kind, a), run, before, cap, res in replay(sequences[profile, seed]):
+            B = len(before)
+            which = list(range(B)) if a.get("index") is None else [a["index"]]
+            changes = kind in ("remove", "transform", "anchor", "join", "fuse") or kind == "extract" and a["mode"] != "probe"
+            behind_open = changes and not a["settle"] and last in TRAFFIC
+            open_here += behind_open
+            last = kind
+            if kind in count and not (kind == "join" and a["expect"] != "ok"):
+                count[kind] += 1
+            count["twin"] += kind == "twin_begin"
+            count["across_256"] += kind == "reserve" and cap <= 256 < run.cap
+            if kind in ("dups", "fuse", "extract") and B > 1 and a["index"] is not None:
+                count["single_index"] += 1
+            if kind == "dups":
+                count["dups_split"] += any(v > 0 for v in a["split"].values())
+                count["dups_max_dist"] += a["max_dist"] is not None
+                count["dups_matched"] += a["matched"] is not None
+            if kind == "fuse":
+                longest = max(len(p) for p in a["pairs"].values())
+                count["fuse_empty"] += longest == 0
+                count["multi_round"] += longest > a["window"]
+                count["nine_in_window_8"] += a["window"] == 8 and longest >= 9
+                count["fuse_open"] += behind_open and longest > 0
+                count["fuse_tile_drop"] += any(mm.lm_tiles(res[i][0]) < mm.lm_tiles(before[b]) for i, b in enumerate(which))
+            if kind == "extract":
+                count["ids_none"] += any(v is None for v in a["ids"].values())
+                count["ids_empty"] += any(v is not None and len(v) == 0 for v in a["ids"].values())
+                count["extract_rewrite"] += a["mode"] != "probe"
+                count["extract_open"] += behind_open
+                modes.add(a["mode"])
+                if a["mode"] != "fork":
+                    scratch.add(a["scratch_cap"] > 256)
+                    assert mm.lm_tiles(a["scratch_cap"]) != mm.lm_tiles(cap)  # a scratch of another tile count
+        count["open"] += open_here
+        assert open_here >= 1, seed
+    print(profile, count, "scratch above 256", scratch, "modes", modes)
+    for k in mm.MAP_KINDS:
+        assert count[k] >= 5, (k, count[k])
+    assert count["twin"] == 2 * len(mm.SEEDS[profile]) and count["open"] >= 5
+    for k in ("multi_round", "nine_in_window_8", "fuse_open", "extract_open", "fuse_tile_drop", "fuse_empty", "dups_split", "dups_max_dist", "dups_matched", "ids_empty",
+              "ids_none", "extract_rewrite"):
+        assert count[k] >= 1, (k, count)
+    assert scratch == {False, True}  # scratch capacities on both sides of 256
+    if profile == "solo_maps":
+        assert count["across_256"] >= 1 and modes == {"probe", "self"}
+    if profile == "batch_maps":
+        assert count["single_index"] >= 5 and modes == {"probe", "fork", "batch"}
+
+
+@pytest.mark.parametrize("profile,seed", [ps for ps in ALL if ps[0] in mm.MAP_PROFILES])
+def test_dups_and_fuse_preconditions(sequences, profile, seed):
+    """Every `dups` op: on the model's state no pair within DUP_MARGIN of the gate or of max_dist and no near-degenerate pair, which
+    is what entitles the replay to compare the library's LIST with the model's.  Every `fuse` op: a list the library accepts (i < j < N,
+    no landmark twice), every pair fused by the reference, every round's S clearly positive definite."""
+    n_dups = n_fuse = 0
+    run = mm.ModelRunner()
+    for op in sequences[profile, seed]:
+        kind, a = op
+        which = list(range(len(run.models))) if a.get("index") is None else [a["index"]]
+        if kind == "dups":
+            assert a["gate"] in mm.DUP_GATES
+            for b in which:
+                m = run.models[b]
+                assert 0 <= a["split"][b] <= m.n_landmarks
+                assert mm.dups_precondition(m.x, m.P, a["gate"], a["max_dist"], a["split"][b]), (a["gate"], b)
+                assert all(not mm.dups_precondition(m.x, m.P, g, a["max_dist"], a["split"][b]) for g in mm.DUP_GATES[:mm.DUP_GATES.index(a["gate"])]) or len(which) > 1
+            n_dups += 1
+        if kind == "fuse":
+            for b in which:
+                m = run.models[b]
+                fu.check_pairs(a["pairs"][b], m.n_landmarks)
+                assert mm.fuse_rounds_definite(m.x, m.P, a["pairs"][b], a["slack"], a["window"])
+            assert a["slack"] in (0.0, 1e-4)
+            n_fuse += 1
+        res = run.step(op)
+        if kind == "fuse":
+            assert [r[1] for r in res] == [len(a["pairs"][b]) for b in which]
+    print("%s seed %d: %d dups, %d fuse ops" % (profile, seed, n_dups, n_fuse))
+
+
+def test_model_fuses_in_rounds_of_the_window():
+    """MapModel.fuse takes the pairs in rounds of the op's window, as the handle does.  Conditioning round after round equals
+    conditioning at once up to rounding (about 1e-15 on the sequences' states), so no state comparison can tell one round size from
+    another; where a round meets an exact copy (S singular with slack 0) the number of fused pairs can."""
+    rng = np.random.default_rng(5)
+    n = 3 + 2 * 12
+    A = rng.normal(size=(n, n))
+    x, P = fu.with_exact_copy(rng.normal(size=n) * 5.0, A @ A.T + n * np.eye(n), 3)  # landmark 12 is landmark 3 again
+    ij = [(0, 6), (1, 7), (2, 8), (3, 12), (4, 9)]
+    for window, want in ((3, (10, 3)), (2, (11, 2)), (1, (10, 3)), (4, (13, 0)), (8, (13, 0))):
+        assert mm.MapModel(x, P).fuse(ij, 0.0, window) == want, window
+    m = mm.MapModel(x, P)
+    assert m.fuse(ij, 1e-4, 3) == (8, 5)
+    run = mm.ModelRunner()
+    run.step(("create", dict(B=1, cap=16, window=3, wgs=None)))
+    run.step(("load", dict(index=0, x=x, P=P)))
+    assert run.step(("fuse", dict(index=0, pairs={0: np.array(ij)}, slack=0.0, window=3, settle=True))) == [(10, 3)]
+
+
 @pytest.mark.parametrize("profile,seed", ALL)
 def test_decision_margins(sequences, profile, seed):
     """Every accepted or rejected measurement of the sequence is at least REL_TOL (relative) away from both gates."""
@@ -123,12 +248,12 @@ def test_decision_margins(sequences, profile, seed):
 def test_reference_precision(sequences, profile, seed):
     """The float64 references against np.longdouble restatements of the dense Jacobian forms, on every state the sequence meets, held
     to the tolerance the GPU comparison uses: the reference's own error is far below it (the maxima are printed)."""
-    worst = {"rigid": [0.0, 0.0, 0], "anchor": [0.0, 0.0, 0], "join": [0.0, 0.0, 0]}
+    worst = {"rigid": [0.0, 0.0, 0], "anchor": [0.0, 0.0, 0], "join": [0.0, 0.0, 0], "fuse": [0.0, 0.0, 0]}
     ld = np.longdouble
     run = mm.ModelRunner()
     for op in sequences[profile, seed]:
         kind, a = op
-        if kind in ("transform", "anchor", "join") and a.get("expect", "ok") == "ok":
+        if kind in ("transform", "anchor", "join", "fuse") and a.get("expect", "ok") == "ok":
             M = run.models
             pairs = [(b, b) for b in range(len(M))] if a["index"] is None else [(a["index"], a.get("src_index", 0))]
             want = {}
@@ -139,6 +264,8 @@ def test_reference_precision(sequences, profile, seed):
                     want[b] = rr.apply_dense(x, P, lambda v, dtype: rr.rigid_g(v, f, dtype), lambda v, dtype: rr.rigid_J(v, f, dtype), dtype=ld)
                 elif kind == "anchor":
                     want[b] = rr.apply_dense(x, P, rr.anchor_g, rr.anchor_J, dtype=ld)
+                elif kind == "fuse":
+                    want[b] = fu.fuse_extended(x, P, a["pairs"][b], a["slack"], a["window"])[:2]
                 else:
                     want[b] = jr.join(x, P, run.src[s].x, run.src[s].P, dtype=ld)
             run.step(op)

@@ -16,6 +16,17 @@ decisions must be bitwise equal, which is the only check that sees what a rewrit
 grow into).  It cannot see the places of a diagonal tile that are nobody's home (a landmark's own block, whose home is D, and the
 blocks below the diagonal): no kernel and no export reads them, the dense pass only updates each from itself.
 
+The *_maps profiles (solo_maps, chain_maps, batch_maps) add the three newer map operations to the same mix.  `dups`:
+ekf_find_duplicates behind whatever the last call left (nothing read in front of it unless `settle`), held to the contract of
+tests/test_find_duplicates.py against tests/dup_ref.py on the export (helpers.check_duplicates) and, list and counts, to the model's
+own answer; twice the same bytes; the handle unchanged.  `fuse`: ekf_fuse_landmarks with the one-to-one matching of the duplicates
+that a join of re-observed landmarks planted in the map the filter built -- the `dups` op in front of it asserts that the device's
+own list gives that matching --, often behind an open window, in rounds of the handle's window, against tests/fuse_ref.py; every
+check a rewrite gets.  `extract`: a scratch handle of another tile count, as a probe (ekf_extract_map and ekf_get_submap are NumPy
+indexing of the export, bit for bit) or as a rewrite: the handle replaced by its own shuffled marginal through the scratch, every
+filter of a batch by ekf_batch_extract_map, or one filter by a fork of a sibling.  At least one of the two twins of such a sequence
+goes on behind a fuse or an extraction.  No more than three handles are open at any time (tests/test_extract_map.py says why).
+
 In the chain_wgs profile EKF_CHAIN_WGS is set for the whole test, which keeps the one-workgroup kernel out of every handle: sources
 and twins run the chain kernel there too; "a source of the other kernel family" happens in the solo and chain profiles."""
 import os
@@ -26,12 +37,12 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import map_model as mm  # noqa: E402
-from helpers import (ABS_P, REL_TOL, assert_bitwise, assert_bitwise_symmetric, assert_state_close, check_joint,  # noqa: E402
-                     stream_starts, windows_closed)
+from helpers import (ABS_P, REL_TOL, assert_bitwise, assert_bitwise_symmetric, assert_state_close, check_duplicates, check_joint,  # noqa: E402
+                     ij, index_state, stream_starts, windows_closed)
 
 pytestmark = pytest.mark.gpu
 
-REWRITES = ("remove", "transform", "anchor", "join", "reserve")
+REWRITES = ("remove", "transform", "anchor", "join", "reserve", "fuse", "extract")  # (an extract of mode "probe" is none)
 TRAFFIC = ("propagate", "update", "compass", "src_propagate", "src_update")
 WORST = {}  # profile -> the largest errors seen so far in this session (printed behind every sequence)
 
@@ -52,7 +63,37 @@ def per_filter(d, B, width, fill):
     return arr
 
 
-def apply(pkg, h, src, op):
+def extract(pkg, h, a, counts):
+    """An `extract` op on handle h: (new landmark counts, what the scratch handle held, ekf_get_submap's answer for a probe).  The
+    scratch lives inside the call."""
+    mode, b, ids = a["mode"], a["index"], a["ids"]
+    if mode == "fork":
+        return [h.extract_map(h, ids[b], index=b, src_index=a["src_index"])], None, None
+    s = pkg.FilterBatch(h.batch if mode == "batch" else 1, a["scratch_cap"], max_pending=16, log_capacity=4096)
+    try:
+        sub = None
+        if mode == "batch":
+            if all(v is None for v in ids.values()):
+                n = s.batch_extract_map(h)
+            else:  # (the batch form has one NULL for all: a filter copied whole lists every landmark)
+                n = s.batch_extract_map(h, [np.arange(counts[c], dtype=np.int32) if ids[c] is None else ids[c] for c in range(h.batch)])
+        else:
+            n = [s.extract_map(h, ids[b], index=0, src_index=b)]
+        held = [s.get_state(c) for c in range(s.batch)]
+        assert [int(v) for v in n] == [(st[0].size - 3) // 2 for st in held] == [int(v) for v in s.num_landmarks()]
+        assert not any(st[k] for st in s.stats() for k in ("n_new", "n_old", "n_ignore")) and not any(s.decisions(c) for c in range(s.batch))
+        if mode == "probe":
+            sub = h.get_submap(np.arange(counts[b], dtype=np.int32) if ids[b] is None else ids[b], index=b)
+        elif mode == "batch":
+            n = h.batch_extract_map(s)
+        else:
+            n = [h.extract_map(s)]
+        return [int(v) for v in n], held, sub
+    finally:
+        s.close()
+
+
+def apply(pkg, h, src, op, counts=None):
     """One operation on handle h (the handle under test or its twin); returns what the library answered."""
     kind, a = op
     B = h.batch
@@ -95,6 +136,18 @@ def apply(pkg, h, src, op):
         return h.landmark_covs(a["index"])
     elif kind == "read":
         return h.get_state(a["index"])
+    elif kind == "dups":
+        if a["index"] is None:
+            return h.find_duplicates(a["gate"], a["max_dist"], split=[a["split"][b] for b in range(B)], index=None)
+        return [h.find_duplicates(a["gate"], a["max_dist"], split=a["split"][a["index"]], index=a["index"])]
+    elif kind == "fuse":
+        assert h.window == a["window"], (h.window, a["window"])  # the round size the model fuses with
+        if a["index"] is None:
+            n, fused = h.fuse_landmarks([a["pairs"][b] for b in range(B)], slack=a["slack"], index=None)
+            return [(int(n[b]), int(fused[b])) for b in range(B)]
+        return [h.fuse_landmarks(a["pairs"][a["index"]], slack=a["slack"], index=a["index"])]
+    elif kind == "extract":
+        return extract(pkg, h, a, counts)
     else:
         raise ValueError(kind)
     return None
@@ -115,8 +168,8 @@ class Replay:
         self.twin_decs = ([], [])
         self.run = mm.ModelRunner()
         self.run.step(ops[0])
-        self.err = {"x": 0.0, "P": 0.0, "joint": 0.0, "covs": 0.0}
-        self.n_twins = self.n_bitwise = self.n_open = self.n_live = 0
+        self.err = {"x": 0.0, "P": 0.0, "d2": 0.0, "joint": 0.0, "covs": 0.0}
+        self.n_twins = self.n_twins_new = self.n_bitwise = self.n_open = self.n_live = 0
         self.want_log, self.want_src_log = [[] for _ in range(self.B)], []
         self.last = None  # the kind of the last library call on the handle
 
@@ -158,9 +211,11 @@ class Replay:
         kind, a = op
         pkg, f, B = self.pkg, self.f, self.B
         what = "op %d (%s)" % (i, kind)
+        prev = self.last
         if kind in ("twin_begin", "twin_end"):
             self.last = kind  # (both export the state)
         if kind == "twin_begin":
+            self.n_twins_new += prev in ("fuse", "extract")  # (the generator starts none behind a probe)
             states = self.export()
             self.twin = pkg.FilterBatch(B, f.capacity, max_pending=self.window, log_capacity=4096)
             for b in range(B):
@@ -196,11 +251,13 @@ class Replay:
             return
 
         which = list(range(B)) if a.get("index") is None else [a["index"]]
-        rewrite = kind in REWRITES
+        rewrite = kind in REWRITES and not (kind == "extract" and a["mode"] == "probe")
         settle = bool(a.get("settle")) or kind == "joint" or (kind == "reserve" and i % 2 == 0)
         # a rewrite that is not `settle` meets the handle (and a join its source) as the last immediate call left it: the window open,
         # the streaming launch of a one-filter handle live -- nothing is read in front of it, reading the counters would stop the launch
         before = self.export() if settle else None
+        if settle and kind == "fuse" and self.twin is not None and not any(len(p) for p in a["pairs"].values()):
+            self.export(self.twin)  # (a fuse of no pair leaves an open window open: the twin's window ends where the handle's does)
         src_before = self.export(self.src) if (kind == "join" and settle) else None
         if rewrite and settle:
             logs0 = self.logs(f)
@@ -208,13 +265,13 @@ class Replay:
         if rewrite and not settle and self.last in TRAFFIC:
             self.n_open += 1
             self.n_live += stream_starts(f)[0] > 0  # (host counters only: this handle streams its immediate calls)
-        if kind == "covs":
+        if kind in ("covs", "fuse"):
             closed0 = windows_closed(f)
         counts0 = [m.n_landmarks for m in self.run.models]
 
-        got = apply(pkg, f, self.src, op)
+        got = apply(pkg, f, self.src, op, counts0)
         if self.twin is not None:
-            got_twin = apply(pkg, self.twin, self.src, op)
+            got_twin = apply(pkg, self.twin, self.src, op, counts0)
             if kind == "update":
                 self.twin_decs[0].extend(got), self.twin_decs[1].extend(got_twin)
         want = self.run.step(op)
@@ -240,10 +297,39 @@ class Replay:
             assert again.tobytes() == got.tobytes(), what  # an unchanged state: the same bits
             for b in range(B):
                 assert_bitwise(f.get_state(b), before[b], "%s: the call only reads, filter %d" % (what, b))
+        elif kind == "dups":
+            after = self.export()
+            again = apply(pkg, f, self.src, op)
+            assert [(r[0].tobytes(), r[1], r[2]) for r in again] == [(r[0].tobytes(), r[1], r[2]) for r in got], what  # an unchanged state: the same bits
+            for k, b in enumerate(which):
+                e = check_duplicates(got[k], *after[b], gate=a["gate"], max_dist=a["max_dist"], split=a["split"][b], what="%s, filter %d" % (what, b))
+                self.err["d2"] = max(self.err["d2"], e)
+                assert len(got[k][0]) == got[k][1] and (ij(got[k][0]), got[k][1], got[k][2]) == want[k], (what, b, got[k], want[k])
+                if a["matched"] is not None:  # what the fuse behind this search is given: the device's own list gives it too
+                    assert pkg.duplicate_matching(got[k][0], counts0[b])[["i", "j"]].tolist() == [tuple(p) for p in a["matched"][b].tolist()], (what, b)
+            for b in range(B):
+                self.compare(b, what, after[b])
+                if settle:
+                    assert_bitwise(after[b], before[b], "%s: the call only reads, filter %d" % (what, b))
+        elif kind == "extract" and not rewrite:
+            b, (_, held, sub) = a["index"], got
+            after = self.export()
+            ref = index_state(after[b], a["ids"][b])
+            assert_bitwise(held[0], ref, "%s: ekf_extract_map into the scratch" % what)
+            assert_bitwise(sub, ref, "%s: ekf_get_submap" % what)
+            for c in range(B):
+                self.compare(c, what, after[c])
+                if settle:
+                    assert_bitwise(after[c], before[c], "%s: the call only reads, filter %d" % (what, c))
         self.last = kind
         if not rewrite:
             return
 
+        held = None
+        if kind == "extract":
+            got, held, _ = got
+        if kind == "fuse":  # the rounds' passes are the call's own: at most the open window was closed, none on a settled handle
+            assert windows_closed(f) - closed0 <= (0 if settle or not any(len(p) for p in a["pairs"].values()) else 1), what
         self.check_logs(f, self.want_log, what)  # counters and decision log do not move
         if kind == "join":
             self.check_logs(self.src, self.want_src_log, what + ", source")
@@ -272,6 +358,9 @@ class Replay:
                     assert_bitwise(s, src_before[b], "%s: the source, filter %d" % (what, b))
                 m = self.run.src[b]
                 assert_state_close(s[0], s[1], m.x, m.P, what="%s: the source, filter %d" % (what, b))
+        if held is not None:  # through the scratch and back: what it held is what the handle holds now
+            for k, b in enumerate(which):
+                assert_bitwise(after[b], held[k], "%s: the scratch handle, filter %d" % (what, b))
         if not settle:
             return
         self.n_bitwise += 1
@@ -286,6 +375,10 @@ class Replay:
             elif kind == "join":
                 e = 3 + 2 * counts0[b]
                 assert np.array_equal(after[b][1][3:e, 3:e], before[b][1][3:, 3:]) and np.array_equal(after[b][0][3:e], before[b][0][3:]), what
+            elif kind == "fuse" and not len(a["pairs"][b]):
+                assert_bitwise(after[b], before[b], "%s: no pair, filter %d" % (what, b))
+            elif kind == "extract":  # no arithmetic: the bits of the export, indexed
+                assert_bitwise(after[b], index_state(before[a["src_index"] if a["mode"] == "fork" else b], a["ids"][b]), "%s: filter %d" % (what, b))
 
 
 def run_sequence(pkg, monkeypatch, profile, seed):
@@ -295,16 +388,16 @@ def run_sequence(pkg, monkeypatch, profile, seed):
         for i, op in enumerate(ops[1:], 1):
             r.step(i, op)
         assert r.twin is None and r.src is None
-        assert r.n_twins == 2 and r.n_open >= 1
+        assert r.n_twins == 2 and r.n_open >= 1 and (profile not in mm.MAP_PROFILES or r.n_twins_new >= 1)
     finally:
         r.close()
     print("%s seed %d: %d ops, %d twins, %d exported rewrites, %d behind open traffic (%d on a streaming handle); max |dx| %.3e, "
-          "max |dP| / max |P| %.3e, joint worst %.3e, covs %.3e"
-          % (profile, seed, len(ops), r.n_twins, r.n_bitwise, r.n_open, r.n_live, r.err["x"], r.err["P"], r.err["joint"], r.err["covs"]))
+          "max |dP| / max |P| %.3e, d2 %.3e, joint worst %.3e, covs %.3e"
+          % (profile, seed, len(ops), r.n_twins, r.n_bitwise, r.n_open, r.n_live, r.err["x"], r.err["P"], r.err["d2"], r.err["joint"], r.err["covs"]))
     w = WORST.setdefault(profile, dict.fromkeys(r.err, 0.0))
     for k in w:
         w[k] = max(w[k], r.err[k])
-    print("%s, worst so far: max |dx| %.3e, max |dP| / max |P| %.3e, joint %.3e, covs %.3e" % (profile, w["x"], w["P"], w["joint"], w["covs"]))
+    print("%s, worst so far: max |dx| %.3e, max |dP| / max |P| %.3e, d2 %.3e, joint %.3e, covs %.3e" % (profile, w["x"], w["P"], w["d2"], w["joint"], w["covs"]))
 
 
 @pytest.mark.parametrize("seed", mm.SEEDS["solo"])
@@ -330,3 +423,23 @@ def test_batch_sequences(pkg, monkeypatch, pipeline_mode, seed):
     """Three to five filters of one handle, each with its own landmark count; the batch forms with masks, and single-index calls on a
     filter b > 0 that must leave the others bit for bit."""
     run_sequence(pkg, monkeypatch, "batch", seed)
+
+
+@pytest.mark.parametrize("seed", mm.SEEDS["solo_maps"])
+def test_solo_maps_sequences(pkg, monkeypatch, pipeline_mode, seed):
+    """The solo profile with duplicate searches, join -> find -> fuse on the map the filter built, and extractions through a scratch
+    handle of another tile count (a probe, or the handle replaced by its own shuffled marginal)."""
+    run_sequence(pkg, monkeypatch, "solo_maps", seed)
+
+
+@pytest.mark.parametrize("seed", mm.SEEDS["chain_maps"])
+def test_chain_maps_sequences(pkg, monkeypatch, pipeline_mode, seed):
+    """The same on the several-workgroup chain kernel (capacity 257-700), scratch handles on either side of 256."""
+    run_sequence(pkg, monkeypatch, "chain_maps", seed)
+
+
+@pytest.mark.parametrize("seed", mm.SEEDS["batch_maps"])
+def test_batch_maps_sequences(pkg, monkeypatch, pipeline_mode, seed):
+    """Three to five filters: the batch forms (a split and a pair list per filter, ekf_batch_extract_map through a scratch batch) and
+    single-index calls -- a fuse on one filter, a filter replaced by a fork of a sibling -- that leave the others bit for bit."""
+    run_sequence(pkg, monkeypatch, "batch_maps", seed)
