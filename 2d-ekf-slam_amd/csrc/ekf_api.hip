@@ -33,6 +33,7 @@
 #include "ekf_factor.hip"
 #include "ekf_pairs.hip"
 #include "ekf_fuse.hip"
+#include "ekf_match.hip"
 #include "ekf_extract.hip"
 
 static thread_local std::string g_last_error;
@@ -87,7 +88,7 @@ struct DevBlock {
     void *p = nullptr;
     size_t bytes = 0;
 };
-enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_COUNT };
+enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_MATCH, BLK_COUNT };
 
 struct GraphEntry {
     int steps, M, has_truth;
@@ -207,7 +208,10 @@ struct ekf_batch {
     // landmark fusion (ekf_fuse_landmarks): pair table, the round's factor and right-hand sides, progress record; one allocation made
     // at the first call, kept and counted in device_bytes
     FuseScratch fuse = {};
-    DevBlock kept[BLK_COUNT];  // the allocations behind fac, dup (boxes and counters; the pair list) and fuse
+    // matched updates (ekf_update_matched, ekf_joint_compat): the call's measurement table, the round's table and the distances; one
+    // allocation made at the first call, replaced by a larger one when a call brings a longer list, kept and counted in device_bytes
+    MatchScratch match = {};
+    DevBlock kept[BLK_COUNT];  // the allocations behind fac, dup (boxes and counters; the pair list), fuse and match
 };
 
 static int sticky_status(ekf_batch *h, bool include_capacity);
@@ -1656,6 +1660,8 @@ static int sticky_status(ekf_batch *h, bool include_capacity) {
 //   ekf_anchor_at_robot (and the batch forms)          QUIET_SETTLED  ST_INVALID_OR_FULL   the state stays as it is under either status
 //   ekf_join_map, ekf_batch_join_map                   QUIET_SETTLED  ST_INVALID_OR_FULL   BOTH handles, the source first (a join without room fails after the settle)
 //   ekf_fuse_landmarks (and the batch form)            QUIET_SETTLED  ST_INVALID_OR_FULL   the pair list is checked first, against the mirror's counts; no pair: returns
+//   ekf_update_matched (and the batch form)            QUIET_SETTLED  ST_INVALID_OR_FULL   values checked first, ids against the mirror's counts; no measurement: returns
+//   ekf_joint_compat (and the batch form)              QUIET_STREAM   ST_INVALID           ids checked; no measurement: returns; else settle(); the state is only read
 //   ekf_extract_map, ekf_batch_extract_map             source: QUIET_STREAM, ST_INVALID, ids checked, settle(); then the destination:
 //                                                      QUIET_SETTLED  ST_NONE              as ekf_set_state (the source is only read)
 //   ekf_get_submap                                     QUIET_STREAM   ST_INVALID           ids checked; size only: returns; else settle(), the dense gather
@@ -1916,7 +1922,7 @@ extern "C" int ekf_set_state(ekf_handle h, int index, const double *x, const dou
 // moves over on the device (k_export into a dense staging matrix, k_import from it: the tile numbering depends on the capacity),
 // the counters, the decision log and a loaded script move with it, and the handle keeps its address.
 static int reserve_move_state(ekf_batch *h, ekf_batch *nh, const std::vector<int> &n_lm);
-static int map_scratch_reserve(ekf_batch *h, const bool want[BLK_COUNT], int dup_cap);  // (ekf_map_api.hip)
+static int map_scratch_reserve(ekf_batch *h, const bool want[BLK_COUNT], int dup_cap, int match_cap);  // (ekf_map_api.hip)
 
 extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     if (!h || capacity_landmarks < 1 || capacity_landmarks > EKF_MAX_CAPACITY) return set_error(EKF_ERR_BAD_ARG, "bad handle / capacity (EKF_MAX_CAPACITY)");
@@ -1981,10 +1987,10 @@ extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     h->script_steps = 0;
     bool had[BLK_COUNT];  // the scratch the map operations keep follows the capacity
     for (int i = 0; i < BLK_COUNT; i++) had[i] = h->kept[i].p != nullptr;
-    const int had_dup_cap = h->dup.cap;
+    const int had_dup_cap = h->dup.cap, had_match_cap = h->match.zcap;
     std::swap(*h, *nh);  // the caller's handle now owns the larger buffers ...
     ekf_destroy(nh);     // ... and the old ones go
-    EKF_TRY(map_scratch_reserve(h, had, had_dup_cap));
+    EKF_TRY(map_scratch_reserve(h, had, had_dup_cap, had_match_cap));
     return refresh_bounds(h);
 }
 

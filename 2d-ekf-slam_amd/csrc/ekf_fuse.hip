@@ -89,6 +89,28 @@ __global__ __launch_bounds__(256) void k_fuse_gather(EkfDev dv, FuseScratch fs, 
 // One workgroup per filter.  A = [S | d | W_R^T], upper triangle, right-looking: step k scales row k by 1 / sqrt(pivot) and takes
 // its outer product off the rows below, the four extra columns with it -- they end as U^-T d = y and U^-T W_R^T = V_R^T.
 #define FUSE_LD (FUSE_MAX_COLS + 5)
+
+// The factorisation itself, by the 256 threads of a workgroup on A in LDS (filled, and a barrier behind it): M rows, NC = M + 4
+// columns.  Returns 0, or 1 + the index of the first pivot that is not positive (FLOOR: not above floor[k]; ekf_match.hip) -- the
+// rows in front of it are final.  The same value in every thread.
+template <bool FLOOR>
+__device__ __forceinline__ int fuse_cholesky(double (*A)[FUSE_LD], int M, int NC, int tid, const double *floor) {
+    for (int k = 0; k < M; k++) {
+        const double piv = A[k][k];  // (the same value in every thread: the loop stays uniform)
+        if (!(piv > (FLOOR ? floor[k] : 0.0))) return k + 1;
+        const double s = sqrt(piv);
+        __syncthreads();
+        for (int c = k + tid; c < NC; c += 256) A[k][c] = A[k][c] / s;
+        __syncthreads();
+        for (int idx = tid; idx < (M - 1 - k) * NC; idx += 256) {
+            const int a = k + 1 + idx / NC, c = idx % NC;
+            if (c >= a) A[a][c] = A[a][c] - A[k][a] * A[k][c];
+        }
+        __syncthreads();
+    }
+    return 0;
+}
+
 __global__ __launch_bounds__(256) void k_fuse_factor(EkfDev dv, FuseScratch fs, int round, double slack, int b_off) {
     __shared__ double A[FUSE_MAX_COLS][FUSE_LD];
     const int b = b_off + blockIdx.x;
@@ -113,22 +135,7 @@ __global__ __launch_bounds__(256) void k_fuse_factor(EkfDev dv, FuseScratch fs, 
             A[a][c] = val;
         }
         __syncthreads();
-        for (int k = 0; k < M; k++) {
-            const double piv = A[k][k];  // (the same value in every thread: the loop stays uniform)
-            if (!(piv > 0.0)) {
-                bad = k + 1;
-                break;
-            }
-            const double s = sqrt(piv);
-            __syncthreads();
-            for (int c = k + tid; c < NC; c += 256) A[k][c] = A[k][c] / s;
-            __syncthreads();
-            for (int idx = tid; idx < (M - 1 - k) * NC; idx += 256) {
-                const int a = k + 1 + idx / NC, c = idx % NC;
-                if (c >= a) A[a][c] = A[a][c] - A[k][a] * A[k][c];
-            }
-            __syncthreads();
-        }
+        bad = fuse_cholesky<false>(A, M, NC, tid, nullptr);
     }
     const bool ok = m > 0 && !bad;
     if (ok) {

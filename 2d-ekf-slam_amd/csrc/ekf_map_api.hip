@@ -1,9 +1,9 @@
 // ekf_map_api.hip -- host side of the map operations of include/ekfslam_c.h: removal, frame change and anchoring, joining, extraction
-// and ekf_get_submap, joint consistency, duplicate search, fusion, ekf_get_landmark_covs.  Included by ekf_api.hip (one translation
-// unit: ekf_batch, HIP_TRY / EKF_TRY, quiesce, finish_rewrite, DevTmp and the kept scratch blocks are that file's).  Every entry point
-// runs once per call on a handle it brings to rest and reads: check, quiesce, plan, upload, launch, finish.  The checks of the
-// caller's lists and the tables the kernels read are pure code in ekf_map_plan.h; the order of those checks relative to quiescing is
-// the table above quiesce().
+// and ekf_get_submap, joint consistency, duplicate search, fusion, matched updates and their score, ekf_get_landmark_covs.  Included
+// by ekf_api.hip (one translation unit: ekf_batch, HIP_TRY / EKF_TRY, quiesce, finish_rewrite, DevTmp and the kept scratch blocks are
+// that file's).  Every entry point runs once per call on a handle it brings to rest and reads: check, quiesce, plan, upload, launch,
+// finish.  The checks of the caller's lists and the tables the kernels read are pure code in ekf_map_plan.h; the order of those
+// checks relative to quiescing is the table above quiesce().
 
 // The filters of a call, [b0, b0 + nb) of a handle: one filter, or (index < 0) the whole batch; and their landmark counts (h_int[]).
 struct Filters {
@@ -497,10 +497,12 @@ static int fuse_reserve(ekf_batch *h) {
 
 // ekf_reserve: the blocks the old buffers had (want[]; the pair list with dup_cap pairs per filter), built for the new capacity.
 // want[BLK_DUP] is not read: dup_reserve builds base and list together, and a base whose list never got allocated is not rebuilt.
-static int map_scratch_reserve(ekf_batch *h, const bool want[BLK_COUNT], int dup_cap) {
+static int match_reserve(ekf_batch *h, int n_meas);
+static int map_scratch_reserve(ekf_batch *h, const bool want[BLK_COUNT], int dup_cap, int match_cap) {
     if (want[BLK_FACTOR]) EKF_TRY(factor_reserve(h));
     if (want[BLK_DUP_LIST]) EKF_TRY(dup_reserve(h, dup_cap));
     if (want[BLK_FUSE]) EKF_TRY(fuse_reserve(h));
+    if (want[BLK_MATCH]) EKF_TRY(match_reserve(h, match_cap));
     return EKF_OK;
 }
 
@@ -577,6 +579,151 @@ extern "C" int ekf_batch_fuse_landmarks(ekf_handle h, const ekf_dup_pair *pairs,
                                         int *n_landmarks_out) {
     if (!h || !n_pairs || ld_pairs < 0 || !n_landmarks_out || !(__builtin_isfinite(slack) && slack >= 0.0)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
     return fuse_impl(h, filters_of(h, -1), pairs, ld_pairs, n_pairs, slack, n_fused_out, n_landmarks_out);
+}
+
+// ---- matched updates ------------------------------------------------------------------------------
+// The scratch of ekf_update_matched and ekf_joint_compat (ekf_match.hip: MatchScratch).  It follows the longest list a call has
+// brought, not the capacity (the same landmark may be measured any number of times): one block for 64 measurements per filter at
+// the first call, replaced by one twice the size until the list fits; ekf_reserve builds it again as large as it was.
+static int match_reserve(ekf_batch *h, int n_meas) {
+    int zcap = h->match.zcap > 64 ? h->match.zcap : 64;
+    while (zcap < n_meas) zcap *= 2;
+    DevBlock &blk = h->kept[BLK_MATCH];
+    if (blk.p && zcap == h->match.zcap) return EKF_OK;
+    const size_t B = (size_t)h->dv.B;
+    const size_t nz = B * zcap * 2, nR = B * zcap * 4, nd = B * zcap, ntab = B * EKF_MAX_PENDING * MATCH_TAB;
+    EKF_TRY(block_alloc(h, &blk, (nz + nR + nd + ntab) * sizeof(double) + (B * zcap + B) * sizeof(int), /*zero*/ true));
+    MatchScratch &ms = h->match;
+    ms.z = (double *)blk.p;
+    ms.Rm = ms.z + nz;
+    ms.d2 = ms.Rm + nR;
+    ms.tab = ms.d2 + nd;
+    ms.ids = (int *)(ms.tab + ntab);
+    ms.cnt = ms.ids + B * zcap;
+    ms.zcap = zcap;
+    return EKF_OK;
+}
+
+// The call's lists into the scratch of filters [b0, b0 + nb), on stream s (the host tables live until the caller has waited).
+static int match_upload(ekf_batch *h, const MatchTable &t, int b0, int nb, hipStream_t s) {
+    const MatchScratch &ms = h->match;
+    const size_t at = (size_t)b0 * ms.zcap, cnt = (size_t)nb * ms.zcap;
+    HIP_TRY(hipMemcpyAsync(ms.z + 2 * at, t.zt.data(), sizeof(double) * 2 * cnt, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ms.Rm + 4 * at, t.Rt.data(), sizeof(double) * 4 * cnt, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ms.ids + at, t.idt.data(), sizeof(int) * cnt, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(ms.cnt + b0, t.cnt.data(), sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
+    return EKF_OK;
+}
+
+// d2 of the device's lists back into the caller's order: entry q of filter k, if it is one of its first n_valid[2 k], to
+// d2_out[k * n_z + src]; everything else NaN.  n_valid == nullptr: every entry.
+static void match_scatter(const MatchTable &t, const std::vector<double> &d2, int zcap, int n_z, int nb, const int *n_valid, double *d2_out) {
+    if (!d2_out) return;
+    for (size_t q = 0; q < (size_t)nb * n_z; q++) d2_out[q] = __builtin_nan("");
+    for (int k = 0; k < nb; k++) {
+        const int cnt = n_valid ? n_valid[2 * k] : t.cnt[k];
+        for (int q = 0; q < cnt; q++) d2_out[(size_t)k * n_z + t.src[(size_t)k * zcap + q]] = d2[(size_t)k * zcap + q];
+    }
+}
+
+// The filters f, filter f.b0 + k with the n_z measurements at z + k * n_z * 2, R + k * n_z * 4, ids + k * n_z.  The values are
+// checked before anything happens to the handle, the ids against the mirror's landmark counts; a call without a measurement returns
+// there.  Then, with the shape of fuse_impl: settle, the tables up, rounds of at most ekf_window() measurements (ekf_match.hip and the
+// apply / finish kernels of ekf_fuse.hip; one dense pass each, in place in the settled buffer in either pipeline mode), the progress
+// record and the distances back in one copy each, and the end of the rewrite (slot rows cleared, the pass sizes restored, the
+// mirror's pose and P_RR refreshed by k_set_meta).
+static int match_impl(ekf_batch *h, Filters f, const double *z, const double *R, const int *ids, int n_z, int *n_applied_out, double *d2_out) {
+    const int b0 = f.b0, nb = f.nb;
+    EKF_TRY(set_error(plan_match_values(z, R, ids, n_z, b0, nb, -1)));
+    HIP_TRY(hipSetDevice(h->device));
+    EKF_TRY(refresh_bounds(h, false));
+    int most;
+    EKF_TRY(set_error(plan_match_ids(ids, n_z, counts_of(h, b0), b0, nb, &most)));
+    if (most == 0) {  // nothing to do: the window stays open
+        for (int k = 0; n_applied_out && k < nb; k++) n_applied_out[k] = 0;
+        for (size_t q = 0; d2_out && q < (size_t)nb * n_z; q++) d2_out[q] = __builtin_nan("");
+        return nb == 1 ? h->h_int[b0] : EKF_OK;
+    }
+    // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
+    // every deferred slot folded, both streams idle
+    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
+    EKF_TRY(fuse_reserve(h));
+    EKF_TRY(match_reserve(h, most));
+    EkfDev &dv = h->dv;
+    const FuseScratch fs = h->fuse;
+    const MatchScratch ms = h->match;
+    hipStream_t s = h->s_chain;
+    const MatchTable tab = plan_match_table(z, R, ids, n_z, nb, ms.zcap);
+    EKF_TRY(match_upload(h, tab, b0, nb, s));
+    HIP_TRY(hipMemsetAsync(fs.done + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
+    HIP_TRY(hipMemsetAsync(fs.m_round + b0, 0, sizeof(int) * (size_t)nb, s));
+    const int n_max = most_landmarks(counts_of(h, b0), nb), nT = lm_tiles(n_max);
+    for (int round = 0; round * dv.maxp < most; round++) {
+        const int m_hi = most - round * dv.maxp < dv.maxp ? most - round * dv.maxp : dv.maxp;
+        hipLaunchKernelGGL(k_match_factor, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->buf_in, round, dv.maxp, /*apply*/ 1, b0);
+        hipLaunchKernelGGL(k_match_gather, dim3((unsigned)cdiv(n_max, 256), (unsigned)m_hi, (unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->buf_in, round, b0);
+        hipLaunchKernelGGL(k_fuse_apply, dim3((unsigned)cdiv(64 * nT, 256), (unsigned)nb), dim3(256), 0, s, dv, fs, b0);
+        hipLaunchKernelGGL(k_fuse_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0);
+        launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->buf_in, h->buf_in, nullptr, /*rev*/ 0, b0, nb);
+    }
+    std::vector<int> done((size_t)2 * nb, 0);
+    std::vector<double> d2((size_t)nb * ms.zcap);
+    HIP_TRY(hipMemcpyAsync(done.data(), fs.done + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));
+    EKF_TRY(check_launch());
+    for (int k = 0; n_applied_out && k < nb; k++) n_applied_out[k] = done[2 * k];  // (filled even where the end of the rewrite fails)
+    match_scatter(tab, d2, ms.zcap, n_z, nb, done.data(), d2_out);
+    const std::vector<int> n_lm(counts_of(h, b0), counts_of(h, b0) + nb);
+    EKF_TRY(finish_rewrite(h, b0, nb, /*rearm*/ true, n_lm.data(), 1, /*flip_buf*/ false));
+    return nb == 1 ? n_lm[0] : EKF_OK;
+}
+
+extern "C" int ekf_update_matched(ekf_handle h, int index, const double *z, const double *R, const int *ids, int n_z, int *n_applied_out, double *d2_out) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return match_impl(h, filters_of(h, index), z, R, ids, n_z, n_applied_out, d2_out);
+}
+
+extern "C" int ekf_batch_update_matched(ekf_handle h, const double *z, const double *R, const int *ids, int n_z, int *n_applied_out, double *d2_out) {
+    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
+    const int rc = match_impl(h, filters_of(h, -1), z, R, ids, n_z, n_applied_out, d2_out);
+    return rc < 0 ? rc : EKF_OK;
+}
+
+// The score alone: the rule of ekf_get_state (the streaming launch leaves, every deferred slot is folded, both streams idle), then
+// the settled state is only read: the tables up, k_match_factor with apply = 0 over one round of up to EKF_MAX_PENDING, d2 back.
+static int compat_impl(ekf_batch *h, Filters f, const double *z, const double *R, const int *ids, int n_z, double *d2_out) {
+    const int b0 = f.b0, nb = f.nb;
+    if (!d2_out && n_z > 0) return set_error(EKF_ERR_BAD_ARG, "d2_out is null");
+    EKF_TRY(set_error(plan_match_values(z, R, ids, n_z, b0, nb, EKF_MAX_PENDING)));
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
+    int most;
+    EKF_TRY(set_error(plan_match_ids(ids, n_z, counts_of(h, b0), b0, nb, &most)));
+    for (size_t q = 0; q < (size_t)nb * (n_z > 0 ? n_z : 0); q++) d2_out[q] = __builtin_nan("");
+    if (most == 0) return EKF_OK;  // (nothing is folded)
+    EKF_TRY(settle(h));
+    EKF_TRY(match_reserve(h, most));
+    const MatchScratch ms = h->match;
+    hipStream_t s = h->s_chain;
+    const MatchTable tab = plan_match_table(z, R, ids, n_z, nb, ms.zcap);
+    EKF_TRY(match_upload(h, tab, b0, nb, s));
+    hipLaunchKernelGGL(k_match_factor, dim3((unsigned)nb), dim3(256), 0, s, h->dv, h->fuse, ms, h->buf_in, 0, EKF_MAX_PENDING, /*apply*/ 0, b0);
+    std::vector<double> d2((size_t)nb * ms.zcap);
+    HIP_TRY(hipMemcpyAsync(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost, s));
+    HIP_TRY(stream_wait(s));
+    EKF_TRY(check_launch());
+    match_scatter(tab, d2, ms.zcap, n_z, nb, nullptr, d2_out);
+    return EKF_OK;
+}
+
+extern "C" int ekf_joint_compat(ekf_handle h, int index, const double *z, const double *R, const int *ids, int n_z, double *d2_out) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return compat_impl(h, filters_of(h, index), z, R, ids, n_z, d2_out);
+}
+
+extern "C" int ekf_batch_joint_compat(ekf_handle h, const double *z, const double *R, const int *ids, int n_z, double *d2_out) {
+    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
+    return compat_impl(h, filters_of(h, -1), z, R, ids, n_z, d2_out);
 }
 
 extern "C" int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max) {

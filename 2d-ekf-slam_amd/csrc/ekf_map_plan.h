@@ -1,8 +1,8 @@
 // ekf_map_plan.h -- the host-side planning of the map operations (ekf_map_api.hip) as pure code: the checks of the lists a caller
-// hands in and the tables the kernels of ekf_rewrite.hip, ekf_extract.hip, ekf_pairs.hip and ekf_fuse.hip read.  No HIP call and no
+// hands in and the tables the kernels of ekf_rewrite.hip, ekf_extract.hip, ekf_pairs.hip, ekf_fuse.hip and ekf_match.hip read.  No HIP call and no
 // handle in here: landmark counts come in as plain arrays, n_lm[k] = landmarks of the k-th filter of the call, whose number in its
 // handle is b0 + k (error texts name that number).  A check reports a status and a text; the caller hands both to set_error.
-// tests/cpp/map_plan_check.cpp runs all of it on the CPU.
+// tests/cpp/map_plan_check.cpp and tests/cpp/match_plan_check.cpp run all of it on the CPU.
 #pragma once
 #include <stdarg.h>
 #include <stdio.h>
@@ -185,4 +185,63 @@ inline PlanStatus plan_fuse_table(const ekf_dup_pair *pairs, int ld_pairs, const
         }
     }
     return {};
+}
+
+// ---- matched updates (ekf_update_matched, ekf_joint_compat) -----------------------------------------------------------------------
+// The lists of nb filters, filter k's n_z measurements at z + k * n_z * 2, R + k * n_z * 4 and ids + k * n_z; ids[q] == -1: no
+// measurement, skipped (its z and R are not looked at).  Checked before the handle is touched: the pointers, n_z, every id >= -1,
+// z and R of every measurement finite, and at most `limit` measurements per filter (limit < 0: any number).
+inline PlanStatus plan_match_values(const double *z, const double *R, const int *ids, int n_z, int b0, int nb, int limit) {
+    if (n_z < 0) return plan_fail(EKF_ERR_BAD_ARG, "negative measurement count");
+    if (n_z > 0 && (!z || !R || !ids)) return plan_fail(EKF_ERR_BAD_ARG, "a null list with n_z > 0");
+    for (int k = 0; k < nb; k++) {
+        int kept = 0;
+        for (int q = 0; q < n_z; q++) {
+            const size_t at = (size_t)k * n_z + q;
+            if (ids[at] < -1) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, measurement %d: id %d (a landmark, or -1 to skip)", b0 + k, q, ids[at]);
+            if (ids[at] < 0) continue;
+            kept++;
+            bool finite = __builtin_isfinite(z[2 * at]) && __builtin_isfinite(z[2 * at + 1]);
+            for (int e = 0; e < 4; e++) finite = finite && __builtin_isfinite(R[4 * at + e]);
+            if (!finite) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, measurement %d: z or R is not finite", b0 + k, q);
+        }
+        if (limit >= 0 && kept > limit) return plan_fail(EKF_ERR_BAD_ARG, "filter %d: %d measurements in one hypothesis (at most %d)", b0 + k, kept, limit);
+    }
+    return {};
+}
+// ... and against the landmark counts n_lm[k], once they are current.  *most = the most measurements of a filter.
+inline PlanStatus plan_match_ids(const int *ids, int n_z, const int *n_lm, int b0, int nb, int *most) {
+    *most = 0;
+    for (int k = 0; k < nb; k++) {
+        int kept = 0;
+        for (int q = 0; q < n_z; q++) {
+            const int id = ids[(size_t)k * n_z + q];
+            if (id < 0) continue;
+            if (id >= n_lm[k]) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, measurement %d: landmark id %d is not one of its %d landmarks", b0 + k, q, id, n_lm[k]);
+            kept++;
+        }
+        *most = std::max(*most, kept);
+    }
+    return {};
+}
+// The tables k_match_factor reads (MatchScratch of the call's filters), nb lists of zcap entries with the skipped measurements
+// left out: zt [nb][zcap][2], Rt [nb][zcap][4], idt [nb][zcap], cnt [nb]; src [nb][zcap] = the caller's index of each entry.
+struct MatchTable {
+    std::vector<double> zt, Rt;
+    std::vector<int> idt, cnt, src;
+};
+inline MatchTable plan_match_table(const double *z, const double *R, const int *ids, int n_z, int nb, int zcap) {
+    MatchTable t;
+    t.zt.assign((size_t)nb * zcap * 2, 0.0), t.Rt.assign((size_t)nb * zcap * 4, 0.0);
+    t.idt.assign((size_t)nb * zcap, 0), t.src.assign((size_t)nb * zcap, -1), t.cnt.assign((size_t)nb, 0);
+    for (int k = 0; k < nb; k++)
+        for (int q = 0; q < n_z; q++) {
+            const size_t at = (size_t)k * n_z + q;
+            if (ids[at] < 0 || t.cnt[k] >= zcap) continue;
+            const size_t to = (size_t)k * zcap + t.cnt[k]++;
+            t.zt[2 * to] = z[2 * at], t.zt[2 * to + 1] = z[2 * at + 1];
+            for (int e = 0; e < 4; e++) t.Rt[4 * to + e] = R[4 * at + e];
+            t.idt[to] = ids[at], t.src[to] = q;
+        }
+    return t;
 }

@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "ekf_joint_consistency", "ekf_batch_joint_consistency", "ekf_debug_joint_factor",
     "ekf_find_duplicates", "ekf_batch_find_duplicates",
     "ekf_fuse_landmarks", "ekf_batch_fuse_landmarks",
+    "ekf_update_matched", "ekf_batch_update_matched", "ekf_joint_compat", "ekf_batch_joint_compat",
 ]
 
 
@@ -140,7 +141,11 @@ def load():
     L.ekf_batch_find_duplicates.argtypes = [_H, ctypes.c_double, ctypes.c_double, _ip, ctypes.POINTER(EkfDupPair), ctypes.c_int, _ip, _ip]
     L.ekf_fuse_landmarks.argtypes = [_H, ctypes.c_int, ctypes.POINTER(EkfDupPair), ctypes.c_int, ctypes.c_double, _ip]
     L.ekf_batch_fuse_landmarks.argtypes = [_H, ctypes.POINTER(EkfDupPair), ctypes.c_int, _ip, ctypes.c_double, _ip, _ip]
-    L.ekf_script_load.argtypes = [_H, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _up, _dp]
+    L.ekf_update_matched.argtypes = [_H, ctypes.c_int, _dp, _dp, _ip, ctypes.c_int, _ip, _dp]
+    L.ekf_batch_update_matched.argtypes = [_H, _dp, _dp, _ip, ctypes.c_int, _ip, _dp]
+    L.ekf_joint_compat.argtypes = [_H, ctypes.c_int, _dp, _dp, _ip, ctypes.c_int, _dp]
+    L.ekf_batch_joint_compat.argtypes = [_H, _dp, _dp, _ip, ctypes.c_int, _dp]
+    L.ekf_script_load.argtypes =[_H, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _up, _dp]
     L.ekf_script_run.argtypes = [_H, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.ekf_sync.argtypes = [_H]
     L.ekf_flush.argtypes = [_H]
@@ -532,6 +537,60 @@ class FilterBatch:
                                            ctypes.byref(fused)))
         return n, fused.value
 
+    def _matched_lists(self, z, R, ids, index):
+        """(z, Rc, ids, n_z) as the C calls take them.  With an index: ids [n_z], z [n_z][2], R [n_z][2][2]; index=None: a leading
+        batch axis on all three (ragged lists: pad ids with -1)."""
+        lead = (self.batch,) if index is None else ()
+        a = np.ascontiguousarray(ids, dtype=np.int64)
+        if a.ndim != len(lead) + 1 or a.shape[:len(lead)] != lead:
+            raise ValueError("ids must be [batch][n_z]" if lead else "ids must be [n_z]")
+        if a.size and (a.min() < -1 or a.max() > np.iinfo(np.int32).max):
+            raise ValueError("an id is a landmark number, or -1 to skip the measurement")
+        n_z = a.shape[-1]
+        z, R = np.asarray(z, dtype=np.float64), np.asarray(R, dtype=np.float64)
+        if z.size != a.size * 2 or R.size != a.size * 4:
+            raise ValueError("z must hold [n_z][2] and R [n_z][2][2] values per filter for %d ids" % n_z)
+        z = _f64(z.reshape(lead + (n_z, 2)))
+        R = R.reshape(lead + (n_z, 2, 2))
+        Rc = _f64(np.swapaxes(R, -1, -2).reshape(lead + (n_z, 4)))  # column-major blocks
+        return z, Rc, np.ascontiguousarray(a, dtype=np.int32), n_z
+
+    def update_matched(self, z, R, ids, index=0):
+        """Apply a scan with the caller's own data association on the device (ekf_update_matched): measurement k is landmark ids[k]
+        (-1: skipped), z [n_z][2], R [n_z][2][2].  The measurements run as joint updates in rounds of `window`, each linearised at
+        its entry state; gates, counters and the decision log are not involved.  Returns (n_landmarks, n_applied, d2): n_applied <
+        the number of non-skipped measurements when a round's S was not positive definite (that round and the later ones were not
+        applied), d2[k] the joint Mahalanobis distance of k's round up to and including k (NaN: skipped or not applied).
+        index=None: every filter in one launch sequence (ekf_batch_update_matched), ids [batch][n_z]; returns (n_applied (batch,),
+        d2 (batch, n_z))."""
+        z, Rc, a, n_z = self._matched_lists(z, R, ids, index)
+        d2 = np.full(a.shape, np.nan)
+        ptrs = (_p(z), _p(Rc), a.ctypes.data_as(_ip)) if n_z else (None, None, None)
+        if index is None:
+            applied = np.zeros(self.batch, dtype=np.int32)
+            _chk(self.L.ekf_batch_update_matched(self.h, *ptrs, n_z, applied.ctypes.data_as(_ip), _p(d2) if n_z else None))
+            return applied, d2
+        applied = ctypes.c_int(0)
+        n = _chk(self.L.ekf_update_matched(self.h, int(index), *ptrs, n_z, ctypes.byref(applied), _p(d2) if n_z else None))
+        return n, applied.value, d2
+
+    def joint_compat(self, z, R, ids, index=0):
+        """The score of one association hypothesis (ekf_joint_compat), nothing applied: d2[k] is the joint Mahalanobis distance of
+        the hypothesis cut after measurement k (at most 32 non-skipped measurements; NaN: skipped, or behind a pivot of S that is
+        not positive).  The same bits as update_matched's d2 for a hypothesis that fits one round.  index=None: ids [batch][n_z],
+        returns d2 (batch, n_z)."""
+        z, Rc, a, n_z = self._matched_lists(z, R, ids, index)
+        if int((a >= 0).sum(axis=-1).max(initial=0)) > 32:
+            raise ValueError("a hypothesis holds at most 32 measurements")
+        d2 = np.full(a.shape, np.nan)
+        if n_z == 0:
+            return d2
+        if index is None:
+            _chk(self.L.ekf_batch_joint_compat(self.h, _p(z), _p(Rc), a.ctypes.data_as(_ip), n_z, _p(d2)))
+        else:
+            _chk(self.L.ekf_joint_compat(self.h, int(index), _p(z), _p(Rc), a.ctypes.data_as(_ip), n_z, _p(d2)))
+        return d2
+
     def joint_factor(self, index=0):
         """Diagnostic: the upper factor U (U^T U = P_LL) the last joint_consistency call left for filter `index`, dense (2N, 2N);
         EkfError ERR_STATE when the state has changed since."""
@@ -723,3 +782,14 @@ class KalmanFilter:
         out = self._f.fuse_landmarks(pairs, slack, 0)
         self._mirror()
         return out
+
+    def update_matched(self, z, R, ids):
+        """Apply measurements with given landmarks as joint updates (FilterBatch.update_matched): (n_landmarks, n_applied, d2);
+        refreshes X, Y, Phi."""
+        out = self._f.update_matched(z, R, ids, 0)
+        self._mirror()
+        return out
+
+    def joint_compat(self, z, R, ids):
+        """The running joint Mahalanobis distance of one association hypothesis (FilterBatch.joint_compat); nothing is applied."""
+        return self._f.joint_compat(z, R, ids, 0)

@@ -94,7 +94,8 @@ void ekf_default_params(ekf_params *p);
  * landmark maps and, in the in-place pipeline (ekf_overlap() == 0), a scratch copy of the reduced maps' tiles -- and the
  * factorisation scratch of ekf_joint_consistency, allocated at its first call and kept: one more P_LL buffer per filter -- and
  * the scratch of ekf_find_duplicates, likewise: a box per 32 landmarks and a pair list that grows with what a call finds -- and
- * the scratch of ekf_fuse_landmarks, likewise: a pair table and one round's 64 x 64 factor per filter).
+ * the scratch of ekf_fuse_landmarks, likewise: a pair table and one round's 64 x 64 factor per filter -- and the measurement
+ * table of ekf_update_matched / ekf_joint_compat, likewise, which grows with the longest list a call brings).
  * The sequential part of a filter runs on a few workgroups that exchange their arg-min candidates while they
  * run, so all of them must be resident on the GPU at once: creation fails with EKF_ERR_STATE when this
  * handle's workgroups do not fit beside those of the handles already live on the device (in this process).
@@ -384,6 +385,57 @@ int ekf_batch_find_duplicates(ekf_handle h, double gate, double max_dist, const 
 int ekf_fuse_landmarks(ekf_handle h, int index, const ekf_dup_pair *pairs, int n_pairs, double slack, int *n_fused_out /* may be NULL */);
 int ekf_batch_fuse_landmarks(ekf_handle h, const ekf_dup_pair *pairs /*[batch][ld_pairs]*/, int ld_pairs, const int *n_pairs /*[batch]*/,
                              double slack, int *n_fused_out /*[batch] or NULL*/, int *n_landmarks_out /*[batch]*/);
+
+/* A scan with the caller's own data association, applied on the device as joint updates: measurement k of the call IS landmark
+ * ids[k] (0-based, as in ekf_remove_landmarks); ids[k] == -1: no measurement, skipped (its z and R are not looked at).  z and R use
+ * the layouts of ekf_batch_update.  The filter's gates and condition limit are NOT consulted -- the decision is the caller's
+ * (joint-compatibility search over ekf_joint_compat below, global nearest neighbour, known ids) -- and counters and decision log
+ * stay as they are: book NIS from d2_out if you want it.  (To force a NEW landmark no call is needed: a fresh one-landmark filter
+ * with x = (0, 0, 0, z), P = blockdiag(0_3, R) handed to ekf_join_map is Update.cpp:155-177.)
+ * The non-skipped measurements run in rounds of at most ekf_window(h) in list order.  A round with measurements k = 0..m-1 of
+ * landmarks i_k is ONE update, every measurement linearised at the round's entry state (C = Rot(phi), J = [[0,-1],[1,0]]):
+ *     dp_k = L_ik - p;   H_R,k = [-C^T | -C^T J dp_k]  (Update.cpp:112-114);   H_L = C^T;   d_k = C^T dp_k - z_k  (= -res);
+ *     column pair k of W = P[:, 0:3] H_R,k^T + P[:, L_ik] C;   S = H W + blockdiag(R_k) = U^T U (from the upper triangle);
+ *     V = W U^-1;   y = U^-T d;   x <- x - V y  (= x + K res);   P <- P - V V^T.
+ * cos phi and sin phi are taken once per round ON THE DEVICE (the device library's cos() and sin() of x[2], which may differ from
+ * the host's libm by an ulp).  With a window of 1 this is the reference's sequence of Old updates for those landmarks.  The same
+ * landmark may appear several times, in one round too: R keeps S regular.
+ * S of a round counts as not positive definite when a pivot of its factorisation is not above 2^-44 of its own diagonal entry of S
+ * (or NaN) -- below that a pivot is rounding noise of the elimination, of either sign; e.g. the same landmark twice with R = 0 on
+ * an anchored filter.  That round and all later ones are then NOT applied: the state is that after the completed rounds and
+ * *n_applied_out (may be NULL) < the number of non-skipped measurements says so.  This is a result, not an error.
+ * d2_out[k] (may be NULL): the joint Mahalanobis distance of the measurements of k's round up to and including k, the running
+ * sum of y^2 over that round's columns 0 .. 2 k_round + 1 -- the last entry of a round is the round's joint distance, and with
+ * rounds of 1 it is the reference's Mahal_dist for that landmark; NaN for skipped and for unapplied measurements.
+ * Checked on the host before the handle is touched: n_z < 0, a NULL z / R / ids with n_z > 0, an id < -1, a non-finite z or R of a
+ * non-skipped measurement, an index out of range -- EKF_ERR_BAD_ARG; then the ids against the landmark count (id >= N:
+ * EKF_ERR_BAD_ARG, the state untouched).  n_z = 0, or every id -1, is a no-op that leaves an open window open.
+ * Otherwise, as ekf_fuse_landmarks: deferred slots are folded first, a streaming launch is stopped (immediate-mode calls stream
+ * again afterwards), each round costs one dense pass over P_LL (in place, in either pipeline mode), a sticky EKF_ERR_TIMEOUT /
+ * EKF_ERR_CAPACITY is returned unchanged with nothing modified, the host mirror shows the new pose and P_RR, every device buffer
+ * ends as ekf_set_state of the result would leave it, and the call synchronises.  No atomics, one writer per value, every sum in a
+ * fixed order: the same bits on every call, and filter b of the batch form gets the bits of the one-filter call on b.
+ * ekf_update_matched returns the landmark count (unchanged) or a negative status; the batch form takes filter b's lists at
+ * z + b * n_z * 2, R + b * n_z * 4, ids + b * n_z (ragged lists: pad with -1) and returns EKF_OK or a negative status.
+ * The scratch -- the call's measurement table (56 bytes per measurement, for at least 64 per filter), one round's table, and the
+ * scratch of ekf_fuse_landmarks -- is allocated at the first call with a measurement, kept on the handle (ekf_device_bytes
+ * counts it, ekf_reserve builds it again) and freed by ekf_destroy. */
+int ekf_update_matched(ekf_handle h, int index, const double *z /*[n_z][2]*/, const double *R /*[n_z][4], column-major 2x2*/,
+                       const int *ids /*[n_z]*/, int n_z, int *n_applied_out /* may be NULL */, double *d2_out /*[n_z] or NULL*/);
+int ekf_batch_update_matched(ekf_handle h, const double *z /*[batch][n_z][2]*/, const double *R /*[batch][n_z][4]*/,
+                             const int *ids /*[batch][n_z]*/, int n_z, int *n_applied_out /*[batch] or NULL*/,
+                             double *d2_out /*[batch][n_z] or NULL*/);
+
+/* The score of ONE association hypothesis, nothing applied: the same S, factor and y as a round of ekf_update_matched (the same
+ * kernel) for at most EKF_MAX_PENDING = 32 non-skipped measurements, whatever the window; more is EKF_ERR_BAD_ARG, and so is
+ * everything ekf_update_matched refuses, and a NULL d2_out with n_z > 0.  d2_out[k] is the joint distance of the hypothesis cut
+ * after measurement k -- the quantity a branch-and-bound search (JCBB) extends by one pairing, free from the right-looking
+ * factorisation; NaN for skipped entries, and from the first pivot that is not positive (the rule above) on: the call still returns
+ * EKF_OK.  For a hypothesis that fits one round of ekf_update_matched the two calls give the same bits of d2.
+ * The filter is only read, behind the rule of ekf_find_duplicates (deferred slots folded, a streaming launch stopped; a sticky
+ * EKF_ERR_TIMEOUT ends the call, a sticky EKF_ERR_CAPACITY does not); a hypothesis without a measurement folds nothing. */
+int ekf_joint_compat(ekf_handle h, int index, const double *z, const double *R, const int *ids, int n_z, double *d2_out /*[n_z]*/);
+int ekf_batch_joint_compat(ekf_handle h, const double *z, const double *R, const int *ids, int n_z, double *d2_out /*[batch][n_z]*/);
 
 /* ---- device-resident step scripts (benchmarks, Monte-Carlo runs) ------------------------------
  * A script is `steps` steps; step s of filter b is
