@@ -29,7 +29,16 @@ The *_maps profiles (appended, so that the four older profiles keep their place 
 The round size of a fuse is the handle's effective window (ekf_window): ekf_batch_create may shorten max_pending to what fits the
 LDS and ekf_reserve plans the geometry again (ekf_geometry.h: plan_geometry), so the generator checks with a restatement of that
 plan (planned_window) that the window of every capacity the handle takes is the max_pending it was created with, in either pipeline
-mode; the op carries it and the replay asserts it."""
+mode; the op carries it and the replay asserts it.
+
+The *_match profiles (appended behind those in turn: the seven older profiles generate what they generated) are the *_maps profiles
+with two more kinds in the deck, twice each; chain_match starts from maps on either side of 256 landmarks:
+  match    ekf_update_matched with the true associations (the hidden world's in_map): per filter a scan of the truly associated
+           landmarks nearest the true pose, 1 to about 2.5 windows' worth of measurements, now and then more than 64, landmarks
+           repeated, entries with id -1 interleaved; about half of them behind an open window.  In batch_match the batch form with
+           one filter's list all -1, or a single-index call on a filter b > 0.  The rounds are the handle's window, which the op
+           carries as for a fuse; on the model every round's S is clearly definite (match_rounds_definite), so every entry is applied.
+  compat   ekf_joint_compat as a read-only probe: up to 32 pairings with the true associations, and the same with two ids exchanged."""
 import math
 import os
 import sys
@@ -41,17 +50,22 @@ import dup_ref as dr  # noqa: E402
 import factor_ref as fr  # noqa: E402
 import fuse_ref as fu  # noqa: E402
 import join_ref as jr  # noqa: E402
+import match_ref as mr  # noqa: E402
 import reframe_ref as rr  # noqa: E402
 from helpers import index_state, shuffled_ids  # noqa: E402
 
-PROFILES = ("solo", "chain", "chain_wgs", "batch", "solo_maps", "chain_maps", "batch_maps")
-MAP_PROFILES = PROFILES[4:]
+PROFILES = ("solo", "chain", "chain_wgs", "batch", "solo_maps", "chain_maps", "batch_maps", "solo_match", "chain_match", "batch_match")
+MAP_PROFILES = PROFILES[4:7]
+MATCH_PROFILES = PROFILES[7:]
 # (a seed whose replay on the model leaves a measurement within 1e-6 relative of a gate is replaced here, never skipped at run time;
 # tests/test_map_model_cpu.py checks every one of these.  The *_maps lists: the first six seeds that the generator's own assertions
 # -- every source landmark mapped, every matched pair a planted one, every pair fused, S clearly definite -- and the coverage
 # the CPU tests ask of a profile let through)
 SEEDS = {"solo": [0, 1, 2, 3, 4, 5, 6, 7], "chain": [0, 1, 2, 3, 4, 5, 6, 7], "chain_wgs": [0, 1, 2, 3, 4, 5, 6, 7], "batch": [0, 1, 2, 3, 4, 5],
-         "solo_maps": [0, 1, 2, 3, 4, 5], "chain_maps": [0, 1, 2, 3, 6, 10], "batch_maps": [3, 4, 5, 6, 7, 13]}
+         "solo_maps": [0, 1, 2, 3, 4, 5], "chain_maps": [0, 1, 2, 3, 6, 10], "batch_maps": [3, 4, 5, 6, 7, 13],
+         # (the *_match lists: the first seeds in which the generator's assertions hold -- every round's S clearly definite, every entry
+         # applied -- and a match and a compat op occur; chain_match: 0, 1, 2 and the next three in which a match measures a landmark >= 256)
+         "solo_match": [1, 2, 3, 4, 5, 6], "chain_match": [0, 1, 2, 9, 18, 24], "batch_match": [0, 1, 3, 5, 6, 7]}
 N_STEPS = 40
 GAMMA_MIN, GAMMA_MAX = 10.0, 50.0  # the gates (ekf_default_params; oracle_c.update's defaults)
 COMPASS_VAR = 0.0005
@@ -61,10 +75,17 @@ REWRITES = ("remove", "transform", "anchor", "reserve", "join", "joint", "covs",
 KINDS = ("propagate", "update", "compass") + REWRITES
 MAP_REWRITES = REWRITES + ("dups", "fuse", "extract")  # the deck of the *_maps profiles
 MAP_KINDS = KINDS + ("dups", "fuse", "extract")
+MATCH_REWRITES = MAP_REWRITES + MAP_REWRITES[-3:] + ("match", "compat") * 2  # the deck of the *_match profiles
+MATCH_KINDS = MAP_KINDS + ("match", "compat")
 DUP_GATES = (9.21, 7.0, 12.0, 5.0, 16.0)
 DUP_MARGIN = 1e-3   # tests/helpers.py: MARGIN
 DUP_MIN_REL = 1e-6  # a pair's S = (a b; b c): a > DUP_MIN_REL (P_ii.xx + P_jj.xx) and det > DUP_MIN_REL a c
 FUSE_MIN_EIG = 1e-6  # every round's S: smallest eigenvalue > FUSE_MIN_EIG x the largest
+# Relative agreement asked of d2 in the `match` and `compat` ops: 20 times what tests/test_map_model_cpu.py measures between
+# match_ref's double arithmetic and its extended-precision restatement on the states the committed *_match seeds meet (5.85e-13 at
+# worst: chain_match seed 0, some seventy rounds of one measurement on a map of four landmarks; 1.05e-12 with cos phi and sin phi
+# an ulp off).  More than match_ref.D2_REL, which stays what it is for the inputs it was measured on.
+MATCH_D2_REL = 1.2e-11
 SCRATCH_CAPS = (8, 40, 96, 130, 200, 300, 400)
 LDS_PER_BLOCK = 163840  # hipDeviceProp_t::sharedMemPerBlock of the MI355X
 
@@ -89,6 +110,11 @@ def duplicate_matching(pairs, n_landmarks):
 def planned_window(batch, cap, max_pending, overlap, wgs=None):
     """ekf_window() of a handle as plan_geometry (csrc/ekf_geometry.h) plans it with EKF_OVERLAP forced to `overlap`, the other
     tunables at their defaults (EKF_CHAIN_WGS = wgs), on a device with LDS_PER_BLOCK bytes of LDS per workgroup."""
+    return planned_geometry(batch, cap, max_pending, overlap, wgs)[2]
+
+
+def planned_geometry(batch, cap, max_pending, overlap, wgs=None):
+    """(workgroups per filter, whether the one-workgroup kernel k_solo runs the handle, ekf_window()) of the same plan."""
     maxp = min(max(int(max_pending), 1), 32)
     budget = LDS_PER_BLOCK - 16384
     sets = 2 if overlap else 1
@@ -115,7 +141,7 @@ def planned_window(batch, cap, max_pending, overlap, wgs=None):
             maxp = budget // (lpw64 * sets * 32)
             if maxp > 1:
                 maxp &= ~1
-    return maxp
+    return G, solo_kernel, maxp
 
 
 def dups_precondition(x, P, gate, max_dist, split):
@@ -152,6 +178,26 @@ def fuse_rounds_definite(x, P, ij, slack, window):
         if not ev[0] > FUSE_MIN_EIG * ev[-1]:
             return False
         x, P = fu.update(x, P, r, slack)
+    return True
+
+
+def match_rounds_definite(x, P, z, R, ids, window):
+    """Every round's S = H W + blockdiag(R_k) of match_ref.update(x, P, z, R, ids, window) clearly positive definite: its smallest
+    eigenvalue above FUSE_MIN_EIG times its largest (window None: one round over everything, as ekf_joint_compat takes it)."""
+    x, P = np.array(x, dtype=np.float64), np.array(P, dtype=np.float64)
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    z, R = np.asarray(z, dtype=np.float64).reshape(-1, 2), np.asarray(R, dtype=np.float64).reshape(-1, 2, 2)
+    kept = np.flatnonzero(ids >= 0)
+    rs = window or max(len(kept), 1)
+    for r0 in range(0, len(kept), rs):
+        sel = kept[r0:r0 + rs]
+        _, S, _ = mr.linearise(x, P, z[sel], R[sel], ids[sel])
+        ev = np.linalg.eigvalsh(0.5 * (S + S.T))
+        if not ev[0] > FUSE_MIN_EIG * ev[-1]:
+            return False
+        x, P, _ = mr.round_update(x, P, z[sel], R[sel], ids[sel])
+        if x is None:
+            return False
     return True
 
 
@@ -221,6 +267,14 @@ class MapModel:
     def extract(self, src, ids):
         self.x, self.P = index_state((src.x, src.P), ids)
         return self.n_landmarks
+
+    def update_matched(self, z, R, ids, window):
+        """(n_landmarks, n_applied, d2) in rounds of `window` measurements, as the handle takes them."""
+        self.x, self.P, applied, d2 = mr.update(self.x, self.P, z, R, ids, window)
+        return self.n_landmarks, applied, d2
+
+    def joint_compat(self, z, R, ids):
+        return mr.joint_compat(self.x, self.P, z, R, ids)
 
     def joint(self, x_true):
         return fr.lapack(self.x, self.P, x_true)
@@ -317,6 +371,10 @@ class ModelRunner:
             if a["mode"] == "probe":
                 return None
             return [M[b].extract(M[a["src_index"] if a["mode"] == "fork" else b], a["ids"][b]) for b in which()]
+        elif kind == "match":
+            return [M[b].update_matched(a["z"][b], a["R"][b], a["ids"][b], a["window"]) for b in which()]
+        elif kind == "compat":  # the true hypothesis and the one with two ids exchanged
+            return [(M[b].joint_compat(a["z"][b], a["R"][b], a["ids"][b]), M[b].joint_compat(a["z"][b], a["R"][b], a["swapped"][b])) for b in which()]
         elif kind in ("read", "twin_begin", "twin_end"):
             pass
         else:
@@ -382,8 +440,10 @@ class _Gen:
         self.oc = _oc()
         self.rng = rng = np.random.default_rng([PROFILES.index(profile), seed, 20261018])
         self.profile = profile
-        self.maps = profile in MAP_PROFILES
-        profile = profile[:-5] if self.maps else profile  # (the parameters of the profile it extends)
+        self.match = profile in MATCH_PROFILES
+        self.maps = profile in MAP_PROFILES or self.match  # (a *_match profile is its *_maps profile with two more kinds in the deck)
+        for suffix in ("_maps", "_match"):  # (the parameters of the profile it extends)
+            profile = profile[:-len(suffix)] if profile.endswith(suffix) else profile
         self.ops = []
         self.run = ModelRunner()
         self.deck = []
@@ -396,9 +456,12 @@ class _Gen:
                 cap = max(40, starts[0] + int(rng.integers(8, 24)))
         elif profile == "chain":
             cap, window, n_world, extent = int(rng.integers(257, 701)), int(rng.choice(WINDOWS)), 420, 20.0
-            starts = [[0, 31, 64, 95, 130, 225, 245, 250][int(rng.integers(0, 8))]]
+            # (chain_match: maps on either side of 256 landmarks, where k_match_gather's second block of 256 begins)
+            starts = [([0, 64, 130, 250, 257, 270, 300, 330] if self.match else [0, 31, 64, 95, 130, 225, 245, 250])[int(rng.integers(0, 8))]]
             if starts[0] >= 225:  # little room: a join will be refused first
                 cap = int(rng.integers(257, 275))
+                if self.match:
+                    cap = max(cap, starts[0] + int(rng.integers(8, 24)))
         elif profile == "chain_wgs":
             cap, window, n_world, extent = int(rng.integers(30, 121)), int(rng.choice((1, 2, 4, 8, 16))), 170, 13.0
             wgs = int(rng.integers(2, 5))
@@ -425,7 +488,7 @@ class _Gen:
     # -- plumbing
     def emit(self, kind, **a):
         # (a rewrite straight behind filter traffic that does not export first meets an open window and a live streaming launch)
-        if (kind in ("remove", "transform", "anchor", "join", "fuse") or kind == "extract" and a["mode"] != "probe") and not a["settle"] \
+        if (kind in ("remove", "transform", "anchor", "join", "fuse", "match") or kind == "extract" and a["mode"] != "probe") and not a["settle"] \
                 and self.behind_traffic:
             self.n_open += 1
         if self.maps and kind in ("create", "reserve"):  # the effective window stays the one asked for, whatever the capacity
@@ -844,11 +907,93 @@ class _Gen:
         if rewrite:
             self.twin_point("extract")
 
+    # -- the *_match profiles: matched updates and the score of a hypothesis
+    def scan_of(self, b, n_meas):
+        """(ids, z, R) of n_meas measurements of filter b: truly associated mapped landmarks (the hidden world's in_map says which)
+        nearest the true pose, about two thirds as many landmarks as measurements, so that some are measured again;
+        z = rel(k) + N(0, 0.03), R of the oracle's measurement model as in `traffic`.  None where nothing true is mapped."""
+        rng, s = self.rng, self.sims[b]
+        cand = [l for l, k in enumerate(s.in_map) if k >= 0]
+        if not cand:
+            return None
+        cand.sort(key=lambda l: float(np.hypot(*(s.world[s.in_map[l]] - s.pose[:2]))))
+        distinct = cand[:max(1, -(-2 * n_meas // 3))]
+        ids = [distinct[int(p)] for p in rng.permutation(len(distinct))][:n_meas]
+        ids += [distinct[int(rng.integers(0, len(distinct)))] for _ in range(n_meas - len(ids))]
+        z = np.array([s.rel(s.in_map[l]) + rng.normal(0.0, 0.03, 2) for l in ids])
+        return np.array(ids, dtype=np.int32), z, np.array([_measurement(self.oc, zz) for zz in z])
+
+    def padded(self, scans, n_z):
+        """The scans (b -> (ids, z, R) or None) as lists of n_z entries each, the entries that are none of the scan's (ids -1, z = 0,
+        R = I) interleaved at random places."""
+        ids, z, R = {}, {}, {}
+        for b, sc in scans.items():
+            ids[b], z[b], R[b] = np.full(n_z, -1, dtype=np.int32), np.zeros((n_z, 2)), np.tile(np.eye(2), (n_z, 1, 1))
+            if sc is not None:
+                at = np.sort(self.rng.permutation(n_z)[:len(sc[0])])
+                ids[b][at], z[b][at], R[b][at] = sc
+        return ids, z, R
+
+    def match_index(self, index):
+        """Which filters a match or a compat op addresses.  One filter: itself.  A batch: the batch form with one filter's list all -1
+        about a third of the time (and whenever an open window is wanted), else a single-index call on a filter b > 0.  Returns
+        (index, the filters of the call, the one that sits out or None)."""
+        rng, B = self.rng, self.B
+        if B == 1:
+            return 0, [0], None
+        if self.force_open or rng.random() < 0.35:
+            return None, list(range(B)), int(rng.integers(0, B))
+        index = index if index is not None else int(rng.integers(1, B))
+        return index, [index], None
+
+    def do_match(self, index):
+        """ekf_update_matched with the true associations: between 1 and about 2.5 windows' worth of measurements per filter, now and
+        then more than the 64 the measurement table starts with; every round's S clearly definite on the model, so every entry is
+        applied.  The op carries the handle's window: the model takes its rounds from there."""
+        rng = self.rng
+        index, which, idle = self.match_index(index)
+        scans = {}
+        for b in which:
+            n_meas = int(rng.integers(65, 76)) if rng.random() < 0.12 else int(rng.integers(1, int(2.5 * self.window) + 2))
+            scans[b] = None if b == idle else self.scan_of(b, n_meas)
+        if not any(sc is not None for sc in scans.values()):
+            self.emit("read", index=int(rng.integers(0, self.B)))  # nothing true is mapped: a call without a measurement is no rewrite
+            return
+        ids, z, R = self.padded(scans, max(len(sc[0]) for sc in scans.values() if sc is not None) + int(rng.integers(0, 4)))
+        for b in which:
+            assert match_rounds_definite(self.models[b].x, self.models[b].P, z[b], R[b], ids[b], self.window), "S of a round is not clearly definite"
+        # (a single-index call on a batch exports first, for the siblings' sake; the batch form makes up for it)
+        res = self.emit("match", index=index, z=z, R=R, ids=ids, window=self.window,
+                        settle=bool(index is not None and self.B > 1 or rng.random() < (0.5 if self.B == 1 else 0.2)) and not self.force_open)
+        assert [r[1] for r in res] == [int((ids[b] >= 0).sum()) for b in which], "the reference did not apply every measurement"
+        self.twin_point("match")
+
+    def do_compat(self, index):
+        """ekf_joint_compat as a read-only probe: up to 32 pairings with the true associations, and the same with two ids exchanged."""
+        rng = self.rng
+        index, which, idle = self.match_index(index)
+        scans = {b: None if b == idle else self.scan_of(b, int(rng.integers(2, 33))) for b in which}
+        if not any(sc is not None for sc in scans.values()):
+            self.emit("read", index=int(rng.integers(0, self.B)))
+            return
+        ids, z, R = self.padded(scans, max(len(sc[0]) for sc in scans.values() if sc is not None) + int(rng.integers(0, 4)))
+        swapped = {}
+        for b in which:
+            swapped[b] = ids[b].copy()
+            kept = np.flatnonzero(ids[b] >= 0)
+            other = [k for k in kept if ids[b][k] != ids[b][kept[0]]] if len(kept) else []
+            if other:  # (a filter with one landmark has nothing to exchange)
+                k = int(other[int(rng.integers(0, len(other)))])
+                swapped[b][kept[0]], swapped[b][k] = ids[b][k], ids[b][kept[0]]
+            m = self.models[b]
+            assert all(match_rounds_definite(m.x, m.P, z[b], R[b], h, None) for h in (ids[b], swapped[b])), "S of the hypothesis is not clearly definite"
+        self.emit("compat", index=index, z=z, R=R, ids=ids, swapped=swapped, settle=bool(index is not None and self.B > 1 or rng.random() < 0.5))
+
     def rewrite_maps(self, forced=None):
         """One rewrite or probe of the *_maps deck; forced "state": a state-changing one, "new": a fuse or an extraction."""
         rng, B = self.rng, self.B
         if not self.deck:
-            self.deck = [str(k) for k in rng.permutation(MAP_REWRITES + MAP_REWRITES[-3:])]  # (the three newer kinds twice)
+            self.deck = [str(k) for k in rng.permutation(MATCH_REWRITES if self.match else MAP_REWRITES + MAP_REWRITES[-3:])]  # (the three newer kinds twice)
         if forced == "new":
             kind = str(rng.choice(["fuse", "extract"]))
         elif forced == "state":
@@ -869,6 +1014,10 @@ class _Gen:
                           settle=bool(index is not None and B > 1 or rng.random() < 0.5))
         elif kind == "extract":
             self.do_extract(index, bool(forced or rng.random() < 0.6))
+        elif kind == "match":
+            self.do_match(index)
+        elif kind == "compat":
+            self.do_compat(index)
         else:
             self.deck.append(kind)
             n = len(self.ops)

@@ -17,7 +17,14 @@ of tests/test_find_duplicates.py): 0, 1, 2, 63, 64, 65 landmarks and a map that 
 landmark is the map's last.  Extraction (NumPy indexing, bit for bit): sources of 0 / 1 / 31 / 32 / 33 / 65 landmarks into a
 destination of another tile count, a destination that held 65 and receives 1, selections of 511 / 512 / 513 landmarks.  And each of
 the three straight behind a window in which a far New landmark has just started a second tile (32 -> 33): they read the settled
-tile layout and must close that window themselves."""
+tile layout and must close that window themselves.
+
+And for the matched updates (ekf_update_matched / ekf_joint_compat; tests/match_ref.py on the witness' export, rounds of the handle's
+window, the scan from match_ref.scan_of on that export; d2 within match_ref.D2_REL_EDGES, which tests/test_update_matched_cpu.py
+derives for exactly these inputs): k_match_gather's grid of 256 landmarks per block at 256 and 257 landmarks, the chunk edge at 511 /
+512 / 513 as an update of two rounds and as a score of 32 pairings, a full round of 32 (and of 24) measurements applied with one more
+behind it in both kernel families, one landmark measured three times in one round, maps that fill their capacity, a landmark alone in
+the last tile, and the landmark the open window has just created."""
 import os
 import sys
 
@@ -31,6 +38,7 @@ import factor_ref as fr  # noqa: E402
 import fuse_ref as fu  # noqa: E402
 import join_ref as jr  # noqa: E402
 import map_model as mm  # noqa: E402
+import match_ref as mr  # noqa: E402
 import reframe_ref as rr  # noqa: E402
 from helpers import (ABS_P, REL_TOL, assert_bitwise, assert_bitwise_symmetric, assert_state_close, batch_script, check_duplicates,  # noqa: E402
                      check_joint, ij, index_state, open_window_pair, run_steps, windows_closed)
@@ -41,11 +49,11 @@ FRAME = (3.0, -2.0, 0.7)
 WINDOW = 8
 
 
-def opened_pair(pkg, N, cap, seed, extent=None):
+def opened_pair(pkg, N, cap, seed, extent=None, window=WINDOW):
     """The handle under test and its witness after the same immediate steps, a window open on both.  N = 0: fresh filters that
     have been propagated twice."""
     if N:
-        a, w, _ = open_window_pair(pkg, N, cap, seed=seed, steps=2, extent=extent, M=min(2, N), max_pending=WINDOW)
+        a, w, _ = open_window_pair(pkg, N, cap, seed=seed, steps=2, extent=extent, M=min(2, N), max_pending=window)
         return a, w
     pair = [pkg.FilterBatch(1, cap, max_pending=WINDOW, log_capacity=4096) for _ in range(2)]
     for f in pair:
@@ -54,10 +62,10 @@ def opened_pair(pkg, N, cap, seed, extent=None):
     return pair
 
 
-def witnessed(pkg, N, cap, seed, extent=None):
+def witnessed(pkg, N, cap, seed, extent=None, window=WINDOW):
     """(handle with its window open and its streaming launch live, what it holds as its witness exported it, the witness' stats and
     decision log).  Nothing is asked of the handle itself: reading its counters would have the resident launch leave."""
-    a, w = opened_pair(pkg, N, cap, seed, extent)
+    a, w = opened_pair(pkg, N, cap, seed, extent, window)
     before, logs = w.get_state(), (w.stats(), w.decisions())
     w.close()
     return a, before, logs
@@ -70,7 +78,7 @@ def settled_checks(a, after, logs, N):
     assert (a.stats(), a.decisions()) == logs  # counters and decision log do not move
 
 
-def twin_goes_on(pkg, a, what):
+def twin_goes_on(pkg, a, what, window=WINDOW):
     """Three more steps on the handle and on a twin loaded with set_state of its export: propagations, Old matches where there are
     landmarks, far New landmarks (steps 0 and 2).  Decisions with their distances and the final exports are equal bit for bit."""
     st = a.get_state()
@@ -78,7 +86,7 @@ def twin_goes_on(pkg, a, what):
     if N + 2 > a.capacity:
         a.reserve(N + 8)
         assert_bitwise(a.get_state(), st, "%s: reserve behind the call" % what)
-    b = pkg.FilterBatch(1, a.capacity, max_pending=WINDOW, log_capacity=4096)
+    b = pkg.FilterBatch(1, a.capacity, max_pending=window, log_capacity=4096)
     b.set_state(*st)
     M = min(2, N)
     if M:
@@ -525,4 +533,94 @@ def test_extract_behind_a_grown_window(pkg, pipeline_mode):
     assert_bitwise(after, before, "the call only reads")
     settled_checks(a, after, logs, 33)
     twin_goes_on(pkg, a, "get_submap behind a grown window")
+    a.close()
+
+
+# ---- matched updates -----------------------------------------------------------------------------------------------------
+def matched_checks(pkg, a, before, logs, z, R, ids, what, window=WINDOW):
+    """a.update_matched(z, R, ids) on the handle whose witness exported `before`: the reference in rounds of the handle's window,
+    the checks every rewrite of this file gets, the twin.  Returns the device's d2."""
+    N = (before[0].size - 3) // 2
+    assert a.window == window
+    closed0 = windows_closed(a)
+    got = a.update_matched(z, R, ids)
+    assert windows_closed(a) - closed0 <= 1  # the open window; the rounds' passes are the call's own
+    ref = mr.update(*before, z, R, ids, window)
+    n_z = sum(1 for i in ids if i >= 0)
+    assert got[:2] == (N, n_z) and ref[2] == n_z, (what, got[:2], ref[2])
+    after = a.get_state()
+    err = assert_state_close(after[0], after[1], ref[0], ref[1], what=what)
+    rel = mr.assert_d2_close(got[2], ref[3], what, mr.D2_REL_EDGES)
+    print("matched %s: %d rounds, max |dx| %.3e, max |dP| / max |P| %.3e, d2 relative %.3e" % (what, -(-n_z // window), err[0], err[1], rel))
+    settled_checks(a, after, logs, N)
+    twin_goes_on(pkg, a, what, window)
+    return got[2]
+
+
+@pytest.mark.parametrize("case", [k for k in mr.MAP_EDGES if k not in mr.FULL_ROUND_CASES])
+def test_update_matched(pkg, pipeline_mode, case):
+    N, cap, window, _, seed = mr.MAP_EDGES[case]
+    a, before, logs = witnessed(pkg, N, cap, seed=seed)
+    ids = mr.map_edge_ids(case, before[0])
+    z, R = mr.scan_of(pkg, before[0], ids, seed + mr.SCAN_OFFSET)
+    matched_checks(pkg, a, before, logs, z, R, ids, case)
+    a.close()
+
+
+@pytest.mark.parametrize("case", mr.FULL_ROUND_CASES)
+def test_update_matched_full_round(pkg, pipeline_mode, case):
+    """A round of as many measurements as the window holds (32: EKF_MAX_PENDING, M = 64 = FUSE_MAX_COLS columns) and a round of one
+    behind it, on the chain kernel's geometry (capacity 320) and on the one-workgroup family's (capacity 200).  Then, on a handle
+    loaded with the same state, the prefixes of 8 / 16 / 24 / 32 measurements that fit one round: ekf_joint_compat and
+    ekf_update_matched give the same bits."""
+    N, cap, window, count, seed = mr.MAP_EDGES[case]
+    assert all(mm.planned_window(1, cap, window, ov) == window for ov in (False, True))  # the window asked for, in either pipeline mode
+    a, before, logs = witnessed(pkg, N, cap, seed=seed, window=window)
+    # capacity 200 is run by the one-workgroup kernel where the dense pass is in place, by the chain kernel in overlap mode; 320 never is
+    assert a.overlap == (pipeline_mode == "overlap")
+    assert mm.planned_geometry(1, cap, window, a.overlap)[:2] == ((1, True) if cap <= 256 and not a.overlap else (5 if cap > 256 else 4, False))
+    ids = mr.map_edge_ids(case, before[0])
+    assert len(ids) == count == window + 1 and len(set(ids.tolist())) == 24
+    z, R = mr.scan_of(pkg, before[0], ids, seed + mr.SCAN_OFFSET)
+    d2 = matched_checks(pkg, a, before, logs, z, R, ids, case, window)
+    a.close()
+    assert np.all(np.diff(d2[:window]) >= 0.0)  # a running distance within the round
+    for p in (8, 16, 24, 32):
+        if p > window:
+            continue
+        h = pkg.FilterBatch(1, cap, max_pending=window, log_capacity=4096)
+        h.set_state(*before)
+        score = h.joint_compat(z[:p], R[:p], ids[:p])
+        mr.assert_d2_close(score, mr.joint_compat(*before, z[:p], R[:p], ids[:p]), "%s, score of %d" % (case, p), mr.D2_REL_EDGES)
+        n, applied, dp = h.update_matched(z[:p], R[:p], ids[:p])
+        assert (n, applied) == (N, p) and dp.tobytes() == score.tobytes(), (case, p)
+        assert d2[:p].tobytes() == dp.tobytes(), (case, p)  # ... and the bits the call behind the open window gave for its first round
+        h.close()
+
+
+@pytest.mark.parametrize("case", mr.CHUNK_CASES)
+def test_joint_compat_across_the_chunk(pkg, pipeline_mode, case):
+    """The score alone on 511 / 512 / 513 landmarks: 32 pairings (M = 64, NC = 68), the last landmark among them."""
+    N, cap, _, _, seed = mr.MAP_EDGES[case]
+    a, before, logs = witnessed(pkg, N, cap, seed=seed)
+    ids = mr.chunk_hypothesis(N)
+    assert len(ids) == 32 and N - 1 in ids
+    z, R = mr.scan_of(pkg, before[0], ids, seed + mr.SCAN_OFFSET + 1)
+    d2 = a.joint_compat(z, R, ids)
+    rel = mr.assert_d2_close(d2, mr.joint_compat(*before, z, R, ids), case, mr.D2_REL_EDGES)
+    print("joint_compat %s: d2 relative %.3e" % (case, rel))
+    assert not np.isnan(d2).any() and np.all(np.diff(d2) >= 0.0)
+    assert a.joint_compat(z, R, ids).tobytes() == d2.tobytes()  # two calls, the same bits
+    after = a.get_state()
+    assert_bitwise(after, before, "the call only reads")
+    settled_checks(a, after, logs, N)
+    twin_goes_on(pkg, a, case)
+    a.close()
+
+
+def test_update_matched_behind_a_grown_window(pkg, pipeline_mode):
+    """Landmark 32 measured straight behind the window in which it was created (a second tile just started), and an old one."""
+    a, before, logs = grown(pkg)
+    z, R = mr.scan_of(pkg, before[0], mr.GROWN_IDS, mr.GROWN_SCAN_SEED)
+    matched_checks(pkg, a, before, logs, z, R, mr.GROWN_IDS, mr.GROWN_NAME)
     a.close()

@@ -6,7 +6,10 @@ For the *_maps profiles also: what they must cover of the duplicate search, the 
 the precondition under which its LIST may be compared (margins to the gate and to max_dist, no near-degenerate pair) and every `fuse`
 op's list is one the library accepts, with every round's S clearly positive definite; fuse_ref.fuse against its np.longdouble
 restatement.  The four older profiles generate what they generated before the *_maps profiles were appended (compared once against the
-previous tests/map_model.py, value for value)."""
+previous tests/map_model.py, value for value), and all seven what they generated before the *_match profiles were (likewise).
+For the *_match profiles: what they must cover of the matched updates; that every `match` and `compat` op meets the generator's
+precondition (every round's S clearly definite, so every entry is applied); that the model takes its rounds from the op's window;
+match_ref against its np.longdouble restatement on every state such an op meets, d2 within 1/20 of map_model.MATCH_D2_REL."""
 import os
 import sys
 
@@ -17,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import fuse_ref as fu  # noqa: E402
 import join_ref as jr  # noqa: E402
 import map_model as mm  # noqa: E402
+import match_ref as mr  # noqa: E402
 import reframe_ref as rr  # noqa: E402
 from helpers import REL_TOL, assert_state_close  # noqa: E402
 
@@ -40,7 +44,8 @@ def replay(ops):
 
 def test_seed_lists():
     assert mm.PROFILES[:4] == ("solo", "chain", "chain_wgs", "batch") and mm.MAP_PROFILES == ("solo_maps", "chain_maps", "batch_maps")
-    assert [len(mm.SEEDS[p]) for p in mm.PROFILES] == [8, 8, 8, 6, 6, 6, 6]
+    assert mm.MATCH_PROFILES == ("solo_match", "chain_match", "batch_match") == mm.PROFILES[7:]
+    assert [len(mm.SEEDS[p]) for p in mm.PROFILES] == [8, 8, 8, 6, 6, 6, 6, 6, 6, 6]
     assert all(len(set(s)) == len(s) for s in mm.SEEDS.values())
 
 
@@ -57,7 +62,7 @@ def test_profile_parameters(sequences, profile):
         ops = sequences[profile, seed]
         c = ops[0][1]
         assert ops[0][0] == "create"
-        maps, base = profile in mm.MAP_PROFILES, profile.replace("_maps", "")
+        maps, base = profile in mm.MAP_PROFILES + mm.MATCH_PROFILES, profile.replace("_maps", "").replace("_match", "")
         if base == "solo":
             assert 40 <= c["cap"] <= 256 and c["window"] in mm.WINDOWS and c["B"] == 1 and c["wgs"] is None
         elif base == "chain":
@@ -70,14 +75,15 @@ def test_profile_parameters(sequences, profile):
             assert len(loaded) == c["B"] - 1 and len(set(loaded.values())) == len(loaded)  # one starts empty, each its own count
         if maps:  # (a fuse may have propagations of its own in front of it)
             assert sum(1 for k, _ in ops if k == "propagate") >= mm.N_STEPS
-            assert all(a["window"] == c["window"] for k, a in ops if k == "fuse")
+            assert all(a["window"] == c["window"] for k, a in ops if k in ("fuse", "match"))
+            assert profile in mm.MATCH_PROFILES or not any(k in ("match", "compat") for k, _ in ops)
             assert all(a["scratch_cap"] in mm.SCRATCH_CAPS for k, a in ops if k == "extract" and a["mode"] != "fork")
             behind = [ops[i - 1] for i, (k, _) in enumerate(ops) if k == "twin_begin"]
             assert all(k != "extract" or a["mode"] != "probe" for k, a in behind)
             assert any(k in ("fuse", "extract") for k, _ in behind), seed  # one twin at least goes on behind a fuse or an extraction
         else:
             assert sum(1 for k, _ in ops if k == "propagate") == mm.N_STEPS
-            assert not any(k in ("dups", "fuse", "extract") for k, _ in ops)
+            assert not any(k in ("dups", "fuse", "extract", "match", "compat") for k, _ in ops)
         assert sum(1 for k, _ in ops if k == "twin_begin") == sum(1 for k, _ in ops if k == "twin_end") == 2
         assert all(a["cap"] in mm.SRC_CAPS for k, a in ops if k == "src_create")
 
@@ -184,7 +190,112 @@ def test_coverage_of_the_map_profiles(sequences, profile):
         assert count["single_index"] >= 5 and modes == {"probe", "fork", "batch"}
 
 
-@pytest.mark.parametrize("profile,seed", [ps for ps in ALL if ps[0] in mm.MAP_PROFILES])
+@pytest.mark.parametrize("profile", mm.MATCH_PROFILES)
+def test_coverage_of_the_match_profiles(sequences, profile):
+    """Every profile: a match of more rounds than one, a match behind an open window, a landmark measured twice in one list, a skipped
+    entry among measured ones, a compat; every seed a match and a compat.  chain_match: a measured landmark >= 256 in three seeds
+    at least (k_match_gather's second block).  batch_match: the batch form more than once, with one filter's list all -1, at least once
+    settled, and single-index calls."""
+    count = dict.fromkeys(("match", "compat", "multi_round", "open", "repeat", "skip", "longer_than_64", "all_skip", "all_skip_settled", "batch_form", "single_index", "settled", "twin_behind"), 0)
+    seeds_past_256 = 0
+    for seed in mm.SEEDS[profile]:
+        last, here, past = None, dict(match=0, compat=0), False
+        for (kind, a), run, before, cap, res in replay(sequences[profile, seed]):
+            if kind in ("match", "compat"):
+                here[kind] += 1
+                count[kind] += 1
+                B = len(before)
+                lists = list(a["ids"].values())
+                assert len(set(len(v) for v in lists)) == 1 and len(lists) == (B if a["index"] is None else 1)
+                assert all(v[v >= 0].max(initial=-1) < before[b] for b, v in a["ids"].items())
+                count["single_index"] += B > 1 and a["index"] is not None
+            if kind == "compat":
+                for b, v in a["ids"].items():
+                    w = a["swapped"][b]
+                    assert int((v >= 0).sum()) <= 32 and sorted(v.tolist()) == sorted(w.tolist()) and np.array_equal(v >= 0, w >= 0)
+                    assert int((v != w).sum()) in (0, 2) and (int((v != w).sum()) == 2 or len(set(v[v >= 0].tolist())) <= 1)
+            if kind == "match":
+                kept = [v[v >= 0] for v in a["ids"].values()]
+                count["multi_round"] += max(len(k) for k in kept) > a["window"]
+                count["longer_than_64"] += max(len(k) for k in kept) > 64
+                count["open"] += not a["settle"] and last in TRAFFIC
+                count["settled"] += bool(a["settle"])
+                count["repeat"] += any(len(set(k.tolist())) < len(k) for k in kept)
+                count["skip"] += any(0 < len(k) < len(v) for k, v in zip(kept, a["ids"].values()))
+                count["all_skip"] += a["index"] is None and len(kept) > 1 and any(len(k) == 0 for k in kept)
+                # (only a settled call has the export in front of it that the replay compares the all -1 filter with, bit for bit)
+                count["all_skip_settled"] += bool(a["settle"]) and a["index"] is None and len(kept) > 1 and any(len(k) == 0 for k in kept)
+                count["batch_form"] += a["index"] is None and len(kept) > 1
+                past = past or any((k >= 256).any() for k in kept)
+                assert [r[:2] for r in res] == [(before[b], len(k)) for b, k in zip(a["ids"], kept)]  # every entry applied
+            if kind == "twin_begin":
+                count["twin_behind"] += last == "match"
+            last = kind
+        assert here["match"] >= 1 and here["compat"] >= 1, (seed, here)
+        seeds_past_256 += past
+    print(profile, count, "seeds with a measured landmark >= 256:", seeds_past_256)
+    for k in ("multi_round", "open", "repeat", "skip", "compat", "settled"):
+        assert count[k] >= 1, (k, count)
+    if profile == "chain_match":
+        assert seeds_past_256 >= 3
+    if profile == "batch_match":
+        assert count["all_skip"] >= 1 and count["all_skip_settled"] >= 1 and count["batch_form"] >= 2 and count["single_index"] >= 1
+
+
+@pytest.mark.parametrize("profile,seed", [ps for ps in ALL if ps[0] in mm.MATCH_PROFILES])
+def test_match_preconditions(sequences, profile, seed):
+    """Every `match` op: every round's S clearly positive definite on the model's state (smallest eigenvalue above FUSE_MIN_EIG times
+    the largest), so every entry is applied and the library cannot decide otherwise.  Every `compat` op: the same for the one round
+    of either hypothesis, no NaN in either answer, and the exchanged hypothesis is the larger distance in the end."""
+    n = 0
+    run = mm.ModelRunner()
+    for op in sequences[profile, seed]:
+        kind, a = op
+        which = list(range(len(run.models))) if a.get("index") is None else [a["index"]]
+        if kind in ("match", "compat"):
+            for b in which:
+                m = run.models[b]
+                for ids in ([a["ids"][b]] if kind == "match" else [a["ids"][b], a["swapped"][b]]):
+                    assert mm.match_rounds_definite(m.x, m.P, a["z"][b], a["R"][b], ids, a["window"] if kind == "match" else None), (kind, b)
+            n += 1
+        res = run.step(op)
+        if kind == "compat":
+            for (true, swapped), b in zip(res, which):
+                kept = a["ids"][b] >= 0
+                assert not np.isnan(true[kept]).any() and not np.isnan(swapped[kept]).any() and np.isnan(true[~kept]).all()
+                if not np.array_equal(a["ids"][b], a["swapped"][b]):
+                    assert np.nanmax(swapped) > np.nanmax(true), (b, np.nanmax(swapped), np.nanmax(true))
+    assert n >= 2
+    print("%s seed %d: %d match and compat ops" % (profile, seed, n))
+
+
+def test_model_matches_in_rounds_of_the_window():
+    """MapModel.update_matched takes the list in rounds of the op's window, every round linearised at its entry state.  As with
+    fusion, a state comparison within the sequences' tolerances may not tell one round size from the next (the difference is the
+    relinearisation, second order in the correction); d2 can -- a running distance starts again with every round -- and so can the
+    number of applied entries where a round holds an exact copy.  The replay asserts the handle's window against the op's."""
+    import __graft_entry__ as ge
+    pkg = ge.load_package()
+    x, P = pkg.scenarios.injected_state(12, seed=3, extent=8.0)
+    ids = [0, 5, 7, 9, 3, 3, 1]
+    z, R = mr.scan_of(pkg, x, ids, 11)
+    by_window = {w: mm.MapModel(x, P).update_matched(z, R, ids, w) for w in (1, 2, 3, 4, 8)}
+    for w, (n, applied, d2) in by_window.items():
+        assert (n, applied) == (12, 7)
+        falls = [k for k in range(1, 7) if d2[k] < d2[k - 1]]  # the running distance falls where a round begins, nowhere else
+        assert all(k % w == 0 for k in falls), (w, falls)
+    assert not np.array_equal(by_window[3][2], by_window[4][2])
+    R[4:6] = 0.0
+    z[5] = z[4]  # landmark 3 twice, exactly: the round that holds both is refused (rounds of 5 would part them: not asked)
+    assert [mm.MapModel(x, P).update_matched(z, R, ids, w)[1] for w in (2, 3, 4, 6, 8)] == [4, 3, 4, 0, 0]
+    run = mm.ModelRunner()
+    run.step(("create", dict(B=1, cap=16, window=3, wgs=None)))
+    run.step(("load", dict(index=0, x=x, P=P)))
+    got = run.step(("match", dict(index=0, z={0: z}, R={0: R}, ids={0: np.array(ids)}, window=3, settle=True)))
+    assert got[0][:2] == (12, 3) and np.isnan(got[0][2][3:]).all()
+
+
+@pytest.mark.parametrize("profile,seed", [ps for ps in ALL if ps[0] in mm.MAP_PROFILES + mm.MATCH_PROFILES])
 def test_dups_and_fuse_preconditions(sequences, profile, seed):
     """Every `dups` op: on the model's state no pair within DUP_MARGIN of the gate or of max_dist and no near-degenerate pair, which
     is what entitles the replay to compare the library's LIST with the model's.  Every `fuse` op: a list the library accepts (i < j < N,
@@ -248,12 +359,19 @@ def test_decision_margins(sequences, profile, seed):
 def test_reference_precision(sequences, profile, seed):
     """The float64 references against np.longdouble restatements of the dense Jacobian forms, on every state the sequence meets, held
     to the tolerance the GPU comparison uses: the reference's own error is far below it (the maxima are printed)."""
-    worst = {"rigid": [0.0, 0.0, 0], "anchor": [0.0, 0.0, 0], "join": [0.0, 0.0, 0], "fuse": [0.0, 0.0, 0]}
+    worst = {"rigid": [0.0, 0.0, 0], "anchor": [0.0, 0.0, 0], "join": [0.0, 0.0, 0], "fuse": [0.0, 0.0, 0], "match": [0.0, 0.0, 0]}
+    worst_d2 = 0.0
     ld = np.longdouble
     run = mm.ModelRunner()
     for op in sequences[profile, seed]:
         kind, a = op
-        if kind in ("transform", "anchor", "join", "fuse") and a.get("expect", "ok") == "ok":
+        if kind == "compat":  # d2 of either hypothesis, double against extended: 1/20 of the bound the replay uses
+            for b, (true, swapped) in zip(range(len(run.models)) if a["index"] is None else [a["index"]], run.step(op)):
+                m = run.models[b]
+                for got, ids in ((true, a["ids"][b]), (swapped, a["swapped"][b])):
+                    worst_d2 = max(worst_d2, mr.assert_d2_close(got, mr.joint_compat(m.x, m.P, a["z"][b], a["R"][b], ids, dtype=ld), "compat", mm.MATCH_D2_REL / 20.0))
+            continue
+        if kind in ("transform", "anchor", "join", "fuse", "match") and a.get("expect", "ok") == "ok":
             M = run.models
             pairs = [(b, b) for b in range(len(M))] if a["index"] is None else [(a["index"], a.get("src_index", 0))]
             want = {}
@@ -266,9 +384,16 @@ def test_reference_precision(sequences, profile, seed):
                     want[b] = rr.apply_dense(x, P, rr.anchor_g, rr.anchor_J, dtype=ld)
                 elif kind == "fuse":
                     want[b] = fu.fuse_extended(x, P, a["pairs"][b], a["slack"], a["window"])[:2]
+                elif kind == "match":
+                    want[b] = mr.update_extended(x, P, a["z"][b], a["R"][b], a["ids"][b], a["window"])
                 else:
                     want[b] = jr.join(x, P, run.src[s].x, run.src[s].P, dtype=ld)
-            run.step(op)
+            res = run.step(op)
+            if kind == "match":
+                for (_, applied, d2), b in zip(res, list(want)):
+                    assert applied == want[b][2]
+                    worst_d2 = max(worst_d2, mr.assert_d2_close(d2, want[b][3], "match", mm.MATCH_D2_REL / 20.0))
+                    want[b] = want[b][:2]
             for b, (xw, Pw) in want.items():
                 assert xw.dtype == ld and Pw.dtype == ld
                 e = assert_state_close(M[b].x, M[b].P, np.asarray(xw, dtype=np.float64), np.asarray((Pw + Pw.T) / 2, dtype=np.float64),
@@ -279,4 +404,6 @@ def test_reference_precision(sequences, profile, seed):
             run.step(op)
     for k, (ex, eP, cases) in worst.items():
         print("%s seed %d %s: float64 vs longdouble over %d cases, max |dx| %.3e, max |dP| / max |P| %.3e" % (profile, seed, k, cases, ex, eP))
+    if profile in mm.MATCH_PROFILES:
+        print("%s seed %d: d2 of the match and compat ops, float64 vs longdouble: %.3e relative" % (profile, seed, worst_d2))
     assert sum(w[2] for w in worst.values()) >= 1

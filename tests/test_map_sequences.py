@@ -27,6 +27,14 @@ indexing of the export, bit for bit) or as a rewrite: the handle replaced by its
 filter of a batch by ekf_batch_extract_map, or one filter by a fork of a sibling.  At least one of the two twins of such a sequence
 goes on behind a fuse or an extraction.  No more than three handles are open at any time (tests/test_extract_map.py says why).
 
+The *_match profiles (solo_match, chain_match, batch_match) add the matched updates to that mix.  `match`: ekf_update_matched with
+the true associations of a scan of the landmarks nearest the robot -- one to about 2.5 windows' worth of measurements, now and then
+more than 64, landmarks repeated, -1 entries interleaved, in chain_match on maps past 256 landmarks --, about half of them behind an
+open window, in rounds of the handle's window, against tests/match_ref.py on the model's state (and on the export where there is
+one): (n, applied) exact, d2 within map_model.MATCH_D2_REL, every check a rewrite gets, a list that is all -1 leaves its filter
+bit for bit.  `compat`: ekf_joint_compat for the true hypothesis and for one with two ids exchanged, twice the same bits, the
+handle unchanged, counters and decision log unmoved.  The set_state twins may start right behind a `match`.
+
 In the chain_wgs profile EKF_CHAIN_WGS is set for the whole test, which keeps the one-workgroup kernel out of every handle: sources
 and twins run the chain kernel there too; "a source of the other kernel family" happens in the solo and chain profiles."""
 import os
@@ -37,12 +45,13 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import map_model as mm  # noqa: E402
+import match_ref as mr  # noqa: E402
 from helpers import (ABS_P, REL_TOL, assert_bitwise, assert_bitwise_symmetric, assert_state_close, check_duplicates, check_joint,  # noqa: E402
                      ij, index_state, stream_starts, windows_closed)
 
 pytestmark = pytest.mark.gpu
 
-REWRITES = ("remove", "transform", "anchor", "join", "reserve", "fuse", "extract")  # (an extract of mode "probe" is none)
+REWRITES = ("remove", "transform", "anchor", "join", "reserve", "fuse", "extract", "match")  # (an extract of mode "probe" is none)
 TRAFFIC = ("propagate", "update", "compass", "src_propagate", "src_update")
 WORST = {}  # profile -> the largest errors seen so far in this session (printed behind every sequence)
 
@@ -148,6 +157,20 @@ def apply(pkg, h, src, op, counts=None):
         return [h.fuse_landmarks(a["pairs"][a["index"]], slack=a["slack"], index=a["index"])]
     elif kind == "extract":
         return extract(pkg, h, a, counts)
+    elif kind == "match":
+        assert h.window == a["window"], (h.window, a["window"])  # the round size the model updates with
+        if a["index"] is None:
+            applied, d2 = h.update_matched(*(np.stack([a[k][b] for b in range(B)]) for k in ("z", "R", "ids")), index=None)
+            return [(int(n), int(applied[b]), d2[b]) for b, n in enumerate(h.num_landmarks())]
+        b = a["index"]
+        return [h.update_matched(a["z"][b], a["R"][b], a["ids"][b], index=b)]
+    elif kind == "compat":  # the true hypothesis, and the one with two ids exchanged
+        if a["index"] is None:
+            z, R = (np.stack([a[k][b] for b in range(B)]) for k in ("z", "R"))
+            both = [h.joint_compat(z, R, np.stack([a[k][b] for b in range(B)]), index=None) for k in ("ids", "swapped")]
+            return [(both[0][b], both[1][b]) for b in range(B)]
+        b = a["index"]
+        return [tuple(h.joint_compat(a["z"][b], a["R"][b], a[k][b], index=b) for k in ("ids", "swapped"))]
     else:
         raise ValueError(kind)
     return None
@@ -168,7 +191,7 @@ class Replay:
         self.twin_decs = ([], [])
         self.run = mm.ModelRunner()
         self.run.step(ops[0])
-        self.err = {"x": 0.0, "P": 0.0, "d2": 0.0, "joint": 0.0, "covs": 0.0}
+        self.err = {"x": 0.0, "P": 0.0, "d2": 0.0, "joint": 0.0, "covs": 0.0, "match_d2": 0.0}
         self.n_twins = self.n_twins_new = self.n_bitwise = self.n_open = self.n_live = 0
         self.want_log, self.want_src_log = [[] for _ in range(self.B)], []
         self.last = None  # the kind of the last library call on the handle
@@ -194,6 +217,9 @@ class Replay:
         if self.B == 1:  # (ekf_get_robot_cov is a one-filter call)
             assert np.array_equal(self.f.robot_cov(), P[:3, :3]), what
         return x, P
+
+    def match_d2(self, got, want, what):
+        self.err["match_d2"] = max(self.err["match_d2"], mr.assert_d2_close(got, want, what, mm.MATCH_D2_REL))
 
     def logs(self, h):
         return h.stats(), [h.decisions(b) for b in range(h.batch)]
@@ -259,19 +285,24 @@ class Replay:
         if settle and kind == "fuse" and self.twin is not None and not any(len(p) for p in a["pairs"].values()):
             self.export(self.twin)  # (a fuse of no pair leaves an open window open: the twin's window ends where the handle's does)
         src_before = self.export(self.src) if (kind == "join" and settle) else None
-        if rewrite and settle:
+        if (rewrite or kind == "compat") and settle:
             logs0 = self.logs(f)
             src_logs0 = self.logs(self.src) if kind == "join" else None
         if rewrite and not settle and self.last in TRAFFIC:
             self.n_open += 1
             self.n_live += stream_starts(f)[0] > 0  # (host counters only: this handle streams its immediate calls)
-        if kind in ("covs", "fuse"):
+        if kind in ("covs", "fuse", "match", "compat"):
             closed0 = windows_closed(f)
         counts0 = [m.n_landmarks for m in self.run.models]
 
         got = apply(pkg, f, self.src, op, counts0)
         if self.twin is not None:
             got_twin = apply(pkg, self.twin, self.src, op, counts0)
+            if kind == "fuse" and not any(len(p) for p in a["pairs"].values()):
+                # ... and the handle is exported behind every rewrite, settled or not: so is the twin behind this no-op.  (This
+                # makes the twin's export in front of a settled no-pair fuse, above, redundant: the call touches nothing, so it does
+                # not matter on which side of it the window ends.  It stays, so that both handles are read at the same points.)
+                self.export(self.twin)
             if kind == "update":
                 self.twin_decs[0].extend(got), self.twin_decs[1].extend(got_twin)
         want = self.run.step(op)
@@ -321,11 +352,40 @@ class Replay:
                 self.compare(c, what, after[c])
                 if settle:
                     assert_bitwise(after[c], before[c], "%s: the call only reads, filter %d" % (what, c))
+        elif kind == "compat":
+            # a probe: the window is folded (at most the open one), nothing else moves; twice the same bits
+            assert windows_closed(f) - closed0 <= (0 if settle else 1), what
+            after = self.export()
+            again = apply(pkg, f, self.src, op)
+            assert windows_closed(f) - closed0 <= (0 if settle else 1), what
+            for k, b in enumerate(which):
+                for h in (0, 1):
+                    assert again[k][h].tobytes() == got[k][h].tobytes(), what  # an unchanged state: the same bits
+                    self.match_d2(got[k][h], want[k][h], "%s, filter %d, hypothesis %d" % (what, b, h))
+                    if settle:  # ... and against the reference on the export itself
+                        self.match_d2(got[k][h], mr.joint_compat(*before[b], a["z"][b], a["R"][b], a[("ids", "swapped")[h]][b]), what)
+            self.check_logs(f, self.want_log, what)  # counters and decision log do not move
+            assert not settle or self.logs(f) == logs0, what
+            for b in range(B):
+                self.compare(b, what, after[b])
+                if settle:
+                    assert_bitwise(after[b], before[b], "%s: the call only reads, filter %d" % (what, b))
         self.last = kind
         if not rewrite:
             return
 
         held = None
+        if kind == "match":
+            # the rounds' passes are the call's own: at most the open window was closed, none on a settled handle
+            assert windows_closed(f) - closed0 <= (0 if settle else 1), what
+            for k, b in enumerate(which):
+                assert got[k][:2] == want[k][:2], (what, b, got[k][:2], want[k][:2])  # (n, applied): exact
+                self.match_d2(got[k][2], want[k][2], "%s, filter %d" % (what, b))
+                if settle:  # ... and against the reference on the export itself, in rounds of the handle's window
+                    ref = mr.update(*before[b], a["z"][b], a["R"][b], a["ids"][b], f.window)
+                    assert ref[2] == got[k][1], what
+                    self.match_d2(got[k][2], ref[3], "%s, filter %d, on the export" % (what, b))
+            got, want = [g[:2] for g in got], [w[:2] for w in want]
         if kind == "extract":
             got, held, _ = got
         if kind == "fuse":  # the rounds' passes are the call's own: at most the open window was closed, none on a settled handle
@@ -377,6 +437,8 @@ class Replay:
                 assert np.array_equal(after[b][1][3:e, 3:e], before[b][1][3:, 3:]) and np.array_equal(after[b][0][3:e], before[b][0][3:]), what
             elif kind == "fuse" and not len(a["pairs"][b]):
                 assert_bitwise(after[b], before[b], "%s: no pair, filter %d" % (what, b))
+            elif kind == "match" and not (a["ids"][b] >= 0).any():
+                assert_bitwise(after[b], before[b], "%s: a list that is all -1, filter %d" % (what, b))
             elif kind == "extract":  # no arithmetic: the bits of the export, indexed
                 assert_bitwise(after[b], index_state(before[a["src_index"] if a["mode"] == "fork" else b], a["ids"][b]), "%s: filter %d" % (what, b))
 
@@ -388,16 +450,17 @@ def run_sequence(pkg, monkeypatch, profile, seed):
         for i, op in enumerate(ops[1:], 1):
             r.step(i, op)
         assert r.twin is None and r.src is None
-        assert r.n_twins == 2 and r.n_open >= 1 and (profile not in mm.MAP_PROFILES or r.n_twins_new >= 1)
+        assert r.n_twins == 2 and r.n_open >= 1 and (profile not in mm.MAP_PROFILES + mm.MATCH_PROFILES or r.n_twins_new >= 1)
     finally:
         r.close()
     print("%s seed %d: %d ops, %d twins, %d exported rewrites, %d behind open traffic (%d on a streaming handle); max |dx| %.3e, "
-          "max |dP| / max |P| %.3e, d2 %.3e, joint worst %.3e, covs %.3e"
-          % (profile, seed, len(ops), r.n_twins, r.n_bitwise, r.n_open, r.n_live, r.err["x"], r.err["P"], r.err["d2"], r.err["joint"], r.err["covs"]))
+          "max |dP| / max |P| %.3e, d2 %.3e, joint worst %.3e, covs %.3e, d2 of the matched updates %.3e"
+          % (profile, seed, len(ops), r.n_twins, r.n_bitwise, r.n_open, r.n_live, r.err["x"], r.err["P"], r.err["d2"], r.err["joint"], r.err["covs"], r.err["match_d2"]))
     w = WORST.setdefault(profile, dict.fromkeys(r.err, 0.0))
     for k in w:
         w[k] = max(w[k], r.err[k])
-    print("%s, worst so far: max |dx| %.3e, max |dP| / max |P| %.3e, d2 %.3e, joint %.3e, covs %.3e" % (profile, w["x"], w["P"], w["d2"], w["joint"], w["covs"]))
+    print("%s, worst so far: max |dx| %.3e, max |dP| / max |P| %.3e, d2 %.3e, joint %.3e, covs %.3e, d2 of the matched updates %.3e"
+          % (profile, w["x"], w["P"], w["d2"], w["joint"], w["covs"], w["match_d2"]))
 
 
 @pytest.mark.parametrize("seed", mm.SEEDS["solo"])
@@ -443,3 +506,23 @@ def test_batch_maps_sequences(pkg, monkeypatch, pipeline_mode, seed):
     """Three to five filters: the batch forms (a split and a pair list per filter, ekf_batch_extract_map through a scratch batch) and
     single-index calls -- a fuse on one filter, a filter replaced by a fork of a sibling -- that leave the others bit for bit."""
     run_sequence(pkg, monkeypatch, "batch_maps", seed)
+
+
+@pytest.mark.parametrize("seed", mm.SEEDS["solo_match"])
+def test_solo_match_sequences(pkg, monkeypatch, pipeline_mode, seed):
+    """The solo_maps mix with matched updates (ekf_update_matched with the true associations, one to about 2.5 windows' worth of
+    measurements, landmarks repeated, -1 entries interleaved, about half of them behind an open window) and ekf_joint_compat probes."""
+    run_sequence(pkg, monkeypatch, "solo_match", seed)
+
+
+@pytest.mark.parametrize("seed", mm.SEEDS["chain_match"])
+def test_chain_match_sequences(pkg, monkeypatch, pipeline_mode, seed):
+    """The same on the chain kernel's geometry (capacity 257-700): maps that grow past 256 landmarks, k_match_gather's second block."""
+    run_sequence(pkg, monkeypatch, "chain_match", seed)
+
+
+@pytest.mark.parametrize("seed", mm.SEEDS["batch_match"])
+def test_batch_match_sequences(pkg, monkeypatch, pipeline_mode, seed):
+    """Three to five filters: the batch form with one filter's list all -1 (it must stay bit for bit), and single-index calls on a
+    filter b > 0 that leave the others bit for bit."""
+    run_sequence(pkg, monkeypatch, "batch_match", seed)

@@ -5,7 +5,12 @@ tests/test_update_matched_cpu.py, where the same inputs agree with their extende
 here), the inputs are match_ref.gpu_inputs' : 24 planted measurements of the landmarks nearest the robot on 200 landmarks in capacity
 320 (k_chain) and 100 in capacity 200 (k_solo where the pipeline mode allows it), as tests/test_fuse_landmarks.py.
 d2 is compared relatively within match_ref.D2_REL = 5e-12: 20 times the 2.48e-13 the CPU test measures between the double reference
-and its extended-precision restatement over these inputs."""
+and its extended-precision restatement over these inputs.
+The batch form where the filters diverge (match_ref.divergent_batch_inputs): one filter of four whose second round is refused while
+its siblings go on to a third (the `stopped` path of k_match_factor), lists of 70 entries on a fresh handle (a table of 128 entries
+per filter under arrays of 70) with a list of 9 behind them, and filters of 257, 0, 33 and 64 landmarks in one call.  The grid, tile
+and chunk edges of a single filter are in tests/test_map_edges.py, matched updates in random operation sequences in
+tests/test_map_sequences.py."""
 import ctypes
 import functools
 import os
@@ -39,12 +44,7 @@ def loaded(pkg, x, P, cap, max_pending=16, batch=1):
 
 
 def assert_d2_close(got, want, what):
-    assert np.array_equal(np.isnan(got), np.isnan(want)), (what, got, want)
-    ok = ~np.isnan(want)
-    if ok.any():
-        rel = np.abs(got[ok] - want[ok]) / np.abs(want[ok])
-        print("%s: d2 relative %.3e" % (what, rel.max()))
-        assert rel.max() <= mr.D2_REL, (what, rel.max())
+    mr.assert_d2_close(got, want, what, mr.D2_REL)
 
 
 def check(f, pre, z, R, ids, got, what, round_size=None):
@@ -196,6 +196,122 @@ def test_batch_equals_single_calls_bit_for_bit(pkg, pipeline_mode):
     assert list(hs[0].num_landmarks()) == list(counts)
     for f in hs:
         f.close()
+
+
+def batch_handle(pkg, states, cap, max_pending):
+    f = pkg.FilterBatch(len(states), cap, max_pending=max_pending, log_capacity=4096)
+    for b, (x, P) in enumerate(states):
+        if x.size > 3:
+            f.set_state(x, P, index=b)
+    return f
+
+
+def check_filter(f, b, pre, z, R, ids, applied, d2, what):
+    """Filter b of a batch handle after a matched update that answered (applied, d2), against the reference on the export `pre`."""
+    ref = mr.update(pre[0], pre[1], z, R, ids, f.window)
+    after = f.get_state(b)
+    assert applied == ref[2], (what, applied, ref[2])
+    err = assert_state_close(after[0], after[1], ref[0], ref[1], what=what)
+    print("%s: %d applied, max |dx| %.3e, max |dP| / max |P| %.3e" % (what, applied, err[0], err[1]))
+    assert_d2_close(d2, ref[3], what)
+    assert_bitwise_symmetric(after[1])
+    return ref
+
+
+def test_one_refused_filter_among_four(pkg, pipeline_mode):
+    """Filter 2's second round is refused (the same exact measurement twice, R = 0) while its siblings go on to their second and third
+    rounds: it stays at the state after its first round, bit for bit, and takes no part in the later rounds' gather, apply and pass;
+    the siblings are what single calls on a second handle give."""
+    states = mr.batch_states(pkg, mr.BATCH_COUNTS, 80)
+    f, g = batch_handle(pkg, states, 128, 4), batch_handle(pkg, states, 128, 4)
+    assert f.window == 4
+    f.anchor_at_robot(index=2), g.anchor_at_robot(index=2)
+    before = [f.get_state(b) for b in range(4)]
+    assert not before[2][1][:3].any() and not before[2][0][:3].any()
+    ids = np.array(mr.REFUSED_IDS)
+    z, R = mr.refused_scan(pkg, before)
+    want = [sum(1 for i in l if i >= 0) for l in mr.REFUSED_IDS]
+    want[2] = 4
+    assert [-(-w // 4) for w in want] == [3, 3, 1, 3]
+    applied, d2 = f.update_matched(z, R, ids, index=None)
+    assert list(applied) == want
+    assert not np.isnan(d2[2, :4]).any() and np.isnan(d2[2, 4:]).all()
+    for b in range(4):
+        check_filter(f, b, before[b], z[b], R[b], ids[b], int(applied[b]), d2[b], "one refused among four, filter %d" % b)
+    for b in (0, 1, 3):
+        n, ap, db = g.update_matched(z[b], R[b], ids[b], index=b)
+        assert (n, ap) == (mr.BATCH_COUNTS[b], want[b]) and db.tobytes() == d2[b].tobytes()
+    n, ap, db = g.update_matched(z[2, :4], R[2, :4], ids[2, :4], index=2)  # filter 2's first round alone
+    assert (n, ap) == (64, 4) and db.tobytes() == d2[2, :4].tobytes()
+    for b in range(4):
+        assert_bitwise(f.get_state(b), g.get_state(b), "batch form with a refused filter vs single calls, filter %d" % b)
+    # a following valid batch call works, the refused filter included
+    mid = [f.get_state(b) for b in range(4)]
+    ids2 = np.array(mr.FOLLOW_IDS)
+    z2, R2 = (np.stack(a) for a in zip(*[mr.scan_of(pkg, mid[b][0], mr.FOLLOW_IDS[b], 840 + b) for b in range(4)]))
+    applied, d2 = f.update_matched(z2, R2, ids2, index=None)
+    assert list(applied) == [sum(1 for i in l if i >= 0) for l in mr.FOLLOW_IDS]
+    for b in range(4):
+        check_filter(f, b, mid[b], z2[b], R2[b], ids2[b], int(applied[b]), d2[b], "behind the refusal, filter %d" % b)
+    assert list(f.num_landmarks()) == list(mr.BATCH_COUNTS)
+    f.close(), g.close()
+
+
+def test_lists_longer_than_the_table_in_the_batch_form(pkg, pipeline_mode):
+    """70 entries per filter on a fresh handle: the measurement table is made for 128 per filter, not 64, so every [B][zcap] offset of
+    the upload, of the kernels and of the way back has that stride while the caller's arrays have 70; then 9 entries in the same
+    table.  Both against single-index calls on a twin handle, bit for bit, and against the reference."""
+    states = mr.batch_states(pkg, mr.LONG_COUNTS, 80)
+    f, g = batch_handle(pkg, states, 128, 16), batch_handle(pkg, states, 128, 16)
+    assert f.window == 16
+    bytes0 = f.device_bytes()
+    grew = []
+    for name, lists, seed in (("list of 70", mr.long_lists(), 870), ("list of 9 behind it", np.array(mr.LONG_NINE), mr.NINE_SCAN_SEED)):
+        pre = [f.get_state(b) for b in range(3)]
+        z, R = (np.stack(a) for a in zip(*[mr.scan_of(pkg, pre[b][0], lists[b], seed + b) for b in range(3)]))
+        want = [int((lists[b] >= 0).sum()) for b in range(3)]
+        applied, d2 = f.update_matched(z, R, lists, index=None)
+        grew.append(f.device_bytes())
+        assert list(applied) == want
+        assert np.array_equal(np.isnan(d2), lists < 0)
+        jc = g.joint_compat(z[:, :9], R[:, :9], lists[:, :9], index=None)  # (the twin's table: made for 64 by this score, replaced by one for 128 in its long call)
+        for b in range(3):
+            check_filter(f, b, pre[b], z[b], R[b], lists[b], int(applied[b]), d2[b], "%s, filter %d" % (name, b))
+            n, ap, db = g.update_matched(z[b], R[b], lists[b], index=b)
+            assert (n, ap) == (mr.LONG_COUNTS[b], want[b]) and db.tobytes() == d2[b].tobytes(), (name, b)
+            assert_bitwise(f.get_state(b), g.get_state(b), "%s: batch form vs single calls, filter %d" % (name, b))
+            assert_d2_close(jc[b], mr.joint_compat(*pre[b], z[b, :9], R[b, :9], lists[b, :9]), "%s: score of the first 9, filter %d" % (name, b))
+    assert max(int((mr.long_lists()[b] >= 0).sum()) for b in range(3)) > 64
+    assert grew[0] > bytes0 and grew[1] == grew[0]  # the table grows once and not again
+    f.close(), g.close()
+
+
+def test_no_landmarks_beside_257(pkg, pipeline_mode):
+    """Counts (257, 0, 33, 64) in capacity 320: k_match_gather's grid has two blocks of 256 landmarks for every filter, filter 0
+    measures landmark 256, filter 1 has nothing to measure and stays bit for bit."""
+    states = mr.batch_states(pkg, mr.WIDE_COUNTS, 90)
+    f, g = batch_handle(pkg, states, 320, 8), batch_handle(pkg, states, 320, 8)
+    assert f.window == 8 and list(f.num_landmarks()) == list(mr.WIDE_COUNTS)
+    f.propagate(0.3, 0.05, 0.05), g.propagate(0.3, 0.05, 0.05)  # (filter 1 away from the all-zero state of a fresh filter)
+    before = [f.get_state(b) for b in range(4)]
+    assert before[1][0].size == 3 and before[1][1].any()
+    ids = np.array(mr.WIDE_IDS)
+    assert ids[0, 0] == 256 and (ids[1] == -1).all()
+    z, R = (np.stack(a) for a in zip(*[mr.scan_of(pkg, before[b][0], mr.WIDE_IDS[b], 890 + b) for b in range(4)]))
+    applied, d2 = f.update_matched(z, R, ids, index=None)
+    assert list(applied) == [int((ids[b] >= 0).sum()) for b in range(4)] and applied[1] == 0
+    assert np.array_equal(np.isnan(d2), ids < 0)
+    jc = g.joint_compat(z, R, ids, index=None)
+    for b in range(4):
+        check_filter(f, b, before[b], z[b], R[b], ids[b], int(applied[b]), d2[b], "0 beside 257, filter %d" % b)
+        assert_d2_close(jc[b], mr.joint_compat(*before[b], z[b], R[b], ids[b]), "0 beside 257: the score, filter %d" % b)
+        if b != 1:
+            n, ap, db = g.update_matched(z[b], R[b], ids[b], index=b)
+            assert (n, ap) == (mr.WIDE_COUNTS[b], int(applied[b])) and db.tobytes() == d2[b].tobytes()
+        assert_bitwise(f.get_state(b), g.get_state(b), "batch form vs single calls, filter %d" % b)
+    assert_bitwise(f.get_state(1), before[1], "the filter without a landmark")
+    assert list(f.num_landmarks()) == list(mr.WIDE_COUNTS)
+    f.close(), g.close()
 
 
 # ---- 7. joint_compat ------------------------------------------------------------------------------------
