@@ -5,8 +5,10 @@
 // scripts and their HIP-graph replay.  There is no CPU fallback: without a gfx950 device
 // ekf_create fails with EKF_ERR_NO_DEVICE.
 //
-// This file is the hot layer -- window and segment planner, streaming command ring, close_set, launch_ops, the graph path -- and the
-// accessors.  The map operations (removal, frame change, joining, extraction, consistency, duplicate search, fusion), which run once
+// This file is the hot layer -- streaming command ring, the enqueuer of the window scheduler (issue_pass, OpsSink, close_set,
+// launch_ops), the graph path -- and the accessors.  What every launch and every dense pass looks like is decided by pure code in
+// ekf_window_plan.h (WindowState, plan_close, plan_ops, route_call); this file resolves its roles to streams and events and makes
+// the HIP calls.  The map operations (removal, frame change, joining, extraction, consistency, duplicate search, fusion), which run once
 // per call on a handle at rest, are in ekf_map_api.hip, included below where they use this file's helpers; their list checks and
 // tables are pure code in ekf_map_plan.h.
 #include <math.h>
@@ -18,13 +20,13 @@
 #include <string>
 #include <atomic>
 #include <mutex>
-#include <functional>
 #include <vector>
 #include <algorithm>
 
 #include "ekf_device.h"
 #include "ekf_geometry.h"
 #include "ekf_map_plan.h"
+#include "ekf_window_plan.h"
 
 // single translation unit: the kernels are compiled together with their launch sites
 #include "ekf_kernels.hip"
@@ -102,20 +104,14 @@ struct ekf_batch {
     hipStream_t s_chain;  // chain kernels (and, without overlap, the dense passes too)
     hipStream_t s_flush;  // overlap: the dense passes; == s_chain otherwise
     bool overlap;         // a window's dense pass runs beside the next window's chain kernels (two slot sets, two Bm buffers)
-    int prev_pending;     // overlap: slots of the other set whose dense pass has been launched but is not in Bm[buf_in]
     hipEvent_t ev_chain, ev_flush[2];
-    hipEvent_t pass_done[2] = {nullptr, nullptr};  // completion of the pass that ev_flush[i] stands for: ev_flush[i] itself, or, while passes are profiled, that pass's stop event
-    int ev_idx;           // ev_flush[ev_idx] belongs to the dense pass launched last
-    bool chain_signalled; // the last chain launch carried ev_chain as its stop event
-    int pass_seq;         // dense passes launched so far (overlap mode); k_mark stores it into dv.pass_flag behind each pass
-    int need_pass;        // the pass the next chain launches have to wait for in-kernel, 0 = none
+    hipEvent_t prof_stop[2] = {nullptr, nullptr};  // EV_PROFi: the stop event of the profiling pair that the pass of slot i took
+    WindowCfg wcfg;       // what the window scheduler (ekf_window_plan.h) knows of this handle: read_debug_hooks fills it
+    WindowState win;      // which window is open and what it waits for
     bool inkernel_wait;   // chain kernels wait for their pass in-kernel (kernels of two streams run side by side), else by event
     long long chain_seq;  // chain launches so far; the kernel stores it into the host mirror when it is done
     int ncu = 0;                            // CUs of the device
     bool persist = true;                    // scripted runs in overlap mode: one chain launch for several windows (EKF_PERSIST=0 switches it off)
-    unsigned long long seg_count_base[EKF_PLAN_MAX] = {};  // value dv.seg_count[i] reaches when every multi-segment launch enqueued so far has finished
-    unsigned long long open_set_gate = 0;   // != 0: the open set was filled by segment open_gate_idx of a multi-segment launch: dv.seg_count[open_gate_idx] >= this opens its pass
-    int open_gate_idx = 0;
     bool stats_in_mirror = false;  // mirror.stats is current (a chain launch ran since the last ekf_reset_stats)
     bool mirror_by_chain; // the newest writer of the host mirror is chain launch number chain_seq (else: some other kernel, synchronise)
     int flush_keep;       // pool key of s_flush: CUs kept free for the chain, -1 = unmasked
@@ -145,16 +141,10 @@ struct ekf_batch {
     int chain_threads;
     // host-side tracking
     int n_lm_hi;    // upper bound on max_b n_lm[b]
-    int cur_set;    // slot set being filled
-    int pending;    // slots used in cur_set
-    int buf_in;     // Bm buffer the chain kernels read (complete up to the sets still open or in flight)
-    int flush_dir;        // direction of the next dense pass (0 = first to last; tn.flush_alternate)
     // Product tunables and experiment variables (read from the environment at ekf_*_create by read_tunables, listed in
     // include/ekfslam_c.h "Tunables" and INTEGRATION.md; every one of them changes scheduling only, never results) -- bench.py
     // records every EKF_* variable it saw.
     Tunables tn;
-    long long windows_closed = 0;      // windows handed to a dense pass by close_set since create (ekf_debug_windows)
-    int last_window_slots = 0;          // ... and the slots of the last one
     // Test / experiment hooks.  They exist only in the debug variant of the library (make debug: -DEKF_DEBUG_HOOKS,
     // libekfslam_hip_debug.so); in the product build the fields keep these values and no environment variable can change them.
     bool dbg_skip_flush = false;        // EKF_DEBUG_SKIP_FLUSH=1: timing experiments only, results are wrong
@@ -463,24 +453,10 @@ static void launch_pass(const EkfDev &dv, hipStream_t s, hipEvent_t e0, hipEvent
         hipExtLaunchKernelGGL(k_flush_rb, dim3(nwg, nb), dim3(256), 0, s, e0, e1, 0, dv, nT_hi, set, nslots, fin, fout, tmap, 0, rev, b0, nb);
 }
 
-// Advance *i over operations until the window holds `limit` slots or EKF_CHAIN_MAX_OPS operations have been taken; `used` slots are
-// taken already.  Returns the slots used afterwards (consumes[q] != 0: operation q takes a slot).
-static int take_ops(const unsigned char *consumes, int nops, int *i, int used, int limit) {
-    const int start = *i;
-    while (*i < nops && *i - start < EKF_CHAIN_MAX_OPS) {
-        if (consumes[*i]) {
-            if (used == limit) break;
-            used++;
-        }
-        (*i)++;
-    }
-    return used;
-}
-
 static int create_impl(ekf_batch *h, int batch, int capacity_landmarks, int device_id, const ekf_params *params, const hipDeviceProp_t &prop);
 
 // The debug variant reads its hooks when a handle is created and again at ekf_set_state (a test switches them off between the
-// two); the product build compiles to nothing.
+// two); the product build reads none.
 static void read_debug_hooks(ekf_batch *h) {
 #ifdef EKF_DEBUG_HOOKS
     h->dv.spin_limit = getenv("EKF_DEBUG_SPIN_LIMIT") ? atoll(getenv("EKF_DEBUG_SPIN_LIMIT")) : (1LL << 24);
@@ -489,9 +465,15 @@ static void read_debug_hooks(ekf_batch *h) {
     h->dbg_drop_marks_to = getenv("EKF_DEBUG_DROP_MARKS_TO") ? atoi(getenv("EKF_DEBUG_DROP_MARKS_TO")) : 0x7fffffff;
     h->dbg_stream_idle_ticks = getenv("EKF_DEBUG_STREAM_IDLE_TICKS") ? atol(getenv("EKF_DEBUG_STREAM_IDLE_TICKS")) : 0;
     h->dbg_stream_no_recheck = getenv("EKF_DEBUG_STREAM_NO_RECHECK") && atoi(getenv("EKF_DEBUG_STREAM_NO_RECHECK")) != 0;
-#else
-    (void)h;
 #endif
+    // ... and the window scheduler's view of the handle (ekf_window_plan.h) is written here, once the geometry, the streams and the hooks are known
+    WindowCfg &c = h->wcfg;
+    const Tunables &tn = h->tn;
+    c.B = h->dv.B, c.maxp = h->dv.maxp, c.overlap = h->overlap, c.inkernel_wait = h->inkernel_wait, c.chain_wgs = h->chain_wgs, c.chain_filters = h->chain_filters;
+    c.solo = h->solo, c.solo_kernel = h->solo_kernel, c.solo_fuse = h->solo_fuse, c.ngroups = h->ngroups, c.persist = h->persist;
+    c.balanced_tail = tn.balanced_tail, c.flush_alternate = tn.flush_alternate, c.batch_interleave = tn.batch_interleave, c.overlap_serial = tn.overlap_serial;
+    c.xcd_map = tn.xcd_map, c.inline_rec = tn.inline_rec, c.solo_fuse_stagger_ticks = tn.solo_fuse_stagger_ticks;
+    c.dbg_skip_flush = h->dbg_skip_flush, c.dbg_drop_marks_from = h->dbg_drop_marks_from, c.dbg_drop_marks_to = h->dbg_drop_marks_to;
 }
 
 extern "C" int ekf_destroy(ekf_handle h);
@@ -879,13 +861,7 @@ static const int *tile_map_for(ekf_batch *h, int nT) {
 }
 
 // ---- chain / dense-pass alternation ------------------------------------------------------------------
-// Close the slot set being filled and hand it to a dense pass; the chain continues into the other set.
-//  * without overlap: the pass folds the set into Bm in place, in stream order behind the chain kernels.
-//  * with overlap: pass k runs on its own stream, Bm[fin] -> Bm[fin ^ 1], while the chain kernels of window
-//    k+1 read Bm[fin] and fold set k themselves (n_prev).  Pass k starts after the chain kernels of window k
-//    (ev_chain) and, by stream order, after pass k-1 whose output it reads; the chain kernels of window k+1
-//    start after pass k-1 (they read its output and overwrite the slot rows it read).
-typedef std::vector<std::function<hipError_t()>> EnqueueList;
+// The decisions are ekf_window_plan.h's (plan_close, plan_ops, ...); what follows carries them out.
 
 // The profiling events (a start / stop pair per dense pass, or per k_solo launch that folds its own windows) are created where
 // profiling is switched on and where a script is loaded -- enough pairs for every window the script can close between two reads --
@@ -920,12 +896,7 @@ static size_t prof_pairs_for_script(const ekf_batch *h) {
 static int stream_start(ekf_batch *h, long long consumed0, int slot0) {
     ChainPlan plan;
     memset(&plan, 0, sizeof plan);
-    ChainSeg &sg = plan.s[0];
-    sg.k0 = 0, sg.nops = 0, sg.slot0 = slot0, sg.set = h->cur_set, sg.buf_read = h->buf_in, sg.n_prev = h->prev_pending;
-    sg.need_pass = h->need_pass, sg.drop = 0;
-    sg.seq = consumed0;  // the last command consumed before this launch
-    // (a one-workgroup filter whose launches fold the windows they fill does so in a streaming launch too, behind the command that closes the window)
-    sg.gate = 0, sg.self_pass = (h->solo_kernel && h->solo_fuse && !h->dbg_skip_flush) ? 1 : 0, sg.stagger = 0;
+    plan.s[0] = stream_segment(h->wcfg, h->win, consumed0, slot0);
     plan.nseg = 1, plan.signal = 0, plan.inl_n = 0;
     if (h->dbg_stream_idle_ticks > 0 || h->dbg_stream_no_recheck) {  // (debug library only: a streaming launch has no inline record, the fields carry the test hooks)
         plan.inl_n = 1 | (h->dbg_stream_no_recheck ? 2 : 0);
@@ -936,7 +907,6 @@ static int stream_start(ekf_batch *h, long long consumed0, int slot0) {
     __atomic_store_n(&h->sctl_h->state, ((unsigned long long)(unsigned)plan.stream << 2) | EKF_STREAM_RUNNING, __ATOMIC_SEQ_CST);
     launch_chain(h, h->s_chain, /*streaming*/ true, /*on_packet*/ true, nullptr, nullptr, (const double *)h->ring_d, nullptr, plan, 0, 1);
     h->stream_alive = true;
-    h->chain_signalled = false;
     h->stream_starts++;
     return check_launch();
 }
@@ -987,7 +957,54 @@ static int stream_stop(ekf_batch *h) {
     return rc;
 }
 
-static int close_set(ekf_batch *h, bool terminal, EnqueueList *defer);
+static hipEvent_t role_event(const ekf_batch *h, EvRole r) {
+    switch (r) {
+    case EV_CHAIN: return h->ev_chain;
+    case EV_FLUSH0: case EV_FLUSH1: return h->ev_flush[r - EV_FLUSH0];
+    case EV_PROF0: case EV_PROF1: return h->prof_stop[r - EV_PROF0];
+    default: return nullptr;
+    }
+}
+
+// A pass that goes out later, behind a launch that is made first: its tile map is built (a synchronous copy) while nothing is resident.
+static int prepare_pass(ekf_batch *h, const PassOrder &o) {
+    if (o.want_tile_map) (void)tile_map_for(h, o.nT_hi);
+    return EKF_OK;
+}
+
+// The only place that turns a PassOrder into calls.
+static int issue_pass(ekf_batch *h, const PassOrder &o) {
+    if (o.nslots == 0) return EKF_OK;
+    const EkfDev &dv = h->dv;
+    const hipStream_t sc = h->s_chain, sf = o.on == ON_CHAIN ? h->s_chain : h->s_flush;
+    hipEvent_t e0 = nullptr, e1 = role_event(h, o.stop);
+    if (o.prof) {
+        EKF_TRY(prof_take_pair(h, &e0, &e1));
+        if (o.done == EV_PROF0 || o.done == EV_PROF1) h->prof_stop[o.done - EV_PROF0] = e1;
+    }
+    const int *tmap = o.want_tile_map ? tile_map_for(h, o.nT_hi) : (const int *)nullptr;
+    const hipEvent_t wait_prev = role_event(h, o.wait_prev), done_ev = role_event(h, o.done);
+    if (o.terminal) {
+        if (wait_prev) HIP_TRY(hipStreamWaitEvent(sc, wait_prev, 0));
+    } else {
+        if (o.gate_seq) HIP_TRY(hipStreamWaitValue64(sf, dv.seg_count + o.gate_idx, o.gate_seq, hipStreamWaitValueGte, 0xffffffffffffffffull));
+        if (o.record_chain) HIP_TRY(hipEventRecord(h->ev_chain, sc));
+        if (o.wait_chain) HIP_TRY(hipStreamWaitEvent(sf, h->ev_chain, 0));
+    }
+    if (o.do_pass) launch_pass(dv, sf, e0, e1, o.interleave, o.nT_hi, o.set, o.nslots, o.fin, o.fout, tmap, o.rev, 0, dv.B);
+    if (!o.terminal && wait_prev) HIP_TRY(hipStreamWaitEvent(sc, wait_prev, 0));
+    if (o.mark) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, sf, dv.pass_flag, o.mark_value);
+    if (o.record_done) HIP_TRY(hipEventRecord(done_ev, sf));
+    if (o.wait_done_on_chain) HIP_TRY(hipStreamWaitEvent(sc, done_ev, 0));
+    HIP_TRY(hipGetLastError());
+    return EKF_OK;
+}
+
+// Close the slot set being filled and hand it to a dense pass (plan_close); the chain continues into the other set.
+static int close_set(ekf_batch *h, bool terminal = false) {
+    EKF_TRY(stream_stop(h));
+    return issue_pass(h, plan_close(h->wcfg, h->win, terminal, h->n_lm_hi, h->prof_flush));
+}
 
 // One immediate-mode operation through the streaming launch: post the command, make sure somebody consumes it, keep the host's
 // window bookkeeping (launch_ops' for a one-operation launch).  rec: the operation's record; consumes: it takes a slot.
@@ -996,7 +1013,7 @@ static int close_set(ekf_batch *h, bool terminal, EnqueueList *defer);
 static int stream_op(ekf_batch *h, const double *rec, int n_slots) {
     StreamCtl *c = h->sctl_h;
     const bool consumes = n_slots > 0;
-    const bool closes = consumes && h->pending + n_slots >= h->dv.maxp;
+    const bool closes = stream_closes(h->wcfg, h->win, n_slots);
     const long long seq = ++h->chain_seq;
     StreamCmd *cmd = &h->sring_h->cmd[(unsigned long long)seq % EKF_STREAM_RING];
     if (h->stream_alive && seq - EKF_STREAM_RING > 0) {  // the slot's previous command (seq - ring) must have been executed: a caller that posts without ever reading
@@ -1021,10 +1038,10 @@ static int stream_op(ekf_batch *h, const double *rec, int n_slots) {
     }
     h->stream_ops++;
     h->stream_last_seq = seq;
-    h->stream_slot_before[(unsigned long long)seq % EKF_STREAM_RING] = h->pending;
+    h->stream_slot_before[(unsigned long long)seq % EKF_STREAM_RING] = h->win.pending;
     if (!h->stream_alive) {
         // (every earlier streamed command has been executed: a launch is only written off behind stream_wait_consumed -- stream_stop, a closing command)
-        EKF_TRY(stream_start(h, seq - 1, h->pending));
+        EKF_TRY(stream_start(h, seq - 1, h->win.pending));
     } else {
         // "write mine, fence, read yours": the launch does the same with its state word and this command slot before it leaves by itself, so
         // normally one of the two sees the other.  RUNNING: the launch will find the command.  Anything else: wait for the outcome (the
@@ -1037,141 +1054,26 @@ static int stream_op(ekf_batch *h, const double *rec, int n_slots) {
     }
     h->mirror_by_chain = true;
     h->stats_in_mirror = true;
-    if (consumes) h->pending += n_slots;
+    if (consumes) h->win.pending += n_slots;
     if (closes) {
         // the launch leaves behind this operation by itself (EKF_STREAM_END_AFTER); the window's dense pass is enqueued behind it once the
         // closing command is known to have been executed (a synchronising caller would wait for it next anyway)
         int rc = stream_wait_consumed(h, seq);
         h->stream_alive = false;
         if (rc) return rc;
-        // The next window's streaming launch goes out at once, IN FRONT of the pass's launch: a pass that is already streaming holds every CU
-        // its mask allows with a queue of workgroups behind them, and a chain launch that arrives later gets its 64 CUs one by one as tiles
-        // finish -- the first exchange then waits for the last workgroup, 100 us (seen as a bimodal p90).  Launched first, it is resident when
-        // the next call comes (within the idle time) and the pass takes what is left.  The event the pass waits for sits between the two.
-        if (h->overlap) {
-            HIP_TRY(hipEventRecord(h->ev_chain, h->s_chain));  // (behind the launch that filled the window)
-            h->chain_signalled = true;
-            EnqueueList pass;
-            EKF_TRY(close_set(h, false, &pass));  // the host's state now describes the next window; the pass's calls wait in `pass`
-            rc = stream_start(h, seq, h->pending);
-            for (auto &enq : pass) {
-                hipError_t e = enq();
-                if (e != hipSuccess && rc == EKF_OK) rc = set_error(EKF_ERR_HIP, "%s", hipGetErrorString(e));
-            }
-            return rc;
+        // the window turns over (plan_stream_turn: with overlap the pass goes out behind the next streaming launch, a k_solo launch has folded
+        // the window itself, in place the pass runs on the chain's stream and the next launch behind it)
+        const StreamTurn t = plan_stream_turn(h->wcfg, h->win, h->n_lm_hi, h->prof_flush);
+        if (t.record_chain) HIP_TRY(hipEventRecord(h->ev_chain, h->s_chain));  // (behind the launch that filled the window)
+        if (!t.pass_after_start) EKF_TRY(issue_pass(h, t.pass));
+        else EKF_TRY(prepare_pass(h, t.pass));
+        rc = stream_start(h, seq, h->win.pending);
+        if (t.pass_after_start) {
+            const int rc_pass = issue_pass(h, t.pass);
+            if (rc == EKF_OK) rc = rc_pass;
         }
-        if (h->solo_kernel && h->solo_fuse && !h->dbg_skip_flush) {
-            // (folded by the launch itself, behind the closing command: the next launch starts an empty window, as launch_ops has it)
-            h->windows_closed++;
-            h->last_window_slots = h->pending;
-            h->cur_set ^= 1;
-            h->pending = 0;
-            return stream_start(h, seq, 0);
-        }
-        EKF_TRY(close_set(h, false, nullptr));  // (in place: the pass runs on the chain's stream, the next launch behind it)
-        return stream_start(h, seq, h->pending);
+        return rc;
     }
-    return EKF_OK;
-}
-
-static int close_set(ekf_batch *h, bool terminal = false, EnqueueList *defer = nullptr) {
-    EKF_TRY(stream_stop(h));
-    if (h->pending == 0) return EKF_OK;
-    int nT_hi = (2 * h->n_lm_hi + 63) / 64;
-    const int fin = (h->overlap && h->prev_pending > 0) ? h->buf_in ^ 1 : h->buf_in;
-    // terminal: the caller asked for everything to be folded (ekf_flush, settle), so no chain kernel will run beside this
-    // pass.  It then goes out on the chain's own stream (no cross-stream event hop: ~16 us, no k_mark: ~9 us), on all CUs,
-    // and in place (the faster form when nothing else uses the memory system); the pipeline restarts empty afterwards.
-    terminal = terminal && h->overlap;
-    const int fout = (h->overlap && !terminal) ? fin ^ 1 : fin;
-    hipStream_t sf = terminal ? h->s_chain : h->s_flush, sc = h->s_chain;
-    // What the pass waits for.  A set filled by a segment of a multi-segment chain launch: the value dv.seg_count shows when
-    // every workgroup has finished that segment (a stream gate, hipStreamWaitValue64: the kernel is still running).  Otherwise
-    // the chain launch's event.
-    const unsigned long long gate_seq = terminal ? 0 : h->open_set_gate;
-    const int gate_idx = h->open_gate_idx;
-    h->open_set_gate = 0;
-    bool record_chain = false, wait_chain = false;
-    hipEvent_t wait_prev = nullptr;
-    if (terminal) {
-        if (h->prev_pending > 0) wait_prev = h->pass_done[h->ev_idx];  // pass k-1 wrote Bm[fin]
-        h->chain_signalled = false;
-    } else if (h->overlap) {
-        if (!gate_seq) record_chain = !h->chain_signalled, wait_chain = true;
-        h->chain_signalled = false;
-    }
-    const bool do_pass = !h->dbg_skip_flush && (nT_hi > 0 || h->overlap);
-    if (nT_hi < 1) nT_hi = 1;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (do_pass) {
-        if (h->overlap && !terminal) e1 = h->ev_flush[h->ev_idx ^ 1];  // pass k's completion, signalled by its own dispatch packet
-        if (h->prof_flush) EKF_TRY(prof_take_pair(h, &e0, &e1));  // (e1 doubles as the pass's completion event)
-    }
-    // Passes alternate direction: a pass starts on the tiles the previous pass touched last, which are the ones the
-    // 256 MB Infinity Cache still holds (P_LL of N=4096 is 270 MB per buffer: walked the same way every time, the
-    // cache has evicted a tile long before the next pass comes back to it).
-    const int rev = h->tn.flush_alternate ? h->flush_dir : 0;
-    if (do_pass) h->flush_dir ^= 1;
-    const bool interleave = h->dv.B > 1 && h->tn.batch_interleave;  // a filter's workgroups on one XCD
-    const int *tmap = (do_pass && !interleave && h->dv.B == 1) ? tile_map_for(h, nT_hi) : (const int *)nullptr;
-    const EkfDev dv = h->dv;
-    const int set = h->cur_set, nslots = h->pending, B = h->dv.B;
-    h->windows_closed++;
-    h->last_window_slots = nslots;
-    bool mark = false, record_done = false, wait_done_on_chain = false, serial = false;
-    int mark_value = 0;
-    hipEvent_t done_ev = nullptr;
-    if (terminal) {
-        h->need_pass = 0;
-        h->buf_in = fin;
-        h->prev_pending = 0;
-    } else if (h->overlap) {
-        // the chain kernels of the next window depend on pass k-1 (they read its output and overwrite the slot rows it
-        // read): they wait for its number in dv.pass_flag themselves
-        // ... or, where kernels of two streams do not run side by side, the stream waits for the pass's event
-        if (h->inkernel_wait) {
-            h->need_pass = h->prev_pending > 0 ? h->pass_seq : 0;  // pass_seq still names pass k-1 here
-        } else {
-            h->need_pass = 0;
-            if (h->prev_pending > 0) wait_prev = h->pass_done[h->ev_idx];  // pass k-1, awaited by the chain's stream
-        }
-        mark = true, mark_value = ++h->pass_seq;  // pass k
-        if (h->dbg_drop_marks_from > 0 && mark_value >= h->dbg_drop_marks_from && mark_value < h->dbg_drop_marks_to) mark = false;  // (test hook of the debug variant: a pass that never reports)
-        h->ev_idx ^= 1;  // pass_done[ev_idx] is pass k's completion: ev_flush[ev_idx] as its stop event, or the profiling pair's stop event
-        record_done = false;
-        done_ev = (h->prof_flush && do_pass) ? e1 : h->ev_flush[h->ev_idx];
-        if (!do_pass) record_done = true, done_ev = h->ev_flush[h->ev_idx];  // (no pass kernel to carry the event: a marker)
-        h->pass_done[h->ev_idx] = done_ev;
-        serial = h->tn.overlap_serial;  // experiment: no concurrency
-        wait_done_on_chain = serial;
-        h->buf_in = fin;
-        h->prev_pending = h->pending;
-    }
-    h->cur_set ^= 1;
-    h->pending = 0;
-    hipEvent_t ev_chain = h->ev_chain;
-    auto enqueue = [=]() -> hipError_t {
-        hipError_t e = hipSuccess;
-        if (terminal) {
-            if (wait_prev && (e = hipStreamWaitEvent(sc, wait_prev, 0)) != hipSuccess) return e;
-        } else {
-            if (gate_seq && (e = hipStreamWaitValue64(sf, dv.seg_count + gate_idx, gate_seq, hipStreamWaitValueGte, 0xffffffffffffffffull)) != hipSuccess) return e;
-            if (record_chain && (e = hipEventRecord(ev_chain, sc)) != hipSuccess) return e;
-            if (wait_chain && (e = hipStreamWaitEvent(sf, ev_chain, 0)) != hipSuccess) return e;
-        }
-        if (do_pass) launch_pass(dv, sf, e0, e1, interleave, nT_hi, set, nslots, fin, fout, tmap, rev, 0, B);
-        if (!terminal && wait_prev && (e = hipStreamWaitEvent(sc, wait_prev, 0)) != hipSuccess) return e;
-        if (mark) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, sf, dv.pass_flag, mark_value);
-        if (record_done && (e = hipEventRecord(done_ev, sf)) != hipSuccess) return e;
-        if (wait_done_on_chain && (e = hipStreamWaitEvent(sc, done_ev, 0)) != hipSuccess) return e;
-        return hipGetLastError();
-    };
-    if (defer) {
-        defer->push_back(enqueue);
-        return EKF_OK;
-    }
-    hipError_t e = enqueue();
-    if (e != hipSuccess) return set_error(EKF_ERR_HIP, "%s", hipGetErrorString(e));
     return EKF_OK;
 }
 
@@ -1179,186 +1081,37 @@ static int close_set(ekf_batch *h, bool terminal = false, EnqueueList *defer = n
 static int settle(ekf_batch *h) {
     EKF_TRY(close_set(h, true));
     HIP_TRY(stream_wait(h->s_chain));
-    if (h->overlap) {
-        HIP_TRY(stream_wait(h->s_flush));
-        if (h->prev_pending > 0) {
-            h->buf_in ^= 1;  // the last pass's output
-            h->prev_pending = 0;
-        }
-    }
+    if (h->overlap) HIP_TRY(stream_wait(h->s_flush));
+    land_last_pass(h->wcfg, h->win);
     return EKF_OK;
 }
 
-// Launch k_chain over ops [k0, k0 + nops) of `in`, cutting at slot-set boundaries.
-// consumes[i] != 0 when op i takes a slot (measurement, masked measurement, compass).
-// defer_last_close: when the last launch of this call fills the set, leave the set closed-to-be: the next call closes it
-// (regular pass) or ekf_flush / a state read does (terminal pass, close_set).  Scripted runs use it; never while capturing.
-static int launch_ops_grouped(ekf_batch *h, const double *in, int k0, const unsigned char *consumes, int nops);
-
-static int launch_ops(ekf_batch *h, const double *in, const int *cursor, int k0, const unsigned char *consumes, int nops, bool defer_last_close = false) {
-    if (h->stream_calls && cursor == nullptr && in == h->ring_d && nops > 0) {
-        // an immediate-mode call of a one-filter handle: its operations go to the resident streaming launch, one command each
-        if (h->pending == h->dv.maxp) EKF_TRY(close_set(h));  // a set whose close a scripted run deferred: more work follows, regular pass
-        for (int q = 0; q < nops; q++) EKF_TRY(stream_op(h, h->ring_h + (size_t)(k0 + q) * 8, consumes[q] ? 1 : 0));
-        return EKF_OK;
-    }
-    if (h->stream_calls && cursor == nullptr && in == h->script_d && nops > 0 && nops <= EKF_CHAIN_MAX_OPS) {
-        // A SHORT scripted chunk of a one-filter handle (ekf_script_run of a step or two: the per-step call pattern of BASELINE.json config 2's
-        // latency figure): one OP_SCRIPT command to the resident launch per stretch that stays inside the open window -- at most HALF a window
-        // of measurements in all: a step or two.  Whole windows and longer runs keep the multi-segment launches (their windows turn over
-        // without the launch leaving, a window they fill exactly stays open for the next call -- what bench.py's timed regions and its
-        // one-window `alone` runs rely on).
-        int slots = 0;
-        for (int q = 0; q < nops; q++) slots += consumes[q] ? 1 : 0;
-        if (2 * slots <= h->dv.maxp) {
-            if (h->pending == h->dv.maxp) EKF_TRY(close_set(h));
-            int q0 = 0;
-            while (q0 < nops) {
-                int q1 = q0;
-                const int used = take_ops(consumes, nops, &q1, h->pending, h->dv.maxp) - h->pending;  // (up to, and including, the measurement that fills the window)
-                double rec[8] = {0, 0, 0, 0, 0, 0, 0, (double)OP_SCRIPT};
-                const long long bits = (long long)(size_t)h->script_d;
-                memcpy(&rec[0], &bits, sizeof bits);
-                rec[1] = (double)(k0 + q0), rec[2] = (double)(q1 - q0);
-                EKF_TRY(stream_op(h, rec, used));
-                q0 = q1;
-            }
-            return EKF_OK;
-        }
-    }
-    EKF_TRY(stream_stop(h));
-    int i = 0;
-    if (h->pending == h->dv.maxp && nops > 0) EKF_TRY(close_set(h));  // a set whose close the previous call deferred: more work follows, regular pass
-    // Scripted runs in overlap mode: the launches of one call become the segments of one launch (up to EKF_PLAN_MAX at a
-    // time).  The workgroups stay resident across window boundaries -- no launch gap (5 us), no refill of the LDS caches
-    // from memory (7 us per 16-measurement window at N = 4096) -- and the dense passes are enqueued behind stream gates that
-    // the running kernel opens (dv.seg_count).  Needs kernels of two streams side by side (the in-kernel pass wait's probe).
-    // ... and CUs on which a pass can run while the chain workgroups stay resident: a chain wave leaves too few registers
-    // on its SIMD for a pass wave, so a pass only runs on CUs without a chain workgroup.  Multi-segment launches are used
-    // while the chain workgroups of ALL live handles hold at most half of the GPU (256 filters of one workgroup each would
-    // wait forever for a pass that cannot start: that batch keeps one launch per segment).
-    bool persist = h->persist && defer_last_close && cursor == nullptr && h->overlap && h->inkernel_wait && h->chain_filters == h->dv.B;
-    if (persist) {
-        std::lock_guard<std::mutex> lk(g_res_mu);
-        persist = (g_cus_claimed[h->device] + g_cus_solo[h->device] - h->solo_cus) * 2 <= h->ncu;  // (everybody else's chain workgroups, solo launches included)
-    }
-    const bool solo = h->solo_kernel;  // one-workgroup filters run by k_solo
-    // k_solo folds a window it fills itself (ChainSeg::self_pass): the launches of one call are the segments of one launch, with
-    // no dense-pass launch between them (EKF_SOLO_FUSE=0: one launch per window and k_flush_rb, for comparisons)
-    const bool fuse = solo && h->solo_fuse;
-    const bool multi = persist || fuse;
-    if (!fuse && h->solo && h->ngroups > 1 && cursor == nullptr) {
-        long slots = h->pending;
-        for (int q = 0; q < nops; q++) slots += consumes[q] ? 1 : 0;
-        if (slots >= 2L * h->dv.maxp) return launch_ops_grouped(h, in, k0, consumes, nops);  // the call closes at least two windows (scripted runs, and immediate-mode chunks that long)
-    }
-    ChainPlan plan;
-    memset(&plan, 0, sizeof plan);
-    EnqueueList passes;
-    int next_drop = 0;
-    auto launch_plan = [&](hipEvent_t stop_ev) -> int {
-        if (plan.nseg == 0) return EKF_OK;
-        // one filter, one segment of one operation, its record in the host-mapped ring (an immediate-mode call, slam.cpp:136-170): the
-        // record rides in the kernel arguments -- the kernel's first trip to host memory brings it along, the ring costs a second one
-        plan.inl_n = 0;
-        if (h->tn.inline_rec && h->dv.B == 1 && plan.nseg == 1 && plan.s[0].nops == 1 && cursor == nullptr && in == h->ring_d) {
-            memcpy(plan.inl, h->ring_h + (size_t)plan.s[0].k0 * 8, 8 * sizeof(double));
-            plan.inl_n = 1;
-        }
-        hipEvent_t pe0 = nullptr, pe1 = nullptr;
-        if (fuse) {
-            int sp = 0;
-            for (int q = 0; q < plan.nseg; q++) sp += plan.s[q].self_pass;
-            // EKF_SOLO_FUSE_STAGGER_US: a one-off phase shift between the filters of a batch (four groups), so that their own passes take
-            // turns in HBM.  Measured: nothing to gain (6.53 M filter-steps/s without, 6.51 / 6.42 / 6.35 M with 35 / 67 / 90 us: one wave
-            // per SIMD is latency-bound on its own tile, not bandwidth-bound), so the default is none.
-            plan.s[0].stagger = (sp >= 4 && h->dv.B >= 16) ? h->tn.solo_fuse_stagger_ticks : 0;
-            if (h->prof_flush && sp > 0) {  // the passes live inside this launch: time the launch, count the passes
-                EKF_TRY(prof_take_pair(h, &pe0, &pe1));
-                h->prof_fused_passes += sp;
-                h->prof_solo_pairs++;
-            }
-        }
-        for (int b0 = 0; b0 < h->dv.B; b0 += h->chain_filters) {
-            const int nb = h->dv.B - b0 < h->chain_filters ? h->dv.B - b0 : h->chain_filters;
-            const bool last = b0 + nb >= h->dv.B;
-            // (the stop event on the last launch's dispatch packet; a fused k_solo launch is bracketed by its profiling pair instead)
-            launch_chain(h, h->s_chain, /*streaming*/ false, /*on_packet*/ true, b0 == 0 ? pe0 : nullptr, last ? (pe1 ? pe1 : stop_ev) : nullptr, in, cursor, plan, b0, nb);
-        }
-        if (plan.signal)
-            for (int q = 0; q < plan.nseg; q++) h->seg_count_base[q] = plan.s[q].gate;
-        plan.nseg = 0;
-        next_drop = 0;
-        for (auto &enq : passes) {
-            hipError_t e = enq();
-            if (e != hipSuccess) {
-                passes.clear();
-                return set_error(EKF_ERR_HIP, "%s", hipGetErrorString(e));
-            }
-        }
-        passes.clear();
-        return check_launch();
-    };
-    // Balanced tail (round 5; multi-workgroup filters in the overlapped multi-segment mode, EKF_BALANCED_TAIL=0 switches it off): when between one
-    // and two windows' worth of measurements are left in this call, the window that begins is closed at HALF of them (rounded up to a whole
-    // slot pair) instead of at max_pending.  A scripted run of 20 steps x 4 measurements at a window of 32 ran 32 | 32 | 16: the pass of the
-    // second window (16 pairs, 165 us beside the chain kernel) outlasted the 16 measurements after it (100 us) and the last window's pass
-    // waited behind it -- 170 us exposed after the chain kernel's end; 32 | 24 | 24 hides the second pass under the third segment and leaves
-    // one 12-pair pass exposed.  Nothing changes for a run whose length is a multiple of the window, nor in the steady state of a long one.
-    const bool balanced_tail = h->tn.balanced_tail;
-    int slots_left = 0;  // slot-consuming operations of this call from op i on
-    for (int q = 0; q < nops; q++) slots_left += consumes[q] ? 1 : 0;
-    int limit = h->dv.maxp;  // where the window being filled closes (a window carried over from an earlier call: max_pending)
-    while (i < nops) {
-        int start = i, used = h->pending;
-        if (used == 0) {
-            limit = h->dv.maxp;
-            if (balanced_tail && persist && !solo && slots_left > h->dv.maxp && slots_left < 2 * h->dv.maxp) {
-                limit = ((slots_left + 1) / 2 + 1) & ~1;
-                if (limit > h->dv.maxp) limit = h->dv.maxp;  // (an odd max_pending: rounding up to a slot pair must not pass the window -- slot_meta rows, the own-row cache and the pass are sized for maxp)
-            }
-        }
-        used = take_ops(consumes, nops, &i, used, limit);
-        slots_left -= used - h->pending;
-        if (i == start) {  // set already full (cannot happen: full sets are closed above and below)
-            EKF_TRY(close_set(h, false, persist ? &passes : nullptr));
-            continue;
-        }
-        // overlap: the launch that fills the set signals ev_chain from its own dispatch packet (no marker packet)
-        const bool closes = h->overlap && used == limit;
-        ChainSeg sg;
-        sg.k0 = k0 + start, sg.nops = i - start, sg.slot0 = h->pending, sg.set = h->cur_set, sg.buf_read = h->buf_in, sg.n_prev = h->prev_pending;
-        if (next_drop > 0 && next_drop < h->prev_pending) EKF_TRY(launch_plan(nullptr));  // (the LDS shift moves whole windows: start a new launch instead)
-        sg.need_pass = h->need_pass, sg.drop = next_drop;
-        sg.seq = ++h->chain_seq;  // (one number per segment: every filter's mirror reaches it)
-        sg.gate = h->seg_count_base[plan.nseg] + (unsigned long long)h->chain_wgs * h->dv.B;  // every workgroup of the launch has finished this segment
-        sg.self_pass = (fuse && used == limit && !h->dbg_skip_flush) ? 1 : 0;
-        sg.stagger = 0;
-        next_drop = 0;
-        plan.s[plan.nseg++] = sg;
-        plan.signal = persist ? 1 : 0;
-        plan.stream = 0;
+// What plan_ops' decisions are carried out on: one call's input, and the handle.
+struct OpsSink {
+    ekf_batch *h;
+    const double *in;
+    const int *cursor;
+    int segment(const ChainSeg &) {
         h->mirror_by_chain = true;
         h->stats_in_mirror = true;
-        h->pending = used;
-        if (!multi) {
-            EKF_TRY(launch_plan(closes ? h->ev_chain : nullptr));
-            h->chain_signalled = closes;
-        } else {
-            h->chain_signalled = false;
-            if (persist && used == limit) h->open_set_gate = sg.gate, h->open_gate_idx = plan.nseg - 1;
-        }
-        if (sg.self_pass) {
-            h->cur_set ^= 1;  // folded by the launch itself: the next segment starts an empty window
-            h->pending = 0;
-        } else if (used == limit && !(defer_last_close && i == nops)) {
-            EKF_TRY(close_set(h, false, persist ? &passes : nullptr));
-            next_drop = sg.n_prev;  // the next segment starts a window: the set whose pass has finished leaves the LDS caches
-        }
-        if (multi && plan.nseg == EKF_PLAN_MAX) EKF_TRY(launch_plan(nullptr));
+        return EKF_OK;
     }
-    return launch_plan(nullptr);
-}
+    int pass(const PassOrder &o) { return issue_pass(h, o); }
+    int prepare(const PassOrder &o) { return prepare_pass(h, o); }
+    // One plan goes out: a launch per chain_filters filters.
+    int launch(ChainPlan &plan, const LaunchOrder &lo) {
+        if (plan.inl_n) memcpy(plan.inl, h->ring_h + (size_t)plan.s[0].k0 * 8, 8 * sizeof(double));
+        hipEvent_t pe0 = nullptr, pe1 = nullptr;
+        if (lo.prof) {  // the passes live inside this launch: time the launch, count the passes
+            EKF_TRY(prof_take_pair(h, &pe0, &pe1));
+            h->prof_fused_passes += lo.fused_passes;
+            h->prof_solo_pairs++;
+        }
+        for (ChainLaunch l = chain_launch(h->wcfg, lo, 0); l.nb > 0; l = chain_launch(h->wcfg, lo, l.b0 + l.nb))
+            launch_chain(h, h->s_chain, /*streaming*/ false, /*on_packet*/ true, l.start_prof ? pe0 : nullptr, l.stop_prof ? pe1 : role_event(h, l.stop), in, cursor, plan, l.b0, l.nb);
+        return check_launch();
+    }
+};
 
 // One-workgroup filters in phase groups: a call that closes several windows (a scripted run) is cut by filter range instead of
 // running the whole batch in lock step.  Group g's stream carries chain launch, dense pass (in place), chain launch, ... for its
@@ -1366,8 +1119,8 @@ static int launch_ops(ekf_batch *h, const double *in, const int *cursor, int k0,
 // group's first launch spreads their phases, so that the passes take turns in HBM while the other groups' chain kernels -- which
 // are latency-bound and leave the memory system idle -- run.  Fork from and join into s_chain, so that every other entry point
 // keeps seeing one stream.
-static int launch_ops_grouped(ekf_batch *h, const double *in, int k0, const unsigned char *consumes, int nops) {
-    const int ng = h->ngroups, B = h->dv.B, maxp = h->dv.maxp;
+static int launch_ops_grouped(ekf_batch *h, const double *in, const OpsCall &call) {
+    const int ng = h->ngroups, B = h->dv.B;
     const int per = (B + ng - 1) / ng;
     hipError_t e;
     if ((e = hipEventRecord(h->ev_fork, h->s_chain)) != hipSuccess) return set_error(EKF_ERR_HIP, "%s", hipGetErrorString(e));
@@ -1381,42 +1134,24 @@ static int launch_ops_grouped(ekf_batch *h, const double *in, int k0, const unsi
     // chain and pass kernels still queued on a group stream.  An error on the way is remembered, the join still happens (where even
     // the join's event calls fail the group stream is drained on the host).
     int rc_pending = EKF_OK;
-    if (h->prof_flush) {  // (event creation can fail: do it in front of the first launch, not between a fork and its join)
-        long passes = 0, used_ = h->pending;
-        for (int q = 0; q < nops; q++)
-            if (consumes[q] && ++used_ == maxp) passes++, used_ = 0;
-        rc_pending = prof_reserve(h, (size_t)ng * (size_t)(passes + 1));
-    }
-    int i = 0;
-    while (i < nops && rc_pending == EKF_OK) {
-        const int start = i, used = take_ops(consumes, nops, &i, h->pending, maxp);
-        ChainPlan plan;
-        memset(&plan, 0, sizeof plan);
-        ChainSeg &sg = plan.s[0];
-        sg.k0 = k0 + start, sg.nops = i - start, sg.slot0 = h->pending, sg.set = h->cur_set, sg.buf_read = h->buf_in;
-        sg.seq = ++h->chain_seq;
-        sg.gate = 0, sg.self_pass = 0, sg.stagger = 0;
-        plan.nseg = 1;
+    // (event creation can fail: do it in front of the first launch, not between a fork and its join)
+    if (h->prof_flush) rc_pending = prof_reserve(h, (size_t)ng * (size_t)grouped_passes(h->wcfg, h->win, call));
+    ChainPlan plan;
+    memset(&plan, 0, sizeof plan);
+    plan.nseg = 1;
+    GroupedWindow w;
+    for (int i = 0; rc_pending == EKF_OK && plan_ops_grouped(h->wcfg, h->win, call, &i, &h->chain_seq, &w);) {
+        plan.s[0] = w.seg;
         h->mirror_by_chain = true;
         h->stats_in_mirror = true;
-        h->pending = used;
-        const bool fold = used == maxp;
-        int nT_hi = (2 * h->n_lm_hi + 63) / 64;
-        const bool do_pass = fold && !h->dbg_skip_flush && nT_hi > 0;
-        const int rev = h->tn.flush_alternate ? h->flush_dir : 0;
         for (int g = 0; g < ng; g++) {
             const int b0 = g * per, nb = B - b0 < per ? B - b0 : per;
             if (nb <= 0) break;
             launch_chain(h, h->s_grp[g], /*streaming*/ false, /*on_packet*/ false, nullptr, nullptr, in, nullptr, plan, b0, nb);
-            if (!do_pass) continue;
+            if (!w.do_pass) continue;
             hipEvent_t e0 = nullptr, e1 = nullptr;
             if (h->prof_flush && h->prof_used + 2 <= h->prof_pool.size()) (void)prof_take_pair(h, &e0, &e1);  // (reserved above: never grows here, between a fork and its join)
-            launch_pass(h->dv, h->s_grp[g], e0, e1, interleave, nT_hi, h->cur_set, maxp, h->buf_in, h->buf_in, nullptr, rev, b0, nb);
-        }
-        if (fold) {
-            if (do_pass) h->flush_dir ^= 1;
-            h->cur_set ^= 1;
-            h->pending = 0;
+            launch_pass(h->dv, h->s_grp[g], e0, e1, interleave, w.nT_hi, w.set, w.nslots, w.buf, w.buf, nullptr, w.rev, b0, nb);
         }
     }
     for (int g = 1; g < ng; g++) {
@@ -1428,6 +1163,44 @@ static int launch_ops_grouped(ekf_batch *h, const double *in, int k0, const unsi
     }
     if (rc_pending != EKF_OK) return rc_pending;
     return check_launch();
+}
+
+// CUs on which a gated pass can run while the chain workgroups of a multi-segment launch stay resident: a chain wave leaves too few
+// registers on its SIMD for a pass wave, so a pass only runs on CUs without a chain workgroup.  Multi-segment launches are used
+// while the chain workgroups of ALL live handles hold at most half of the GPU (256 filters of one workgroup each would
+// wait forever for a pass that cannot start: that batch keeps one launch per segment).
+static bool residency_ok(const ekf_batch *h) {
+    std::lock_guard<std::mutex> lk(g_res_mu);
+    return (g_cus_claimed[h->device] + g_cus_solo[h->device] - h->solo_cus) * 2 <= h->ncu;  // (everybody else's chain workgroups, solo launches included)
+}
+
+// Run ops [k0, k0 + nops) of `in` (the input ring, or the loaded script: at *cursor while a graph is captured) on the route that
+// route_call chooses.  consumes, defer_last_close: OpsCall.
+static int launch_ops(ekf_batch *h, const double *in, const int *cursor, int k0, const unsigned char *consumes, int nops, bool defer_last_close = false) {
+    const WindowCfg &cfg = h->wcfg;
+    if (nops > 0 && h->win.pending == cfg.maxp) EKF_TRY(close_set(h));  // a set whose close the previous call deferred: more work follows, regular pass
+    const CallSource src = cursor ? FROM_CURSOR : (in == h->ring_d ? FROM_RING : FROM_SCRIPT);
+    const CallPlan cp = route_call(cfg, h->win, h->stream_calls, src, consumes, nops, defer_last_close, persist_possible(cfg, src, defer_last_close) && residency_ok(h));
+    if (cp.route == ROUTE_STREAM_OPS) {
+        for (int q = 0; q < nops; q++) EKF_TRY(stream_op(h, h->ring_h + (size_t)(k0 + q) * 8, consumes[q] ? 1 : 0));
+        return EKF_OK;
+    }
+    if (cp.route == ROUTE_STREAM_SCRIPT) {
+        for (int q0 = 0, q1 = 0; q0 < nops; q0 = q1) {
+            const int used = take_ops(consumes, nops, &q1, h->win.pending, cfg.maxp) - h->win.pending;  // (up to, and including, the measurement that fills the window)
+            double rec[8] = {0, 0, 0, 0, 0, 0, 0, (double)OP_SCRIPT};
+            const long long bits = (long long)(size_t)h->script_d;
+            memcpy(&rec[0], &bits, sizeof bits);
+            rec[1] = (double)(k0 + q0), rec[2] = (double)(q1 - q0);
+            EKF_TRY(stream_op(h, rec, used));
+        }
+        return EKF_OK;
+    }
+    EKF_TRY(stream_stop(h));
+    const OpsCall call = {src, k0, nops, consumes, defer_last_close, h->n_lm_hi, h->prof_flush};
+    if (cp.route == ROUTE_GROUPED) return launch_ops_grouped(h, in, call);
+    OpsSink sink = {h, in, cursor};
+    return plan_ops(cfg, h->win, cp, call, &h->chain_seq, sink);
 }
 
 static void bump_bound(ekf_batch *h, int measurements) {
@@ -1688,13 +1461,13 @@ static int finish_rewrite(ekf_batch *h, int b0, int nb, bool rearm, const int *c
     if (rearm) {
         HIP_TRY(hipMemsetAsync(dv.FA + (size_t)b0 * 2 * dv.f_stride, 0, sizeof(double) * (size_t)nb * 2 * dv.f_stride, s));
         HIP_TRY(hipMemsetAsync(dv.FB + (size_t)b0 * 2 * dv.f_stride, 0, sizeof(double) * (size_t)nb * 2 * dv.f_stride, s));
-        if (h->overlap) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, s, dv.pass_flag, h->pass_seq);
+        if (h->overlap) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, s, dv.pass_flag, h->win.pass_seq);
     }
     if (counts)
         for (int k = 0; k < nb; k++) hipLaunchKernelGGL(k_set_meta, dim3(1), dim3(64), 0, s, dv, b0 + k, counts[(size_t)k * count_stride]);
     HIP_TRY(stream_wait(s));
     EKF_TRY(check_launch());
-    if (flip_buf) h->buf_in ^= 1;
+    if (flip_buf) h->win.buf_in ^= 1;
     h->mirror_by_chain = false;
     h->state_edits++;
     return refresh_bounds(h);
@@ -1873,7 +1646,7 @@ extern "C" int ekf_get_state(ekf_handle h, int index, double *x_out, double *P_o
     EKF_TRY(settle(h));
     DevTmp<double> stage;  // transient staging: dense n x n + x
     HIP_TRY(stage.alloc((size_t)n * n + n));
-    hipLaunchKernelGGL(k_export, dim3(cdiv(n, 256), n), dim3(256), 0, h->s_chain, h->dv, index, h->buf_in, stage.p + (size_t)n * n, stage.p, n, n);
+    hipLaunchKernelGGL(k_export, dim3(cdiv(n, 256), n), dim3(256), 0, h->s_chain, h->dv, index, h->win.buf_in, stage.p + (size_t)n * n, stage.p, n, n);
     EKF_TRY(read_back_dense(h, stage.p, n, x_out, P_out, ld));
     return n;  // (a failed launch of k_export is not looked for here, as it is in ekf_get_submap)
 }
@@ -1888,9 +1661,9 @@ static int restart_waits(ekf_batch *h) {
     hipStream_t s = h->s_chain;
     read_debug_hooks(h);
     HIP_TRY(hipMemsetAsync(dv.seg_count, 0, sizeof(unsigned long long) * EKF_PLAN_MAX, s));
-    for (int q = 0; q < EKF_PLAN_MAX; q++) h->seg_count_base[q] = 0;
-    h->open_set_gate = 0;
-    if (h->overlap) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, s, dv.pass_flag, h->pass_seq);
+    for (int q = 0; q < EKF_PLAN_MAX; q++) h->win.seg_count_base[q] = 0;
+    h->win.open_set_gate = 0;
+    if (h->overlap) hipLaunchKernelGGL(k_mark, dim3(1), dim3(64), 0, s, dv.pass_flag, h->win.pass_seq);
     return EKF_OK;
 }
 
@@ -1912,7 +1685,7 @@ extern "C" int ekf_set_state(ekf_handle h, int index, const double *x, const dou
         HIP_TRY(hipMemsetAsync(a.at(index), 0, a.filter_bytes(), s));
         if (a.slot == (void **)&dv.Bm[0] && h->overlap) HIP_TRY(hipMemsetAsync(dv.Bm[1] + (size_t)index * dv.bm_stride, 0, sizeof(double) * dv.bm_stride, s));
     }
-    hipLaunchKernelGGL(k_import, dim3(cdiv(n, 256), n), dim3(256), 0, s, dv, index, h->buf_in, (const double *)xd, (const double *)stage.p, n, n);
+    hipLaunchKernelGGL(k_import, dim3(cdiv(n, 256), n), dim3(256), 0, s, dv, index, h->win.buf_in, (const double *)xd, (const double *)stage.p, n, n);
     if (N > h->n_lm_hi) h->n_lm_hi = N;
     return finish_rewrite(h, index, 1, /*rearm*/ false, &N, 1, /*flip_buf*/ false);
 }
@@ -1972,7 +1745,7 @@ extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     nh->prof_used = h->prof_used, h->prof_used = 0;
     nh->prof_ms = h->prof_ms, nh->prof_launches = h->prof_launches;
     nh->prof_fused_passes = h->prof_fused_passes, nh->prof_solo_pairs = h->prof_solo_pairs;
-    nh->windows_closed = h->windows_closed, nh->last_window_slots = h->last_window_slots;  // (ekf_debug_windows counts since create, across growths)
+    nh->win.windows_closed = h->win.windows_closed, nh->win.last_window_slots = h->win.last_window_slots;  // (ekf_debug_windows counts since create, across growths)
     {
         const hipStream_t s_new = nh->s_chain, s_old = h->s_chain;
         if (nh->s_flush == s_new) nh->s_flush = s_old;
@@ -2005,9 +1778,9 @@ static int reserve_move_state(ekf_batch *h, ekf_batch *nh, const std::vector<int
         for (int b = 0; b < B; b++) {
             const int n = 3 + 2 * n_lm[b];
             double *xd = stage.p + (size_t)n * n;
-            hipLaunchKernelGGL(k_export, dim3(cdiv(n, 256), n), dim3(256), 0, h->s_chain, h->dv, b, h->buf_in, xd, stage.p, n, n);
+            hipLaunchKernelGGL(k_export, dim3(cdiv(n, 256), n), dim3(256), 0, h->s_chain, h->dv, b, h->win.buf_in, xd, stage.p, n, n);
             HIP_TRY(stream_wait(h->s_chain));
-            hipLaunchKernelGGL(k_import, dim3(cdiv(n, 256), n), dim3(256), 0, nh->s_chain, nh->dv, b, nh->buf_in, (const double *)xd, (const double *)stage.p, n, n);
+            hipLaunchKernelGGL(k_import, dim3(cdiv(n, 256), n), dim3(256), 0, nh->s_chain, nh->dv, b, nh->win.buf_in, (const double *)xd, (const double *)stage.p, n, n);
             HIP_TRY(stream_wait(nh->s_chain));
         }
     }
@@ -2038,8 +1811,8 @@ extern "C" int ekf_broadcast_state(ekf_handle h) {
                 continue;
             }
             // (the covariance tiles: the settled buffer, whichever of the two it is)
-            HIP_TRY(hipMemcpyAsync(dv.Bm[h->buf_in] + (size_t)b * dv.bm_stride, dv.Bm[h->buf_in], sizeof(double) * dv.bm_stride, hipMemcpyDeviceToDevice, s));
-            if (h->overlap) HIP_TRY(hipMemsetAsync(dv.Bm[h->buf_in ^ 1] + (size_t)b * dv.bm_stride, 0, sizeof(double) * dv.bm_stride, s));  // no stale tiles beyond the copied map
+            HIP_TRY(hipMemcpyAsync(dv.Bm[h->win.buf_in] + (size_t)b * dv.bm_stride, dv.Bm[h->win.buf_in], sizeof(double) * dv.bm_stride, hipMemcpyDeviceToDevice, s));
+            if (h->overlap) HIP_TRY(hipMemsetAsync(dv.Bm[h->win.buf_in ^ 1] + (size_t)b * dv.bm_stride, 0, sizeof(double) * dv.bm_stride, s));  // no stale tiles beyond the copied map
         }
     HIP_TRY(stream_wait(s));
     for (int b = 1; b < dv.B; b++) hipLaunchKernelGGL(k_set_meta, dim3(1), dim3(64), 0, s, dv, b, h->mirror_h[0].n_lm);  // also refreshes the host mirror
@@ -2139,7 +1912,7 @@ extern "C" int ekf_script_run(ekf_handle h, int first_step, int n_steps, int use
             GraphEntry *ge = nullptr;
             for (auto &g : h->graphs)
                 if (g.steps == S && g.M == h->script_M && g.has_truth == h->script_has_truth) ge = &g;
-            int save_set = h->cur_set, save_buf = h->buf_in;
+            int save_set = h->win.cur_set, save_buf = h->win.buf_in;
             if (!ge) {
                 bool prof_saved = h->prof_flush;
                 int hi_saved = h->n_lm_hi;
@@ -2148,14 +1921,14 @@ extern "C" int ekf_script_run(ekf_handle h, int first_step, int n_steps, int use
                 (void)tile_map_for(h, (2 * h->n_lm_hi + 63) / 64);  // built before the capture: the captured passes find it ready
                 HIP_TRY(hipStreamBeginCapture(h->s_chain, hipStreamCaptureModeThreadLocal));
                 int rc2 = enqueue_script_steps(h, h->cursor_d, 0, S);
-                if (rc2 == EKF_OK && h->pending != 0) rc2 = set_error(EKF_ERR_STATE, "graph block does not end on an empty slot set");
+                if (rc2 == EKF_OK && h->win.pending != 0) rc2 = set_error(EKF_ERR_STATE, "graph block does not end on an empty slot set");
                 hipLaunchKernelGGL(k_advance, dim3(1), dim3(64), 0, h->s_chain, h->cursor_d, S * ops);
                 hipGraph_t graph = nullptr;
                 hipError_t e = hipStreamEndCapture(h->s_chain, &graph);
                 h->prof_flush = prof_saved;
                 h->n_lm_hi = hi_saved;
                 if (rc2 == EKF_OK && e != hipSuccess) rc2 = set_error(EKF_ERR_HIP, "graph capture failed");
-                if (rc2 == EKF_OK && (h->cur_set != save_set || h->buf_in != save_buf)) rc2 = set_error(EKF_ERR_STATE, "graph block does not restore the ping-pong state");
+                if (rc2 == EKF_OK && (h->win.cur_set != save_set || h->win.buf_in != save_buf)) rc2 = set_error(EKF_ERR_STATE, "graph block does not restore the ping-pong state");
                 GraphEntry g;
                 g.steps = S, g.M = h->script_M, g.has_truth = h->script_has_truth;
                 g.exec = nullptr;
@@ -2178,7 +1951,7 @@ extern "C" int ekf_script_run(ekf_handle h, int first_step, int n_steps, int use
             // The captured chain launches carry the sequence numbers of the capture: a replay stores those into the host
             // mirror, so mirror.seq says nothing about which replay has finished.  Readers fall back to a stream synchronise.
             h->mirror_by_chain = false;
-            h->pending = 0;
+            h->win.pending = 0;
             h->n_lm_hi = h->dv.Ncap;  // landmarks may have been appended inside the graphs; unknown until a sync
         }
     }
@@ -2193,8 +1966,8 @@ extern "C" int ekf_script_run(ekf_handle h, int first_step, int n_steps, int use
 // (tests) windows closed since create and the slot count of the last one: how launch_ops cut a scripted run
 extern "C" int ekf_debug_windows(ekf_handle h, long long *closed, int *last_slots) {
     if (!h || !closed || !last_slots) return set_error(EKF_ERR_BAD_ARG, "null argument");
-    *closed = h->windows_closed;
-    *last_slots = h->last_window_slots;
+    *closed = h->win.windows_closed;
+    *last_slots = h->win.last_window_slots;
     return EKF_OK;
 }
 
@@ -2243,7 +2016,7 @@ extern "C" int ekf_timer_start(ekf_handle h) {
 extern "C" int ekf_timer_stop(ekf_handle h, double *ms_out) {
     if (!h || !ms_out) return set_error(EKF_ERR_BAD_ARG, "null argument");
     EKF_TRY(quiesce(h, QUIET_STREAM, ST_NONE));
-    if (h->overlap && h->prev_pending > 0) HIP_TRY(hipStreamWaitEvent(h->s_chain, h->pass_done[h->ev_idx], 0));  // the pass in flight counts
+    if (h->overlap && h->win.prev_pending > 0) HIP_TRY(hipStreamWaitEvent(h->s_chain, role_event(h, h->win.pass_done[h->win.ev_idx]), 0));  // the pass in flight counts
     HIP_TRY(hipEventRecord(h->t1, h->s_chain));
     HIP_TRY(event_wait(h->t1));
     float ms = 0;

@@ -59,12 +59,12 @@ static int remove_settled(ekf_batch *h, Filters f, const unsigned char *keep, in
     if (nTo > 0) {
         const dim3 grid((unsigned)(nTo * (nTo + 1) / 2), (unsigned)B);
         if (h->overlap) {
-            hipLaunchKernelGGL(k_rm_gather, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, mstride, nTo, dv.Bm[h->buf_in ^ 1], dv.T, dv.bm_stride, 0);
-            hipLaunchKernelGGL(k_rm_finish, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, nTo, (const double *)nullptr, 0, (size_t)0);
+            hipLaunchKernelGGL(k_rm_gather, grid, dim3(256), 0, s, dv, h->win.buf_in, (const int *)rm_d.p, mstride, nTo, dv.Bm[h->win.buf_in ^ 1], dv.T, dv.bm_stride, 0);
+            hipLaunchKernelGGL(k_rm_finish, grid, dim3(256), 0, s, dv, h->win.buf_in, (const int *)rm_d.p, nTo, (const double *)nullptr, 0, (size_t)0);
         } else {
             if (scratch.p)
-                hipLaunchKernelGGL(k_rm_gather, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, mstride, nTo, scratch.p, nTn, scratch_stride, 1);
-            hipLaunchKernelGGL(k_rm_finish, grid, dim3(256), 0, s, dv, h->buf_in, (const int *)rm_d.p, nTo, (const double *)scratch.p, nTn, scratch_stride);
+                hipLaunchKernelGGL(k_rm_gather, grid, dim3(256), 0, s, dv, h->win.buf_in, (const int *)rm_d.p, mstride, nTo, scratch.p, nTn, scratch_stride, 1);
+            hipLaunchKernelGGL(k_rm_finish, grid, dim3(256), 0, s, dv, h->win.buf_in, (const int *)rm_d.p, nTo, (const double *)scratch.p, nTn, scratch_stride);
         }
     }
     // D is read by the gather (landmarks' own blocks): compacted behind it
@@ -130,7 +130,7 @@ static int reframe_impl(ekf_batch *h, Filters f, const double *frames) {
     if (nT > 0) {
         const dim3 gv((unsigned)cdiv(32 * nT, 256), (unsigned)nb), gt((unsigned)(nT * (nT + 1) / 2), (unsigned)nb);
         hipLaunchKernelGGL(k_vec, gv, dim3(256), 0, s, dv, one, frc, b_off);
-        hipLaunchKernelGGL(k_tiles, gt, dim3(256), 0, s, dv, h->buf_in, one, frc, b_off, nT);
+        hipLaunchKernelGGL(k_tiles, gt, dim3(256), 0, s, dv, h->win.buf_in, one, frc, b_off, nT);
     }
     hipLaunchKernelGGL(k_finish, dim3(nb), dim3(64), 0, s, dv, one, frc, b_off);
     return finish_rewrite(h, b_off, nb, /*rearm*/ true, nullptr, 0, /*flip_buf*/ false);
@@ -163,7 +163,7 @@ extern "C" int ekf_batch_anchor_at_robot(ekf_handle h) {
 // What the join and extraction kernels read of a source handle at rest.
 static JoinSrc join_src_of(const ekf_batch *s) {
     const EkfDev &sd = s->dv;
-    return {sd.x, sd.R, sd.D, sd.Bm[s->buf_in], sd.n_lm, sd.xs, sd.dn, sd.T, sd.bm_stride};
+    return {sd.x, sd.R, sd.D, sd.Bm[s->win.buf_in], sd.n_lm, sd.xs, sd.dn, sd.T, sd.bm_stride};
 }
 
 // Map joining on the device (ekf_rewrite.hip: k_join_tiles, k_join_vec, k_join_finish): filter bs0 + k of `s` into filter
@@ -193,8 +193,8 @@ static int join_impl(ekf_batch *d, Filters fd, ekf_batch *s, int bs0) {
     const JoinSrc sv = join_src_of(s);
     const double *rotc = rot_d.p;
     hipStream_t st = d->s_chain;
-    if (nt > 0) hipLaunchKernelGGL(k_join_tiles, dim3((unsigned)nt, (unsigned)nb), dim3(256), 0, st, dv, d->buf_in, sv, one, rotc, bd0, bs0);
-    if (nv > 0) hipLaunchKernelGGL(k_join_vec, dim3((unsigned)cdiv(nv, 256), (unsigned)nb), dim3(256), 0, st, dv, d->buf_in, sv, one, rotc, bd0, bs0);
+    if (nt > 0) hipLaunchKernelGGL(k_join_tiles, dim3((unsigned)nt, (unsigned)nb), dim3(256), 0, st, dv, d->win.buf_in, sv, one, rotc, bd0, bs0);
+    if (nv > 0) hipLaunchKernelGGL(k_join_vec, dim3((unsigned)cdiv(nv, 256), (unsigned)nb), dim3(256), 0, st, dv, d->win.buf_in, sv, one, rotc, bd0, bs0);
     hipLaunchKernelGGL(k_join_finish, dim3(nb), dim3(64), 0, st, dv, sv, one, rotc, bd0, bs0);
     return finish_rewrite(d, bd0, nb, /*rearm*/ true, nullptr, 0, /*flip_buf*/ false);
 }
@@ -248,9 +248,9 @@ static int extract_impl(ekf_batch *d, Filters fd, ekf_batch *s, int bs0, const i
     DevTmp<int> ex_d;
     HIP_TRY(ex_d.upload(ex.data(), ex.size(), st));
     const JoinSrc sv = join_src_of(s);
-    double *other = d->overlap ? dv.Bm[d->buf_in ^ 1] : nullptr;
+    double *other = d->overlap ? dv.Bm[d->win.buf_in ^ 1] : nullptr;
     if (nT > 0)
-        hipLaunchKernelGGL(k_ext_tiles, dim3((unsigned)(nT * (nT + 1) / 2), (unsigned)nb), dim3(256), 0, st, dv, d->buf_in, other, sv, (const int *)ex_d.p, mstride, nb, nT, bd0,
+        hipLaunchKernelGGL(k_ext_tiles, dim3((unsigned)(nT * (nT + 1) / 2), (unsigned)nb), dim3(256), 0, st, dv, d->win.buf_in, other, sv, (const int *)ex_d.p, mstride, nb, nT, bd0,
                            bs0);
     hipLaunchKernelGGL(k_ext_vec, dim3(7, (unsigned)nb), dim3(1024), 0, st, dv, sv, (const int *)ex_d.p, mstride, nb, bd0, bs0);
     EKF_TRY(finish_rewrite(d, bd0, nb, /*rearm*/ true, &ex[1], 2, /*flip_buf*/ false));
@@ -334,7 +334,7 @@ static int joint_impl(ekf_batch *h, Filters f, const double *x_true, int ld_true
         HIP_TRY(hipMemcpy2DAsync(fs.xt + (size_t)b0 * dv.xs, (size_t)dv.xs * sizeof(double), x_true, (size_t)ld_true * sizeof(double),
                                  (size_t)(3 + 2 * n_max) * sizeof(double), nb, hipMemcpyHostToDevice, s));
     const int nT = lm_tiles(n_max);
-    if (nT > 0) hipLaunchKernelGGL(k_chol_stage, dim3((unsigned)(nT * (nT + 1) / 2), (unsigned)nb), dim3(256), 0, s, dv, fs, h->buf_in, b0, nT, have_truth);
+    if (nT > 0) hipLaunchKernelGGL(k_chol_stage, dim3((unsigned)(nT * (nT + 1) / 2), (unsigned)nb), dim3(256), 0, s, dv, fs, h->win.buf_in, b0, nT, have_truth);
     for (int k = 0; k < nT; k++) {
         hipLaunchKernelGGL(k_chol_diag, dim3((unsigned)nb), dim3(320), 0, s, dv, fs, k, b0);
         if (k + 1 < nT) {
@@ -429,7 +429,7 @@ static int dup_impl(ekf_batch *h, Filters f, double gate, double max_dist, int s
         const DupScratch ds = h->dup;
         HIP_TRY(hipMemsetAsync(ds.cnt + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
         if (da.md2 >= 0.0) hipLaunchKernelGGL(k_dup_boxes, dim3((unsigned)cdiv(lm_tiles(n_max), 64), (unsigned)nb), dim3(64), 0, s, dv, ds, b0);
-        hipLaunchKernelGGL(k_dup_tiles, dim3((unsigned)nt, (unsigned)nb), dim3(256), 0, s, dv, ds, da, h->buf_in, b0);
+        hipLaunchKernelGGL(k_dup_tiles, dim3((unsigned)nt, (unsigned)nb), dim3(256), 0, s, dv, ds, da, h->win.buf_in, b0);
         HIP_TRY(hipMemcpyAsync(cnt.data(), ds.cnt + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost, s));
         HIP_TRY(stream_wait(s));
         EKF_TRY(check_launch());
@@ -544,11 +544,11 @@ static int fuse_impl(ekf_batch *h, Filters f, const ekf_dup_pair *pairs, int ld_
     const int nT = lm_tiles(n_max);
     for (int round = 0; round * dv.maxp < most; round++) {
         const int m_hi = most - round * dv.maxp < dv.maxp ? most - round * dv.maxp : dv.maxp;
-        hipLaunchKernelGGL(k_fuse_gather, dim3((unsigned)cdiv(n_max, 256), (unsigned)m_hi, (unsigned)nb), dim3(256), 0, s, dv, fs, h->buf_in, round, b0);
+        hipLaunchKernelGGL(k_fuse_gather, dim3((unsigned)cdiv(n_max, 256), (unsigned)m_hi, (unsigned)nb), dim3(256), 0, s, dv, fs, h->win.buf_in, round, b0);
         hipLaunchKernelGGL(k_fuse_factor, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, round, slack, b0);
         hipLaunchKernelGGL(k_fuse_apply, dim3((unsigned)cdiv(64 * nT, 256), (unsigned)nb), dim3(256), 0, s, dv, fs, b0);
         hipLaunchKernelGGL(k_fuse_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0);
-        launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->buf_in, h->buf_in, nullptr, /*rev*/ 0, b0, nb);
+        launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->win.buf_in, h->win.buf_in, nullptr, /*rev*/ 0, b0, nb);
     }
     std::vector<int> done((size_t)2 * nb, 0);
     HIP_TRY(hipMemcpyAsync(done.data(), fs.done + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost, s));
@@ -660,11 +660,11 @@ static int match_impl(ekf_batch *h, Filters f, const double *z, const double *R,
     const int n_max = most_landmarks(counts_of(h, b0), nb), nT = lm_tiles(n_max);
     for (int round = 0; round * dv.maxp < most; round++) {
         const int m_hi = most - round * dv.maxp < dv.maxp ? most - round * dv.maxp : dv.maxp;
-        hipLaunchKernelGGL(k_match_factor, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->buf_in, round, dv.maxp, /*apply*/ 1, b0);
-        hipLaunchKernelGGL(k_match_gather, dim3((unsigned)cdiv(n_max, 256), (unsigned)m_hi, (unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->buf_in, round, b0);
+        hipLaunchKernelGGL(k_match_factor, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->win.buf_in, round, dv.maxp, /*apply*/ 1, b0);
+        hipLaunchKernelGGL(k_match_gather, dim3((unsigned)cdiv(n_max, 256), (unsigned)m_hi, (unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->win.buf_in, round, b0);
         hipLaunchKernelGGL(k_fuse_apply, dim3((unsigned)cdiv(64 * nT, 256), (unsigned)nb), dim3(256), 0, s, dv, fs, b0);
         hipLaunchKernelGGL(k_fuse_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0);
-        launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->buf_in, h->buf_in, nullptr, /*rev*/ 0, b0, nb);
+        launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->win.buf_in, h->win.buf_in, nullptr, /*rev*/ 0, b0, nb);
     }
     std::vector<int> done((size_t)2 * nb, 0);
     std::vector<double> d2((size_t)nb * ms.zcap);
@@ -707,7 +707,7 @@ static int compat_impl(ekf_batch *h, Filters f, const double *z, const double *R
     hipStream_t s = h->s_chain;
     const MatchTable tab = plan_match_table(z, R, ids, n_z, nb, ms.zcap);
     EKF_TRY(match_upload(h, tab, b0, nb, s));
-    hipLaunchKernelGGL(k_match_factor, dim3((unsigned)nb), dim3(256), 0, s, h->dv, h->fuse, ms, h->buf_in, 0, EKF_MAX_PENDING, /*apply*/ 0, b0);
+    hipLaunchKernelGGL(k_match_factor, dim3((unsigned)nb), dim3(256), 0, s, h->dv, h->fuse, ms, h->win.buf_in, 0, EKF_MAX_PENDING, /*apply*/ 0, b0);
     std::vector<double> d2((size_t)nb * ms.zcap);
     HIP_TRY(hipMemcpyAsync(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost, s));
     HIP_TRY(stream_wait(s));

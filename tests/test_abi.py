@@ -92,6 +92,28 @@ def test_chain_geometry_matches_the_recorded_table(tmp_path):
     assert out.returncode == 1 and "chain_wgs = 64, want 63" in out.stdout, out.stdout + out.stderr
 
 
+def test_window_plans_match_the_recorded_decisions(tmp_path):
+    """The window scheduler (csrc/ekf_window_plan.h) decides every segment, chain launch and dense-pass order.  The record was taken
+    from the text of close_set, launch_ops, launch_ops_grouped, stream_op and settle before the header was cut out of them (its first
+    line names the commit); every field of every line must agree, the planner's own invariants must hold, and a doctored line must
+    make the check fail and name the field."""
+    exe = str(tmp_path / "window_plan_check")
+    import gzip
+    record = str(tmp_path / "window_plans.txt")  # (12 289 lines: kept packed)
+    lines = gzip.open(os.path.join(ROOT, "tests", "golden", "window_plans.txt.gz"), "rt").read().splitlines()
+    open(record, "w").write("\n".join(lines) + "\n")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-O1", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "cpp", "window_plan_check.cpp")])
+    out = subprocess.run([exe, record], capture_output=True, text=True)
+    assert out.returncode == 0 and "window plans ok" in out.stdout, out.stdout + out.stderr
+    # the balanced tail's pass of 18 slots behind the stream gate of a multi-segment launch (32 workgroups, second launch of the handle)
+    at = lines.index("pass 0 1 flush 1 18 1 0 10 1 0 1 64 0 0 0 none 0 flush0 1 2 0 0 flush0")
+    lines[at] = lines[at].replace(" 1 64 0 ", " 1 63 0 ", 1)
+    doctored = tmp_path / "doctored.txt"
+    doctored.write_text("\n".join(lines) + "\n")
+    out = subprocess.run([exe, str(doctored)], capture_output=True, text=True)
+    assert out.returncode == 1 and "pass gate_seq = 64, want 63" in out.stdout and "overlap_persist_w32" in out.stdout, out.stdout + out.stderr
+
+
 def test_generated_assembly_passes_the_exec_mask_lint(built):
     """The build's guard against the live-range-split miscompile: no run of register copies directly
     in front of an exec-widening s_or_b64 in any kernel."""
