@@ -38,6 +38,7 @@
 #include "ekf_match.hip"
 #include "ekf_extract.hip"
 #include "ekf_gate.hip"
+#include "ekf_assoc.hip"
 
 static thread_local std::string g_last_error;
 
@@ -91,7 +92,7 @@ struct DevBlock {
     void *p = nullptr;
     size_t bytes = 0;
 };
-enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_MATCH, BLK_GATE, BLK_GATE_LIST, BLK_COUNT };
+enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_MATCH, BLK_GATE, BLK_GATE_LIST, BLK_ASSOC, BLK_COUNT };
 
 struct GraphEntry {
     int steps, M, has_truth;
@@ -206,7 +207,10 @@ struct ekf_batch {
     // at the first call (replaced by a larger one for a longer scan), the candidate list in a second one that grows when a call finds
     // more than it holds; both kept and counted in device_bytes
     GateScratch gate = {};
-    DevBlock kept[BLK_COUNT];  // the allocations behind fac, dup (boxes and counters; the pair list), fuse, match and gate (tables; the list)
+    // joint compatibility search (ekf_associate_joint): the candidate table and the results, one allocation made at the first call
+    // that searches, kept and counted in device_bytes
+    AssocScratch assoc = {};
+    DevBlock kept[BLK_COUNT];  // the allocations behind fac, dup (boxes and counters; the pair list), fuse, match, gate (tables; the list) and assoc
 };
 
 static int sticky_status(ekf_batch *h, bool include_capacity);
@@ -1451,6 +1455,8 @@ static int sticky_status(ekf_batch *h, bool include_capacity) {
 //   ekf_extract_map, ekf_batch_extract_map             source: QUIET_STREAM, ST_INVALID, ids checked, settle(); then the destination:
 //                                                      QUIET_SETTLED  ST_NONE              as ekf_set_state (the source is only read)
 //   ekf_get_submap                                     QUIET_STREAM   ST_INVALID           ids checked; size only: returns; else settle(), the dense gather
+//   ekf_associate_joint (and the batch form)           QUIET_STREAM   ST_INVALID           values checked first; the sweep of ekf_gate_candidates; no candidate: returns;
+//                                                                                          else settle(), the search; the state is only read
 //   ekf_gate_candidates (and the batch form)           refresh_bounds alone (as ekf_get_landmark_covs): values checked first; no measurement: returns;
 //                                                      the chain stream drained, a sticky EKF_ERR_TIMEOUT ends it, EKF_ERR_CAPACITY does not; NO settle():
 //                                                      the open window stays open, x / robot rows / D are only read, the flush stream is untouched

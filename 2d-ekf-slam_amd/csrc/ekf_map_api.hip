@@ -1,6 +1,6 @@
 // ekf_map_api.hip -- host side of the map operations of include/ekfslam_c.h: removal, frame change and anchoring, joining, extraction
 // and ekf_get_submap, joint consistency, duplicate search, fusion, matched updates and their score, the individual compatibility table,
-// ekf_get_landmark_covs.  Included
+// the joint compatibility search, ekf_get_landmark_covs.  Included
 // by ekf_api.hip (one translation unit: ekf_batch, HIP_TRY / EKF_TRY, quiesce, finish_rewrite, DevTmp and the kept scratch blocks are
 // that file's).  Every entry point runs once per call on a handle it brings to rest and reads: check, quiesce, plan, upload, launch,
 // finish.  The checks of the caller's lists and the tables the kernels read are pure code in ekf_map_plan.h; the order of those
@@ -500,12 +500,14 @@ static int fuse_reserve(ekf_batch *h) {
 // want[BLK_DUP] is not read: dup_reserve builds base and list together, and a base whose list never got allocated is not rebuilt.
 static int match_reserve(ekf_batch *h, int n_meas);
 static int gate_reserve(ekf_batch *h, int n_meas, int cand);
+static int assoc_reserve(ekf_batch *h);
 static int map_scratch_reserve(ekf_batch *h, const bool want[BLK_COUNT], int dup_cap, int match_cap, int gate_zcap, int gate_ccap) {
     if (want[BLK_FACTOR]) EKF_TRY(factor_reserve(h));
     if (want[BLK_DUP_LIST]) EKF_TRY(dup_reserve(h, dup_cap));
     if (want[BLK_FUSE]) EKF_TRY(fuse_reserve(h));
     if (want[BLK_MATCH]) EKF_TRY(match_reserve(h, match_cap));
     if (want[BLK_GATE]) EKF_TRY(gate_reserve(h, gate_zcap, gate_ccap));
+    if (want[BLK_ASSOC]) EKF_TRY(assoc_reserve(h));
     return EKF_OK;
 }
 
@@ -851,6 +853,110 @@ extern "C" int ekf_batch_gate_candidates(ekf_handle h, const double *z, const do
                                          int max_cand, int *n_found_out, ekf_decision *nearest_out, int *n_skipped_out) {
     if (!h || !n_found_out) return set_error(EKF_ERR_BAD_ARG, "bad argument");
     return gate_impl(h, filters_of(h, -1), z, R, valid, n_z, gate, cand_out, max_cand, n_found_out, nearest_out, n_skipped_out);
+}
+
+// ---- joint compatibility search -------------------------------------------------------------------
+// The scratch of ekf_associate_joint (ekf_assoc.hip: AssocScratch): the candidate table, the chosen landmarks and the search's
+// record, 2 328 bytes per filter whatever the capacity: one block at the first call that searches; ekf_reserve builds it again.
+static int assoc_reserve(ekf_batch *h) {
+    DevBlock &blk = h->kept[BLK_ASSOC];
+    if (blk.p) return EKF_OK;
+    const size_t B = (size_t)h->dv.B, per = EKF_MAX_PENDING * (2 + EKF_ASSOC_MAX_BRANCH);
+    EKF_TRY(block_alloc(h, &blk, B * (sizeof(AssocResult) + per * sizeof(int)), /*zero*/ true));
+    AssocScratch &as = h->assoc;
+    as.out = (AssocResult *)blk.p;
+    as.ncand = (int *)(as.out + B);
+    as.cand = as.ncand + B * EKF_MAX_PENDING;
+    as.ids = as.cand + B * EKF_MAX_PENDING * EKF_ASSOC_MAX_BRANCH;
+    return EKF_OK;
+}
+
+extern "C" int ekf_joint_gates(double confidence, double *out) {
+    if (!out || !plan_assoc_gates(confidence, out)) return set_error(EKF_ERR_BAD_ARG, "bad argument (a confidence inside (0, 1))");
+    return EKF_OK;
+}
+
+// The filters f with the scans of gate_impl.  The values are checked before anything happens to the handle.  Then the rule of
+// ekf_joint_compat: the streaming launch leaves, a sticky EKF_ERR_TIMEOUT ends the call; the sweep of ekf_gate_candidates (gate_impl
+// itself, nothing folded: its list comes back sorted, and GateScratch keeps the compacted measurements on the device); the
+// per-measurement table from the list (plan_assoc_table: this is the one trip through the host, the sort gate_impl makes anyway --
+// a second sweep only when a filter lists more than 2 048 pairs).  No candidate anywhere: returns, nothing folded.  Else settle(),
+// the table up, k_assoc_search (one launch: one wave per filter), k_match_factor with apply = 0 on the winner it left in
+// MatchScratch -- ekf_joint_compat's kernel, so d2_out has ekf_joint_compat's bits --, the results back in three copies.
+static int assoc_impl(ekf_batch *h, Filters f, const double *z, const double *R, const unsigned char *valid, int n_z, double gate, const double *joint_gate, int max_branch,
+                      long long max_nodes, int *ids_out, double *d2_out, ekf_decision *nearest_out, int *n_skipped_out, ekf_assoc *info_out) {
+    const int b0 = f.b0, nb = f.nb;
+    EKF_TRY(set_error(plan_assoc_args(z, R, valid, n_z, b0, nb, gate, joint_gate, max_branch, max_nodes, ids_out, EKF_MAX_PENDING)));
+    AssocArgs aa;
+    if (joint_gate) memcpy(aa.jg, joint_gate, sizeof aa.jg);
+    else plan_assoc_gates(0.99, aa.jg);
+    aa.max_nodes = max_nodes;
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
+    std::vector<int> found((size_t)nb, 0);
+    std::vector<ekf_candidate> cands;
+    size_t ld = 0;
+    if (n_z > 0) {
+        const size_t all = (size_t)n_z * (size_t)(h->dv.Ncap > 0 ? h->dv.Ncap : 1);  // (a filter cannot list more)
+        ld = all < 2048 ? all : 2048;
+        for (int round = 0;; round++) {
+            cands.resize((size_t)nb * ld);
+            const int rc = gate_impl(h, f, z, R, valid, n_z, gate, cands.data(), (int)ld, found.data(), nearest_out, n_skipped_out);
+            if (rc < 0) return rc;
+            const size_t most = (size_t)most_landmarks(found.data(), nb);
+            if (most <= ld) break;
+            if (round > 0) return set_error(EKF_ERR_STATE, "the candidate count changed between two passes over an unchanged state");
+            ld = most;
+        }
+    }
+    const AssocTable tab = plan_assoc_table(cands.data(), ld, found.data(), valid, n_z, nb, max_branch);
+    std::vector<ekf_assoc> info((size_t)nb);
+    for (int k = 0; k < nb; k++) info[k] = ekf_assoc{0, 0.0, 0, 1, tab.listed[k], tab.dropped[k]};
+    std::vector<int> ids;
+    std::vector<double> d2;
+    size_t ld_d2 = 0;
+    if (tab.any) {
+        EKF_TRY(settle(h));
+        EKF_TRY(assoc_reserve(h));
+        EKF_TRY(match_reserve(h, EKF_MAX_PENDING));
+        const AssocScratch as = h->assoc;
+        const MatchScratch ms = h->match;
+        hipStream_t s = h->s_chain;
+        const size_t per = EKF_MAX_PENDING;
+        std::vector<AssocResult> out((size_t)nb);
+        ids.resize((size_t)nb * per), d2.resize((size_t)nb * ms.zcap), ld_d2 = (size_t)ms.zcap;
+        // (every copy uses a pageable buffer of this function: the first failure stops the enqueueing, and the stream is waited for on every way out)
+        hipError_t e = hipMemcpyAsync(as.ncand + b0 * per, tab.ncand.data(), sizeof(int) * nb * per, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(as.cand + b0 * per * EKF_ASSOC_MAX_BRANCH, tab.cand.data(), sizeof(int) * nb * per * EKF_ASSOC_MAX_BRANCH, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(k_assoc_search, dim3((unsigned)nb), dim3(64), 0, s, h->dv, h->gate, as, ms, aa, h->win.buf_in, b0);
+            hipLaunchKernelGGL(k_match_factor, dim3((unsigned)nb), dim3(256), 0, s, h->dv, h->fuse, ms, h->win.buf_in, 0, EKF_MAX_PENDING, /*apply*/ 0, b0);
+            e = hipMemcpyAsync(ids.data(), as.ids + b0 * per, sizeof(int) * nb * per, hipMemcpyDeviceToHost, s);
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(out.data(), as.out + b0, sizeof(AssocResult) * (size_t)nb, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost, s);
+        const hipError_t w = stream_wait(s);
+        HIP_TRY(e);
+        HIP_TRY(w);
+        EKF_TRY(check_launch());
+        for (int k = 0; k < nb; k++) info[k].nodes = out[k].nodes, info[k].d2 = out[k].d2, info[k].n_paired = out[k].n_paired, info[k].complete = out[k].complete;
+    }
+    if (n_z > 0) plan_assoc_scatter(tab, tab.any ? ids.data() : nullptr, d2.data(), ld_d2, n_z, nb, ids_out, d2_out);
+    for (int k = 0; info_out && k < nb; k++) info_out[k] = info[k];
+    return nb == 1 ? info[0].n_paired : EKF_OK;
+}
+
+extern "C" int ekf_associate_joint(ekf_handle h, int index, const double *z, const double *R, int n_z, double gate, const double *joint_gate, int max_branch, long long max_nodes,
+                                   int *ids_out, double *d2_out, ekf_decision *nearest_out, int *n_skipped_out, ekf_assoc *info_out) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return assoc_impl(h, filters_of(h, index), z, R, nullptr, n_z, gate, joint_gate, max_branch, max_nodes, ids_out, d2_out, nearest_out, n_skipped_out, info_out);
+}
+
+extern "C" int ekf_batch_associate_joint(ekf_handle h, const double *z, const double *R, const unsigned char *valid, int n_z, double gate, const double *joint_gate,
+                                         int max_branch, long long max_nodes, int *ids_out, double *d2_out, ekf_decision *nearest_out, int *n_skipped_out,
+                                         ekf_assoc *info_out) {
+    if (!h || !info_out) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    const int rc = assoc_impl(h, filters_of(h, -1), z, R, valid, n_z, gate, joint_gate, max_branch, max_nodes, ids_out, d2_out, nearest_out, n_skipped_out, info_out);
+    return rc < 0 ? rc : EKF_OK;
 }
 
 extern "C" int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max) {

@@ -2,8 +2,10 @@
 // hands in and the tables the kernels of ekf_rewrite.hip, ekf_extract.hip, ekf_pairs.hip, ekf_fuse.hip, ekf_match.hip and ekf_gate.hip read.  No HIP call and no
 // handle in here: landmark counts come in as plain arrays, n_lm[k] = landmarks of the k-th filter of the call, whose number in its
 // handle is b0 + k (error texts name that number).  A check reports a status and a text; the caller hands both to set_error.
-// tests/cpp/map_plan_check.cpp, tests/cpp/match_plan_check.cpp and tests/cpp/gate_plan_check.cpp run all of it on the CPU.
+// tests/cpp/map_plan_check.cpp, tests/cpp/match_plan_check.cpp, tests/cpp/gate_plan_check.cpp and tests/cpp/assoc_plan_check.cpp run
+// all of it on the CPU.
 #pragma once
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -325,4 +327,105 @@ inline void plan_gate_scatter(const GateTable &t, int zcap, int n_z, int nb, con
             if (nearest_out) nearest_out[to] = near[from];
             if (n_skipped_out) n_skipped_out[to] = skip[from];
         }
+}
+
+// ---- joint compatibility search (ekf_associate_joint) -----------------------------------------------------------------------------
+// What plan_gate_args checks of the scan, then: ids_out, the branch limit and the node budget, the joint gates (null: the defaults),
+// and at most `limit` (EKF_MAX_PENDING) valid entries per filter.  Checked before the handle is touched.
+inline PlanStatus plan_assoc_args(const double *z, const double *R, const unsigned char *valid, int n_z, int b0, int nb, double gate, const double *joint_gate, int max_branch,
+                                  long long max_nodes, const int *ids_out, int limit) {
+    const PlanStatus st = plan_gate_args(z, R, valid, n_z, b0, nb, gate, nullptr, 0);
+    if (st.code) return st;
+    if (n_z > 0 && !ids_out) return plan_fail(EKF_ERR_BAD_ARG, "ids_out is null");
+    if (max_branch < 1 || max_branch > EKF_ASSOC_MAX_BRANCH) return plan_fail(EKF_ERR_BAD_ARG, "max_branch = %d is outside [1, %d]", max_branch, EKF_ASSOC_MAX_BRANCH);
+    if (max_nodes < 1 || max_nodes > EKF_ASSOC_MAX_NODES) return plan_fail(EKF_ERR_BAD_ARG, "max_nodes = %lld is outside [1, %d]", max_nodes, EKF_ASSOC_MAX_NODES);
+    for (int q = 0; joint_gate && q < EKF_MAX_PENDING; q++)
+        if (!(joint_gate[q] >= 0.0)) return plan_fail(EKF_ERR_BAD_ARG, "joint_gate[%d] is negative or NaN", q);
+    for (int k = 0; k < nb; k++) {
+        int kept = 0;
+        for (int q = 0; q < n_z; q++) kept += !valid || valid[(size_t)k * n_z + q];
+        if (kept > limit) return plan_fail(EKF_ERR_BAD_ARG, "filter %d: %d valid measurements in one scan (at most %d)", b0 + k, kept, limit);
+    }
+    return {};
+}
+// The survival function of chi-square with 2 q degrees of freedom, exp(-x / 2) sum_{i < q} (x / 2)^i / i! (positive terms: no
+// cancellation).
+inline double plan_chi2_even_sf(double x, int q) {
+    double term = 1.0, sum = 0.0;
+    for (int i = 0; i < q; i++) sum += term, term = term * (0.5 * x) / (i + 1);
+    return exp(-0.5 * x) * sum;
+}
+// out[q - 1] = the `confidence` quantile for q = 1 .. EKF_MAX_PENDING pairings: bisection of the survival function down to two
+// neighbouring doubles.  false: confidence is not inside (0, 1).
+inline bool plan_assoc_gates(double confidence, double *out) {
+    if (!(confidence > 0.0 && confidence < 1.0)) return false;
+    const double tail = 1.0 - confidence;
+    for (int q = 1; q <= EKF_MAX_PENDING; q++) {
+        double lo = 0.0, hi = 1.0;
+        while (plan_chi2_even_sf(hi, q) > tail) hi *= 2.0;
+        for (int it = 0; it < 200; it++) {
+            const double mid = 0.5 * (lo + hi);
+            if (!(mid > lo && mid < hi)) break;
+            if (plan_chi2_even_sf(mid, q) > tail) lo = mid;
+            else hi = mid;
+        }
+        out[q - 1] = hi;
+    }
+    return true;
+}
+// The candidate table k_assoc_search reads, nb filters: ncand [nb][32] and cand [nb][32][EKF_ASSOC_MAX_BRANCH] by the COMPACTED
+// index of a measurement (its place among the filter's valid entries, as plan_gate_table counts them), from filter k's list in
+// ekf_gate_candidates' order at lists + k * ld with found[k] entries (meas = the caller's index): the first max_branch of each
+// measurement.  listed / dropped [nb]: the pairs of the list, those cut.  src [nb][32]: the caller's index of a compacted entry.
+struct AssocTable {
+    std::vector<int> ncand, cand, listed, dropped, src, cnt;
+    bool any = false;  // some filter has a candidate
+};
+inline AssocTable plan_assoc_table(const ekf_candidate *lists, size_t ld, const int *found, const unsigned char *valid, int n_z, int nb, int max_branch) {
+    AssocTable t;
+    t.ncand.assign((size_t)nb * EKF_MAX_PENDING, 0), t.cand.assign((size_t)nb * EKF_MAX_PENDING * EKF_ASSOC_MAX_BRANCH, -1);
+    t.listed.assign((size_t)nb, 0), t.dropped.assign((size_t)nb, 0), t.cnt.assign((size_t)nb, 0), t.src.assign((size_t)nb * EKF_MAX_PENDING, -1);
+    std::vector<int> place((size_t)(n_z > 0 ? n_z : 0));
+    for (int k = 0; k < nb; k++) {
+        int kept = 0;
+        for (int q = 0; q < n_z; q++) {
+            const bool look = !valid || valid[(size_t)k * n_z + q];
+            place[q] = look && kept < EKF_MAX_PENDING ? kept : -1;
+            if (place[q] >= 0) t.src[(size_t)k * EKF_MAX_PENDING + kept++] = q;
+        }
+        t.cnt[k] = kept;
+        for (int q = 0; q < found[k]; q++) {
+            const ekf_candidate &c = lists[(size_t)k * ld + q];
+            if (c.meas < 0 || c.meas >= n_z || place[c.meas] < 0) continue;
+            t.listed[k]++;
+            int &n = t.ncand[(size_t)k * EKF_MAX_PENDING + place[c.meas]];
+            if (n >= max_branch) {
+                t.dropped[k]++;
+                continue;
+            }
+            t.cand[((size_t)k * EKF_MAX_PENDING + place[c.meas]) * EKF_ASSOC_MAX_BRANCH + n++] = c.landmark;
+            t.any = true;
+        }
+    }
+    return t;
+}
+// The device's results back into the caller's order: ids [nb][32] by compacted index to ids_out [nb][n_z] (-1 elsewhere), and the
+// winner's running distances d2 (filter k's at d2 + k * ld_d2, one per PAIRED measurement in order) to d2_out (NaN elsewhere; may
+// be null) -- what ekf_joint_compat returns for ids_out.  ids == nullptr: nothing was searched.
+inline void plan_assoc_scatter(const AssocTable &t, const int *ids, const double *d2, size_t ld_d2, int n_z, int nb, int *ids_out, double *d2_out) {
+    for (size_t q = 0; q < (size_t)nb * (n_z > 0 ? n_z : 0); q++) {
+        ids_out[q] = -1;
+        if (d2_out) d2_out[q] = __builtin_nan("");
+    }
+    for (int k = 0; ids && k < nb; k++) {
+        int j = 0;
+        for (int q = 0; q < t.cnt[k]; q++) {
+            const int id = ids[(size_t)k * EKF_MAX_PENDING + q];
+            if (id < 0) continue;
+            const size_t to = (size_t)k * n_z + t.src[(size_t)k * EKF_MAX_PENDING + q];
+            ids_out[to] = id;
+            if (d2_out) d2_out[to] = d2[(size_t)k * ld_d2 + j];
+            j++;
+        }
+    }
 }

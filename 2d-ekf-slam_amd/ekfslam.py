@@ -32,6 +32,7 @@ ABI_SYMBOLS = [
     "ekf_fuse_landmarks", "ekf_batch_fuse_landmarks",
     "ekf_update_matched", "ekf_batch_update_matched", "ekf_joint_compat", "ekf_batch_joint_compat",
     "ekf_gate_candidates", "ekf_batch_gate_candidates",
+    "ekf_associate_joint", "ekf_batch_associate_joint", "ekf_joint_gates",
 ]
 
 
@@ -76,6 +77,16 @@ class EkfCandidate(ctypes.Structure):
 
 CAND_DTYPE = np.dtype([("meas", "i4"), ("landmark", "i4"), ("d2", "f8")])
 assert CAND_DTYPE.itemsize == ctypes.sizeof(EkfCandidate) == 16
+
+
+class EkfAssoc(ctypes.Structure):
+    _fields_ = [("nodes", ctypes.c_longlong), ("d2", ctypes.c_double), ("n_paired", ctypes.c_int), ("complete", ctypes.c_int),
+                ("n_candidates", ctypes.c_int), ("n_dropped", ctypes.c_int)]
+
+
+ASSOC_DTYPE = np.dtype([("nodes", "i8"), ("d2", "f8"), ("n_paired", "i4"), ("complete", "i4"), ("n_candidates", "i4"), ("n_dropped", "i4")])
+assert ASSOC_DTYPE.itemsize == ctypes.sizeof(EkfAssoc) == 32
+ASSOC_MAX_MEAS, ASSOC_MAX_BRANCH, ASSOC_MAX_NODES = 32, 16, 1 << 20
 DECISION_DTYPE = np.dtype([("decision", "i4"), ("matched", "i4"), ("mahal", "f8")])
 assert DECISION_DTYPE.itemsize == ctypes.sizeof(EkfDecision) == 16
 
@@ -159,6 +170,11 @@ def load():
                                       ctypes.POINTER(EkfDecision), _ip]
     L.ekf_batch_gate_candidates.argtypes = [_H, _dp, _dp, _up, ctypes.c_int, ctypes.c_double, ctypes.POINTER(EkfCandidate), ctypes.c_int, _ip,
                                             ctypes.POINTER(EkfDecision), _ip]
+    L.ekf_associate_joint.argtypes = [_H, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_double, _dp, ctypes.c_int, ctypes.c_longlong, _ip, _dp,
+                                      ctypes.POINTER(EkfDecision), _ip, ctypes.POINTER(EkfAssoc)]
+    L.ekf_batch_associate_joint.argtypes = [_H, _dp, _dp, _up, ctypes.c_int, ctypes.c_double, _dp, ctypes.c_int, ctypes.c_longlong, _ip, _dp,
+                                            ctypes.POINTER(EkfDecision), _ip, ctypes.POINTER(EkfAssoc)]
+    L.ekf_joint_gates.argtypes = [ctypes.c_double, _dp]
     L.ekf_script_load.argtypes =[_H, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _up, _dp]
     L.ekf_script_run.argtypes = [_H, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.ekf_sync.argtypes = [_H]
@@ -251,6 +267,17 @@ def candidate_matching(cands, n_z):
         ids[m] = l
         taken.add(l)
     return ids
+
+
+def joint_gates(confidence=0.99):
+    """The joint gates associate_joint uses by default (ekf_joint_gates): [q - 1] is the `confidence` quantile of chi-square with
+    2 q degrees of freedom, q = 1 .. 32."""
+    confidence = float(confidence)
+    if not 0.0 < confidence < 1.0:
+        raise ValueError("confidence must lie inside (0, 1)")
+    out = np.empty(ASSOC_MAX_MEAS)
+    _chk(load().ekf_joint_gates(confidence, _p(out)))
+    return out
 
 
 def _pair_buffer(pairs):
@@ -680,6 +707,46 @@ class FilterBatch:
         out = [(buf[b, :min(int(found[b]), max_cand)].copy(), int(found[b]), near[b].copy(), skip[b].copy()) for b in range(nb)]
         return out if index is None else out[0]
 
+    def associate_joint(self, z, R, gate=9.21, joint_gate=None, max_branch=8, max_nodes=65536, index=0, valid=None):
+        """The joint-compatibility search of a scan on the device (ekf_associate_joint): the candidates of every measurement are
+        those gate_candidates lists at `gate` (the first max_branch of each), a hypothesis pairs every measurement with one of them
+        or nothing, every prefix of q pairings within joint_gate[q - 1] (None: joint_gates(0.99)); the result has the most
+        pairings, then the smallest joint distance, found by branch and bound within max_nodes expanded nodes.  Returns
+        (ids, d2, info, nearest, n_skipped): ids int32 [n_z] as update_matched takes them (-1: unpaired), d2 what joint_compat
+        gives for ids, info an ASSOC_DTYPE record (nodes, d2, n_paired, complete, n_candidates, n_dropped), nearest and n_skipped as
+        gate_candidates.  index=None: every filter in one launch sequence, leading batch axes, valid [batch][n_z] masks entries.
+        At most 32 valid measurements per filter.  The filter is only read; deferred slots are folded when something is searched."""
+        gate, max_branch, max_nodes = float(gate), int(max_branch), int(max_nodes)
+        if not gate >= 0.0:
+            raise ValueError("gate must not be negative or NaN")
+        if not 1 <= max_branch <= ASSOC_MAX_BRANCH:
+            raise ValueError("max_branch must lie in 1 .. %d" % ASSOC_MAX_BRANCH)
+        if not 1 <= max_nodes <= ASSOC_MAX_NODES:
+            raise ValueError("max_nodes must lie in 1 .. %d" % ASSOC_MAX_NODES)
+        jg = None
+        if joint_gate is not None:
+            jg = _f64(joint_gate).reshape(-1)
+            if jg.shape != (ASSOC_MAX_MEAS,) or not (jg >= 0.0).all():
+                raise ValueError("joint_gate must hold %d gates, none negative or NaN" % ASSOC_MAX_MEAS)
+        z, Rc, valid, n_z = self._scan_lists(z, R, valid, index)
+        nb = self.batch if index is None else 1
+        kept = np.full(nb, n_z) if valid is None else (valid != 0).sum(axis=-1)
+        if int(np.max(kept, initial=0)) > ASSOC_MAX_MEAS:
+            raise ValueError("a scan holds at most %d valid measurements" % ASSOC_MAX_MEAS)
+        ids, d2 = np.full((nb, n_z), -1, dtype=np.int32), np.full((nb, n_z), np.nan)
+        near, skip = np.zeros((nb, n_z), dtype=DECISION_DTYPE), np.zeros((nb, n_z), dtype=np.int32)
+        info = np.zeros(nb, dtype=ASSOC_DTYPE)
+        ptrs = (_p(z), _p(Rc)) if n_z else (None, None)
+        outs = (ids.ctypes.data_as(_ip), _p(d2), near.ctypes.data_as(ctypes.POINTER(EkfDecision)), skip.ctypes.data_as(_ip)) if n_z else (None,) * 4
+        ip = info.ctypes.data_as(ctypes.POINTER(EkfAssoc))
+        jp = _p(jg) if jg is not None else None
+        if index is None:
+            vp = valid.ctypes.data_as(_up) if valid is not None and n_z else None
+            _chk(self.L.ekf_batch_associate_joint(self.h, *ptrs, vp, n_z, gate, jp, max_branch, max_nodes, *outs, ip))
+            return [(ids[b].copy(), d2[b].copy(), info[b].copy(), near[b].copy(), skip[b].copy()) for b in range(nb)]
+        _chk(self.L.ekf_associate_joint(self.h, int(index), *ptrs, n_z, gate, jp, max_branch, max_nodes, *outs, ip))
+        return ids[0], d2[0], info[0], near[0], skip[0]
+
     def joint_factor(self, index=0):
         """Diagnostic: the upper factor U (U^T U = P_LL) the last joint_consistency call left for filter `index`, dense (2N, 2N);
         EkfError ERR_STATE when the state has changed since."""
@@ -882,6 +949,11 @@ class KalmanFilter:
     def joint_compat(self, z, R, ids):
         """The running joint Mahalanobis distance of one association hypothesis (FilterBatch.joint_compat); nothing is applied."""
         return self._f.joint_compat(z, R, ids, 0)
+
+    def associate_joint(self, z, R, gate=9.21, joint_gate=None, max_branch=8, max_nodes=65536):
+        """The joint-compatibility search of a scan (FilterBatch.associate_joint): (ids, d2, info, nearest, n_skipped); nothing is
+        applied -- update_matched(z, R, ids) applies the decision."""
+        return self._f.associate_joint(z, R, gate, joint_gate, max_branch, max_nodes, 0)
 
     def gate_candidates(self, z, R, gate=9.21):
         """The gate-passing landmarks of every measurement, the filter's own decision for each and the skip counts

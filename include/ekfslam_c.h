@@ -480,6 +480,74 @@ int ekf_batch_gate_candidates(ekf_handle h, const double *z /*[batch][n_z][2]*/,
                               ekf_candidate *cand_out /*[batch][max_cand] or NULL*/, int max_cand, int *n_found_out /*[batch]*/,
                               ekf_decision *nearest_out /*[batch][n_z] or NULL*/, int *n_skipped_out /*[batch][n_z] or NULL*/);
 
+/* From the table to a decision: the joint-compatibility branch-and-bound search (JCBB) on the device, one launch whatever the
+ * number of nodes.  z, R (and valid, batch form) as for ekf_gate_candidates; at most EKF_MAX_PENDING = 32 valid measurements per
+ * filter, more is EKF_ERR_BAD_ARG as for ekf_joint_compat.
+ * CANDIDATES of measurement k: the pairs ekf_gate_candidates lists for it at this state and `gate` (so the condition rule
+ * applies), in its order (d2 ascending, then landmark), the first max_branch of them (1 .. EKF_ASSOC_MAX_BRANCH = 16);
+ * info.n_candidates counts the listed pairs of the filter, info.n_dropped those cut by max_branch.
+ * A HYPOTHESIS gives every valid measurement, in list order, one of its candidates or nothing, a landmark at most once.  It is
+ * feasible when every prefix is jointly compatible: after each pairing, q pairings so far, D2 <= joint_gate[q - 1], D2 the joint
+ * distance ekf_joint_compat defines (S, d, U, y of ekf_update_matched, everything linearised at the one entry state).  An extension
+ * whose 2 x 2 Schur complement has a pivot that is not above 2^-44 of its own diagonal entry of S (or NaN) is not compatible: a
+ * result, never an error.  joint_gate == NULL: ekf_joint_gates(0.99, .), the 99 % quantiles of chi-square with 2 q dof.
+ * THE SEARCH (m valid measurements; Best starts empty: 0 pairings, D2 0; `nodes` counts expanded nodes up to max_nodes,
+ * 1 .. EKF_ASSOC_MAX_NODES = 2^20):
+ *     search(H, i, cnt, D2):
+ *         if cnt + (m - i) <  Best.cnt: return
+ *         if cnt + (m - i) == Best.cnt and D2 >= Best.D2: return                  (D2 never decreases along a branch)
+ *         if i == m: (H beats Best: more pairings, or as many and a smaller D2)  Best = H; return
+ *         if nodes == max_nodes: complete = 0; stop the whole search
+ *         nodes += 1
+ *         for l in candidates(i) in list order, l not used in H:
+ *             D2' = joint distance of H + (i, l);  if D2' <= joint_gate[cnt]: search(H + (i, l), i + 1, cnt + 1, D2')
+ *         search(H + (i, nothing), i + 1, cnt, D2)
+ * The result is Best: the most pairings, then the smallest D2, then the first found in this order.  complete = 1: the optimum over
+ * all feasible hypotheses; complete = 0: the best found when the budget ran out -- the order is fixed, so that is reproducible too.
+ * A filter without a candidate (no valid measurement, no landmark, nothing inside the gate) is not searched: everything -1,
+ * n_paired = 0, complete = 1, nodes = 0.
+ * ids_out[k]: the landmark of measurement k, -1 for unpaired and masked entries -- what ekf_update_matched takes.  d2_out (may be
+ * NULL): what ekf_joint_compat returns for ids_out, the same bits (the same kernel runs on the winner).  nearest_out, n_skipped_out
+ * (may be NULL): those of ekf_gate_candidates, the same bits (the same sweep).  info.d2: the winner's distance as the search
+ * accumulated it (agrees with the last d2_out to rounding, not to the bit: another order of the same elimination).
+ * The search reads cross blocks of P_LL, so it follows the rule of ekf_joint_compat and ekf_find_duplicates: a streaming launch is
+ * stopped (immediate-mode calls stream again afterwards), deferred slots are folded, a sticky EKF_ERR_TIMEOUT is returned
+ * unchanged, a sticky EKF_ERR_CAPACITY does not block the call; the filter is only read: state, counters, decision log, loaded
+ * script and host mirror stay what ekf_get_state at the same point would leave.  A call without a candidate in any filter folds
+ * nothing.  The call synchronises.
+ * EKF_ERR_BAD_ARG, found on the host before the handle is touched: everything ekf_gate_candidates refuses of z, R, valid, n_z and
+ * gate; ids_out NULL with n_z > 0; info_out NULL (batch form); max_branch or max_nodes out of range; a joint_gate entry that is
+ * NaN or negative; more than 32 valid entries in a filter; an index out of range.
+ * ekf_associate_joint returns n_paired or a negative status; the batch form writes filter b's results at ids_out + b * n_z (and
+ * so on) and info_out[b], and returns EKF_OK or a negative status.
+ * The candidate table is ordered on the host (the one trip ekf_gate_candidates makes for its sort); from there to ids_out one
+ * wave per filter runs the whole search: no floating-point atomics, one writer per value, every sum in a fixed order -- two calls
+ * on an unchanged state give the same bits, and filter b of the batch form gets the bits of the one-filter call on b.
+ * The scratch -- 2 328 bytes per filter beside those of ekf_gate_candidates and ekf_joint_compat -- is allocated at the first call
+ * that searches, kept on the handle (ekf_device_bytes counts it, ekf_reserve builds it again) and freed by ekf_destroy. */
+#define EKF_ASSOC_MAX_BRANCH 16
+#define EKF_ASSOC_MAX_NODES (1 << 20)
+typedef struct ekf_assoc {
+    long long nodes;   /* expanded nodes */
+    double d2;         /* joint distance of the result */
+    int n_paired;
+    int complete;      /* 1: the optimum; 0: max_nodes ran out */
+    int n_candidates;  /* pairs inside the individual gate */
+    int n_dropped;     /* ... of which max_branch cut */
+} ekf_assoc;
+int ekf_associate_joint(ekf_handle h, int index, const double *z /*[n_z][2]*/, const double *R /*[n_z][4], column-major 2x2*/, int n_z, double gate,
+                        const double *joint_gate /*[32] or NULL*/, int max_branch, long long max_nodes, int *ids_out /*[n_z]*/,
+                        double *d2_out /*[n_z] or NULL*/, ekf_decision *nearest_out /*[n_z] or NULL*/, int *n_skipped_out /*[n_z] or NULL*/,
+                        ekf_assoc *info_out /* may be NULL */);
+int ekf_batch_associate_joint(ekf_handle h, const double *z /*[batch][n_z][2]*/, const double *R /*[batch][n_z][4]*/,
+                              const unsigned char *valid /*[batch][n_z] or NULL*/, int n_z, double gate, const double *joint_gate /*[32] or NULL*/,
+                              int max_branch, long long max_nodes, int *ids_out /*[batch][n_z]*/, double *d2_out /*[batch][n_z] or NULL*/,
+                              ekf_decision *nearest_out /*[batch][n_z] or NULL*/, int *n_skipped_out /*[batch][n_z] or NULL*/,
+                              ekf_assoc *info_out /*[batch]*/);
+/* out[q - 1], q = 1 .. 32: the `confidence` quantile of chi-square with 2 q degrees of freedom, from the closed form for even dof,
+ * CDF(x) = 1 - exp(-x / 2) sum_{i < q} (x / 2)^i / i!, by bisection on the host.  A confidence outside (0, 1): EKF_ERR_BAD_ARG. */
+int ekf_joint_gates(double confidence, double *out /*[32]*/);
+
 /* ---- device-resident step scripts (benchmarks, Monte-Carlo runs) ------------------------------
  * A script is `steps` steps; step s of filter b is
  *     Propagate(ctrl[s][b] = v, w, dt)  with Q from params as ekf_propagate does,
