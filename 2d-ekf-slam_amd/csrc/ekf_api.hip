@@ -92,7 +92,7 @@ struct DevBlock {
     void *p = nullptr;
     size_t bytes = 0;
 };
-enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_MATCH, BLK_GATE, BLK_GATE_LIST, BLK_ASSOC, BLK_COUNT };
+enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_MATCH, BLK_GATE, BLK_GATE_LIST, BLK_ASSOC, BLK_ADD, BLK_COUNT };
 
 struct GraphEntry {
     int steps, M, has_truth;
@@ -210,7 +210,10 @@ struct ekf_batch {
     // joint compatibility search (ekf_associate_joint): the candidate table and the results, one allocation made at the first call
     // that searches, kept and counted in device_bytes
     AssocScratch assoc = {};
-    DevBlock kept[BLK_COUNT];  // the allocations behind fac, dup (boxes and counters; the pair list), fuse, match, gate (tables; the list) and assoc
+    // landmark initialisation (ekf_add_landmarks, ekf_update_joint): the call's measurement table and the new rows' operands; one
+    // allocation made at the first call that adds, replaced by a larger one for a longer list, kept and counted in device_bytes
+    AddScratch add = {};
+    DevBlock kept[BLK_COUNT];  // the allocations behind fac, dup (boxes and counters; the pair list), fuse, match, gate (tables; the list), assoc and add
 };
 
 static int sticky_status(ekf_batch *h, bool include_capacity);
@@ -294,7 +297,11 @@ static Tunables read_tunables() {
 // a hardware queue of its own (unmasked ones share GPU_MAX_HW_QUEUES).  OPEN: a 256-filter overlap-mode handle (256 chain workgroups
 // that wait in-kernel for a dense pass which only runs on CUs without a chain workgroup, residency_ok) has run out its bounded wait
 // (EKF_ERR_TIMEOUT) when it was created late in a process that had opened many handles -- behind test modules with four handles open
-// at once, and behind the ekf_gate_candidates tests with two.  The cause is not found; that the pool's state (how many queues, which
+// at once, behind the ekf_gate_candidates tests with two, and behind the ekf_add_landmarks tests with two (window 16 of the 256-filter
+// test that time, window 32 before; that test passes when its module is collected first or runs alone, on this and on the previous
+// commit's library).  Neither call can hold anything back itself: gate_impl and add_impl enqueue on s_chain alone, wait for it before
+// they return, and create no stream, event or queue; what those test modules share is dozens of handles opened and closed in both
+// pipeline modes ahead of the 256-filter one, i.e. the pool's contents.  The cause is not found; that the pool's state (how many queues, which
 // stream the handle is given) decides whether the pass reaches the CUs ahead of the spinning launch is a supposition.
 // INTEGRATION.md §3.
 struct PooledStream {
@@ -1452,6 +1459,8 @@ static int sticky_status(ekf_batch *h, bool include_capacity) {
 //   ekf_fuse_landmarks (and the batch form)            QUIET_SETTLED  ST_INVALID_OR_FULL   the pair list is checked first, against the mirror's counts; no pair: returns
 //   ekf_update_matched (and the batch form)            QUIET_SETTLED  ST_INVALID_OR_FULL   values checked first, ids against the mirror's counts; no measurement: returns
 //   ekf_joint_compat (and the batch form)              QUIET_STREAM   ST_INVALID           ids checked; no measurement: returns; else settle(); the state is only read
+//   ekf_add_landmarks (and the batch form)             QUIET_SETTLED  ST_INVALID_OR_FULL   values checked first; nothing selected: returns (an add without room fails after the settle)
+//   ekf_update_joint (and the batch form)              ekf_associate_joint's, then ekf_update_matched's, then ekf_add_landmarks' (the room is checked between the first two)
 //   ekf_extract_map, ekf_batch_extract_map             source: QUIET_STREAM, ST_INVALID, ids checked, settle(); then the destination:
 //                                                      QUIET_SETTLED  ST_NONE              as ekf_set_state (the source is only read)
 //   ekf_get_submap                                     QUIET_STREAM   ST_INVALID           ids checked; size only: returns; else settle(), the dense gather
@@ -1717,7 +1726,7 @@ extern "C" int ekf_set_state(ekf_handle h, int index, const double *x, const dou
 // moves over on the device (k_export into a dense staging matrix, k_import from it: the tile numbering depends on the capacity),
 // the counters, the decision log and a loaded script move with it, and the handle keeps its address.
 static int reserve_move_state(ekf_batch *h, ekf_batch *nh, const std::vector<int> &n_lm);
-static int map_scratch_reserve(ekf_batch *h, const bool want[BLK_COUNT], int dup_cap, int match_cap, int gate_zcap, int gate_ccap);  // (ekf_map_api.hip)
+static int map_scratch_reserve(ekf_batch *h, const bool want[BLK_COUNT], int dup_cap, int match_cap, int gate_zcap, int gate_ccap, int add_zcap);  // (ekf_map_api.hip)
 
 extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     if (!h || capacity_landmarks < 1 || capacity_landmarks > EKF_MAX_CAPACITY) return set_error(EKF_ERR_BAD_ARG, "bad handle / capacity (EKF_MAX_CAPACITY)");
@@ -1782,10 +1791,10 @@ extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     h->script_steps = 0;
     bool had[BLK_COUNT];  // the scratch the map operations keep follows the capacity
     for (int i = 0; i < BLK_COUNT; i++) had[i] = h->kept[i].p != nullptr;
-    const int had_dup_cap = h->dup.cap, had_match_cap = h->match.zcap, had_gate_zcap = h->gate.zcap, had_gate_ccap = h->gate.ccap;
+    const int had_dup_cap = h->dup.cap, had_match_cap = h->match.zcap, had_gate_zcap = h->gate.zcap, had_gate_ccap = h->gate.ccap, had_add_zcap = h->add.zcap;
     std::swap(*h, *nh);  // the caller's handle now owns the larger buffers ...
     ekf_destroy(nh);     // ... and the old ones go
-    EKF_TRY(map_scratch_reserve(h, had, had_dup_cap, had_match_cap, had_gate_zcap, had_gate_ccap));
+    EKF_TRY(map_scratch_reserve(h, had, had_dup_cap, had_match_cap, had_gate_zcap, had_gate_ccap, had_add_zcap));
     return refresh_bounds(h);
 }
 

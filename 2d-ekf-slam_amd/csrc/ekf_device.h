@@ -285,6 +285,11 @@ __host__ __device__ inline int join_tile_count(int Ng, int Ns) {
     return Ns > 0 ? J1 * (J1 + 1) / 2 - J0 * (J0 + 1) / 2 : 0;
 }
 
+// Landmark initialisation (ekf_add_landmarks) walks the same tile columns with a measurement table in place of a source filter: a
+// filter's record is {count, 0} and then zcap entries of six doubles {z_x, z_y, R00, R10, R01, R11}; its stride in doubles, a
+// multiple of four (what lies behind the table stays 32-byte aligned).
+__host__ __device__ inline size_t add_tab_stride(int zcap) { return (2 + 6 * (size_t)zcap + 3) & ~(size_t)3; }
+
 // Where element (i', j') of the joined P_LL (landmark space, either order) comes from.  The SOURCE filter has a layout of its own
 // (Ts tiles per side, D stride dns: its capacity's, not the destination's).
 //   JM_OLD    both landmarks are the destination's: the element stays, bit for bit
@@ -295,6 +300,16 @@ __host__ __device__ inline int join_tile_count(int Ng, int Ns) {
 //   JM_D      a new landmark's own block: the source's D (offset comp * dns + landmark)
 //   JM_ZERO   beyond the joined map
 enum { JM_ZERO = 0, JM_OLD = 1, JM_ROBOT = 2, JM_BM = 3, JM_D = 4 };
+// ... of the block (landmark li, landmark lj) alone: all that ekf_add_landmarks' tile kernel needs (its new landmarks have no source
+// layout: Ns = the number of additions).  join_source below keeps its own words for the same cases -- written through this function,
+// k_join_tiles came out with 70 instead of 63 VGPRs and one wave per SIMD less, and the join's code is to stay as it was measured --;
+// tests/cpp/add_plan_check.cpp holds the two to each other.
+__host__ __device__ inline int join_where(int Ng, int Ns, int li, int lj) {
+    if (li >= Ng + Ns || lj >= Ng + Ns) return JM_ZERO;
+    if (li < Ng && lj < Ng) return JM_OLD;
+    if (li < Ng || lj < Ng) return JM_ROBOT;
+    return li == lj ? JM_D : JM_BM;
+}
 struct JoinSource {
     int where;
     int si, sj;  // JM_BM / JM_D: rows of the source's landmark space, in the order asked for

@@ -1,6 +1,6 @@
 // ekf_map_api.hip -- host side of the map operations of include/ekfslam_c.h: removal, frame change and anchoring, joining, extraction
 // and ekf_get_submap, joint consistency, duplicate search, fusion, matched updates and their score, the individual compatibility table,
-// the joint compatibility search, ekf_get_landmark_covs.  Included
+// the joint compatibility search, landmark initialisation and the scan step built from those, ekf_get_landmark_covs.  Included
 // by ekf_api.hip (one translation unit: ekf_batch, HIP_TRY / EKF_TRY, quiesce, finish_rewrite, DevTmp and the kept scratch blocks are
 // that file's).  Every entry point runs once per call on a handle it brings to rest and reads: check, quiesce, plan, upload, launch,
 // finish.  The checks of the caller's lists and the tables the kernels read are pure code in ekf_map_plan.h; the order of those
@@ -501,13 +501,15 @@ static int fuse_reserve(ekf_batch *h) {
 static int match_reserve(ekf_batch *h, int n_meas);
 static int gate_reserve(ekf_batch *h, int n_meas, int cand);
 static int assoc_reserve(ekf_batch *h);
-static int map_scratch_reserve(ekf_batch *h, const bool want[BLK_COUNT], int dup_cap, int match_cap, int gate_zcap, int gate_ccap) {
+static int add_reserve(ekf_batch *h, int n_meas);
+static int map_scratch_reserve(ekf_batch *h, const bool want[BLK_COUNT], int dup_cap, int match_cap, int gate_zcap, int gate_ccap, int add_zcap) {
     if (want[BLK_FACTOR]) EKF_TRY(factor_reserve(h));
     if (want[BLK_DUP_LIST]) EKF_TRY(dup_reserve(h, dup_cap));
     if (want[BLK_FUSE]) EKF_TRY(fuse_reserve(h));
     if (want[BLK_MATCH]) EKF_TRY(match_reserve(h, match_cap));
     if (want[BLK_GATE]) EKF_TRY(gate_reserve(h, gate_zcap, gate_ccap));
     if (want[BLK_ASSOC]) EKF_TRY(assoc_reserve(h));
+    if (want[BLK_ADD]) EKF_TRY(add_reserve(h, add_zcap));
     return EKF_OK;
 }
 
@@ -957,6 +959,120 @@ extern "C" int ekf_batch_associate_joint(ekf_handle h, const double *z, const do
     if (!h || !info_out) return set_error(EKF_ERR_BAD_ARG, "bad argument");
     const int rc = assoc_impl(h, filters_of(h, -1), z, R, valid, n_z, gate, joint_gate, max_branch, max_nodes, ids_out, d2_out, nearest_out, n_skipped_out, info_out);
     return rc < 0 ? rc : EKF_OK;
+}
+
+// ---- landmark initialisation ----------------------------------------------------------------------
+// The scratch of ekf_add_landmarks (ekf_rewrite.hip: AddScratch).  It follows the longest list a call has brought, not the capacity:
+// one block for 64 additions per filter at the first call that adds, replaced by one twice the size until the list fits; ekf_reserve
+// builds it again as large as it was.
+static int add_reserve(ekf_batch *h, int n_meas) {
+    AddScratch &as = h->add;
+    const int zcap = plan_add_zcap(as.zcap, n_meas);
+    DevBlock &blk = h->kept[BLK_ADD];
+    if (blk.p && zcap == as.zcap) return EKF_OK;
+    const size_t B = (size_t)h->dv.B, ntab = B * add_tab_stride(zcap), nops = B * zcap * 8;
+    EKF_TRY(block_alloc(h, &blk, (ntab + nops) * sizeof(double), /*zero*/ true));
+    as.tab = (double *)blk.p;
+    as.ops = as.tab + ntab;
+    as.zcap = zcap;
+    return EKF_OK;
+}
+
+// The filters f, filter f.b0 + k with the n_z measurements at z + k * n_z * 2 and R + k * n_z * 4, of which add + k * n_z selects
+// (the caller has run plan_add_args).  Nothing selected anywhere: the counts from the mirror, the window stays open.  Else the
+// join's order: settle, the room (one filter without it ends the call: not sticky, nothing has run), the table up in one copy, the
+// three kernels on the chain stream (ekf_rewrite.hip), in place in the settled buffer in either pipeline mode, and the end of the
+// rewrite.  ids_out [nb][n_z] (may be null), n_out [nb].
+static int add_impl(ekf_batch *h, Filters f, const double *z, const double *R, const unsigned char *add, int n_z, int *ids_out, int *n_out) {
+    const int b0 = f.b0, nb = f.nb;
+    const int most = plan_gate_most(add, n_z, nb);
+    HIP_TRY(hipSetDevice(h->device));
+    if (most == 0) {  // nothing to do: the window stays open
+        EKF_TRY(refresh_bounds(h, false));
+        for (size_t q = 0; ids_out && q < (size_t)nb * (n_z > 0 ? n_z : 0); q++) ids_out[q] = -1;
+        for (int k = 0; k < nb; k++) n_out[k] = h->h_int[b0 + k];
+        return EKF_OK;
+    }
+    // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
+    // every deferred slot folded, both streams idle
+    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
+    EkfDev &dv = h->dv;
+    const int zcap = plan_add_zcap(h->add.zcap, most);
+    const AddTable tab = plan_add_table(z, R, add, n_z, nb, zcap);
+    EKF_TRY(set_error(plan_add_room(counts_of(h, b0), tab.cnt.data(), b0, nb, dv.Ncap, "add")));
+    EKF_TRY(add_reserve(h, most));
+    const AddScratch as = h->add;
+    std::vector<int> ids((size_t)nb * (n_z > 0 ? n_z : 0)), n_new((size_t)nb);
+    int nt, m_hi;
+    plan_add_ids(tab, counts_of(h, b0), n_z, nb, zcap, ids.data(), n_new.data(), &nt, &m_hi);
+    hipStream_t s = h->s_chain;
+    struct Drain {  // the asynchronous copy uses the pageable table above: a return with it in flight waits for the stream first
+        hipStream_t s;
+        ~Drain() { (void)hipStreamSynchronize(s); }
+    } drain{s};
+    HIP_TRY(hipMemcpyAsync(as.tab + (size_t)b0 * add_tab_stride(zcap), tab.tab.data(), sizeof(double) * tab.tab.size(), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_add_vec, dim3((unsigned)cdiv(m_hi, 64), (unsigned)nb), dim3(64), 0, s, dv, as, b0);
+    if (nt > 0) hipLaunchKernelGGL(k_add_tiles, dim3((unsigned)nt, (unsigned)nb), dim3(256), 0, s, dv, h->win.buf_in, as, b0);
+    hipLaunchKernelGGL(k_add_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, as, b0);
+    EKF_TRY(finish_rewrite(h, b0, nb, /*rearm*/ true, nullptr, 0, /*flip_buf*/ false));
+    if (ids_out && !ids.empty()) memcpy(ids_out, ids.data(), sizeof(int) * ids.size());
+    for (int k = 0; k < nb; k++) n_out[k] = n_new[k];
+    return EKF_OK;
+}
+
+extern "C" int ekf_add_landmarks(ekf_handle h, int index, const double *z, const double *R, const unsigned char *add, int n_z, int *ids_out) {
+    if (!h || index < 0) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    EKF_TRY(set_error(plan_add_args(z, R, add, n_z, index, h->dv.B, nullptr)));
+    int n;
+    EKF_TRY(add_impl(h, filters_of(h, index), z, R, add, n_z, ids_out, &n));
+    return n;
+}
+
+extern "C" int ekf_batch_add_landmarks(ekf_handle h, const double *z, const double *R, const unsigned char *add, int n_z, int *ids_out, int *n_out) {
+    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
+    EKF_TRY(set_error(plan_add_args(z, R, add, n_z, -1, h->dv.B, n_out)));
+    return add_impl(h, filters_of(h, -1), z, R, add, n_z, ids_out, n_out);
+}
+
+// ---- the scan step --------------------------------------------------------------------------------
+// ekf_associate_joint, ekf_update_matched and ekf_add_landmarks of one scan as one call: assoc_impl at the entry state (ids and the
+// filter's own gate per measurement), the kinds (plan_joint_kinds), the room for the New ones -- nothing has been applied yet --,
+// match_impl with the pairings, add_impl with the New ones at the state the matched step left.  Every step is the public call's own
+// implementation with the public call's arguments: the same bits.
+static int update_joint_impl(ekf_batch *h, Filters f, const double *z, const double *R, const unsigned char *valid, int n_z, double gate, const double *joint_gate,
+                             int max_branch, long long max_nodes, int *ids_out, int *kind_out, double *d2_out, ekf_assoc *info_out, int *n_out) {
+    const int b0 = f.b0, nb = f.nb;
+    const size_t all = (size_t)nb * (n_z > 0 ? n_z : 0);
+    std::vector<ekf_decision> near(all);
+    int rc = assoc_impl(h, f, z, R, valid, n_z, gate, joint_gate, max_branch, max_nodes, ids_out, nullptr, near.data(), nullptr, info_out);
+    if (rc < 0) return rc;
+    std::vector<int> kind(all), n_add((size_t)nb, 0), applied((size_t)nb, 0), new_ids(all, -1);
+    std::vector<unsigned char> is_new(all);
+    plan_joint_kinds(ids_out, near.data(), valid, n_z, nb, kind.data(), is_new.data());
+    for (int k = 0; k < nb; k++)
+        for (int q = 0; q < n_z; q++) n_add[k] += is_new[(size_t)k * n_z + q];
+    EKF_TRY(set_error(plan_add_room(counts_of(h, b0), n_add.data(), b0, nb, h->dv.Ncap, "update")));  // (assoc_impl has refreshed the counts)
+    rc = match_impl(h, f, z, R, ids_out, n_z, applied.data(), d2_out);
+    if (rc < 0) return rc;
+    rc = add_impl(h, f, z, R, is_new.data(), n_z, new_ids.data(), n_out);
+    if (rc < 0) return rc;
+    plan_joint_merge(applied.data(), new_ids.data(), n_z, nb, ids_out, kind.data());
+    if (kind_out && all) memcpy(kind_out, kind.data(), sizeof(int) * all);
+    return EKF_OK;
+}
+
+extern "C" int ekf_update_joint(ekf_handle h, int index, const double *z, const double *R, int n_z, double gate, const double *joint_gate, int max_branch,
+                                long long max_nodes, int *ids_out, int *kind_out, double *d2_out, ekf_assoc *info_out) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    int n;
+    EKF_TRY(update_joint_impl(h, filters_of(h, index), z, R, nullptr, n_z, gate, joint_gate, max_branch, max_nodes, ids_out, kind_out, d2_out, info_out, &n));
+    return n;
+}
+
+extern "C" int ekf_batch_update_joint(ekf_handle h, const double *z, const double *R, const unsigned char *valid, int n_z, double gate, const double *joint_gate,
+                                      int max_branch, long long max_nodes, int *ids_out, int *kind_out, double *d2_out, ekf_assoc *info_out, int *n_out) {
+    if (!h || !info_out || !n_out) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return update_joint_impl(h, filters_of(h, -1), z, R, valid, n_z, gate, joint_gate, max_branch, max_nodes, ids_out, kind_out, d2_out, info_out, n_out);
 }
 
 extern "C" int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max) {

@@ -2,8 +2,8 @@
 // hands in and the tables the kernels of ekf_rewrite.hip, ekf_extract.hip, ekf_pairs.hip, ekf_fuse.hip, ekf_match.hip and ekf_gate.hip read.  No HIP call and no
 // handle in here: landmark counts come in as plain arrays, n_lm[k] = landmarks of the k-th filter of the call, whose number in its
 // handle is b0 + k (error texts name that number).  A check reports a status and a text; the caller hands both to set_error.
-// tests/cpp/map_plan_check.cpp, tests/cpp/match_plan_check.cpp, tests/cpp/gate_plan_check.cpp and tests/cpp/assoc_plan_check.cpp run
-// all of it on the CPU.
+// tests/cpp/map_plan_check.cpp, tests/cpp/match_plan_check.cpp, tests/cpp/gate_plan_check.cpp, tests/cpp/assoc_plan_check.cpp and
+// tests/cpp/add_plan_check.cpp run all of it on the CPU.
 #pragma once
 #include <math.h>
 #include <stdarg.h>
@@ -48,6 +48,13 @@ inline int most_landmarks(const int *n_lm, int nb) { return nb > 0 ? std::max(0,
 inline PlanStatus plan_no_room(int filter, int n, int joined, int Ncap, const char *verb) {
     if (joined < 0) return plan_fail(EKF_ERR_CAPACITY, "filter %d: %d landmarks do not fit capacity_landmarks = %d (ekf_reserve, then %s again)", filter, n, Ncap, verb);
     return plan_fail(EKF_ERR_CAPACITY, "filter %d: %d + %d landmarks do not fit capacity_landmarks = %d (ekf_reserve, then %s again)", filter, n, joined, Ncap, verb);
+}
+
+// z and R of entry `at` of a call's measurement lists (z [..][2], R [..][4]) are finite: the check of every call that takes such lists.
+inline bool plan_entry_finite(const double *z, const double *R, size_t at) {
+    bool finite = __builtin_isfinite(z[2 * at]) && __builtin_isfinite(z[2 * at + 1]);
+    for (int e = 0; e < 4; e++) finite = finite && __builtin_isfinite(R[4 * at + e]);
+    return finite;
 }
 
 // ---- id lists (ekf_extract_map, ekf_get_submap) ---------------------------------------------------------------------------------
@@ -203,9 +210,7 @@ inline PlanStatus plan_match_values(const double *z, const double *R, const int 
             if (ids[at] < -1) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, measurement %d: id %d (a landmark, or -1 to skip)", b0 + k, q, ids[at]);
             if (ids[at] < 0) continue;
             kept++;
-            bool finite = __builtin_isfinite(z[2 * at]) && __builtin_isfinite(z[2 * at + 1]);
-            for (int e = 0; e < 4; e++) finite = finite && __builtin_isfinite(R[4 * at + e]);
-            if (!finite) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, measurement %d: z or R is not finite", b0 + k, q);
+            if (!plan_entry_finite(z, R, at)) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, measurement %d: z or R is not finite", b0 + k, q);
         }
         if (limit >= 0 && kept > limit) return plan_fail(EKF_ERR_BAD_ARG, "filter %d: %d measurements in one hypothesis (at most %d)", b0 + k, kept, limit);
     }
@@ -261,9 +266,7 @@ inline PlanStatus plan_gate_args(const double *z, const double *R, const unsigne
         for (int q = 0; q < n_z; q++) {
             const size_t at = (size_t)k * n_z + q;
             if (valid && !valid[at]) continue;
-            bool finite = __builtin_isfinite(z[2 * at]) && __builtin_isfinite(z[2 * at + 1]);
-            for (int e = 0; e < 4; e++) finite = finite && __builtin_isfinite(R[4 * at + e]);
-            if (!finite) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, measurement %d: z or R is not finite", b0 + k, q);
+            if (!plan_entry_finite(z, R, at)) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, measurement %d: z or R is not finite", b0 + k, q);
         }
     return {};
 }
@@ -426,6 +429,98 @@ inline void plan_assoc_scatter(const AssocTable &t, const int *ids, const double
             ids_out[to] = id;
             if (d2_out) d2_out[to] = d2[(size_t)k * ld_d2 + j];
             j++;
+        }
+    }
+}
+
+// ---- landmark initialisation (ekf_add_landmarks, the end of ekf_update_joint) -----------------------------------------------------
+// The lists of nb filters, filter k's n_z measurements at z + k * n_z * 2 and R + k * n_z * 4, entry q added unless
+// add[k * n_z + q] == 0 (add == nullptr: every entry).  Checked before the handle is touched: the filter (index, one of B, or -1: the
+// batch form, which needs n_out), n_z, the pointers, z and R of every selected entry finite.
+inline PlanStatus plan_add_args(const double *z, const double *R, const unsigned char *add, int n_z, int index, int B, const int *n_out) {
+    if (index < -1 || index >= B) return plan_fail(EKF_ERR_BAD_ARG, "filter %d is not one of the handle's %d", index, B);
+    if (index < 0 && !n_out) return plan_fail(EKF_ERR_BAD_ARG, "n_out is null");
+    if (n_z < 0) return plan_fail(EKF_ERR_BAD_ARG, "negative measurement count");
+    if (n_z > 0 && (!z || !R)) return plan_fail(EKF_ERR_BAD_ARG, "a null list with n_z > 0");
+    const int b0 = index < 0 ? 0 : index, nb = index < 0 ? B : 1;
+    for (int k = 0; k < nb; k++)
+        for (int q = 0; q < n_z; q++) {
+            const size_t at = (size_t)k * n_z + q;
+            if (add && !add[at]) continue;
+            if (!plan_entry_finite(z, R, at)) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, measurement %d: z or R is not finite", b0 + k, q);
+        }
+    return {};
+}
+// The entries a table holds for a longest list of `most` when the handle's holds `have`: at least 64, doubled until the list fits.
+inline int plan_add_zcap(int have, int most) {
+    int zcap = have > 64 ? have : 64;
+    while (zcap < most) zcap *= 2;
+    return zcap;
+}
+// The table k_add_vec and k_add_tiles read (AddScratch::tab of the call's filters), ONE block so that one copy carries it: nb records
+// of add_tab_stride(zcap) doubles (ekf_device.h), record k = {count, 0, then zcap entries {z_x, z_y, R00, R10, R01, R11}} with the
+// entries that are not added left out; cnt [nb] = the counts again, src [nb][zcap] = the caller's index of each entry (increasing).
+struct AddTable {
+    std::vector<double> tab;
+    std::vector<int> cnt, src;
+};
+inline AddTable plan_add_table(const double *z, const double *R, const unsigned char *add, int n_z, int nb, int zcap) {
+    AddTable t;
+    const size_t stride = add_tab_stride(zcap);
+    t.tab.assign((size_t)nb * stride, 0.0), t.cnt.assign((size_t)nb, 0), t.src.assign((size_t)nb * zcap, -1);
+    for (int k = 0; k < nb; k++) {
+        for (int q = 0; q < n_z; q++) {
+            const size_t at = (size_t)k * n_z + q;
+            if ((add && !add[at]) || t.cnt[k] >= zcap) continue;
+            double *e = t.tab.data() + (size_t)k * stride + 2 + 6 * (size_t)t.cnt[k];
+            e[0] = z[2 * at], e[1] = z[2 * at + 1];
+            for (int c = 0; c < 4; c++) e[2 + c] = R[4 * at + c];
+            t.src[(size_t)k * zcap + t.cnt[k]++] = q;
+        }
+        t.tab[(size_t)k * stride] = (double)t.cnt[k];
+    }
+    return t;
+}
+// Room for every filter's additions (n_lm[k] landmarks now, cnt[k] more), or the join's refusal: one filter without room ends the call.
+inline PlanStatus plan_add_room(const int *n_lm, const int *cnt, int b0, int nb, int Ncap, const char *verb) {
+    for (int k = 0; k < nb; k++)
+        if (n_lm[k] + cnt[k] > Ncap) return plan_no_room(b0 + k, n_lm[k], cnt[k], Ncap, verb);
+    return {};
+}
+// What the caller gets back: ids_out [nb][n_z] (may be null) = the new landmark's number, n_lm[k] + its place among the added, -1
+// for the others; n_new [nb] = the new counts.  *nt / *most = the most tiles (join_tile_count) / additions of a filter.
+inline void plan_add_ids(const AddTable &t, const int *n_lm, int n_z, int nb, int zcap, int *ids_out, int *n_new, int *nt, int *most) {
+    *nt = 0, *most = 0;
+    for (size_t q = 0; ids_out && q < (size_t)nb * (n_z > 0 ? n_z : 0); q++) ids_out[q] = -1;
+    for (int k = 0; k < nb; k++) {
+        for (int q = 0; ids_out && q < t.cnt[k]; q++) ids_out[(size_t)k * n_z + t.src[(size_t)k * zcap + q]] = n_lm[k] + q;
+        n_new[k] = n_lm[k] + t.cnt[k];
+        *nt = std::max(*nt, join_tile_count(n_lm[k], t.cnt[k])), *most = std::max(*most, t.cnt[k]);
+    }
+}
+
+// ---- the scan step (ekf_update_joint) ---------------------------------------------------------------------------------------------
+// The kinds of a scan from the search's result: ids [nb][n_z] (ekf_associate_joint's ids_out) and near [nb][n_z] (its nearest_out).
+// kind [nb][n_z]: a masked entry 0, a paired one EKF_DECISION_OLD, an unpaired one EKF_DECISION_NEW iff the filter's own gate says
+// New at the entry state, else EKF_DECISION_IGNORE; is_new [nb][n_z] = the mask ekf_add_landmarks takes.
+inline void plan_joint_kinds(const int *ids, const ekf_decision *near, const unsigned char *valid, int n_z, int nb, int *kind, unsigned char *is_new) {
+    for (size_t at = 0; at < (size_t)nb * (n_z > 0 ? n_z : 0); at++) {
+        is_new[at] = 0;
+        if (valid && !valid[at]) kind[at] = 0;
+        else if (ids[at] >= 0) kind[at] = EKF_DECISION_OLD;
+        else if (near[at].decision == EKF_DECISION_NEW) kind[at] = EKF_DECISION_NEW, is_new[at] = 1;
+        else kind[at] = EKF_DECISION_IGNORE;
+    }
+}
+// ... and after the matched step: filter k applied its first applied[k] pairings; the later ones (a round that was not positive
+// definite, and everything behind it) become EKF_DECISION_IGNORE with id -1.  Then the added landmarks' numbers (new_ids, -1: none).
+inline void plan_joint_merge(const int *applied, const int *new_ids, int n_z, int nb, int *ids, int *kind) {
+    for (int k = 0; k < nb; k++) {
+        int paired = 0;
+        for (int q = 0; q < n_z; q++) {
+            const size_t at = (size_t)k * n_z + q;
+            if (kind[at] == EKF_DECISION_OLD && paired++ >= applied[k]) kind[at] = EKF_DECISION_IGNORE, ids[at] = -1;
+            if (kind[at] == EKF_DECISION_NEW) ids[at] = new_ids[at];
         }
     }
 }

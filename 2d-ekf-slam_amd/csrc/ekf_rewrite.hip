@@ -616,3 +616,130 @@ __global__ void k_join_finish(EkfDev dv, JoinSrc sv, Rot2 one, const double *rot
     dv.n_lm[bd] = n_lm;
     settle_meta(dv, bd, n_lm, x, &p[0][0], 3);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Landmark initialisation (ekf_add_landmarks): the m measurements of a table become landmarks Ng .. Ng + m - 1, all linearised at
+// the entry state -- the join of a source x = (0, 0, 0, z_0, z_1, ..), P_s = blockdiag(0_3, R_0, R_1, ..) (u = 0, so G_R = I: the
+// pose, P_RR and every old row stay untouched) without the source.  With C = Rot(phi), h_k = C J z_k, G_k = [I | h_k]:
+//   L_k = p + C z_k,   P[k, robot] = G_k P_RR,   P[k, old m] = G_k P_R,m,   P[k, l] = G_k P_RR G_l^T + [k == l] C R_k C^T.
+// Per landmark-space row i' the tile kernel needs the join's four doubles {w (3), h}: an old row's w = P_iR; a new row's h = h_k[e]
+// and w = P_RR[e] + h P_RR[2].  Element (i', j'), j' new, is w_i[f] + w_i[2] h_j (f = j' & 1).
+// Launch order on the chain stream, every slot folded in and both streams idle:
+//   k_add_vec (a thread per new landmark: x, the three robot-row entries, D, and its two operand rows into AddScratch::ops; reads
+//   the pose and P_RR)  ->  k_add_tiles (the tiles that hold a new column, join_tile_ij; reads the old robot rows, the operand rows
+//   and the new D)  ->  k_add_finish (count, bookkeeping, host mirror).  Nothing that is read is ever written: the pose, P_RR and the
+//   old landmarks' robot rows stay as they are.  cos / sin of the heading are taken on the device, sincos(x[2]) as the chain kernels
+//   take them, in k_add_vec alone: the tiles see them through the operand rows.
+// The table (ekf_device.h: add_tab_stride) and the operand rows live in a scratch the handle keeps; a record's count is a double.
+// The launch covers filters b0 + blockIdx.y.
+// ---------------------------------------------------------------------------------------------
+struct AddScratch {
+    double *tab;  // [B][add_tab_stride(zcap)]
+    double *ops;  // [B][zcap][2]{w0, w1, w2, h}
+    int zcap;
+};
+__device__ __forceinline__ const double *add_record(const AddScratch &as, int b) { return as.tab + (size_t)b * add_tab_stride(as.zcap); }
+
+__global__ __launch_bounds__(64) void k_add_vec(EkfDev dv, AddScratch as, int b0) {
+    const int b = b0 + blockIdx.y;
+    const double *rec = add_record(as, b);
+    const int m = (int)rec[0], Ng = dv.n_lm[b];
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    const int l = Ng + k;
+    if (k >= m || k >= as.zcap || l >= dv.Ncap) return;  // (the host has checked the room: no thread leaves here)
+    double *x = filt_x(dv, b);
+    double *R0 = filt_R(dv, b);
+    double s, c;
+    sincos(x[2], &s, &c);
+    const double *e = rec + 2 + 6 * (size_t)k;
+    const double zx = e[0], zy = e[1];
+    const double cx = c * zx - s * zy, cy = s * zx + c * zy;
+    const double h[2] = {-cy, cx};
+    double w[2][3];
+    for (int r = 0; r < 2; r++)
+        for (int j = 0; j < 3; j++) w[r][j] = R0[(size_t)r * dv.xs + j] + h[r] * R0[2 * (size_t)dv.xs + j];
+    const double rxy = 0.5 * (e[3] + e[4]);  // only the symmetric part of R enters (Update.cpp:193)
+    double d[4];
+    rot_block(Rot2{c, -s}, e[2], rxy, rxy, e[5], d);  // C R C^T
+    const double dxx = (w[0][0] + w[0][2] * h[0]) + d[0], dxy = (w[0][1] + w[0][2] * h[1]) + d[1], dyy = (w[1][1] + w[1][2] * h[1]) + d[3];
+    x[3 + 2 * l] = x[0] + cx, x[4 + 2 * l] = x[1] + cy;
+    for (int j = 0; j < 3; j++) R0[(size_t)j * dv.xs + 3 + 2 * l] = w[0][j], R0[(size_t)j * dv.xs + 4 + 2 * l] = w[1][j];
+    double *Dx = filt_D(dv, b);
+    Dx[l] = dxx, Dx[dv.dn + l] = dxy, Dx[2 * (size_t)dv.dn + l] = dyy;
+    double *op = as.ops + ((size_t)b * as.zcap + k) * 8;
+    for (int r = 0; r < 2; r++) *(double4_t *)(op + 4 * r) = (double4_t){w[r][0], w[r][1], w[r][2], h[r]};
+}
+
+// One workgroup per tile that holds a new column and filter, in place in Bm[buf], walked and stored as k_join_tiles walks its tiles
+// (reframe_item; join_where with m in place of the source's count classifies the blocks).  Old x old blocks of a straddling tile
+// are loaded and stored back unchanged, stale places included; the places below the diagonal of a diagonal tile get the transposed
+// upper value (the same expression, so the same bits) and a new landmark's own block the new D, as k_import stores them.
+__global__ __launch_bounds__(256) void k_add_tiles(EkfDev dv, int buf, AddScratch as, int b0) {
+    __shared__ double ops[128][4];  // [tile row | 64 + tile column]{w0, w1, w2, h}
+    const int b = b0 + blockIdx.y;
+    const int m = (int)add_record(as, b)[0], Ng = dv.n_lm[b];
+    if (m <= 0 || m > as.zcap || Ng + m > dv.Ncap) return;
+    int I, J;
+    if (!join_tile_ij(blockIdx.x, Ng >> 5, lm_tiles(Ng + m), &I, &J)) return;
+    const int tid = threadIdx.x;
+    if (tid < 128) {
+        const int ip = 64 * (tid < 64 ? I : J) + (tid & 63), l = ip >> 1;
+        double4_t op = {0.0, 0.0, 0.0, 0.0};  // (beyond the map)
+        if (l < Ng) {
+            const double *R0 = filt_R(dv, b);
+            op = (double4_t){R0[3 + ip], R0[(size_t)dv.xs + 3 + ip], R0[2 * (size_t)dv.xs + 3 + ip], 0.0};
+        } else if (l < Ng + m) {
+            op = *(const double4_t *)(as.ops + ((size_t)b * as.zcap + (l - Ng)) * 8 + 4 * (ip & 1));
+        }
+        *(double4_t *)&ops[tid][0] = op;
+    }
+    __syncthreads();
+    double *tp = filt_Bm(dv, buf, b) + bm_tile_base(dv.T, I, J);
+    const double *Dx = filt_D(dv, b);
+    ReframeItem it[2];
+    double o[2][2][4];  // [item][block]{(0,0), (0,1), (1,0), (1,1)}
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+        it[r] = reframe_item(r * 256 + tid);
+        const int lc = 32 * J + (it[r].col >> 1);
+        int lr[2], where[2];
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            lr[k] = 32 * I + (it[r].row[k] >> 1);
+            where[k] = join_where(Ng, m, lr[k] > lc ? lc : lr[k], lr[k] > lc ? lr[k] : lc);
+        }
+        double4_t v[2] = {{0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0}};
+        if (where[0] == JM_OLD || where[1] == JM_OLD) item_load(tp, it[r], v);
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            double *ob = o[r][k];
+            ob[0] = ob[1] = ob[2] = ob[3] = 0.0;  // beyond the new map
+            const bool swap = lr[k] > lc;         // (a diagonal tile's places below the diagonal)
+            if (where[k] == JM_OLD) {
+                item_block(v, k, ob);
+            } else if (where[k] == JM_D) {
+                const double xy = Dx[dv.dn + lc];
+                ob[0] = Dx[lc], ob[1] = xy, ob[2] = xy, ob[3] = Dx[2 * (size_t)dv.dn + lc];
+            } else if (where[k] == JM_ROBOT || where[k] == JM_BM) {
+                const int ri = swap ? 64 + it[r].col : it[r].row[k], ci = swap ? it[r].row[k] : 64 + it[r].col;
+                double g[2][2];
+                for (int e = 0; e < 2; e++)
+                    for (int f = 0; f < 2; f++) g[e][f] = ops[ri + e][f] + ops[ri + e][2] * ops[ci + f][3];
+                ob[0] = g[0][0], ob[3] = g[1][1];
+                ob[1] = swap ? g[1][0] : g[0][1], ob[2] = swap ? g[0][1] : g[1][0];
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; r++) item_store(tp, it[r], o[r]);
+}
+
+// Thread 0 of block blockIdx.x: the new landmark count and k_set_meta's bookkeeping and host mirror (pose and P_RR as they lie).
+__global__ void k_add_finish(EkfDev dv, AddScratch as, int b0) {
+    if (threadIdx.x != 0) return;
+    const int b = b0 + blockIdx.x;
+    const int m = (int)add_record(as, b)[0];
+    const int n_lm = dv.n_lm[b] + (m > 0 && m <= as.zcap && dv.n_lm[b] + m <= dv.Ncap ? m : 0);
+    dv.n_lm[b] = n_lm;
+    settle_meta(dv, b, n_lm, filt_x(dv, b), filt_R(dv, b), dv.xs);
+}

@@ -33,6 +33,7 @@ ABI_SYMBOLS = [
     "ekf_update_matched", "ekf_batch_update_matched", "ekf_joint_compat", "ekf_batch_joint_compat",
     "ekf_gate_candidates", "ekf_batch_gate_candidates",
     "ekf_associate_joint", "ekf_batch_associate_joint", "ekf_joint_gates",
+    "ekf_add_landmarks", "ekf_batch_add_landmarks", "ekf_update_joint", "ekf_batch_update_joint",
 ]
 
 
@@ -175,6 +176,12 @@ def load():
     L.ekf_batch_associate_joint.argtypes = [_H, _dp, _dp, _up, ctypes.c_int, ctypes.c_double, _dp, ctypes.c_int, ctypes.c_longlong, _ip, _dp,
                                             ctypes.POINTER(EkfDecision), _ip, ctypes.POINTER(EkfAssoc)]
     L.ekf_joint_gates.argtypes = [ctypes.c_double, _dp]
+    L.ekf_add_landmarks.argtypes = [_H, ctypes.c_int, _dp, _dp, _up, ctypes.c_int, _ip]
+    L.ekf_batch_add_landmarks.argtypes = [_H, _dp, _dp, _up, ctypes.c_int, _ip, _ip]
+    L.ekf_update_joint.argtypes = [_H, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_double, _dp, ctypes.c_int, ctypes.c_longlong, _ip, _ip, _dp,
+                                   ctypes.POINTER(EkfAssoc)]
+    L.ekf_batch_update_joint.argtypes = [_H, _dp, _dp, _up, ctypes.c_int, ctypes.c_double, _dp, ctypes.c_int, ctypes.c_longlong, _ip, _ip, _dp,
+                                         ctypes.POINTER(EkfAssoc), _ip]
     L.ekf_script_load.argtypes =[_H, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _up, _dp]
     L.ekf_script_run.argtypes = [_H, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.ekf_sync.argtypes = [_H]
@@ -707,15 +714,9 @@ class FilterBatch:
         out = [(buf[b, :min(int(found[b]), max_cand)].copy(), int(found[b]), near[b].copy(), skip[b].copy()) for b in range(nb)]
         return out if index is None else out[0]
 
-    def associate_joint(self, z, R, gate=9.21, joint_gate=None, max_branch=8, max_nodes=65536, index=0, valid=None):
-        """The joint-compatibility search of a scan on the device (ekf_associate_joint): the candidates of every measurement are
-        those gate_candidates lists at `gate` (the first max_branch of each), a hypothesis pairs every measurement with one of them
-        or nothing, every prefix of q pairings within joint_gate[q - 1] (None: joint_gates(0.99)); the result has the most
-        pairings, then the smallest joint distance, found by branch and bound within max_nodes expanded nodes.  Returns
-        (ids, d2, info, nearest, n_skipped): ids int32 [n_z] as update_matched takes them (-1: unpaired), d2 what joint_compat
-        gives for ids, info an ASSOC_DTYPE record (nodes, d2, n_paired, complete, n_candidates, n_dropped), nearest and n_skipped as
-        gate_candidates.  index=None: every filter in one launch sequence, leading batch axes, valid [batch][n_z] masks entries.
-        At most 32 valid measurements per filter.  The filter is only read; deferred slots are folded when something is searched."""
+    def _assoc_args(self, z, R, gate, joint_gate, max_branch, max_nodes, index, valid):
+        """The arguments of associate_joint / update_joint checked and laid out: (gate, joint gates or None, max_branch, max_nodes,
+        z, Rc, valid, n_z, filters of the call)."""
         gate, max_branch, max_nodes = float(gate), int(max_branch), int(max_nodes)
         if not gate >= 0.0:
             raise ValueError("gate must not be negative or NaN")
@@ -733,6 +734,18 @@ class FilterBatch:
         kept = np.full(nb, n_z) if valid is None else (valid != 0).sum(axis=-1)
         if int(np.max(kept, initial=0)) > ASSOC_MAX_MEAS:
             raise ValueError("a scan holds at most %d valid measurements" % ASSOC_MAX_MEAS)
+        return gate, jg, max_branch, max_nodes, z, Rc, valid, n_z, nb
+
+    def associate_joint(self, z, R, gate=9.21, joint_gate=None, max_branch=8, max_nodes=65536, index=0, valid=None):
+        """The joint-compatibility search of a scan on the device (ekf_associate_joint): the candidates of every measurement are
+        those gate_candidates lists at `gate` (the first max_branch of each), a hypothesis pairs every measurement with one of them
+        or nothing, every prefix of q pairings within joint_gate[q - 1] (None: joint_gates(0.99)); the result has the most
+        pairings, then the smallest joint distance, found by branch and bound within max_nodes expanded nodes.  Returns
+        (ids, d2, info, nearest, n_skipped): ids int32 [n_z] as update_matched takes them (-1: unpaired), d2 what joint_compat
+        gives for ids, info an ASSOC_DTYPE record (nodes, d2, n_paired, complete, n_candidates, n_dropped), nearest and n_skipped as
+        gate_candidates.  index=None: every filter in one launch sequence, leading batch axes, valid [batch][n_z] masks entries.
+        At most 32 valid measurements per filter.  The filter is only read; deferred slots are folded when something is searched."""
+        gate, jg, max_branch, max_nodes, z, Rc, valid, n_z, nb = self._assoc_args(z, R, gate, joint_gate, max_branch, max_nodes, index, valid)
         ids, d2 = np.full((nb, n_z), -1, dtype=np.int32), np.full((nb, n_z), np.nan)
         near, skip = np.zeros((nb, n_z), dtype=DECISION_DTYPE), np.zeros((nb, n_z), dtype=np.int32)
         info = np.zeros(nb, dtype=ASSOC_DTYPE)
@@ -746,6 +759,56 @@ class FilterBatch:
             return [(ids[b].copy(), d2[b].copy(), info[b].copy(), near[b].copy(), skip[b].copy()) for b in range(nb)]
         _chk(self.L.ekf_associate_joint(self.h, int(index), *ptrs, n_z, gate, jp, max_branch, max_nodes, *outs, ip))
         return ids[0], d2[0], info[0], near[0], skip[0]
+
+    def add_landmarks(self, z, R, add=None, index=0):
+        """Initialise landmarks from measurements on the device (ekf_add_landmarks): the entries of z [n_z][2], R [n_z][2][2] with
+        add[k] != 0 (None: all) become landmarks N, N + 1, .. in list order, all linearised at the entry state; pose, P_RR and every
+        old row stay bit for bit.  Returns (n_landmarks, ids): ids int32 [n_z], the new landmark's number or -1.  index=None: every
+        filter in one launch sequence (ekf_batch_add_landmarks), leading batch axes on z, R and add; returns (n_landmarks (batch,),
+        ids (batch, n_z)).  EkfError ERR_CAPACITY (not sticky, nothing changed) when a filter has no room: reserve(), add again."""
+        lead = (self.batch,) if index is None else ()
+        z, R = np.asarray(z, dtype=np.float64), np.asarray(R, dtype=np.float64)
+        if z.ndim != len(lead) + 2 or z.shape[:len(lead)] != lead or z.shape[-1] != 2:
+            raise ValueError("z must be [batch][n_z][2]" if lead else "z must be [n_z][2]")
+        n_z = z.shape[-2]
+        if R.size != z.size * 2:
+            raise ValueError("R must hold [n_z][2][2] values per filter for %d measurements" % n_z)
+        Rc = _f64(np.swapaxes(R.reshape(lead + (n_z, 2, 2)), -1, -2).reshape(lead + (n_z, 4)))  # column-major blocks
+        z = _f64(z)
+        if add is not None:
+            add = np.ascontiguousarray(np.asarray(add) != 0, dtype=np.uint8)
+            if add.shape != lead + (n_z,):
+                raise ValueError("add must be [batch][n_z]" if lead else "add must be [n_z]")
+        ids = np.full(lead + (n_z,), -1, dtype=np.int32)
+        ptrs = (_p(z), _p(Rc), add.ctypes.data_as(_up) if add is not None else None) if n_z else (None, None, None)
+        if index is None:
+            n = np.zeros(self.batch, dtype=np.int32)
+            _chk(self.L.ekf_batch_add_landmarks(self.h, *ptrs, n_z, ids.ctypes.data_as(_ip) if n_z else None, n.ctypes.data_as(_ip)))
+            return n, ids
+        n = _chk(self.L.ekf_add_landmarks(self.h, int(index), *ptrs, n_z, ids.ctypes.data_as(_ip) if n_z else None))
+        return n, ids
+
+    def update_joint(self, z, R, gate=9.21, joint_gate=None, max_branch=8, max_nodes=65536, index=0, valid=None):
+        """One scan with joint-compatibility data association as one call (ekf_update_joint): associate_joint at the entry state,
+        update_matched with the pairings, add_landmarks with the measurements the filter's own gate calls New -- at the state the
+        matched step left.  Arguments as associate_joint.  Returns (n_landmarks, ids, kinds, d2, info): ids int32 [n_z] the
+        landmark each measurement ended as (-1: none), kinds int32 [n_z] OLD / NEW / IGNORE (0: masked), d2 as update_matched, info
+        as associate_joint.  index=None: every filter, leading batch axes, valid [batch][n_z]; n_landmarks is (batch,).  Bit for bit
+        the three calls in sequence; counters and decision log are not involved."""
+        gate, jg, max_branch, max_nodes, z, Rc, valid, n_z, nb = self._assoc_args(z, R, gate, joint_gate, max_branch, max_nodes, index, valid)
+        ids, kinds, d2 = np.full((nb, n_z), -1, dtype=np.int32), np.zeros((nb, n_z), dtype=np.int32), np.full((nb, n_z), np.nan)
+        info = np.zeros(nb, dtype=ASSOC_DTYPE)
+        ptrs = (_p(z), _p(Rc)) if n_z else (None, None)
+        outs = (ids.ctypes.data_as(_ip), kinds.ctypes.data_as(_ip), _p(d2)) if n_z else (None,) * 3
+        ip = info.ctypes.data_as(ctypes.POINTER(EkfAssoc))
+        jp = _p(jg) if jg is not None else None
+        if index is None:
+            n = np.zeros(nb, dtype=np.int32)
+            vp = valid.ctypes.data_as(_up) if valid is not None and n_z else None
+            _chk(self.L.ekf_batch_update_joint(self.h, *ptrs, vp, n_z, gate, jp, max_branch, max_nodes, *outs, ip, n.ctypes.data_as(_ip)))
+            return n, ids, kinds, d2, info
+        n = _chk(self.L.ekf_update_joint(self.h, int(index), *ptrs, n_z, gate, jp, max_branch, max_nodes, *outs, ip))
+        return n, ids[0], kinds[0], d2[0], info[0]
 
     def joint_factor(self, index=0):
         """Diagnostic: the upper factor U (U^T U = P_LL) the last joint_consistency call left for filter `index`, dense (2N, 2N);
@@ -959,3 +1022,16 @@ class KalmanFilter:
         """The gate-passing landmarks of every measurement, the filter's own decision for each and the skip counts
         (FilterBatch.gate_candidates): (cands, n_found, nearest, n_skipped); nothing is applied."""
         return self._f.gate_candidates(z, R, gate, 0)
+
+    def add_landmarks(self, z, R, add=None):
+        """Initialise landmarks from measurements (FilterBatch.add_landmarks): (n_landmarks, ids)."""
+        out = self._f.add_landmarks(z, R, add, 0)
+        self._mirror()
+        return out
+
+    def update_joint(self, z, R, gate=9.21, joint_gate=None, max_branch=8, max_nodes=65536):
+        """One scan with joint-compatibility data association (FilterBatch.update_joint): (n_landmarks, ids, kinds, d2, info);
+        refreshes X, Y, Phi."""
+        out = self._f.update_joint(z, R, gate, joint_gate, max_branch, max_nodes, 0)
+        self._mirror()
+        return out

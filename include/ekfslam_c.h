@@ -390,8 +390,8 @@ int ekf_batch_fuse_landmarks(ekf_handle h, const ekf_dup_pair *pairs /*[batch][l
  * ids[k] (0-based, as in ekf_remove_landmarks); ids[k] == -1: no measurement, skipped (its z and R are not looked at).  z and R use
  * the layouts of ekf_batch_update.  The filter's gates and condition limit are NOT consulted -- the decision is the caller's
  * (joint-compatibility search over ekf_joint_compat below, global nearest neighbour, known ids) -- and counters and decision log
- * stay as they are: book NIS from d2_out if you want it.  (To force a NEW landmark no call is needed: a fresh one-landmark filter
- * with x = (0, 0, 0, z), P = blockdiag(0_3, R) handed to ekf_join_map is Update.cpp:155-177.)
+ * stay as they are: book NIS from d2_out if you want it.  (To force a NEW landmark: ekf_add_landmarks below, Update.cpp:155-177 for any number of
+ * measurements in one call; ekf_update_joint is search, this update and the additions together.)
  * The non-skipped measurements run in rounds of at most ekf_window(h) in list order.  A round with measurements k = 0..m-1 of
  * landmarks i_k is ONE update, every measurement linearised at the round's entry state (C = Rot(phi), J = [[0,-1],[1,0]]):
  *     dp_k = L_ik - p;   H_R,k = [-C^T | -C^T J dp_k]  (Update.cpp:112-114);   H_L = C^T;   d_k = C^T dp_k - z_k  (= -res);
@@ -547,6 +547,65 @@ int ekf_batch_associate_joint(ekf_handle h, const double *z /*[batch][n_z][2]*/,
 /* out[q - 1], q = 1 .. 32: the `confidence` quantile of chi-square with 2 q degrees of freedom, from the closed form for even dof,
  * CDF(x) = 1 - exp(-x / 2) sum_{i < q} (x / 2)^i / i!, by bisection on the host.  A confidence outside (0, 1): EKF_ERR_BAD_ARG. */
 int ekf_joint_gates(double confidence, double *out /*[32]*/);
+
+/* Growing the map without the filter's own gate: the m measurements with add[k] != 0 (NULL: all n_z) become landmarks N, N + 1, ..,
+ * N + m - 1 in list order, on the device, ALL linearised at the entry state.  z and R use the layouts of ekf_batch_update.  With
+ * p, phi, P the settled entry state, C = Rot(phi), J = [[0,-1],[1,0]]:
+ *     h_k = C J z_k = (-(s z_x + c z_y), c z_x - s z_y);   G_k = [I_2 | h_k]  (2 x 3; = -C H_R of Update.cpp:163-166);
+ *     L_new,k = p + C z_k  (Update.cpp:155);   P[new k, robot] = G_k P_RR  (:169);   P[new k, old m] = G_k P_R,m;
+ *     P[new k, new l] = G_k P_RR G_l^T + [k == l] C R_k C^T  (:168; the k != l term is what the reference's sequential New leaves
+ *     between two landmarks initialised from one pose).
+ * Only the symmetric part of R_k enters, xy = (R01 + R10) / 2 (Update.cpp:193).  cos phi and sin phi are taken once per call and
+ * filter on the device (sincos of x[2], as the chain kernels take them).  This is ekf_join_map of the source x = (0, 0, 0, z_0, ..),
+ * P = blockdiag(0_3, R_0, ..) without the source: no second handle, no dense matrix through the host, three launches whatever m,
+ * and (N + m) m blocks written -- only the tile columns from N / 32 on are touched.
+ * The pose, P_RR, every old row and column, the counters and the decision log stay bit for bit; P stays bitwise symmetric (one home
+ * per element); the host mirror shows the new count; every device buffer ends as ekf_set_state of the result would leave it.
+ * ids_out[k] (may be NULL): the new landmark's number, -1 for an entry that was not added.
+ * As ekf_join_map: deferred slots are folded first, a streaming launch is stopped (immediate-mode calls stream again afterwards),
+ * the blocks are written in place into the settled buffer in either pipeline mode, a sticky EKF_ERR_TIMEOUT / EKF_ERR_CAPACITY is
+ * returned unchanged with nothing modified, and the call synchronises.  No atomics, one writer per value: the same bits on every
+ * call, and filter b of the batch form gets the bits of the one-filter call on b.
+ * EKF_ERR_BAD_ARG, found on the host before the handle is touched: n_z < 0, a NULL z or R with n_z > 0, a non-finite z or R of a
+ * selected entry, a NULL n_out (batch form), an index out of range.  n_z == 0, or nothing selected in any filter, is a no-op that
+ * leaves an open window open, returns the counts from the host mirror and does not look at a sticky status (as the no-ops of
+ * ekf_update_matched and ekf_fuse_landmarks).  N + m > ekf_capacity(h): EKF_ERR_CAPACITY with the exported state unchanged (deferred slots have
+ * been folded nonetheless); it is NOT sticky (no kernel ran): call ekf_reserve and add again.
+ * ekf_add_landmarks returns the new landmark count N + m or a negative status; the batch form takes filter b's lists at
+ * z + b * n_z * 2, R + b * n_z * 4, add + b * n_z, writes the counts to n_out[b] and returns EKF_OK or a negative status; one
+ * filter without room fails the whole call with nothing modified.
+ * The scratch -- the measurement table (48 bytes per addition, for at least 64 per filter) and the new rows' operands (64 bytes
+ * each) -- is allocated at the first call that adds, kept on the handle (ekf_device_bytes counts it, ekf_reserve builds it again)
+ * and freed by ekf_destroy. */
+int ekf_add_landmarks(ekf_handle h, int index, const double *z /*[n_z][2]*/, const double *R /*[n_z][4], column-major 2x2*/,
+                      const unsigned char *add /*[n_z] or NULL = all*/, int n_z, int *ids_out /*[n_z] or NULL*/);
+int ekf_batch_add_landmarks(ekf_handle h, const double *z /*[batch][n_z][2]*/, const double *R /*[batch][n_z][4]*/,
+                            const unsigned char *add /*[batch][n_z] or NULL*/, int n_z, int *ids_out /*[batch][n_z] or NULL*/,
+                            int *n_out /*[batch]*/);
+
+/* The scan step of a JCBB-SLAM loop as one call: gate, search, joint update, initialisation.  In this order:
+ *   1. ekf_associate_joint at the entry state with the same z, R, n_z, gate, joint_gate, max_branch, max_nodes (and valid).
+ *   2. The kinds: a paired measurement is EKF_DECISION_OLD; an unpaired valid one is EKF_DECISION_NEW iff the filter's own gate
+ *      says New for it at the entry state (ekf_associate_joint's nearest_out: no kept landmark, or the individual arg-min above
+ *      gamma_max); every other unpaired valid one is EKF_DECISION_IGNORE (near something, not jointly compatible); masked: 0.
+ *   3. The room: N + #NEW > ekf_capacity(h) returns EKF_ERR_CAPACITY, not sticky, with nothing applied (the search only reads).
+ *   4. ekf_update_matched with the pairings, then ekf_add_landmarks with the NEW ones AT THE STATE THE MATCHED STEP LEFT: update
+ *      first, then augment with the posterior pose.  A paired measurement whose round was not applied (ekf_update_matched's rule
+ *      for an S that is not positive definite) is reported EKF_DECISION_IGNORE with id -1 and NaN d2; the additions still run.
+ * ids_out[k]: the landmark measurement k ended as -- an id below the entry count: OLD; from the entry count on: NEW; -1 otherwise.
+ * kind_out (may be NULL): the EKF_DECISION_* codes above.  d2_out (may be NULL): that of ekf_update_matched.  info_out: that of
+ * ekf_associate_joint.  State and outputs are bit for bit those of the three public calls made in sequence with these arguments
+ * (the same implementations run).  Counters and decision log stay as they are, as for ekf_update_matched: book NIS from d2_out.
+ * Limits and refusals are those of ekf_associate_joint (at most 32 valid measurements per filter), then those of the two others;
+ * ekf_update_joint returns the new landmark count, the batch form writes it to n_out[b] (NULL: EKF_ERR_BAD_ARG, as a NULL info_out)
+ * and returns EKF_OK; a negative status otherwise. */
+int ekf_update_joint(ekf_handle h, int index, const double *z /*[n_z][2]*/, const double *R /*[n_z][4]*/, int n_z, double gate,
+                     const double *joint_gate /*[32] or NULL*/, int max_branch, long long max_nodes, int *ids_out /*[n_z]*/,
+                     int *kind_out /*[n_z] or NULL*/, double *d2_out /*[n_z] or NULL*/, ekf_assoc *info_out /* may be NULL */);
+int ekf_batch_update_joint(ekf_handle h, const double *z /*[batch][n_z][2]*/, const double *R /*[batch][n_z][4]*/,
+                           const unsigned char *valid /*[batch][n_z] or NULL*/, int n_z, double gate, const double *joint_gate /*[32] or NULL*/,
+                           int max_branch, long long max_nodes, int *ids_out /*[batch][n_z]*/, int *kind_out /*[batch][n_z] or NULL*/,
+                           double *d2_out /*[batch][n_z] or NULL*/, ekf_assoc *info_out /*[batch]*/, int *n_out /*[batch]*/);
 
 /* ---- device-resident step scripts (benchmarks, Monte-Carlo runs) ------------------------------
  * A script is `steps` steps; step s of filter b is
