@@ -26,6 +26,7 @@
 #include "ekf_device.h"
 #include "ekf_geometry.h"
 #include "ekf_map_plan.h"
+#include "ekf_map_scratch.h"
 #include "ekf_window_plan.h"
 
 // single translation unit: the kernels are compiled together with their launch sites
@@ -86,13 +87,81 @@ struct DevTmp {
     }
 };
 
+// Asynchronous copies between the device and pageable host memory -- a local std::vector, a caller's buffer -- on one stream.  Every
+// enqueue goes through the guard and arms it; wait() is stream_wait and disarms; a return with a copy still in flight (HIP_TRY /
+// EKF_TRY past a later failure) waits for the stream in the destructor, before the buffers go.  Declare it BEHIND the buffers it
+// guards.  A success path pays nothing: it ends disarmed, by wait() or, where something else has waited for the stream, by waited().
+static hipError_t stream_wait(hipStream_t s);
+struct HostCopies {
+    hipStream_t s;
+    bool armed = false;
+    explicit HostCopies(hipStream_t stream) : s(stream) {}
+    HostCopies(const HostCopies &) = delete;
+    HostCopies &operator=(const HostCopies &) = delete;
+    ~HostCopies() {
+        if (armed) (void)hipStreamSynchronize(s);
+    }
+    hipError_t copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+        armed = true;
+        return hipMemcpyAsync(dst, src, bytes, kind, s);
+    }
+    hipError_t copy2d(void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height, hipMemcpyKind kind) {
+        armed = true;
+        return hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, kind, s);
+    }
+    template <typename T>
+    hipError_t upload(DevTmp<T> *tmp, const T *src, size_t count) {
+        armed = true;
+        return tmp->upload(src, count, s);
+    }
+    hipError_t wait() {
+        const hipError_t e = stream_wait(s);
+        armed = false;
+        return e;
+    }
+    void waited() { armed = false; }  // the stream has been waited for behind the last enqueue (finish_rewrite, read_back_dense)
+};
+
 // Device scratch that a handle keeps from the first call of an operation on (ekf_map_api.hip), counted in ekf_device_bytes while it
-// lives: block_alloc / block_release; ekf_destroy releases every block, ekf_reserve has those that existed built again.
+// lives: block_alloc; ekf_destroy releases every block, ekf_reserve has those that existed built again.
 struct DevBlock {
     void *p = nullptr;
     size_t bytes = 0;
 };
 enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_MATCH, BLK_GATE, BLK_GATE_LIST, BLK_ASSOC, BLK_ADD, BLK_COUNT };
+
+// Everything the map operations keep on a handle: the scratch structs their kernels take (ekf_map_scratch.h: arrays and layout) and
+// the allocations behind them.  A block is built by the first call that needs it (block_build in ekf_map_api.hip) and kept.
+//
+//   block          struct  built by the first                          follows                               zeroed
+//   BLK_FACTOR     fac     ekf_joint_consistency                       the capacity                          yes
+//   BLK_DUP        dup     ekf_find_duplicates                         the capacity                          yes
+//   BLK_DUP_LIST   dup     ekf_find_duplicates                         the pairs asked for or found (cap,    no
+//                                                                      from 256)
+//   BLK_FUSE       fuse    ekf_fuse_landmarks, ekf_update_matched      the capacity                          yes
+//   BLK_MATCH      match   ekf_update_matched, ekf_joint_compat,       the longest list brought (zcap,       yes
+//                          ekf_associate_joint that searches           from 64)
+//   BLK_GATE       gate    ekf_gate_candidates with a valid entry      the longest scan brought (zcap, from  yes
+//                                                                      64) and the capacity (npart)
+//   BLK_GATE_LIST  gate    ekf_gate_candidates that hands pairs out,   the pairs asked for or found (ccap,   no
+//                          ekf_associate_joint                         from 256)
+//   BLK_ASSOC      assoc   ekf_associate_joint that searches           the batch alone                       yes
+//   BLK_ADD        add     ekf_add_landmarks that adds                 the longest list brought (zcap,       yes
+//                                                                      from 64)
+// A capacity that a call outgrows is doubled until it fits (plan_grown_cap) and the block replaced.
+// ekf_reserve (map_scratch_rebuild) builds again, for the new capacity and as large as it was, every block the old buffers had --
+// with one irregularity: BLK_DUP and BLK_DUP_LIST are built together, when the old handle had the LIST (a base whose list never
+// got allocated is not rebuilt); BLK_GATE_LIST follows BLK_GATE's presence with the old ccap (0: no list).
+struct MapKept {
+    FactorScratch fac = {};
+    DupScratch dup = {};
+    FuseScratch fuse = {};
+    MatchScratch match = {};
+    GateScratch gate = {};
+    AssocScratch assoc = {};
+    AddScratch add = {};
+    DevBlock blk[BLK_COUNT];
+};
 
 struct GraphEntry {
     int steps, M, has_truth;
@@ -188,32 +257,11 @@ struct ekf_batch {
     ekf_params params_requested;
     // scratch
     std::vector<int> h_int;
-    // map assessment (ekf_joint_consistency): the factorisation's scratch, one device allocation made at the first call and kept
-    FactorScratch fac = {};
+    MapKept map;  // the map operations' kept scratch
     long long state_edits = 0;     // rewrites, broadcasts and scripted runs so far: with chain_seq and stream_ops, "has the state changed?"
-    long long fac_stamp[3] = {-1, -1, -1};  // those three when the scratch was last filled (ekf_debug_joint_factor)
+    long long fac_stamp[3] = {-1, -1, -1};  // those three when map.fac was last filled (ekf_debug_joint_factor)
     int fac_b0 = 0;                // ... by a call over filters [fac_b0, fac_b0 + fac_n.size()) with fac_n landmarks each
     std::vector<int> fac_n;
-    // duplicate search (ekf_find_duplicates): bounding boxes, counters and split table in one allocation made at the first call, the
-    // pair list in a second one that grows when a call finds more pairs than it holds; both kept and counted in device_bytes
-    DupScratch dup = {};
-    // landmark fusion (ekf_fuse_landmarks): pair table, the round's factor and right-hand sides, progress record; one allocation made
-    // at the first call, kept and counted in device_bytes
-    FuseScratch fuse = {};
-    // matched updates (ekf_update_matched, ekf_joint_compat): the call's measurement table, the round's table and the distances; one
-    // allocation made at the first call, replaced by a larger one when a call brings a longer list, kept and counted in device_bytes
-    MatchScratch match = {};
-    // individual compatibility (ekf_gate_candidates): measurement table, per-workgroup partial minima and counters in one allocation made
-    // at the first call (replaced by a larger one for a longer scan), the candidate list in a second one that grows when a call finds
-    // more than it holds; both kept and counted in device_bytes
-    GateScratch gate = {};
-    // joint compatibility search (ekf_associate_joint): the candidate table and the results, one allocation made at the first call
-    // that searches, kept and counted in device_bytes
-    AssocScratch assoc = {};
-    // landmark initialisation (ekf_add_landmarks, ekf_update_joint): the call's measurement table and the new rows' operands; one
-    // allocation made at the first call that adds, replaced by a larger one for a longer list, kept and counted in device_bytes
-    AddScratch add = {};
-    DevBlock kept[BLK_COUNT];  // the allocations behind fac, dup (boxes and counters; the pair list), fuse, match, gate (tables; the list), assoc and add
 };
 
 static int sticky_status(ekf_batch *h, bool include_capacity);
@@ -753,7 +801,7 @@ extern "C" int ekf_destroy(ekf_handle h) {
     for (int i = 0; i < 2; i++)
         if (h->ev_flush[i]) hipEventDestroy(h->ev_flush[i]);
     if (h->bm1_base) hipFree(h->bm1_base);
-    for (DevBlock &blk : h->kept)
+    for (DevBlock &blk : h->map.blk)
         if (blk.p) hipFree(blk.p);
     for (auto &g : h->graphs) hipGraphExecDestroy(g.exec);
     for (const DevArray &a : device_arrays(h))
@@ -1726,7 +1774,7 @@ extern "C" int ekf_set_state(ekf_handle h, int index, const double *x, const dou
 // moves over on the device (k_export into a dense staging matrix, k_import from it: the tile numbering depends on the capacity),
 // the counters, the decision log and a loaded script move with it, and the handle keeps its address.
 static int reserve_move_state(ekf_batch *h, ekf_batch *nh, const std::vector<int> &n_lm);
-static int map_scratch_reserve(ekf_batch *h, const bool want[BLK_COUNT], int dup_cap, int match_cap, int gate_zcap, int gate_ccap, int add_zcap);  // (ekf_map_api.hip)
+static int map_scratch_rebuild(ekf_batch *h, const MapKept &old);  // (ekf_map_api.hip)
 
 extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     if (!h || capacity_landmarks < 1 || capacity_landmarks > EKF_MAX_CAPACITY) return set_error(EKF_ERR_BAD_ARG, "bad handle / capacity (EKF_MAX_CAPACITY)");
@@ -1789,12 +1837,10 @@ extern "C" int ekf_reserve(ekf_handle h, int capacity_landmarks) {
     std::swap(nh->script_d, h->script_d);
     nh->script_steps = h->script_steps, nh->script_M = h->script_M, nh->script_has_truth = h->script_has_truth;
     h->script_steps = 0;
-    bool had[BLK_COUNT];  // the scratch the map operations keep follows the capacity
-    for (int i = 0; i < BLK_COUNT; i++) had[i] = h->kept[i].p != nullptr;
-    const int had_dup_cap = h->dup.cap, had_match_cap = h->match.zcap, had_gate_zcap = h->gate.zcap, had_gate_ccap = h->gate.ccap, had_add_zcap = h->add.zcap;
+    const MapKept old = h->map;  // the scratch the map operations keep follows the capacity (only which blocks it had, and how large, is read)
     std::swap(*h, *nh);  // the caller's handle now owns the larger buffers ...
     ekf_destroy(nh);     // ... and the old ones go
-    EKF_TRY(map_scratch_reserve(h, had, had_dup_cap, had_match_cap, had_gate_zcap, had_gate_ccap, had_add_zcap));
+    EKF_TRY(map_scratch_rebuild(h, old));
     return refresh_bounds(h);
 }
 

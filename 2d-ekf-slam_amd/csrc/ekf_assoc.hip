@@ -19,12 +19,7 @@
 
 #include "ekf_assoc_search.h"
 
-struct AssocScratch {
-    int *ncand;        // [B][32]      candidates kept of each valid measurement (compacted index, as GateScratch)
-    int *cand;         // [B][32][16]  their landmarks in list order
-    int *ids;          // [B][32]      out: the landmark of each valid measurement, -1: none
-    AssocResult *out;  // [B]
-};
+#include "ekf_map_scratch.h"  // AssocScratch
 
 struct AssocArgs {
     double jg[ASSOC_MAX_MEAS];

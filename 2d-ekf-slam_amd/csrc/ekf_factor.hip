@@ -20,15 +20,7 @@
 // A filter whose pivot is not positive records `info` and min_pivot; every later kernel of the call returns at once for it.
 // Every sum has one writer and a fixed order: no atomics, the same bits on every call and in the batch form.
 
-enum { FAC_LOGDET = 0, FAC_MINP = 1, FAC_MAXP = 2, FAC_YY = 3, FAC_WW = 4 /* 00 01 02 11 12 22 */, FAC_WY = 10 /* 3 */, FAC_INFO = 13, FAC_ACC = 16 };
-
-struct FactorScratch {
-    double *S;       // [B][bm_stride]   the factor in the making: tiles of U at and above step k's row, the Schur complement below
-    double *rhs;     // [B][rows][4]     {e_L, P_LR (3)} -> {y, W (3)}
-    double *acc;     // [B][FAC_ACC]
-    double *xt;      // [B][xs]          x_true
-    ekf_joint *out;  // [B]
-};
+#include "ekf_map_scratch.h"  // FactorScratch, FAC_*
 
 // One workgroup per stored tile (blockIdx.x over the triangle of side nT_grid) and filter b_off + blockIdx.y: the settled tile into
 // the scratch.  A landmark's own 2 x 2 block comes from D (the tile's own-block places are nobody's home: remove_source); rows and

@@ -22,16 +22,7 @@
 // to zero tiles; this round and the later ones return at once for it, and nothing of it but the slot rows (cleared at the end of
 // the call) has been written.
 
-#define FUSE_MAX_COLS (2 * EKF_MAX_PENDING)
-struct FuseScratch {
-    double *wr;    // [B][4][FUSE_MAX_COLS]  rows 0..2: W's robot rows of the round, after k_fuse_factor V's; row 3: d, then y
-    double *U;     // [B][FUSE_MAX_COLS][FUSE_MAX_COLS]  the round's factor, row-major, upper
-    int *pairs;    // [B][pcap][2]  the call's pair list {i, j}
-    int *cnt;      // [B]           pairs in the list
-    int *done;     // [B][2]        {pairs fused so far; 0, or 1 + the index of the first pivot of S that was not positive}
-    int *m_round;  // [B]           pairs of the current round once k_fuse_factor has accepted it, else 0
-    int pcap;
-};
+#include "ekf_map_scratch.h"  // FuseScratch, FUSE_MAX_COLS
 
 // pairs of filter b in round `round` (0: none left, or the filter has stopped)
 __device__ __forceinline__ int fuse_round_pairs(const EkfDev &dv, const FuseScratch &fs, int b, int round) {

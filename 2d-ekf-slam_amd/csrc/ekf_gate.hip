@@ -18,21 +18,8 @@
 // (measurement, landmark) pair alone or comes out of a fixed-order reduction: the same bits on every call and in the batch form.
 
 #define GATE_CHUNK 32
-#define GATE_THREADS 256
 
-struct GateScratch {
-    double *z;            // [B][zcap][2]        the call's valid measurements of each filter, compacted
-    double *Rm;           // [B][zcap][4]
-    double *pd;           // [B][npart][zcap]    workgroup g's nearest distance of measurement k (EKF_INF: none)
-    ekf_decision *near;   // [B][zcap]
-    int *pl;              // [B][npart][zcap]    ... its landmark (0x7fffffff: none)
-    int *ps;              // [B][npart][zcap]    ... the landmarks it skipped
-    int *skip;            // [B][zcap]
-    int *nz;              // [B]                 valid measurements of the call
-    int *cnt;             // [B]                 pairs listed by the call
-    ekf_candidate *list;  // [B][ccap]           the first ccap pairs appended (meas = the compacted index)
-    int zcap, ccap, npart;
-};
+#include "ekf_map_scratch.h"  // GateScratch, GATE_THREADS
 
 __global__ __launch_bounds__(GATE_THREADS) void k_gate(EkfDev dv, GateScratch gs, double gate, int b_off) {
     __shared__ SweepConst kc[GATE_CHUNK];

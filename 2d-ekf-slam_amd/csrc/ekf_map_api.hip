@@ -1,10 +1,14 @@
 // ekf_map_api.hip -- host side of the map operations of include/ekfslam_c.h: removal, frame change and anchoring, joining, extraction
 // and ekf_get_submap, joint consistency, duplicate search, fusion, matched updates and their score, the individual compatibility table,
 // the joint compatibility search, landmark initialisation and the scan step built from those, ekf_get_landmark_covs.  Included
-// by ekf_api.hip (one translation unit: ekf_batch, HIP_TRY / EKF_TRY, quiesce, finish_rewrite, DevTmp and the kept scratch blocks are
+// by ekf_api.hip (one translation unit: ekf_batch, HIP_TRY / EKF_TRY, quiesce, finish_rewrite, DevTmp, HostCopies and MapKept are
 // that file's).  Every entry point runs once per call on a handle it brings to rest and reads: check, quiesce, plan, upload, launch,
 // finish.  The checks of the caller's lists and the tables the kernels read are pure code in ekf_map_plan.h; the order of those
-// checks relative to quiescing is the table above quiesce().
+// checks relative to quiescing is the table above quiesce().  Every asynchronous copy that touches a local buffer or a caller's goes
+// through a HostCopies guard declared behind those buffers.
+// Adding a kept block: (1) its struct and carve function in ekf_map_scratch.h (and a case in tests/cpp/map_scratch_check.cpp); (2) a
+// BLK_ value, a member and a row of the table of MapKept (ekf_api.hip), and a line in map_scratch_rebuild if ekf_reserve is to build
+// it again; (3) a block_build call where the operation finds the block absent or too small.
 
 // The filters of a call, [b0, b0 + nb) of a handle: one filter, or (index < 0) the whole batch; and their landmark counts (h_int[]).
 struct Filters {
@@ -15,12 +19,6 @@ static const int *counts_of(const ekf_batch *h, int b0) { return h->h_int.data()
 
 // A block of device scratch for the handle to keep (DevBlock), optionally zeroed on the chain stream and waited for; a failure
 // leaves *blk as it was.  A block that *blk held goes once the new one exists.
-static void block_release(ekf_batch *h, DevBlock *blk) {
-    if (!blk->p) return;
-    hipFree(blk->p);
-    h->device_bytes -= blk->bytes;
-    *blk = DevBlock();
-}
 static int block_alloc(ekf_batch *h, DevBlock *blk, size_t bytes, bool zero) {
     void *p = nullptr;
     HIP_TRY(hipMalloc(&p, bytes));
@@ -30,9 +28,67 @@ static int block_alloc(ekf_batch *h, DevBlock *blk, size_t bytes, bool zero) {
         hipFree(p);
         return set_error(EKF_ERR_HIP, "%s", hipGetErrorString(e));
     }
-    block_release(h, blk);
+    if (blk->p) hipFree(blk->p);
+    h->device_bytes += bytes - blk->bytes;
     blk->p = p, blk->bytes = bytes;
-    h->device_bytes += bytes;
+    return EKF_OK;
+}
+// Block `id` of h->map built (again) for scratch struct *sc by its carve function of ekf_map_scratch.h: sized by a carve without a
+// base (into a copy: a failure leaves *sc as it was, too), allocated, carved.
+template <typename S, typename... Cap>
+static int block_build(ekf_batch *h, int id, bool zero, S *sc, void (*carve)(S &, Carver &, const ScratchGeom &, Cap...), Cap... cap) {
+    const EkfDev &dv = h->dv;
+    const ScratchGeom g = {(size_t)dv.B, dv.Ncap, (size_t)dv.rows, (size_t)dv.xs, (size_t)dv.dn, dv.bm_stride};
+    S probe = *sc;
+    Carver size{nullptr};
+    carve(probe, size, g, cap...);
+    EKF_TRY(block_alloc(h, &h->map.blk[id], size.bytes(), zero));
+    Carver at{(char *)h->map.blk[id].p};
+    carve(*sc, at, g, cap...);
+    return EKF_OK;
+}
+
+// Each operation's scratch, asked for by every call that needs it: built where it is absent or, where it follows what calls bring
+// (n_meas entries of a list, `cap` / `cand` entries found), outgrown.  Which block follows what: the table of MapKept.
+static int factor_reserve(ekf_batch *h) {
+    if (h->map.blk[BLK_FACTOR].p) return EKF_OK;
+    h->fac_stamp[0] = -1;
+    return block_build(h, BLK_FACTOR, /*zero*/ true, &h->map.fac, carve_factor);
+}
+static int dup_reserve(ekf_batch *h, int cap) {
+    if (!h->map.blk[BLK_DUP].p) EKF_TRY(block_build(h, BLK_DUP, /*zero*/ true, &h->map.dup, carve_dup));
+    return cap > h->map.dup.cap ? block_build(h, BLK_DUP_LIST, /*zero*/ false, &h->map.dup, carve_dup_list, cap) : EKF_OK;
+}
+static int fuse_reserve(ekf_batch *h) { return h->map.blk[BLK_FUSE].p ? EKF_OK : block_build(h, BLK_FUSE, /*zero*/ true, &h->map.fuse, carve_fuse); }
+static int match_reserve(ekf_batch *h, int n_meas) {
+    const int zcap = plan_grown_cap(h->map.match.zcap, n_meas, 64);
+    if (h->map.blk[BLK_MATCH].p && zcap == h->map.match.zcap) return EKF_OK;
+    return block_build(h, BLK_MATCH, /*zero*/ true, &h->map.match, carve_match, zcap);
+}
+static int gate_reserve(ekf_batch *h, int n_meas, int cand) {
+    GateScratch &gs = h->map.gate;
+    const int zcap = plan_grown_cap(gs.zcap, n_meas, 64);
+    if (!h->map.blk[BLK_GATE].p || zcap != gs.zcap) EKF_TRY(block_build(h, BLK_GATE, /*zero*/ true, &gs, carve_gate, zcap));
+    return cand > gs.ccap ? block_build(h, BLK_GATE_LIST, /*zero*/ false, &gs, carve_gate_list, cand) : EKF_OK;
+}
+static int assoc_reserve(ekf_batch *h) { return h->map.blk[BLK_ASSOC].p ? EKF_OK : block_build(h, BLK_ASSOC, /*zero*/ true, &h->map.assoc, carve_assoc); }
+static int add_reserve(ekf_batch *h, int n_meas) {
+    const int zcap = plan_add_zcap(h->map.add.zcap, n_meas);
+    if (h->map.blk[BLK_ADD].p && zcap == h->map.add.zcap) return EKF_OK;
+    return block_build(h, BLK_ADD, /*zero*/ true, &h->map.add, carve_add, zcap);
+}
+// The entries of a device list (pairs, candidates) for a call that may hand out up to `want` of them (a call that finds more grows it).
+static int list_cap_for(int want) { return plan_grown_cap(0, want < 4096 ? want : 4096, 256); }
+
+// ekf_reserve: `old` is what the smaller buffers had (its pointers are gone); the rule is in the table of MapKept.
+static int map_scratch_rebuild(ekf_batch *h, const MapKept &old) {
+    if (old.blk[BLK_FACTOR].p) EKF_TRY(factor_reserve(h));
+    if (old.blk[BLK_DUP_LIST].p) EKF_TRY(dup_reserve(h, old.dup.cap));
+    if (old.blk[BLK_FUSE].p) EKF_TRY(fuse_reserve(h));
+    if (old.blk[BLK_MATCH].p) EKF_TRY(match_reserve(h, old.match.zcap));
+    if (old.blk[BLK_GATE].p) EKF_TRY(gate_reserve(h, old.gate.zcap, old.gate.ccap));
+    if (old.blk[BLK_ASSOC].p) EKF_TRY(assoc_reserve(h));
+    if (old.blk[BLK_ADD].p) EKF_TRY(add_reserve(h, old.add.zcap));
     return EKF_OK;
 }
 
@@ -55,8 +111,9 @@ static int remove_settled(ekf_batch *h, Filters f, const unsigned char *keep, in
     DevTmp<int> rm_d;
     DevTmp<double> scratch;
     const size_t scratch_stride = (size_t)nTn * (nTn + 1) / 2 * 4096;
+    HostCopies hc(s);
     if (!h->overlap && scratch_stride) HIP_TRY(scratch.alloc((size_t)B * scratch_stride));
-    HIP_TRY(rm_d.upload(pl.rm.data(), pl.rm.size(), s));
+    HIP_TRY(hc.upload(&rm_d, pl.rm.data(), pl.rm.size()));
     if (nTo > 0) {
         const dim3 grid((unsigned)(nTo * (nTo + 1) / 2), (unsigned)B);
         if (h->overlap) {
@@ -70,7 +127,9 @@ static int remove_settled(ekf_batch *h, Filters f, const unsigned char *keep, in
     }
     // D is read by the gather (landmarks' own blocks): compacted behind it
     hipLaunchKernelGGL(k_rm_vec, dim3(7, B), dim3(1024), 0, s, dv, (const int *)rm_d.p, mstride);
-    return finish_rewrite(h, 0, B, /*rearm*/ true, &pl.rm[1], 2, /*flip_buf: the gather's output*/ h->overlap && nTo > 0);
+    EKF_TRY(finish_rewrite(h, 0, B, /*rearm*/ true, &pl.rm[1], 2, /*flip_buf: the gather's output*/ h->overlap && nTo > 0));
+    hc.waited();
+    return EKF_OK;
 }
 
 static int remove_impl(ekf_batch *h, Filters f, const unsigned char *keep, int ld_keep, int *n_out) {
@@ -247,7 +306,8 @@ static int extract_impl(ekf_batch *d, Filters fd, ekf_batch *s, int bs0, const i
     hipStream_t st = d->s_chain;
     EKF_TRY(restart_waits(d));
     DevTmp<int> ex_d;
-    HIP_TRY(ex_d.upload(ex.data(), ex.size(), st));
+    HostCopies hc(st);
+    HIP_TRY(hc.upload(&ex_d, ex.data(), ex.size()));
     const JoinSrc sv = join_src_of(s);
     double *other = d->overlap ? dv.Bm[d->win.buf_in ^ 1] : nullptr;
     if (nT > 0)
@@ -255,6 +315,7 @@ static int extract_impl(ekf_batch *d, Filters fd, ekf_batch *s, int bs0, const i
                            bs0);
     hipLaunchKernelGGL(k_ext_vec, dim3(7, (unsigned)nb), dim3(1024), 0, st, dv, sv, (const int *)ex_d.p, mstride, nb, bd0, bs0);
     EKF_TRY(finish_rewrite(d, bd0, nb, /*rearm*/ true, &ex[1], 2, /*flip_buf*/ false));
+    hc.waited();
     for (int k = 0; n_out && k < nb; k++) n_out[k] = ex[2 * k + 1];
     return EKF_OK;
 }
@@ -291,34 +352,18 @@ extern "C" int ekf_get_submap(ekf_handle h, int index, const int *ids, int count
     hipStream_t s = h->s_chain;
     DevTmp<double> stage;  // transient staging: dense n x n + x
     DevTmp<int> ids_d;
+    HostCopies hc(s);
     HIP_TRY(stage.alloc((size_t)n * n + n));
-    HIP_TRY(ids_d.upload(ids, (size_t)count, s));
+    HIP_TRY(hc.upload(&ids_d, ids, (size_t)count));
     hipLaunchKernelGGL(k_ext_dense, dim3((unsigned)cdiv(n, 256), (unsigned)n), dim3(256), 0, s, join_src_of(h), index, (const int *)ids_d.p, count, stage.p + (size_t)n * n,
                        stage.p, n, n);
     EKF_TRY(read_back_dense(h, stage.p, n, x_out, P_out, ld));
+    hc.waited();
     EKF_TRY(check_launch());
     return n;
 }
 
 // ---- map assessment -------------------------------------------------------------------------------
-// The scratch of ekf_joint_consistency (ekf_factor.hip: FactorScratch), sized by the handle's capacity: one block at the first
-// call; ekf_reserve builds the larger one.
-static int factor_reserve(ekf_batch *h) {
-    DevBlock &blk = h->kept[BLK_FACTOR];
-    if (blk.p) return EKF_OK;
-    const EkfDev &dv = h->dv;
-    const size_t B = (size_t)dv.B;
-    const size_t nS = B * dv.bm_stride, nrhs = B * (size_t)dv.rows * 4, nacc = B * FAC_ACC, nxt = B * (size_t)dv.xs;
-    EKF_TRY(block_alloc(h, &blk, (nS + nrhs + nacc + nxt) * sizeof(double) + B * sizeof(ekf_joint), /*zero*/ true));
-    h->fac.S = (double *)blk.p;
-    h->fac.rhs = h->fac.S + nS;
-    h->fac.acc = h->fac.rhs + nrhs;
-    h->fac.xt = h->fac.acc + nacc;
-    h->fac.out = (ekf_joint *)(h->fac.xt + nxt);
-    h->fac_stamp[0] = -1;
-    return EKF_OK;
-}
-
 // The filters f: the rule of ekf_get_state (the streaming launch leaves, every deferred slot is folded, both streams idle),
 // then the settled state is only read: stage, 3 launches per tile step with the grid over the filters, finish, one copy back.
 static int joint_impl(ekf_batch *h, Filters f, const double *x_true, int ld_true, ekf_joint *out) {
@@ -328,12 +373,13 @@ static int joint_impl(ekf_batch *h, Filters f, const double *x_true, int ld_true
     EKF_TRY(settle(h));
     EKF_TRY(factor_reserve(h));
     const EkfDev &dv = h->dv;
-    const FactorScratch fs = h->fac;
+    const FactorScratch fs = h->map.fac;
     hipStream_t s = h->s_chain;
     const int have_truth = x_true ? 1 : 0;
+    HostCopies hc(s);
     if (x_true)
-        HIP_TRY(hipMemcpy2DAsync(fs.xt + (size_t)b0 * dv.xs, (size_t)dv.xs * sizeof(double), x_true, (size_t)ld_true * sizeof(double),
-                                 (size_t)(3 + 2 * n_max) * sizeof(double), nb, hipMemcpyHostToDevice, s));
+        HIP_TRY(hc.copy2d(fs.xt + (size_t)b0 * dv.xs, (size_t)dv.xs * sizeof(double), x_true, (size_t)ld_true * sizeof(double), (size_t)(3 + 2 * n_max) * sizeof(double), nb,
+                          hipMemcpyHostToDevice));
     const int nT = lm_tiles(n_max);
     if (nT > 0) hipLaunchKernelGGL(k_chol_stage, dim3((unsigned)(nT * (nT + 1) / 2), (unsigned)nb), dim3(256), 0, s, dv, fs, h->win.buf_in, b0, nT, have_truth);
     for (int k = 0; k < nT; k++) {
@@ -344,8 +390,8 @@ static int joint_impl(ekf_batch *h, Filters f, const double *x_true, int ld_true
         }
     }
     hipLaunchKernelGGL(k_chol_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0, have_truth);
-    HIP_TRY(hipMemcpyAsync(out, fs.out + b0, sizeof(ekf_joint) * (size_t)nb, hipMemcpyDeviceToHost, s));
-    HIP_TRY(stream_wait(s));
+    HIP_TRY(hc.copy(out, fs.out + b0, sizeof(ekf_joint) * (size_t)nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hc.wait());
     EKF_TRY(check_launch());
     h->fac_stamp[0] = h->chain_seq, h->fac_stamp[1] = h->stream_ops, h->fac_stamp[2] = h->state_edits;
     h->fac_b0 = b0;
@@ -365,7 +411,7 @@ extern "C" int ekf_batch_joint_consistency(ekf_handle h, const double *x_true, i
 
 extern "C" int ekf_debug_joint_factor(ekf_handle h, int index, double *U_out, int ld) {
     if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    const bool current = h->kept[BLK_FACTOR].p && h->fac_stamp[0] == h->chain_seq && h->fac_stamp[1] == h->stream_ops && h->fac_stamp[2] == h->state_edits;
+    const bool current = h->map.blk[BLK_FACTOR].p && h->fac_stamp[0] == h->chain_seq && h->fac_stamp[1] == h->stream_ops && h->fac_stamp[2] == h->state_edits;
     if (!current || index < h->fac_b0 || index >= h->fac_b0 + (int)h->fac_n.size())
         return set_error(EKF_ERR_STATE, "no factor of this filter's current state: call ekf_joint_consistency first");
     const int m = 2 * h->fac_n[index - h->fac_b0];
@@ -374,40 +420,13 @@ extern "C" int ekf_debug_joint_factor(ekf_handle h, int index, double *U_out, in
     HIP_TRY(hipSetDevice(h->device));
     DevTmp<double> stage;
     HIP_TRY(stage.alloc((size_t)m * m));
-    hipLaunchKernelGGL(k_chol_export, dim3(cdiv(m, 256), m), dim3(256), 0, h->s_chain, h->dv, h->fac, index, m, stage.p, m);
+    hipLaunchKernelGGL(k_chol_export, dim3(cdiv(m, 256), m), dim3(256), 0, h->s_chain, h->dv, h->map.fac, index, m, stage.p, m);
     EKF_TRY(read_back_dense(h, stage.p, m, nullptr, U_out, ld));
     EKF_TRY(check_launch());
     return m;
 }
 
 // ---- duplicate search -----------------------------------------------------------------------------
-// The scratch of ekf_find_duplicates (ekf_pairs.hip: DupScratch).  Boxes, counters and the split table are sized by the handle's
-// capacity: one block at the first call; the pair list, a block of its own that is not zeroed, holds `cap` pairs per filter and is
-// replaced by a larger one when a call finds more than it holds.  ekf_reserve builds both again for the larger capacity.
-static int dup_reserve(ekf_batch *h, int cap) {
-    const EkfDev &dv = h->dv;
-    const size_t B = (size_t)dv.B;
-    if (!h->kept[BLK_DUP].p) {
-        const size_t nbox = B * (size_t)(dv.dn >> 5) * 4;
-        EKF_TRY(block_alloc(h, &h->kept[BLK_DUP], nbox * sizeof(double) + B * 3 * sizeof(int), /*zero*/ true));
-        h->dup.box = (double *)h->kept[BLK_DUP].p;
-        h->dup.cnt = (int *)(h->dup.box + nbox);
-        h->dup.split = h->dup.cnt + 2 * B;
-    }
-    if (cap > h->dup.cap) {
-        EKF_TRY(block_alloc(h, &h->kept[BLK_DUP_LIST], B * (size_t)cap * sizeof(ekf_dup_pair), /*zero*/ false));
-        h->dup.list = (ekf_dup_pair *)h->kept[BLK_DUP_LIST].p;
-        h->dup.cap = cap;
-    }
-    return EKF_OK;
-}
-
-static int dup_cap_for(long long pairs) {
-    long long cap = 256;
-    while (cap < pairs) cap *= 2;
-    return (int)cap;
-}
-
 // The filters f: the rule of ekf_get_state (the streaming launch leaves, every deferred slot is folded, both streams idle),
 // then the settled state is only read: boxes (with a Euclidean bound), tiles, the counters back, the lists back.  A call that
 // finds more pairs than the device list holds and has to hand some out runs the two kernels once more with a list that fits (the
@@ -419,35 +438,36 @@ static int dup_impl(ekf_batch *h, Filters f, double gate, double max_dist, int s
     int nt;
     EKF_TRY(set_error(plan_dup_tiles(counts_of(h, b0), b0, nb, split_one, split, &nt)));
     EKF_TRY(settle(h));
-    EKF_TRY(dup_reserve(h, dup_cap_for(max_pairs < 4096 ? max_pairs : 4096)));  // (a call that finds more grows the list below)
+    EKF_TRY(dup_reserve(h, list_cap_for(max_pairs)));
     const EkfDev &dv = h->dv;
     hipStream_t s = h->s_chain;
     DupArgs da;
     da.gate = gate, da.md2 = max_dist > 0.0 ? max_dist * max_dist : -1.0, da.split_one = split_one, da.use_tab = split ? 1 : 0;
-    if (split) HIP_TRY(hipMemcpyAsync(h->dup.split + b0, split, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
     std::vector<int> cnt((size_t)2 * nb, 0);
+    std::vector<ekf_dup_pair> got;
+    HostCopies hc(s);
+    if (split && nt > 0) HIP_TRY(hc.copy(h->map.dup.split + b0, split, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice));  // (no tile: no kernel, and nothing waits)
     for (int round = 0; nt > 0; round++) {
-        const DupScratch ds = h->dup;
+        const DupScratch ds = h->map.dup;
         HIP_TRY(hipMemsetAsync(ds.cnt + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
         if (da.md2 >= 0.0) hipLaunchKernelGGL(k_dup_boxes, dim3((unsigned)cdiv(lm_tiles(n_max), 64), (unsigned)nb), dim3(64), 0, s, dv, ds, b0);
         hipLaunchKernelGGL(k_dup_tiles, dim3((unsigned)nt, (unsigned)nb), dim3(256), 0, s, dv, ds, da, h->win.buf_in, b0);
-        HIP_TRY(hipMemcpyAsync(cnt.data(), ds.cnt + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost, s));
-        HIP_TRY(stream_wait(s));
+        HIP_TRY(hc.copy(cnt.data(), ds.cnt + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost));
+        HIP_TRY(hc.wait());
         EKF_TRY(check_launch());
         int most = 0;
         for (int k = 0; k < nb; k++) most = cnt[2 * k] > most ? cnt[2 * k] : most;
         if (most <= ds.cap || max_pairs == 0) break;
         if (round > 0) return set_error(EKF_ERR_STATE, "the pair count changed between two passes over an unchanged state");
-        EKF_TRY(dup_reserve(h, dup_cap_for(most)));
+        EKF_TRY(dup_reserve(h, plan_grown_cap(0, most, 256)));
     }
-    std::vector<ekf_dup_pair> got;
     std::vector<size_t> at((size_t)nb + 1, 0);
     for (int k = 0; k < nb; k++) at[k + 1] = at[k] + (max_pairs > 0 ? (size_t)cnt[2 * k] : 0);
     got.resize(at[nb]);
     for (int k = 0; k < nb; k++)
         if (at[k + 1] > at[k])
-            HIP_TRY(hipMemcpyAsync(got.data() + at[k], h->dup.list + (size_t)(b0 + k) * h->dup.cap, sizeof(ekf_dup_pair) * (at[k + 1] - at[k]), hipMemcpyDeviceToHost, s));
-    if (at[nb] > 0) HIP_TRY(stream_wait(s));
+            HIP_TRY(hc.copy(got.data() + at[k], h->map.dup.list + (size_t)(b0 + k) * h->map.dup.cap, sizeof(ekf_dup_pair) * (at[k + 1] - at[k]), hipMemcpyDeviceToHost));
+    if (at[nb] > 0) HIP_TRY(hc.wait());
     for (int k = 0; k < nb; k++) {
         const int found = cnt[2 * k];
         if (n_found_out) n_found_out[k] = found;
@@ -476,43 +496,6 @@ extern "C" int ekf_batch_find_duplicates(ekf_handle h, double gate, double max_d
 }
 
 // ---- landmark fusion ------------------------------------------------------------------------------
-// The scratch of ekf_fuse_landmarks (ekf_fuse.hip: FuseScratch), sized by the handle's capacity (a landmark is in at most one pair
-// of a call: Ncap / 2 pairs per filter): one block at the first call; ekf_reserve builds the larger one.
-static int fuse_reserve(ekf_batch *h) {
-    DevBlock &blk = h->kept[BLK_FUSE];
-    if (blk.p) return EKF_OK;
-    const EkfDev &dv = h->dv;
-    const size_t B = (size_t)dv.B;
-    const int pcap = dv.Ncap / 2 + 1;
-    const size_t nwr = B * 4 * FUSE_MAX_COLS, nU = B * FUSE_MAX_COLS * FUSE_MAX_COLS, nint = B * ((size_t)pcap * 2 + 4);
-    EKF_TRY(block_alloc(h, &blk, (nwr + nU) * sizeof(double) + nint * sizeof(int), /*zero*/ true));
-    h->fuse.wr = (double *)blk.p;
-    h->fuse.U = h->fuse.wr + nwr;
-    h->fuse.pairs = (int *)(h->fuse.U + nU);
-    h->fuse.cnt = h->fuse.pairs + B * (size_t)pcap * 2;
-    h->fuse.done = h->fuse.cnt + B;
-    h->fuse.m_round = h->fuse.done + 2 * B;
-    h->fuse.pcap = pcap;
-    return EKF_OK;
-}
-
-// ekf_reserve: the blocks the old buffers had (want[]; the pair list with dup_cap pairs per filter), built for the new capacity.
-// want[BLK_DUP] is not read: dup_reserve builds base and list together, and a base whose list never got allocated is not rebuilt.
-static int match_reserve(ekf_batch *h, int n_meas);
-static int gate_reserve(ekf_batch *h, int n_meas, int cand);
-static int assoc_reserve(ekf_batch *h);
-static int add_reserve(ekf_batch *h, int n_meas);
-static int map_scratch_reserve(ekf_batch *h, const bool want[BLK_COUNT], int dup_cap, int match_cap, int gate_zcap, int gate_ccap, int add_zcap) {
-    if (want[BLK_FACTOR]) EKF_TRY(factor_reserve(h));
-    if (want[BLK_DUP_LIST]) EKF_TRY(dup_reserve(h, dup_cap));
-    if (want[BLK_FUSE]) EKF_TRY(fuse_reserve(h));
-    if (want[BLK_MATCH]) EKF_TRY(match_reserve(h, match_cap));
-    if (want[BLK_GATE]) EKF_TRY(gate_reserve(h, gate_zcap, gate_ccap));
-    if (want[BLK_ASSOC]) EKF_TRY(assoc_reserve(h));
-    if (want[BLK_ADD]) EKF_TRY(add_reserve(h, add_zcap));
-    return EKF_OK;
-}
-
 // The filters f, filter f.b0 + k with n_pairs[k] pairs at pairs + k * ld_pairs.  The list is checked against the mirror's
 // landmark counts before anything else happens to the handle; a call without a pair returns there.  Then: settle, the pair table
 // up, rounds of at most ekf_window() pairs (ekf_fuse.hip; one dense pass each, in place in the settled buffer in either pipeline
@@ -539,13 +522,14 @@ static int fuse_impl(ekf_batch *h, Filters f, const ekf_dup_pair *pairs, int ld_
     EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
     EKF_TRY(fuse_reserve(h));
     EkfDev &dv = h->dv;
-    const FuseScratch fs = h->fuse;
+    const FuseScratch fs = h->map.fuse;
     hipStream_t s = h->s_chain;
     const int n_max = most_landmarks(counts_of(h, b0), nb);
-    std::vector<int> tab;
+    std::vector<int> tab, done((size_t)2 * nb, 0);
     EKF_TRY(set_error(plan_fuse_table(pairs, ld_pairs, n_pairs, nb, fs.pcap, &tab)));
-    HIP_TRY(hipMemcpyAsync(fs.pairs + (size_t)b0 * fs.pcap * 2, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(fs.cnt + b0, n_pairs, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
+    HostCopies hc(s);
+    HIP_TRY(hc.copy(fs.pairs + (size_t)b0 * fs.pcap * 2, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hc.copy(fs.cnt + b0, n_pairs, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(fs.done + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
     HIP_TRY(hipMemsetAsync(fs.m_round + b0, 0, sizeof(int) * (size_t)nb, s));
     const int nT = lm_tiles(n_max);
@@ -557,9 +541,8 @@ static int fuse_impl(ekf_batch *h, Filters f, const ekf_dup_pair *pairs, int ld_
         hipLaunchKernelGGL(k_fuse_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0);
         launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->win.buf_in, h->win.buf_in, nullptr, /*rev*/ 0, b0, nb);
     }
-    std::vector<int> done((size_t)2 * nb, 0);
-    HIP_TRY(hipMemcpyAsync(done.data(), fs.done + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost, s));
-    HIP_TRY(stream_wait(s));
+    HIP_TRY(hc.copy(done.data(), fs.done + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hc.wait());
     EKF_TRY(check_launch());
     // the fused pairs' j go, exactly as ekf_remove_landmarks with keep[j] = 0 removes them
     const int ld_keep = n_max > 0 ? n_max : 1;
@@ -589,36 +572,14 @@ extern "C" int ekf_batch_fuse_landmarks(ekf_handle h, const ekf_dup_pair *pairs,
 }
 
 // ---- matched updates ------------------------------------------------------------------------------
-// The scratch of ekf_update_matched and ekf_joint_compat (ekf_match.hip: MatchScratch).  It follows the longest list a call has
-// brought, not the capacity (the same landmark may be measured any number of times): one block for 64 measurements per filter at
-// the first call, replaced by one twice the size until the list fits; ekf_reserve builds it again as large as it was.
-static int match_reserve(ekf_batch *h, int n_meas) {
-    int zcap = h->match.zcap > 64 ? h->match.zcap : 64;
-    while (zcap < n_meas) zcap *= 2;
-    DevBlock &blk = h->kept[BLK_MATCH];
-    if (blk.p && zcap == h->match.zcap) return EKF_OK;
-    const size_t B = (size_t)h->dv.B;
-    const size_t nz = B * zcap * 2, nR = B * zcap * 4, nd = B * zcap, ntab = B * EKF_MAX_PENDING * MATCH_TAB;
-    EKF_TRY(block_alloc(h, &blk, (nz + nR + nd + ntab) * sizeof(double) + (B * zcap + B) * sizeof(int), /*zero*/ true));
-    MatchScratch &ms = h->match;
-    ms.z = (double *)blk.p;
-    ms.Rm = ms.z + nz;
-    ms.d2 = ms.Rm + nR;
-    ms.tab = ms.d2 + nd;
-    ms.ids = (int *)(ms.tab + ntab);
-    ms.cnt = ms.ids + B * zcap;
-    ms.zcap = zcap;
-    return EKF_OK;
-}
-
-// The call's lists into the scratch of filters [b0, b0 + nb), on stream s (the host tables live until the caller has waited).
-static int match_upload(ekf_batch *h, const MatchTable &t, int b0, int nb, hipStream_t s) {
-    const MatchScratch &ms = h->match;
+// The call's lists into the scratch of filters [b0, b0 + nb), through the caller's guard (the host tables live until it has waited).
+static int match_upload(ekf_batch *h, const MatchTable &t, int b0, int nb, HostCopies *hc) {
+    const MatchScratch &ms = h->map.match;
     const size_t at = (size_t)b0 * ms.zcap, cnt = (size_t)nb * ms.zcap;
-    HIP_TRY(hipMemcpyAsync(ms.z + 2 * at, t.zt.data(), sizeof(double) * 2 * cnt, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ms.Rm + 4 * at, t.Rt.data(), sizeof(double) * 4 * cnt, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ms.ids + at, t.idt.data(), sizeof(int) * cnt, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(ms.cnt + b0, t.cnt.data(), sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hc->copy(ms.z + 2 * at, t.zt.data(), sizeof(double) * 2 * cnt, hipMemcpyHostToDevice));
+    HIP_TRY(hc->copy(ms.Rm + 4 * at, t.Rt.data(), sizeof(double) * 4 * cnt, hipMemcpyHostToDevice));
+    HIP_TRY(hc->copy(ms.ids + at, t.idt.data(), sizeof(int) * cnt, hipMemcpyHostToDevice));
+    HIP_TRY(hc->copy(ms.cnt + b0, t.cnt.data(), sizeof(int) * (size_t)nb, hipMemcpyHostToDevice));
     return EKF_OK;
 }
 
@@ -657,11 +618,14 @@ static int match_impl(ekf_batch *h, Filters f, const double *z, const double *R,
     EKF_TRY(fuse_reserve(h));
     EKF_TRY(match_reserve(h, most));
     EkfDev &dv = h->dv;
-    const FuseScratch fs = h->fuse;
-    const MatchScratch ms = h->match;
+    const FuseScratch fs = h->map.fuse;
+    const MatchScratch ms = h->map.match;
     hipStream_t s = h->s_chain;
     const MatchTable tab = plan_match_table(z, R, ids, n_z, nb, ms.zcap);
-    EKF_TRY(match_upload(h, tab, b0, nb, s));
+    std::vector<int> done((size_t)2 * nb, 0);
+    std::vector<double> d2((size_t)nb * ms.zcap);
+    HostCopies hc(s);
+    EKF_TRY(match_upload(h, tab, b0, nb, &hc));
     HIP_TRY(hipMemsetAsync(fs.done + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
     HIP_TRY(hipMemsetAsync(fs.m_round + b0, 0, sizeof(int) * (size_t)nb, s));
     const int n_max = most_landmarks(counts_of(h, b0), nb), nT = lm_tiles(n_max);
@@ -673,11 +637,9 @@ static int match_impl(ekf_batch *h, Filters f, const double *z, const double *R,
         hipLaunchKernelGGL(k_fuse_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0);
         launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->win.buf_in, h->win.buf_in, nullptr, /*rev*/ 0, b0, nb);
     }
-    std::vector<int> done((size_t)2 * nb, 0);
-    std::vector<double> d2((size_t)nb * ms.zcap);
-    HIP_TRY(hipMemcpyAsync(done.data(), fs.done + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(stream_wait(s));
+    HIP_TRY(hc.copy(done.data(), fs.done + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hc.copy(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hc.wait());
     EKF_TRY(check_launch());
     for (int k = 0; n_applied_out && k < nb; k++) n_applied_out[k] = done[2 * k];  // (filled even where the end of the rewrite fails)
     match_scatter(tab, d2, ms.zcap, n_z, nb, done.data(), d2_out);
@@ -710,14 +672,15 @@ static int compat_impl(ekf_batch *h, Filters f, const double *z, const double *R
     if (most == 0) return EKF_OK;  // (nothing is folded)
     EKF_TRY(settle(h));
     EKF_TRY(match_reserve(h, most));
-    const MatchScratch ms = h->match;
+    const MatchScratch ms = h->map.match;
     hipStream_t s = h->s_chain;
     const MatchTable tab = plan_match_table(z, R, ids, n_z, nb, ms.zcap);
-    EKF_TRY(match_upload(h, tab, b0, nb, s));
-    hipLaunchKernelGGL(k_match_factor, dim3((unsigned)nb), dim3(256), 0, s, h->dv, h->fuse, ms, h->win.buf_in, 0, EKF_MAX_PENDING, /*apply*/ 0, b0);
     std::vector<double> d2((size_t)nb * ms.zcap);
-    HIP_TRY(hipMemcpyAsync(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost, s));
-    HIP_TRY(stream_wait(s));
+    HostCopies hc(s);
+    EKF_TRY(match_upload(h, tab, b0, nb, &hc));
+    hipLaunchKernelGGL(k_match_factor, dim3((unsigned)nb), dim3(256), 0, s, h->dv, h->map.fuse, ms, h->win.buf_in, 0, EKF_MAX_PENDING, /*apply*/ 0, b0);
+    HIP_TRY(hc.copy(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hc.wait());
     EKF_TRY(check_launch());
     match_scatter(tab, d2, ms.zcap, n_z, nb, nullptr, d2_out);
     return EKF_OK;
@@ -734,38 +697,6 @@ extern "C" int ekf_batch_joint_compat(ekf_handle h, const double *z, const doubl
 }
 
 // ---- individual compatibility ---------------------------------------------------------------------
-// The scratch of ekf_gate_candidates (ekf_gate.hip: GateScratch).  The tables follow the longest scan a call has brought (for 64
-// valid measurements per filter at the first call, doubled until the scan fits) and the capacity (a partial per workgroup of 256
-// landmarks): one zeroed block; the candidate list, a block of its own that is not zeroed, holds `cand` entries per filter and is
-// replaced by a larger one when a call finds more than it holds.  ekf_reserve builds both again, as large as they were.
-static int gate_reserve(ekf_batch *h, int n_meas, int cand) {
-    GateScratch &gs = h->gate;
-    int zcap = gs.zcap > 64 ? gs.zcap : 64;
-    while (zcap < n_meas) zcap *= 2;
-    const size_t B = (size_t)h->dv.B;
-    if (!h->kept[BLK_GATE].p || zcap != gs.zcap) {
-        const int npart = cdiv(h->dv.Ncap, GATE_THREADS);
-        const size_t nz = B * zcap * 2, nR = B * zcap * 4, np = B * npart * (size_t)zcap, nd = B * zcap;
-        EKF_TRY(block_alloc(h, &h->kept[BLK_GATE], (nz + nR + np) * sizeof(double) + nd * sizeof(ekf_decision) + (2 * np + nd + 2 * B) * sizeof(int), /*zero*/ true));
-        gs.z = (double *)h->kept[BLK_GATE].p;
-        gs.Rm = gs.z + nz;
-        gs.pd = gs.Rm + nR;
-        gs.near = (ekf_decision *)(gs.pd + np);
-        gs.pl = (int *)(gs.near + nd);
-        gs.ps = gs.pl + np;
-        gs.skip = gs.ps + np;
-        gs.nz = gs.skip + nd;
-        gs.cnt = gs.nz + B;
-        gs.zcap = zcap, gs.npart = npart;
-    }
-    if (cand > gs.ccap) {
-        EKF_TRY(block_alloc(h, &h->kept[BLK_GATE_LIST], B * (size_t)cand * sizeof(ekf_candidate), /*zero*/ false));
-        gs.list = (ekf_candidate *)h->kept[BLK_GATE_LIST].p;
-        gs.ccap = cand;
-    }
-    return EKF_OK;
-}
-
 // The filters f, filter f.b0 + k with the n_z measurements at z + k * n_z * 2 and R + k * n_z * 4 (valid + k * n_z masks them).  The
 // values are checked before anything happens to the handle; a call without a measurement returns there.  Then the rule of
 // ekf_get_landmark_covs: the chain stream idle (a resident streaming launch leaves first), NOTHING folded -- x, the robot rows and D
@@ -786,53 +717,43 @@ static int gate_impl(ekf_batch *h, Filters f, const double *z, const double *R, 
         plan_gate_scatter(plan_gate_table(z, R, valid, n_z, nb, 1), 1, n_z, nb, nullptr, nullptr, nearest_out, n_skipped_out);
         return EKF_OK;
     }
-    EKF_TRY(gate_reserve(h, most, max_cand > 0 ? dup_cap_for(max_cand < 4096 ? max_cand : 4096) : 0));  // (a call that finds more grows the list below)
+    EKF_TRY(gate_reserve(h, most, max_cand > 0 ? list_cap_for(max_cand) : 0));
     const EkfDev &dv = h->dv;
     hipStream_t s = h->s_chain;
-    const int zcap = h->gate.zcap, n_max = most_landmarks(counts_of(h, b0), nb);
+    const int zcap = h->map.gate.zcap, n_max = most_landmarks(counts_of(h, b0), nb);
     const GateTable tab = plan_gate_table(z, R, valid, n_z, nb, zcap);
     const size_t at0 = (size_t)b0 * zcap, nent = (size_t)nb * zcap;
     std::vector<int> cnt((size_t)nb, 0), skip(nent);
     std::vector<ekf_decision> near(nent);
     std::vector<ekf_candidate> got;
-    struct Drain {  // the asynchronous copies use the pageable buffers above: a return with one in flight waits for the stream before they go
-        hipStream_t s;
-        bool armed;
-        ~Drain() {
-            if (armed) (void)hipStreamSynchronize(s);
-        }
-    } drain{s, true};
-    HIP_TRY(hipMemcpyAsync(h->gate.z + 2 * at0, tab.zt.data(), sizeof(double) * 2 * nent, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->gate.Rm + 4 * at0, tab.Rt.data(), sizeof(double) * 4 * nent, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(h->gate.nz + b0, tab.cnt.data(), sizeof(int) * (size_t)nb, hipMemcpyHostToDevice, s));
+    HostCopies hc(s);
+    HIP_TRY(hc.copy(h->map.gate.z + 2 * at0, tab.zt.data(), sizeof(double) * 2 * nent, hipMemcpyHostToDevice));
+    HIP_TRY(hc.copy(h->map.gate.Rm + 4 * at0, tab.Rt.data(), sizeof(double) * 4 * nent, hipMemcpyHostToDevice));
+    HIP_TRY(hc.copy(h->map.gate.nz + b0, tab.cnt.data(), sizeof(int) * (size_t)nb, hipMemcpyHostToDevice));
     for (int round = 0;; round++) {
-        const GateScratch gs = h->gate;
-        drain.armed = true;
+        const GateScratch gs = h->map.gate;
         HIP_TRY(hipMemsetAsync(gs.cnt + b0, 0, sizeof(int) * (size_t)nb, s));
         if (n_max > 0) hipLaunchKernelGGL(k_gate, dim3((unsigned)cdiv(n_max, GATE_THREADS), (unsigned)nb), dim3(GATE_THREADS), 0, s, dv, gs, gate, b0);
         if (round == 0) hipLaunchKernelGGL(k_gate_nearest, dim3((unsigned)cdiv(most, 64), (unsigned)nb), dim3(64), 0, s, dv, gs, b0);
-        HIP_TRY(hipMemcpyAsync(cnt.data(), gs.cnt + b0, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hc.copy(cnt.data(), gs.cnt + b0, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost));
         if (round == 0) {
-            HIP_TRY(hipMemcpyAsync(near.data(), gs.near + at0, sizeof(ekf_decision) * nent, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipMemcpyAsync(skip.data(), gs.skip + at0, sizeof(int) * nent, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hc.copy(near.data(), gs.near + at0, sizeof(ekf_decision) * nent, hipMemcpyDeviceToHost));
+            HIP_TRY(hc.copy(skip.data(), gs.skip + at0, sizeof(int) * nent, hipMemcpyDeviceToHost));
         }
-        HIP_TRY(stream_wait(s));
-        drain.armed = false;
+        HIP_TRY(hc.wait());
         EKF_TRY(check_launch());
         const int most_found = most_landmarks(cnt.data(), nb);
         if (most_found <= gs.ccap || max_cand == 0) break;
         if (round > 0) return set_error(EKF_ERR_STATE, "the candidate count changed between two passes over an unchanged state");
-        EKF_TRY(gate_reserve(h, most, dup_cap_for(most_found)));
+        EKF_TRY(gate_reserve(h, most, plan_grown_cap(0, most_found, 256)));
     }
     // the lists back in ONE copy, a row of the longest list per filter (what lies behind a filter's own count is not looked at)
     const size_t row = max_cand > 0 ? (size_t)most_landmarks(cnt.data(), nb) : 0;
     got.resize((size_t)nb * row);
     if (row > 0) {
-        drain.armed = true;
-        HIP_TRY(hipMemcpy2DAsync(got.data(), row * sizeof(ekf_candidate), h->gate.list + (size_t)b0 * h->gate.ccap, (size_t)h->gate.ccap * sizeof(ekf_candidate),
-                                 row * sizeof(ekf_candidate), (size_t)nb, hipMemcpyDeviceToHost, s));
-        HIP_TRY(stream_wait(s));
-        drain.armed = false;
+        HIP_TRY(hc.copy2d(got.data(), row * sizeof(ekf_candidate), h->map.gate.list + (size_t)b0 * h->map.gate.ccap, (size_t)h->map.gate.ccap * sizeof(ekf_candidate),
+                          row * sizeof(ekf_candidate), (size_t)nb, hipMemcpyDeviceToHost));
+        HIP_TRY(hc.wait());
     }
     for (int k = 0; k < nb; k++) {
         if (n_found_out) n_found_out[k] = cnt[k];
@@ -858,21 +779,6 @@ extern "C" int ekf_batch_gate_candidates(ekf_handle h, const double *z, const do
 }
 
 // ---- joint compatibility search -------------------------------------------------------------------
-// The scratch of ekf_associate_joint (ekf_assoc.hip: AssocScratch): the candidate table, the chosen landmarks and the search's
-// record, 2 328 bytes per filter whatever the capacity: one block at the first call that searches; ekf_reserve builds it again.
-static int assoc_reserve(ekf_batch *h) {
-    DevBlock &blk = h->kept[BLK_ASSOC];
-    if (blk.p) return EKF_OK;
-    const size_t B = (size_t)h->dv.B, per = EKF_MAX_PENDING * (2 + EKF_ASSOC_MAX_BRANCH);
-    EKF_TRY(block_alloc(h, &blk, B * (sizeof(AssocResult) + per * sizeof(int)), /*zero*/ true));
-    AssocScratch &as = h->assoc;
-    as.out = (AssocResult *)blk.p;
-    as.ncand = (int *)(as.out + B);
-    as.cand = as.ncand + B * EKF_MAX_PENDING;
-    as.ids = as.cand + B * EKF_MAX_PENDING * EKF_ASSOC_MAX_BRANCH;
-    return EKF_OK;
-}
-
 extern "C" int ekf_joint_gates(double confidence, double *out) {
     if (!out || !plan_assoc_gates(confidence, out)) return set_error(EKF_ERR_BAD_ARG, "bad argument (a confidence inside (0, 1))");
     return EKF_OK;
@@ -920,25 +826,21 @@ static int assoc_impl(ekf_batch *h, Filters f, const double *z, const double *R,
         EKF_TRY(settle(h));
         EKF_TRY(assoc_reserve(h));
         EKF_TRY(match_reserve(h, EKF_MAX_PENDING));
-        const AssocScratch as = h->assoc;
-        const MatchScratch ms = h->match;
+        const AssocScratch as = h->map.assoc;
+        const MatchScratch ms = h->map.match;
         hipStream_t s = h->s_chain;
         const size_t per = EKF_MAX_PENDING;
         std::vector<AssocResult> out((size_t)nb);
         ids.resize((size_t)nb * per), d2.resize((size_t)nb * ms.zcap), ld_d2 = (size_t)ms.zcap;
-        // (every copy uses a pageable buffer of this function: the first failure stops the enqueueing, and the stream is waited for on every way out)
-        hipError_t e = hipMemcpyAsync(as.ncand + b0 * per, tab.ncand.data(), sizeof(int) * nb * per, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(as.cand + b0 * per * EKF_ASSOC_MAX_BRANCH, tab.cand.data(), sizeof(int) * nb * per * EKF_ASSOC_MAX_BRANCH, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_assoc_search, dim3((unsigned)nb), dim3(64), 0, s, h->dv, h->gate, as, ms, aa, h->win.buf_in, b0);
-            hipLaunchKernelGGL(k_match_factor, dim3((unsigned)nb), dim3(256), 0, s, h->dv, h->fuse, ms, h->win.buf_in, 0, EKF_MAX_PENDING, /*apply*/ 0, b0);
-            e = hipMemcpyAsync(ids.data(), as.ids + b0 * per, sizeof(int) * nb * per, hipMemcpyDeviceToHost, s);
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out.data(), as.out + b0, sizeof(AssocResult) * (size_t)nb, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost, s);
-        const hipError_t w = stream_wait(s);
-        HIP_TRY(e);
-        HIP_TRY(w);
+        HostCopies hc(s);
+        HIP_TRY(hc.copy(as.ncand + b0 * per, tab.ncand.data(), sizeof(int) * nb * per, hipMemcpyHostToDevice));
+        HIP_TRY(hc.copy(as.cand + b0 * per * EKF_ASSOC_MAX_BRANCH, tab.cand.data(), sizeof(int) * nb * per * EKF_ASSOC_MAX_BRANCH, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_assoc_search, dim3((unsigned)nb), dim3(64), 0, s, h->dv, h->map.gate, as, ms, aa, h->win.buf_in, b0);
+        hipLaunchKernelGGL(k_match_factor, dim3((unsigned)nb), dim3(256), 0, s, h->dv, h->map.fuse, ms, h->win.buf_in, 0, EKF_MAX_PENDING, /*apply*/ 0, b0);
+        HIP_TRY(hc.copy(ids.data(), as.ids + b0 * per, sizeof(int) * nb * per, hipMemcpyDeviceToHost));
+        HIP_TRY(hc.copy(out.data(), as.out + b0, sizeof(AssocResult) * (size_t)nb, hipMemcpyDeviceToHost));
+        HIP_TRY(hc.copy(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hc.wait());
         EKF_TRY(check_launch());
         for (int k = 0; k < nb; k++) info[k].nodes = out[k].nodes, info[k].d2 = out[k].d2, info[k].n_paired = out[k].n_paired, info[k].complete = out[k].complete;
     }
@@ -962,22 +864,6 @@ extern "C" int ekf_batch_associate_joint(ekf_handle h, const double *z, const do
 }
 
 // ---- landmark initialisation ----------------------------------------------------------------------
-// The scratch of ekf_add_landmarks (ekf_rewrite.hip: AddScratch).  It follows the longest list a call has brought, not the capacity:
-// one block for 64 additions per filter at the first call that adds, replaced by one twice the size until the list fits; ekf_reserve
-// builds it again as large as it was.
-static int add_reserve(ekf_batch *h, int n_meas) {
-    AddScratch &as = h->add;
-    const int zcap = plan_add_zcap(as.zcap, n_meas);
-    DevBlock &blk = h->kept[BLK_ADD];
-    if (blk.p && zcap == as.zcap) return EKF_OK;
-    const size_t B = (size_t)h->dv.B, ntab = B * add_tab_stride(zcap), nops = B * zcap * 8;
-    EKF_TRY(block_alloc(h, &blk, (ntab + nops) * sizeof(double), /*zero*/ true));
-    as.tab = (double *)blk.p;
-    as.ops = as.tab + ntab;
-    as.zcap = zcap;
-    return EKF_OK;
-}
-
 // The filters f, filter f.b0 + k with the n_z measurements at z + k * n_z * 2 and R + k * n_z * 4, of which add + k * n_z selects
 // (the caller has run plan_add_args).  Nothing selected anywhere: the counts from the mirror, the window stays open.  Else the
 // join's order: settle, the room (one filter without it ends the call: not sticky, nothing has run), the table up in one copy, the
@@ -997,24 +883,22 @@ static int add_impl(ekf_batch *h, Filters f, const double *z, const double *R, c
     // every deferred slot folded, both streams idle
     EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
     EkfDev &dv = h->dv;
-    const int zcap = plan_add_zcap(h->add.zcap, most);
+    const int zcap = plan_add_zcap(h->map.add.zcap, most);
     const AddTable tab = plan_add_table(z, R, add, n_z, nb, zcap);
     EKF_TRY(set_error(plan_add_room(counts_of(h, b0), tab.cnt.data(), b0, nb, dv.Ncap, "add")));
     EKF_TRY(add_reserve(h, most));
-    const AddScratch as = h->add;
+    const AddScratch as = h->map.add;
     std::vector<int> ids((size_t)nb * (n_z > 0 ? n_z : 0)), n_new((size_t)nb);
     int nt, m_hi;
     plan_add_ids(tab, counts_of(h, b0), n_z, nb, zcap, ids.data(), n_new.data(), &nt, &m_hi);
     hipStream_t s = h->s_chain;
-    struct Drain {  // the asynchronous copy uses the pageable table above: a return with it in flight waits for the stream first
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{s};
-    HIP_TRY(hipMemcpyAsync(as.tab + (size_t)b0 * add_tab_stride(zcap), tab.tab.data(), sizeof(double) * tab.tab.size(), hipMemcpyHostToDevice, s));
+    HostCopies hc(s);
+    HIP_TRY(hc.copy(as.tab + (size_t)b0 * add_tab_stride(zcap), tab.tab.data(), sizeof(double) * tab.tab.size(), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_add_vec, dim3((unsigned)cdiv(m_hi, 64), (unsigned)nb), dim3(64), 0, s, dv, as, b0);
     if (nt > 0) hipLaunchKernelGGL(k_add_tiles, dim3((unsigned)nt, (unsigned)nb), dim3(256), 0, s, dv, h->win.buf_in, as, b0);
     hipLaunchKernelGGL(k_add_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, as, b0);
     EKF_TRY(finish_rewrite(h, b0, nb, /*rearm*/ true, nullptr, 0, /*flip_buf*/ false));
+    hc.waited();
     if (ids_out && !ids.empty()) memcpy(ids_out, ids.data(), sizeof(int) * ids.size());
     for (int k = 0; k < nb; k++) n_out[k] = n_new[k];
     return EKF_OK;
@@ -1083,9 +967,10 @@ extern "C" int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, i
     const int cnt = N < n_max ? N : n_max;
     if (cnt == 0) return N;
     std::vector<double> comp((size_t)3 * cnt);  // the three components of the always-current diagonal blocks
-    HIP_TRY(hipMemcpy2DAsync(comp.data(), (size_t)cnt * sizeof(double), h->dv.D + (size_t)index * 3 * h->dv.dn, (size_t)h->dv.dn * sizeof(double),
-                             (size_t)cnt * sizeof(double), 3, hipMemcpyDeviceToHost, h->s_chain));
-    HIP_TRY(stream_wait(h->s_chain));
+    HostCopies hc(h->s_chain);
+    HIP_TRY(hc.copy2d(comp.data(), (size_t)cnt * sizeof(double), h->dv.D + (size_t)index * 3 * h->dv.dn, (size_t)h->dv.dn * sizeof(double), (size_t)cnt * sizeof(double), 3,
+                      hipMemcpyDeviceToHost));
+    HIP_TRY(hc.wait());
     for (int l = 0; l < cnt; l++)
         for (int c = 0; c < 3; c++) cov_out[3 * l + c] = comp[(size_t)c * cnt + l];
     return N;

@@ -44,6 +44,14 @@ __attribute__((format(printf, 2, 3))) inline PlanStatus plan_fail(int code, cons
 
 inline int most_landmarks(const int *n_lm, int nb) { return nb > 0 ? std::max(0, *std::max_element(n_lm, n_lm + nb)) : 0; }
 
+// The one growth rule of the kept scratch (ekf_map_scratch.h): the entries per filter a table or list holds for `need` when the
+// handle's holds `have` -- at least `floor`, doubled until it fits, never shrunk (tests/cpp/map_scratch_check.cpp).
+inline int plan_grown_cap(int have, long long need, int floor) {
+    long long cap = have > floor ? have : floor;
+    while (cap < need) cap *= 2;
+    return (int)cap;
+}
+
 // A map of n landmarks (and joined: more behind them) that a handle of capacity Ncap cannot hold; joined < 0: n alone.
 inline PlanStatus plan_no_room(int filter, int n, int joined, int Ncap, const char *verb) {
     if (joined < 0) return plan_fail(EKF_ERR_CAPACITY, "filter %d: %d landmarks do not fit capacity_landmarks = %d (ekf_reserve, then %s again)", filter, n, Ncap, verb);
@@ -451,12 +459,8 @@ inline PlanStatus plan_add_args(const double *z, const double *R, const unsigned
         }
     return {};
 }
-// The entries a table holds for a longest list of `most` when the handle's holds `have`: at least 64, doubled until the list fits.
-inline int plan_add_zcap(int have, int most) {
-    int zcap = have > 64 ? have : 64;
-    while (zcap < most) zcap *= 2;
-    return zcap;
-}
+// The entries a table holds for a longest list of `most` when the handle's holds `have`: the growth rule from 64.
+inline int plan_add_zcap(int have, int most) { return plan_grown_cap(have, most, 64); }
 // The table k_add_vec and k_add_tiles read (AddScratch::tab of the call's filters), ONE block so that one copy carries it: nb records
 // of add_tab_stride(zcap) doubles (ekf_device.h), record k = {count, 0, then zcap entries {z_x, z_y, R00, R10, R01, R11}} with the
 // entries that are not added left out; cnt [nb] = the counts again, src [nb][zcap] = the caller's index of each entry (increasing).

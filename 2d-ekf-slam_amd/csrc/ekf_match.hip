@@ -27,17 +27,8 @@
 // A pivot counts as positive when it exceeds MATCH_PIVOT_TOL times its own diagonal entry of S: what is left of an exactly singular
 // S after the elimination (the same landmark measured twice with R = 0) is rounding noise of either sign, a few 2^-52 of that entry.
 
-#define MATCH_TAB 8                // doubles per measurement in MatchScratch::tab: H_R row 0, H_R row 1, cos phi, sin phi
 #define MATCH_PIVOT_TOL 0x1p-44
-struct MatchScratch {
-    double *z;    // [B][zcap][2]  the call's measurements, the skipped ones left out
-    double *Rm;   // [B][zcap][4]  their covariances, column-major
-    double *d2;   // [B][zcap]     running joint distance within each measurement's round (NaN from a refused pivot on)
-    double *tab;  // [B][EKF_MAX_PENDING][MATCH_TAB]  the round's table, k_match_factor to k_match_gather
-    int *ids;     // [B][zcap]     their landmarks
-    int *cnt;     // [B]           measurements in the list
-    int zcap;
-};
+#include "ekf_map_scratch.h"  // MatchScratch, MATCH_TAB
 
 // measurements of filter b in round `round` of rounds of rs
 __device__ __forceinline__ int match_round_count(const MatchScratch &ms, int b, int round, int rs) {

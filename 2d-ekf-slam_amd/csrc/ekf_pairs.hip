@@ -14,13 +14,7 @@
 // by (i, j)), a degenerate pair is counted the same way: every value written is a function of the pair alone, so the sorted list
 // has the same bits on every call and in the batch form.
 
-struct DupScratch {
-    double *box;         // [B][dn / 32][4]  {min x, max x, min y, max y} of landmarks [32 g, 32 g + 32) (below the filter's count)
-    int *cnt;            // [B][2]           {pairs found, degenerate pairs} of the call
-    int *split;          // [B]              the batch form's per-filter splits
-    ekf_dup_pair *list;  // [B][cap]         the first cap pairs appended
-    int cap;
-};
+#include "ekf_map_scratch.h"  // DupScratch
 
 // What a call carries in its kernel arguments; md2 < 0: no Euclidean bound.
 struct DupArgs {

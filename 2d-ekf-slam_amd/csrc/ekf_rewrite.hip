@@ -633,11 +633,7 @@ __global__ void k_join_finish(EkfDev dv, JoinSrc sv, Rot2 one, const double *rot
 // The table (ekf_device.h: add_tab_stride) and the operand rows live in a scratch the handle keeps; a record's count is a double.
 // The launch covers filters b0 + blockIdx.y.
 // ---------------------------------------------------------------------------------------------
-struct AddScratch {
-    double *tab;  // [B][add_tab_stride(zcap)]
-    double *ops;  // [B][zcap][2]{w0, w1, w2, h}
-    int zcap;
-};
+#include "ekf_map_scratch.h"  // AddScratch
 __device__ __forceinline__ const double *add_record(const AddScratch &as, int b) { return as.tab + (size_t)b * add_tab_stride(as.zcap); }
 
 __global__ __launch_bounds__(64) void k_add_vec(EkfDev dv, AddScratch as, int b0) {

@@ -47,6 +47,14 @@ def test_map_plan_checks_and_tables(tmp_path):
     assert out.returncode == 0 and "map plan ok" in out.stdout, out.stdout + out.stderr
 
 
+def test_kept_scratch_layout_and_growth_rule(tmp_path):
+    """csrc/ekf_map_scratch.h and plan_grown_cap called directly (tests/cpp/map_scratch_check.cpp): every kept block's size is the
+    byte count the hand-written reserve functions computed, its arrays are aligned, disjoint and fill it, at capacities around the
+    tile and workgroup edges; the growth rule against a brute-force loop."""
+    out = run_cpp_check(tmp_path, "map_scratch_check")
+    assert out.returncode == 0 and "map scratch ok" in out.stdout, out.stdout + out.stderr
+
+
 def test_bench_case_table_and_byte_model():
     assert b_ext.CASES == list(b_ext.TABLE)
     c = {case: b_ext.parse(case) for case in b_ext.CASES}

@@ -267,3 +267,117 @@ def test_scratch_of_joint_find_and_fuse_follows_a_reserve_together(pkg, pipeline
     round_of_calls([(17, 36), (1, 30)], same_capacity=True, rises=False)
     assert [int(n) for n in a.num_landmarks()] == [36, 36]
     a.close()
+
+
+def test_scratch_of_matched_gate_assoc_and_add_follows_a_reserve_together(pkg, pipeline_mode):
+    """The other rows of the kept scratch's table (csrc/ekf_api.hip: MapKept): ekf_joint_compat and ekf_update_matched, ekf_gate_candidates,
+    ekf_associate_joint and ekf_add_landmarks each keep device scratch in the handle -- tables that follow the longest list a call
+    has brought, a candidate list that follows what was found -- and ekf_reserve builds every block again, as large as it was.  One
+    handle (two filters of 40 landmarks in capacity 64) makes the five calls (8 measurements of the 8 nearest landmarks, a gate wide
+    enough to list pairs, 3 new landmarks), grows to 96 -- a third tile -- and makes them again.  Every call's results are bit for
+    bit those of a twin of the handle's capacity that holds the same state (ekf_set_state of the handle's export) and makes that
+    call as its first of the kind, with no scratch yet; after the reserve that is a twin created at capacity 96.  ekf_device_bytes
+    rises at the first call of each kind, rises with the reserve and is the same figure after each call behind it."""
+    import add_ref
+    import match_ref as mr
+    from helpers import assert_bitwise
+
+    B, CAP0, CAP1, NZ = 2, 64, 96, 8
+    a = pkg.FilterBatch(B, CAP0, max_pending=8, log_capacity=4096)
+    for b in range(B):
+        a.set_state(*pkg.scenarios.injected_state(40, seed=320 + b, extent=15.0), index=b)
+
+    def twin():
+        t = pkg.FilterBatch(B, a.capacity, max_pending=8, log_capacity=4096)
+        for b in range(B):
+            t.set_state(*a.get_state(b), index=b)
+        return t
+
+    def scan(seed):
+        """A noisy measurement of each filter's NZ nearest landmarks at the handle's state now: z [B][NZ][2], R [B][NZ][2][2], ids [B][NZ]."""
+        z, R, ids = np.empty((B, NZ, 2)), np.empty((B, NZ, 2, 2)), np.empty((B, NZ), dtype=np.int32)
+        for b in range(B):
+            x = a.get_state(b)[0]
+            L = x[3:].reshape(-1, 2)
+            ids[b] = np.argsort(np.hypot(L[:, 0] - x[0], L[:, 1] - x[1]), kind="stable")[:NZ]
+            z[b], R[b] = mr.scan_of(pkg, x, ids[b], seed + b)
+        return z, R, ids
+
+    def gate(f, z, R, max_cand=1024):
+        """ekf_batch_gate_candidates at gate 25, asked for up to 1024 pairs per filter whatever the capacity, per filter (pairs,
+        found, nearest, skipped).  FilterBatch.gate_candidates asks for at most n_z * capacity, and so does ekf_associate_joint's
+        own sweep: 512 before the reserve, 768 behind it.  The device list follows what a call asks for (doubled from 256), so
+        only a list that holds 1024 from its first call on stays as it is across the reserve."""
+        import ctypes
+        ek = pkg.ekfslam
+        z, Rc, _, n_z = f._scan_lists(z, R, None, None)
+        buf, found = np.empty((B, max_cand), dtype=ek.CAND_DTYPE), np.zeros(B, dtype=np.int32)
+        near, skip = np.zeros((B, n_z), dtype=ek.DECISION_DTYPE), np.zeros((B, n_z), dtype=np.int32)
+        ek._chk(f.L.ekf_batch_gate_candidates(f.h, ek._p(z), ek._p(Rc), None, n_z, 25.0, buf.ctypes.data_as(ctypes.POINTER(ek.EkfCandidate)), max_cand,
+                                              found.ctypes.data_as(ek._ip), near.ctypes.data_as(ctypes.POINTER(ek.EkfDecision)), skip.ctypes.data_as(ek._ip)))
+        assert int(found.max()) <= max_cand
+        return [(buf[b, :int(found[b])].copy(), int(found[b]), near[b].copy(), skip[b].copy()) for b in range(B)]
+
+    def same_states(t, what):
+        for b in range(B):
+            sa = a.get_state(b)
+            assert_bitwise(sa, t.get_state(b), "%s, filter %d" % (what, b))
+            assert_bitwise_symmetric(sa[1])
+
+    def round_of_calls(seed, first_new, rises):
+        def moved(what, before):
+            assert (a.device_bytes() > before) if rises else (a.device_bytes() == before), (what, before, a.device_bytes())
+
+        z, R, ids = scan(seed)
+        # the score of the pairing, then the pairing applied
+        t, before = twin(), a.device_bytes()
+        da, dt = a.joint_compat(z, R, ids, index=None), t.joint_compat(z, R, ids, index=None)
+        assert da.tobytes() == dt.tobytes() and np.all(np.isfinite(da)), "joint compat"
+        moved("joint compat", before)
+        before = a.device_bytes()
+        (na, da), (nt, dt) = a.update_matched(z, R, ids, index=None), t.update_matched(z, R, ids, index=None)
+        assert list(na) == list(nt) == [NZ] * B and da.tobytes() == dt.tobytes(), "update matched"
+        same_states(t, "update matched")
+        moved("update matched", before)
+        t.close()
+        # the compatibility table of a scan at the new state
+        z, R, ids = scan(seed + 10)
+        t, before = twin(), a.device_bytes()
+        ga, gt = gate(a, z, R), gate(t, z, R)
+        for b in range(B):
+            print("filter %d: %d pairs listed" % (b, ga[b][1]))
+            assert ga[b][1] == gt[b][1] >= NZ and len(ga[b][0]) == ga[b][1]
+            for k in (0, 2, 3):
+                assert ga[b][k].tobytes() == gt[b][k].tobytes(), ("gate candidates", b, k)
+        moved("gate candidates", before)
+        t.close()
+        # the search over it
+        t, before = twin(), a.device_bytes()
+        sa, st = a.associate_joint(z, R, index=None), t.associate_joint(z, R, index=None)
+        for b in range(B):
+            assert int(sa[b][2]["n_paired"]) > 0  # (something was searched)
+            for k in range(5):
+                assert sa[b][k].tobytes() == st[b][k].tobytes(), ("associate joint", b, k)
+        moved("associate joint", before)
+        t.close()
+        # three new landmarks
+        zn, Rn = add_ref.grid_scan(pkg, 3, first=first_new)
+        zn, Rn = np.tile(zn, (B, 1, 1)), np.tile(Rn, (B, 1, 1, 1))
+        t, before = twin(), a.device_bytes()
+        n0 = [int(n) for n in a.num_landmarks()]
+        (na, ia), (nt, it) = a.add_landmarks(zn, Rn, index=None), t.add_landmarks(zn, Rn, index=None)
+        assert list(na) == list(nt) == [n + 3 for n in n0] and ia.tobytes() == it.tobytes(), "add landmarks"
+        same_states(t, "add landmarks")
+        moved("add landmarks", before)
+        t.close()
+
+    round_of_calls(seed=500, first_new=0, rises=True)
+    assert [int(n) for n in a.num_landmarks()] == [43, 43]
+    held, before = [a.get_state(b) for b in range(B)], a.device_bytes()
+    a.reserve(CAP1)
+    assert a.capacity == CAP1 and a.device_bytes() > before
+    for b in range(B):
+        assert_bitwise(a.get_state(b), held[b], "filter %d across the reserve" % b)
+    round_of_calls(seed=600, first_new=3, rises=False)
+    assert [int(n) for n in a.num_landmarks()] == [46, 46]
+    a.close()
