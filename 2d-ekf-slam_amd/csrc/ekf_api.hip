@@ -37,6 +37,7 @@
 #include "ekf_pairs.hip"
 #include "ekf_fuse.hip"
 #include "ekf_match.hip"
+#include "ekf_fix.hip"
 #include "ekf_extract.hip"
 #include "ekf_gate.hip"
 #include "ekf_assoc.hip"
@@ -138,9 +139,11 @@ enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_MATCH, BLK_GATE, BLK_GAT
 //   BLK_DUP        dup     ekf_find_duplicates                         the capacity                          yes
 //   BLK_DUP_LIST   dup     ekf_find_duplicates                         the pairs asked for or found (cap,    no
 //                                                                      from 256)
-//   BLK_FUSE       fuse    ekf_fuse_landmarks, ekf_update_matched      the capacity                          yes
+//   BLK_FUSE       fuse    ekf_fuse_landmarks, ekf_update_matched,     the capacity                          yes
+//                          ekf_update_fixes
 //   BLK_MATCH      match   ekf_update_matched, ekf_joint_compat,       the longest list brought (zcap,       yes
-//                          ekf_associate_joint that searches           from 64)
+//                          ekf_associate_joint that searches,          from 64)
+//                          ekf_update_fixes, ekf_fix_compat
 //   BLK_GATE       gate    ekf_gate_candidates with a valid entry      the longest scan brought (zcap, from  yes
 //                                                                      64) and the capacity (npart)
 //   BLK_GATE_LIST  gate    ekf_gate_candidates that hands pairs out,   the pairs asked for or found (ccap,   no
@@ -1507,6 +1510,8 @@ static int sticky_status(ekf_batch *h, bool include_capacity) {
 //   ekf_fuse_landmarks (and the batch form)            QUIET_SETTLED  ST_INVALID_OR_FULL   the pair list is checked first, against the mirror's counts; no pair: returns
 //   ekf_update_matched (and the batch form)            QUIET_SETTLED  ST_INVALID_OR_FULL   values checked first, ids against the mirror's counts; no measurement: returns
 //   ekf_joint_compat (and the batch form)              QUIET_STREAM   ST_INVALID           ids checked; no measurement: returns; else settle(); the state is only read
+//   ekf_update_fixes (and the batch form)              QUIET_SETTLED  ST_INVALID_OR_FULL   as ekf_update_matched: values checked first, landmark ids against the mirror's counts; no entry: returns
+//   ekf_fix_compat (and the batch form)                QUIET_STREAM   ST_INVALID           as ekf_joint_compat
 //   ekf_add_landmarks (and the batch form)             QUIET_SETTLED  ST_INVALID_OR_FULL   values checked first; nothing selected: returns (an add without room fails after the settle)
 //   ekf_update_joint (and the batch form)              ekf_associate_joint's, then ekf_update_matched's, then ekf_add_landmarks' (the room is checked between the first two)
 //   ekf_extract_map, ekf_batch_extract_map             source: QUIET_STREAM, ST_INVALID, ids checked, settle(); then the destination:

@@ -696,6 +696,107 @@ extern "C" int ekf_batch_joint_compat(ekf_handle h, const double *z, const doubl
     return compat_impl(h, filters_of(h, -1), z, R, ids, n_z, d2_out);
 }
 
+// ---- absolute fixes -------------------------------------------------------------------------------
+// match_impl with the kernels of ekf_fix.hip: the same checks in the same order (plan_fix_values before the handle is touched,
+// plan_fix_ids against the mirror's counts), the same scratch (MatchScratch, its ids carrying the kinds), the same rounds and the
+// same end.  What match_impl never meets: a call none of whose filters has a landmark (a position or heading fix on a fresh
+// filter) -- the gather, k_fuse_apply and the pass would be launches of zero blocks, so the round is the factor and k_fuse_finish
+// (P_RR and the pose) alone.
+static int fix_impl(ekf_batch *h, Filters f, const double *z, const double *R, const int *what, int n, int *n_applied_out, double *d2_out) {
+    const int b0 = f.b0, nb = f.nb;
+    EKF_TRY(set_error(plan_fix_values(z, R, what, n, b0, nb, -1)));
+    HIP_TRY(hipSetDevice(h->device));
+    EKF_TRY(refresh_bounds(h, false));
+    int most;
+    EKF_TRY(set_error(plan_fix_ids(what, n, counts_of(h, b0), b0, nb, &most)));
+    if (most == 0) {  // nothing to do: the window stays open
+        for (int k = 0; n_applied_out && k < nb; k++) n_applied_out[k] = 0;
+        for (size_t q = 0; d2_out && q < (size_t)nb * n; q++) d2_out[q] = __builtin_nan("");
+        return nb == 1 ? h->h_int[b0] : EKF_OK;
+    }
+    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
+    EKF_TRY(fuse_reserve(h));
+    EKF_TRY(match_reserve(h, most));
+    EkfDev &dv = h->dv;
+    const FuseScratch fs = h->map.fuse;
+    const MatchScratch ms = h->map.match;
+    hipStream_t s = h->s_chain;
+    const MatchTable tab = plan_fix_table(z, R, what, n, nb, ms.zcap);
+    std::vector<int> done((size_t)2 * nb, 0);
+    std::vector<double> d2((size_t)nb * ms.zcap);
+    HostCopies hc(s);
+    EKF_TRY(match_upload(h, tab, b0, nb, &hc));
+    HIP_TRY(hipMemsetAsync(fs.done + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
+    HIP_TRY(hipMemsetAsync(fs.m_round + b0, 0, sizeof(int) * (size_t)nb, s));
+    const int n_max = most_landmarks(counts_of(h, b0), nb), nT = lm_tiles(n_max);
+    for (int round = 0; round * dv.maxp < most; round++) {
+        const int m_hi = most - round * dv.maxp < dv.maxp ? most - round * dv.maxp : dv.maxp;
+        hipLaunchKernelGGL(k_fix_factor, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->win.buf_in, round, dv.maxp, /*apply*/ 1, b0);
+        if (n_max > 0) {
+            hipLaunchKernelGGL(k_fix_gather, dim3((unsigned)cdiv(n_max, 256), (unsigned)m_hi, (unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->win.buf_in, round, b0);
+            hipLaunchKernelGGL(k_fuse_apply, dim3((unsigned)cdiv(64 * nT, 256), (unsigned)nb), dim3(256), 0, s, dv, fs, b0);
+        }
+        hipLaunchKernelGGL(k_fuse_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0);
+        if (n_max > 0) launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->win.buf_in, h->win.buf_in, nullptr, /*rev*/ 0, b0, nb);
+    }
+    HIP_TRY(hc.copy(done.data(), fs.done + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost));
+    HIP_TRY(hc.copy(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hc.wait());
+    EKF_TRY(check_launch());
+    for (int k = 0; n_applied_out && k < nb; k++) n_applied_out[k] = done[2 * k];  // (filled even where the end of the rewrite fails)
+    match_scatter(tab, d2, ms.zcap, n, nb, done.data(), d2_out);
+    const std::vector<int> n_lm(counts_of(h, b0), counts_of(h, b0) + nb);
+    EKF_TRY(finish_rewrite(h, b0, nb, /*rearm*/ true, n_lm.data(), 1, /*flip_buf*/ false));
+    return nb == 1 ? n_lm[0] : EKF_OK;
+}
+
+extern "C" int ekf_update_fixes(ekf_handle h, int index, const double *z, const double *R, const int *what, int n, int *n_applied_out, double *d2_out) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return fix_impl(h, filters_of(h, index), z, R, what, n, n_applied_out, d2_out);
+}
+
+extern "C" int ekf_batch_update_fixes(ekf_handle h, const double *z, const double *R, const int *what, int n, int *n_applied_out, double *d2_out) {
+    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
+    const int rc = fix_impl(h, filters_of(h, -1), z, R, what, n, n_applied_out, d2_out);
+    return rc < 0 ? rc : EKF_OK;
+}
+
+// The score alone, as compat_impl: k_fix_factor with apply = 0 over one round of up to EKF_MAX_PENDING, d2 back.
+static int fix_compat_impl(ekf_batch *h, Filters f, const double *z, const double *R, const int *what, int n, double *d2_out) {
+    const int b0 = f.b0, nb = f.nb;
+    if (!d2_out && n > 0) return set_error(EKF_ERR_BAD_ARG, "d2_out is null");
+    EKF_TRY(set_error(plan_fix_values(z, R, what, n, b0, nb, EKF_MAX_PENDING)));
+    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
+    int most;
+    EKF_TRY(set_error(plan_fix_ids(what, n, counts_of(h, b0), b0, nb, &most)));
+    for (size_t q = 0; q < (size_t)nb * (n > 0 ? n : 0); q++) d2_out[q] = __builtin_nan("");
+    if (most == 0) return EKF_OK;  // (nothing is folded)
+    EKF_TRY(settle(h));
+    EKF_TRY(match_reserve(h, most));
+    const MatchScratch ms = h->map.match;
+    hipStream_t s = h->s_chain;
+    const MatchTable tab = plan_fix_table(z, R, what, n, nb, ms.zcap);
+    std::vector<double> d2((size_t)nb * ms.zcap);
+    HostCopies hc(s);
+    EKF_TRY(match_upload(h, tab, b0, nb, &hc));
+    hipLaunchKernelGGL(k_fix_factor, dim3((unsigned)nb), dim3(256), 0, s, h->dv, h->map.fuse, ms, h->win.buf_in, 0, EKF_MAX_PENDING, /*apply*/ 0, b0);
+    HIP_TRY(hc.copy(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(hc.wait());
+    EKF_TRY(check_launch());
+    match_scatter(tab, d2, ms.zcap, n, nb, nullptr, d2_out);
+    return EKF_OK;
+}
+
+extern "C" int ekf_fix_compat(ekf_handle h, int index, const double *z, const double *R, const int *what, int n, double *d2_out) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return fix_compat_impl(h, filters_of(h, index), z, R, what, n, d2_out);
+}
+
+extern "C" int ekf_batch_fix_compat(ekf_handle h, const double *z, const double *R, const int *what, int n, double *d2_out) {
+    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
+    return fix_compat_impl(h, filters_of(h, -1), z, R, what, n, d2_out);
+}
+
 // ---- individual compatibility ---------------------------------------------------------------------
 // The filters f, filter f.b0 + k with the n_z measurements at z + k * n_z * 2 and R + k * n_z * 4 (valid + k * n_z masks them).  The
 // values are checked before anything happens to the handle; a call without a measurement returns there.  Then the rule of

@@ -1,9 +1,9 @@
 // ekf_map_plan.h -- the host-side planning of the map operations (ekf_map_api.hip) as pure code: the checks of the lists a caller
-// hands in and the tables the kernels of ekf_rewrite.hip, ekf_extract.hip, ekf_pairs.hip, ekf_fuse.hip, ekf_match.hip and ekf_gate.hip read.  No HIP call and no
-// handle in here: landmark counts come in as plain arrays, n_lm[k] = landmarks of the k-th filter of the call, whose number in its
+// hands in and the tables the kernels of ekf_rewrite.hip, ekf_extract.hip, ekf_pairs.hip, ekf_fuse.hip, ekf_match.hip, ekf_fix.hip
+// and ekf_gate.hip read.  No HIP call and no handle in here: landmark counts come in as plain arrays, n_lm[k] = landmarks of the k-th filter of the call, whose number in its
 // handle is b0 + k (error texts name that number).  A check reports a status and a text; the caller hands both to set_error.
-// tests/cpp/map_plan_check.cpp, tests/cpp/match_plan_check.cpp, tests/cpp/gate_plan_check.cpp, tests/cpp/assoc_plan_check.cpp and
-// tests/cpp/add_plan_check.cpp run all of it on the CPU.
+// tests/cpp/map_plan_check.cpp, tests/cpp/match_plan_check.cpp, tests/cpp/fix_plan_check.cpp, tests/cpp/gate_plan_check.cpp,
+// tests/cpp/assoc_plan_check.cpp and tests/cpp/add_plan_check.cpp run all of it on the CPU.
 #pragma once
 #include <math.h>
 #include <stdarg.h>
@@ -257,6 +257,71 @@ inline MatchTable plan_match_table(const double *z, const double *R, const int *
             t.zt[2 * to] = z[2 * at], t.zt[2 * to + 1] = z[2 * at + 1];
             for (int e = 0; e < 4; e++) t.Rt[4 * to + e] = R[4 * at + e];
             t.idt[to] = ids[at], t.src[to] = q;
+        }
+    return t;
+}
+
+// ---- absolute fixes (ekf_update_fixes, ekf_fix_compat) ----------------------------------------------------------------------------
+// The lists of nb filters, filter k's n entries at z + k * n * 2, R + k * n * 4 and what + k * n; what[q] == EKF_FIX_SKIP: no
+// entry (its z and R are not looked at).  Checked before the handle is touched: the pointers, n, every kind >= EKF_FIX_HEADING, the
+// values a kind reads finite (EKF_FIX_HEADING: z[0] and R[0] alone, and R[0] not negative), and at most `limit` entries per filter
+// (limit < 0: any number).
+inline PlanStatus plan_fix_values(const double *z, const double *R, const int *what, int n, int b0, int nb, int limit) {
+    if (n < 0) return plan_fail(EKF_ERR_BAD_ARG, "negative entry count");
+    if (n > 0 && (!z || !R || !what)) return plan_fail(EKF_ERR_BAD_ARG, "a null list with n > 0");
+    for (int k = 0; k < nb; k++) {
+        int kept = 0;
+        for (int q = 0; q < n; q++) {
+            const size_t at = (size_t)k * n + q;
+            const int w = what[at];
+            if (w < EKF_FIX_HEADING)
+                return plan_fail(EKF_ERR_BAD_ARG, "filter %d, entry %d: kind %d (a landmark, EKF_FIX_POSITION, EKF_FIX_HEADING or EKF_FIX_SKIP)", b0 + k, q, w);
+            if (w == EKF_FIX_SKIP) continue;
+            kept++;
+            if (w == EKF_FIX_HEADING) {
+                if (!__builtin_isfinite(z[2 * at]) || !__builtin_isfinite(R[4 * at])) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, entry %d: z or R is not finite", b0 + k, q);
+                if (R[4 * at] < 0.0) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, entry %d: a negative heading variance", b0 + k, q);
+            } else if (!plan_entry_finite(z, R, at)) {
+                return plan_fail(EKF_ERR_BAD_ARG, "filter %d, entry %d: z or R is not finite", b0 + k, q);
+            }
+        }
+        if (limit >= 0 && kept > limit) return plan_fail(EKF_ERR_BAD_ARG, "filter %d: %d entries in one list (at most %d)", b0 + k, kept, limit);
+    }
+    return {};
+}
+// ... and the landmark entries against the landmark counts n_lm[k], once they are current.  *most = the most entries of a filter.
+inline PlanStatus plan_fix_ids(const int *what, int n, const int *n_lm, int b0, int nb, int *most) {
+    *most = 0;
+    for (int k = 0; k < nb; k++) {
+        int kept = 0;
+        for (int q = 0; q < n; q++) {
+            const int w = what[(size_t)k * n + q];
+            if (w == EKF_FIX_SKIP) continue;
+            if (w >= n_lm[k]) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, entry %d: landmark id %d is not one of its %d landmarks", b0 + k, q, w, n_lm[k]);
+            kept++;
+        }
+        *most = std::max(*most, kept);
+    }
+    return {};
+}
+// The tables k_fix_factor reads, in the shape of plan_match_table (idt carries the kinds; src the caller's index of each entry):
+// the skipped entries left out, and of a heading entry z[0] and R[0] alone -- the rest of its row stays 0.
+inline MatchTable plan_fix_table(const double *z, const double *R, const int *what, int n, int nb, int zcap) {
+    MatchTable t;
+    t.zt.assign((size_t)nb * zcap * 2, 0.0), t.Rt.assign((size_t)nb * zcap * 4, 0.0);
+    t.idt.assign((size_t)nb * zcap, 0), t.src.assign((size_t)nb * zcap, -1), t.cnt.assign((size_t)nb, 0);
+    for (int k = 0; k < nb; k++)
+        for (int q = 0; q < n; q++) {
+            const size_t at = (size_t)k * n + q;
+            if (what[at] == EKF_FIX_SKIP || t.cnt[k] >= zcap) continue;
+            const size_t to = (size_t)k * zcap + t.cnt[k]++;
+            const bool heading = what[at] == EKF_FIX_HEADING;
+            t.zt[2 * to] = z[2 * at], t.Rt[4 * to] = R[4 * at];
+            if (!heading) {
+                t.zt[2 * to + 1] = z[2 * at + 1];
+                for (int e = 1; e < 4; e++) t.Rt[4 * to + e] = R[4 * at + e];
+            }
+            t.idt[to] = what[at], t.src[to] = q;
         }
     return t;
 }

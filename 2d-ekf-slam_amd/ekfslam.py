@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("EKFSLAM_LIB", os.path.join(_HERE, "lib", "libekfslam_
 
 OK, ERR_BAD_ARG, ERR_CAPACITY, ERR_HIP, ERR_NO_DEVICE, ERR_STATE, ERR_TIMEOUT = 0, -1, -2, -3, -4, -5, -6
 NEW, OLD, IGNORE = 1, 2, 3
+FIX_SKIP, FIX_POSITION, FIX_HEADING = -1, -2, -3  # the kinds of ekf_update_fixes beside a landmark number
 
 # every symbol include/ekfslam_c.h declares
 ABI_SYMBOLS = [
@@ -31,6 +32,7 @@ ABI_SYMBOLS = [
     "ekf_find_duplicates", "ekf_batch_find_duplicates",
     "ekf_fuse_landmarks", "ekf_batch_fuse_landmarks",
     "ekf_update_matched", "ekf_batch_update_matched", "ekf_joint_compat", "ekf_batch_joint_compat",
+    "ekf_update_fixes", "ekf_batch_update_fixes", "ekf_fix_compat", "ekf_batch_fix_compat",
     "ekf_gate_candidates", "ekf_batch_gate_candidates",
     "ekf_associate_joint", "ekf_batch_associate_joint", "ekf_joint_gates",
     "ekf_add_landmarks", "ekf_batch_add_landmarks", "ekf_update_joint", "ekf_batch_update_joint",
@@ -167,6 +169,10 @@ def load():
     L.ekf_batch_update_matched.argtypes = [_H, _dp, _dp, _ip, ctypes.c_int, _ip, _dp]
     L.ekf_joint_compat.argtypes = [_H, ctypes.c_int, _dp, _dp, _ip, ctypes.c_int, _dp]
     L.ekf_batch_joint_compat.argtypes = [_H, _dp, _dp, _ip, ctypes.c_int, _dp]
+    L.ekf_update_fixes.argtypes = [_H, ctypes.c_int, _dp, _dp, _ip, ctypes.c_int, _ip, _dp]
+    L.ekf_batch_update_fixes.argtypes = [_H, _dp, _dp, _ip, ctypes.c_int, _ip, _dp]
+    L.ekf_fix_compat.argtypes = [_H, ctypes.c_int, _dp, _dp, _ip, ctypes.c_int, _dp]
+    L.ekf_batch_fix_compat.argtypes = [_H, _dp, _dp, _ip, ctypes.c_int, _dp]
     L.ekf_gate_candidates.argtypes = [_H, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.POINTER(EkfCandidate), ctypes.c_int,
                                       ctypes.POINTER(EkfDecision), _ip]
     L.ekf_batch_gate_candidates.argtypes = [_H, _dp, _dp, _up, ctypes.c_int, ctypes.c_double, ctypes.POINTER(EkfCandidate), ctypes.c_int, _ip,
@@ -660,6 +666,90 @@ class FilterBatch:
             _chk(self.L.ekf_joint_compat(self.h, int(index), _p(z), _p(Rc), a.ctypes.data_as(_ip), n_z, _p(d2)))
         return d2
 
+    def _fix_lists(self, z, R, what, index):
+        """(z, Rc, what, n) as ekf_update_fixes takes them.  With an index: what [n], z [n][2], R [n][2][2], and a heading entry may
+        be given as a scalar z[k] with a scalar variance R[k] (a single heading fix: three scalars); index=None: a leading batch
+        axis on all three, every entry with two values of z and four of R (ragged lists: pad what with FIX_SKIP)."""
+        lead = (self.batch,) if index is None else ()
+        a = np.asarray(what, dtype=np.int64)
+        if a.ndim == 0 and not lead:
+            a, z, R = a.reshape(1), [z], [R]
+        if a.ndim != len(lead) + 1 or a.shape[:len(lead)] != lead:
+            raise ValueError("what must be [batch][n]" if lead else "what must be [n]")
+        if a.size and (a.min() < FIX_HEADING or a.max() > np.iinfo(np.int32).max):
+            raise ValueError("a kind is a landmark number, FIX_POSITION, FIX_HEADING or FIX_SKIP")
+        n = a.shape[-1]
+
+        def as_array(v):
+            try:
+                return np.asarray(v, dtype=np.float64)
+            except ValueError:  # ragged: scalars among the entries
+                return None
+
+        za, Ra = as_array(z), as_array(R)
+        if za is not None and Ra is not None and za.size == a.size * 2 and Ra.size == a.size * 4:  # (the lists of _matched_lists)
+            Rc = _f64(np.swapaxes(Ra.reshape(lead + (n, 2, 2)), -1, -2).reshape(lead + (n, 4)))  # column-major blocks
+            return _f64(za.reshape(lead + (n, 2))), Rc, np.ascontiguousarray(a, dtype=np.int32), n
+
+        def entries(v, arr, width, name):
+            """v as [count][width] values, an entry given as one scalar standing for (scalar, 0, ..); and the mask of those."""
+            count = a.size
+            if lead or (arr is not None and arr.size not in (count, count * width)) or (arr is None and len(v) != count):
+                raise ValueError("%s must hold %d values per entry for %d entries" % (name, width, n))
+            if arr is not None and arr.size == count * width:
+                return arr.reshape(count, width), np.zeros(count, dtype=bool)
+            out, scalar = np.zeros((count, width)), np.zeros(count, dtype=bool)
+            for k in range(count):
+                e = np.asarray(arr.reshape(-1)[k] if arr is not None else v[k], dtype=np.float64).reshape(-1)
+                if e.size not in (1, width):
+                    raise ValueError("%s[%d] must hold %d values (or one, for a heading entry)" % (name, k, width))
+                out[k, :e.size], scalar[k] = e, e.size == 1
+            return out, scalar
+
+        zz, zs = entries(z, za, 2, "z")
+        RR, Rs = entries(R, Ra, 4, "R")
+        flat = a.reshape(-1)
+        if np.any((zs | Rs) & (flat != FIX_HEADING) & (flat != FIX_SKIP)):
+            raise ValueError("only a heading entry takes a scalar z and a scalar variance")
+        Rc = np.swapaxes(RR.reshape(-1, 2, 2), -1, -2).reshape(-1, 4)  # column-major blocks (a scalar's [[R, 0], [0, 0]] is its own)
+        return _f64(zz.reshape(n, 2)), _f64(Rc), np.ascontiguousarray(a, dtype=np.int32), n
+
+    def update_fixes(self, z, R, what, index=0):
+        """Apply absolute observations on the device (ekf_update_fixes): entry k is of kind what[k] -- FIX_POSITION (z = the robot's
+        position, R 2x2), FIX_HEADING (z = the heading, R its variance; both may be scalars), a landmark number (z = its position)
+        or FIX_SKIP.  The entries run as joint updates in rounds of `window`; gates, counters and the decision log are not involved.
+        Returns (n_landmarks, n_applied, d2): n_applied < the number of non-skipped entries when a round's S was not positive
+        definite (that round and the later ones were not applied), d2[k] the joint Mahalanobis distance of k's round up to and
+        including k (NaN: skipped or not applied).  index=None: every filter in one launch sequence (ekf_batch_update_fixes), what
+        [batch][n]; returns (n_applied (batch,), d2 (batch, n))."""
+        z, Rc, a, n = self._fix_lists(z, R, what, index)
+        d2 = np.full(a.shape, np.nan)
+        ptrs = (_p(z), _p(Rc), a.ctypes.data_as(_ip)) if n else (None, None, None)
+        if index is None:
+            applied = np.zeros(self.batch, dtype=np.int32)
+            _chk(self.L.ekf_batch_update_fixes(self.h, *ptrs, n, applied.ctypes.data_as(_ip), _p(d2) if n else None))
+            return applied, d2
+        applied = ctypes.c_int(0)
+        cnt = _chk(self.L.ekf_update_fixes(self.h, int(index), *ptrs, n, ctypes.byref(applied), _p(d2) if n else None))
+        return cnt, applied.value, d2
+
+    def fix_compat(self, z, R, what, index=0):
+        """The score of one list of fixes (ekf_fix_compat), nothing applied: d2[k] is the joint Mahalanobis distance of the list cut
+        after entry k (at most 32 non-skipped entries; NaN: skipped, or behind a refused pivot of S) -- the chi-square test of a fix
+        before it is applied.  The same bits as update_fixes' d2 for a list that fits one round.  index=None: what [batch][n],
+        returns d2 (batch, n)."""
+        z, Rc, a, n = self._fix_lists(z, R, what, index)
+        if int((a != FIX_SKIP).sum(axis=-1).max(initial=0)) > 32:
+            raise ValueError("a list to score holds at most 32 entries")
+        d2 = np.full(a.shape, np.nan)
+        if n == 0:
+            return d2
+        if index is None:
+            _chk(self.L.ekf_batch_fix_compat(self.h, _p(z), _p(Rc), a.ctypes.data_as(_ip), n, _p(d2)))
+        else:
+            _chk(self.L.ekf_fix_compat(self.h, int(index), _p(z), _p(Rc), a.ctypes.data_as(_ip), n, _p(d2)))
+        return d2
+
     def _scan_lists(self, z, R, valid, index):
         """(z, Rc, valid or None, n_z) as ekf_gate_candidates takes them.  With an index: z [n_z][2], R [n_z][2][2]; index=None: a
         leading batch axis on both, and on valid [batch][n_z]."""
@@ -1012,6 +1102,17 @@ class KalmanFilter:
     def joint_compat(self, z, R, ids):
         """The running joint Mahalanobis distance of one association hypothesis (FilterBatch.joint_compat); nothing is applied."""
         return self._f.joint_compat(z, R, ids, 0)
+
+    def update_fixes(self, z, R, what):
+        """Apply absolute position, heading and landmark fixes as joint updates (FilterBatch.update_fixes): (n_landmarks, n_applied,
+        d2); refreshes X, Y, Phi."""
+        out = self._f.update_fixes(z, R, what, 0)
+        self._mirror()
+        return out
+
+    def fix_compat(self, z, R, what):
+        """The running joint Mahalanobis distance of one list of fixes (FilterBatch.fix_compat); nothing is applied."""
+        return self._f.fix_compat(z, R, what, 0)
 
     def associate_joint(self, z, R, gate=9.21, joint_gate=None, max_branch=8, max_nodes=65536):
         """The joint-compatibility search of a scan (FilterBatch.associate_joint): (ids, d2, info, nearest, n_skipped); nothing is

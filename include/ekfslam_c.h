@@ -437,6 +437,59 @@ int ekf_batch_update_matched(ekf_handle h, const double *z /*[batch][n_z][2]*/, 
 int ekf_joint_compat(ekf_handle h, int index, const double *z, const double *R, const int *ids, int n_z, double *d2_out /*[n_z]*/);
 int ekf_batch_joint_compat(ekf_handle h, const double *z, const double *R, const int *ids, int n_z, double *d2_out /*[batch][n_z]*/);
 
+/* Absolute observations, applied on the device as joint updates: a position fix of the robot (GNSS, an overhead camera), a heading
+ * from another source, a surveyed position of a landmark.  The reference's one absolute observation is its scalar compass
+ * (kalmanfilter.cpp:96-130, called at slam.cpp:144-147; here ekf_update_compass); this is its generalisation, the contract that of
+ * ekf_update_matched with another H.  Entry k of the call is of kind what[k]: */
+#define EKF_FIX_SKIP     (-1)  /* no observation: z and R not looked at */
+#define EKF_FIX_POSITION (-2)  /* z = (x_R, y_R) + v,  cov(v) = R (2x2, layout of ekf_update_matched) */
+#define EKF_FIX_HEADING  (-3)  /* z[0] = phi + v,  var(v) = R[0];  z[1], R[1..3] not looked at */
+/* what[k] >= 0: z = L_what[k] + v, a fix of that landmark's position (0-based, as in ekf_remove_landmarks).
+ * The non-skipped entries run in rounds of at most ekf_window(h) in list order.  A round is ONE update, every entry one slot, two
+ * columns of W; with n = 3 + 2N and e_r the unit vectors:
+ *     POSITION:    rows e_0, e_1 of H;           columns P[:, 0], P[:, 1];            d = (x_R - z_0, y_R - z_1)
+ *     HEADING:     row e_2 and an inert row;     columns P[:, 2], 0;                  d = (wrap(phi - z_0), 0)
+ *     landmark i:  rows e_{3+2i}, e_{4+2i};      columns P[:, 3+2i], P[:, 4+2i];      d = L_i - z
+ *     S = H W + blockdiag(R_k) = U^T U (from the upper triangle: of R's off-diagonal pair R(0,1) is used);
+ *     V = W U^-1;   y = U^-T d;   x <- x - V y;   P <- P - V V^T.
+ * wrap(e) = e - 2 pi floor((e + pi) / (2 pi)), in [-pi, pi); the heading itself stays unwrapped afterwards, as everywhere else.
+ * The inert row of a heading entry has a zero row and column of S, the diagonal entry exactly 1 and d = 0: its pivot is 1, its y
+ * and its column of V are exact zeros.  Nothing is linearised, so the result depends on how the list is cut into rounds by rounding
+ * alone.  R = 0 is legal (a hard fix); the same thing may be fixed several times in one round where R keeps S regular.
+ * S of a round counts as not positive definite by ekf_update_matched's rule: a pivot not above 2^-44 of its own diagonal entry of S
+ * (or NaN), e.g. the same thing fixed twice with R = 0.  That round and all later ones are then NOT applied: the state is that after
+ * the completed rounds and *n_applied_out (may be NULL) < the number of non-skipped entries says so.  A result, not an error.
+ * d2_out[k] (may be NULL): the running sum of y^2 of k's round up to and including k -- the joint Mahalanobis distance of the
+ * round's entries so far; NaN for skipped and for unapplied entries.  A HEADING fix alone in a round: wrap(phi - z)^2 / (P_phiphi + R).
+ * Checked on the host before the handle is touched: n < 0, a NULL z / R / what with n > 0, what < -3, a non-finite value among
+ * those a kind reads (HEADING: z[0] and R[0] only), a negative R[0] of a heading entry, an index out of range -- EKF_ERR_BAD_ARG;
+ * then landmark ids against the landmark count (id >= N: EKF_ERR_BAD_ARG, the state untouched).  n = 0, or every entry skipped,
+ * is a no-op that leaves an open window open.  A POSITION or HEADING fix is valid on a filter without landmarks.
+ * Otherwise, as ekf_update_matched: deferred slots are folded first, a streaming launch is stopped (immediate-mode calls stream
+ * again afterwards), each round costs one dense pass over P_LL (in place, in either pipeline mode), a sticky EKF_ERR_TIMEOUT /
+ * EKF_ERR_CAPACITY is returned unchanged with nothing modified, counters and decision log stay as they are, the host mirror shows
+ * the new pose and P_RR, every device buffer ends as ekf_set_state of the result would leave it, and the call synchronises.  No
+ * atomics, one writer per value, every sum in a fixed order: the same bits on every call, and filter b of the batch form gets the
+ * bits of the one-filter call on b.
+ * ekf_update_fixes returns the landmark count (unchanged) or a negative status; the batch form takes filter b's lists at
+ * z + b * n * 2, R + b * n * 4, what + b * n (ragged lists: pad with EKF_FIX_SKIP) and returns EKF_OK or a negative status.
+ * The scratch is that of ekf_update_matched (the same blocks: a handle that has made either call has them). */
+int ekf_update_fixes(ekf_handle h, int index, const double *z /*[n][2]*/, const double *R /*[n][4], column-major 2x2*/,
+                     const int *what /*[n]*/, int n, int *n_applied_out /* may be NULL */, double *d2_out /*[n] or NULL*/);
+int ekf_batch_update_fixes(ekf_handle h, const double *z /*[batch][n][2]*/, const double *R /*[batch][n][4]*/,
+                           const int *what /*[batch][n]*/, int n, int *n_applied_out /*[batch] or NULL*/,
+                           double *d2_out /*[batch][n] or NULL*/);
+
+/* The score of ONE list of fixes, nothing applied -- the chi-square test to run on a GNSS outlier before applying it: the same S,
+ * factor and y as a round of ekf_update_fixes (the same kernel) for at most EKF_MAX_PENDING = 32 non-skipped entries, whatever the
+ * window; more is EKF_ERR_BAD_ARG, and so is everything ekf_update_fixes refuses, and a NULL d2_out with n > 0.  d2_out[k]: the
+ * joint distance of the list cut after entry k; NaN for skipped entries, and from the first refused pivot on (the call still
+ * returns EKF_OK).  For a list that fits one round of ekf_update_fixes the two calls give the same bits of d2.  The filter is only
+ * read, behind the rule of ekf_joint_compat (deferred slots folded, a streaming launch stopped; a sticky EKF_ERR_TIMEOUT ends the
+ * call, a sticky EKF_ERR_CAPACITY does not); a list without an entry folds nothing. */
+int ekf_fix_compat(ekf_handle h, int index, const double *z, const double *R, const int *what, int n, double *d2_out /*[n]*/);
+int ekf_batch_fix_compat(ekf_handle h, const double *z, const double *R, const int *what, int n, double *d2_out /*[batch][n]*/);
+
 /* Where the hypotheses come from: the individual compatibility table of a scan.  For every measurement k and every landmark l of
  * the filter, res, S (symmetrised) and d2 = res^T S^-1 res of the association sweep (Update.cpp:103-136), EVERY measurement against
  * the same, unchanged state -- not the sequential chain of ekf_update.  z and R use the layouts of ekf_batch_update; cos phi and
