@@ -11,18 +11,12 @@
 // k_fuse_apply, k_fuse_finish and the dense pass over set 0 run unchanged.  z[1] and R[1..3] of a heading entry are not read.
 //
 // Not on the hot path: once per call and round on a settled handle, all streams idle.  Included by ekf_api.hip behind ekf_match.hip
-// (MATCH_PIVOT_TOL, match_round_count; FuseScratch, fuse_block, fuse_cholesky of ekf_fuse.hip); blocks of P come through
-// fuse_block and the R rows, the slot rows through fuse_slot_offset.
-//
-// A round (at most dv.maxp entries of every filter of the call), on the chain stream:
-//   k_fix_factor  one workgroup per filter: every column's state row; A = [S | d | W_R^T] straight from P_RR, the R rows and the
-//                 blocks (i_k, i_l); the Cholesky of k_match_factor with the same pivot rule; the running sum of y^2 per entry.
-//                 apply != 0: U, y, V's robot rows, the slot flags and the progress record as k_match_factor leaves them
-//   k_fix_gather  W's landmark rows into the FA slot rows, one thread per (landmark, entry) of the filters that take part
-//   k_fuse_apply, k_fuse_finish, k_flush_rb over set 0: as in a fusion round
-// The factor runs BEFORE the gather: a filter whose S is refused gathers nothing.  ekf_fix_compat is k_fix_factor alone with
-// apply = 0 and a round of up to EKF_MAX_PENDING: the same code, so the same bits of d2 for a list that fits one round.
-// One writer per value, every sum in a fixed order, no atomics: the same bits on every call and in the batch form.
+// (MATCH_PIVOT_TOL, match_round_count) and ekf_fuse.hip, whose header says what the machinery takes from a client and what it
+// gives back.  This client's own, per round of at most dv.maxp entries of every filter:
+//   k_fix_factor  every column's state row; A = [S | d | W_R^T] straight from P_RR, the R rows and the blocks (i_k, i_l); the pivot
+//                 rule of k_match_factor
+//   k_fix_gather  W's landmark rows, one thread per (landmark, entry) of the filters that take part: from the R rows or fuse_block
+// The factor runs BEFORE the gather, and ekf_fix_compat is k_fix_factor alone with apply = 0, as in ekf_match.hip.
 
 #define FIX_ROW_NONE (-1)  // the inert row of a heading entry
 
@@ -107,36 +101,9 @@ __global__ __launch_bounds__(256) void k_fix_factor(EkfDev dv, FuseScratch fs, M
         __syncthreads();
         bad = fuse_cholesky<true>(A, M, NC, tid, sFloor);
     }
-    if (tid == 0 && m > 0) {  // the joint distance of the round cut after each entry; NaN from the refused pivot on
-        double acc = 0.0;
-        for (int k = 0; k < m; k++) {
-            const bool have = !bad || 2 * k + 1 < bad - 1;
-            acc = acc + A[2 * k][M] * A[2 * k][M];
-            acc = acc + A[2 * k + 1][M] * A[2 * k + 1][M];
-            ms.d2[z0 + k] = have ? acc : __builtin_nan("");
-        }
-    }
+    if (tid == 0 && m > 0) fuse_prefix_d2(ms.d2 + z0, A, m, bad);
     if (!apply) return;
-    const bool ok = m > 0 && !bad;
-    if (ok) {
-        double *U = fs.U + (size_t)b * FUSE_MAX_COLS * FUSE_MAX_COLS;
-        double *wr = fs.wr + (size_t)b * 4 * FUSE_MAX_COLS;
-        for (int idx = tid; idx < M * M; idx += 256) {
-            const int a = idx / M, c = idx - a * M;
-            U[a * FUSE_MAX_COLS + c] = c >= a ? A[a][c] : 0.0;
-        }
-        for (int idx = tid; idx < 4 * M; idx += 256) {
-            const int r = idx / M, a = idx - r * M;
-            wr[(size_t)r * FUSE_MAX_COLS + a] = A[a][M + ((r + 1) & 3)];
-        }
-    }
-    if (tid < dv.maxp) dv.slot_active[((size_t)b * 2) * dv.maxp + tid] = ok && tid < m ? 1 : 0;
-    if (tid == 0) {
-        dv.n_lm_flush[(size_t)b * 2] = ok ? dv.n_lm[b] : 0;  // (0: the pass skips every tile of this filter)
-        fs.m_round[b] = ok ? m : 0;
-        if (ok) fs.done[2 * b] += m;
-        if (bad) fs.done[2 * b + 1] = bad;
-    }
+    fuse_publish(dv, fs, A, b, m, bad, tid);
 }
 
 // grid (landmarks / 256, entries of the round, filters); behind k_fix_factor, which has accepted fs.m_round[b] entries.
@@ -162,7 +129,5 @@ __global__ __launch_bounds__(256) void k_fix_gather(EkfDev dv, FuseScratch fs, M
                 w[2 * e + f] = rc < 0 ? 0.0 : filt_R(dv, b, rc)[3 + 2 * l + e];
             }
     }
-    double *fa = dv.FA + (size_t)b * 2 * dv.f_stride;
-    *(double2_t *)(fa + fuse_slot_offset(dv.rows, 2 * l, 2 * k)) = (double2_t){w[0], w[1]};
-    *(double2_t *)(fa + fuse_slot_offset(dv.rows, 2 * l + 1, 2 * k)) = (double2_t){w[2], w[3]};
+    fuse_store_w(dv, b, l, k, w);
 }

@@ -21,6 +21,14 @@
 // A filter whose S is not positive definite stops: k_fuse_factor records the pivot, leaves its slots inactive and sizes its pass
 // to zero tiles; this round and the later ones return at once for it, and nothing of it but the slot rows (cleared at the end of
 // the call) has been written.
+//
+// The machinery and its clients (fusion here, ekf_match.hip, ekf_fix.hip).  A client supplies, per round, a factor kernel -- one
+// workgroup per filter that fills A = [S | d | W_R^T] in LDS, runs fuse_cholesky and ends in fuse_publish -- and a gather kernel
+// that leaves W's landmark rows in the FA slot rows (fuse_store_w), for the entries fuse_publish accepted (fs.m_round) or, in front
+// of the factor, for all of them.  It gets back x -= V y and P -= V V^T from k_fuse_apply, k_fuse_finish and the pass, the count
+// of applied entries and the refused pivot in fs.done, and from fuse_prefix_d2 the joint distance cut after every entry.  The host
+// side of a round is fuse_rounds (ekf_map_api.hip).  A client keeps the rule above -- one writer per value, every sum in a fixed
+// order, no atomics -- and so the same bits on every call and in the batch form.
 
 #include "ekf_map_scratch.h"  // FuseScratch, FUSE_MAX_COLS
 
@@ -49,6 +57,14 @@ __device__ __forceinline__ void fuse_block(const F &dv, const double *bm, const 
     t[0] = half ? v[0][1] : v[0][0], t[1] = half ? v[0][3] : v[0][2], t[2] = half ? v[1][1] : v[1][0], t[3] = half ? v[1][3] : v[1][2];
     const bool tr = s.where == FW_BM_T;
     m[0] = t[0], m[1] = tr ? t[2] : t[1], m[2] = tr ? t[1] : t[2], m[3] = t[3];
+}
+
+// The rows of landmark l in column pair k of W (w: element (row e, column f) at 2 e + f) into filter b's FA slot rows: the end of
+// a list client's gather (k_fuse_gather forms its differences in the stores themselves).
+__device__ __forceinline__ void fuse_store_w(const EkfDev &dv, int b, int l, int k, const double w[4]) {
+    double *fa = dv.FA + (size_t)b * 2 * dv.f_stride;
+    *(double2_t *)(fa + fuse_slot_offset(dv.rows, 2 * l, 2 * k)) = (double2_t){w[0], w[1]};
+    *(double2_t *)(fa + fuse_slot_offset(dv.rows, 2 * l + 1, 2 * k)) = (double2_t){w[2], w[3]};
 }
 
 // grid (landmarks / 256, pairs of the round, filters)
@@ -102,6 +118,47 @@ __device__ __forceinline__ int fuse_cholesky(double (*A)[FUSE_LD], int M, int NC
     return 0;
 }
 
+// The end of every client's factor kernel, by the 256 threads of filter b's workgroup behind fuse_cholesky (m entries, `bad` its
+// return value): U, y and V's robot rows into the scratch, the slot flags of set 0, the size of the pass, and the progress record
+// -- fs.m_round[b] = the entries the rest of the round applies (0: k_fuse_apply, k_fuse_finish and the client's gather return at
+// once), fs.done[2 b] += them, fs.done[2 b + 1] = the refused pivot (1 + its index), which stops the filter for the later rounds.
+__device__ __forceinline__ void fuse_publish(const EkfDev &dv, const FuseScratch &fs, double (*A)[FUSE_LD], int b, int m, int bad, int tid) {
+    const int M = 2 * m;
+    const bool ok = m > 0 && !bad;
+    if (ok) {
+        double *U = fs.U + (size_t)b * FUSE_MAX_COLS * FUSE_MAX_COLS;
+        double *wr = fs.wr + (size_t)b * 4 * FUSE_MAX_COLS;
+        for (int idx = tid; idx < M * M; idx += 256) {
+            const int a = idx / M, c = idx - a * M;
+            U[a * FUSE_MAX_COLS + c] = c >= a ? A[a][c] : 0.0;
+        }
+        for (int idx = tid; idx < 4 * M; idx += 256) {
+            const int r = idx / M, a = idx - r * M;
+            wr[(size_t)r * FUSE_MAX_COLS + a] = A[a][M + ((r + 1) & 3)];
+        }
+    }
+    if (tid < dv.maxp) dv.slot_active[((size_t)b * 2) * dv.maxp + tid] = ok && tid < m ? 1 : 0;
+    if (tid == 0) {
+        dv.n_lm_flush[(size_t)b * 2] = ok ? dv.n_lm[b] : 0;  // (0: the pass skips every tile of this filter)
+        fs.m_round[b] = ok ? m : 0;
+        if (ok) fs.done[2 * b] += m;
+        if (bad) fs.done[2 * b + 1] = bad;
+    }
+}
+
+// The joint distance of a round cut after each of its m entries, by one thread behind fuse_cholesky: d2[k] = the sum of y^2 up to
+// and including entry k, every addition in this order; NaN from the refused pivot on.
+__device__ __forceinline__ void fuse_prefix_d2(double *d2, double (*A)[FUSE_LD], int m, int bad) {
+    const int M = 2 * m;
+    double acc = 0.0;
+    for (int k = 0; k < m; k++) {
+        const bool have = !bad || 2 * k + 1 < bad - 1;
+        acc = acc + A[2 * k][M] * A[2 * k][M];
+        acc = acc + A[2 * k + 1][M] * A[2 * k + 1][M];
+        d2[k] = have ? acc : __builtin_nan("");
+    }
+}
+
 __global__ __launch_bounds__(256) void k_fuse_factor(EkfDev dv, FuseScratch fs, int round, double slack, int b_off) {
     __shared__ double A[FUSE_MAX_COLS][FUSE_LD];
     const int b = b_off + blockIdx.x;
@@ -128,25 +185,7 @@ __global__ __launch_bounds__(256) void k_fuse_factor(EkfDev dv, FuseScratch fs, 
         __syncthreads();
         bad = fuse_cholesky<false>(A, M, NC, tid, nullptr);
     }
-    const bool ok = m > 0 && !bad;
-    if (ok) {
-        double *U = fs.U + (size_t)b * FUSE_MAX_COLS * FUSE_MAX_COLS;
-        for (int idx = tid; idx < M * M; idx += 256) {
-            const int a = idx / M, c = idx - a * M;
-            U[a * FUSE_MAX_COLS + c] = c >= a ? A[a][c] : 0.0;
-        }
-        for (int idx = tid; idx < 4 * M; idx += 256) {
-            const int r = idx / M, a = idx - r * M;
-            wr[(size_t)r * FUSE_MAX_COLS + a] = A[a][M + ((r + 1) & 3)];
-        }
-    }
-    if (tid < dv.maxp) dv.slot_active[((size_t)b * 2) * dv.maxp + tid] = ok && tid < m ? 1 : 0;
-    if (tid == 0) {
-        dv.n_lm_flush[(size_t)b * 2] = ok ? dv.n_lm[b] : 0;  // (0: the pass skips every tile of this filter)
-        fs.m_round[b] = ok ? m : 0;
-        if (ok) fs.done[2 * b] += m;
-        if (bad) fs.done[2 * b + 1] = bad;
-    }
+    fuse_publish(dv, fs, A, b, m, bad, tid);
 }
 
 // Thread = landmark-space row ip of filter b_off + blockIdx.y, up to the end of the map's last tile row (rows beyond the map get

@@ -495,13 +495,40 @@ extern "C" int ekf_batch_find_duplicates(ekf_handle h, double gate, double max_d
     return dup_impl(h, filters_of(h, -1), gate, max_dist, 0, split, pairs_out, max_pairs, n_found_out, n_degenerate_out);
 }
 
+// ---- the rounds of the fusion machinery -----------------------------------------------------------
+// What every client's call does around its own kernels (ekf_fuse.hip), on a settled handle with FuseScratch built and the client's
+// tables queued: the progress record of the filters f cleared; per round of at most ekf_window() of the longest list's `most`
+// entries the client's front(round, m_hi) -- m_hi the most entries of a filter in the round; n_max the most landmarks of a filter
+// of the call, the caller's --, which ends with its factor's fuse_publish and W's landmark rows in the FA slot rows, then k_fuse_apply, k_fuse_finish
+// and one dense pass over set 0, in place in the settled buffer in either pipeline mode (also on handles whose chain kernel folds
+// its own windows); last the progress record's copy to done [nb][2], queued on *hc: the caller waits.
+// n_max == 0 -- a position or heading fix where no filter of the call has a landmark; a fused pair or a matched measurement names
+// a landmark of its filter, so for those clients the guards never fail -- would make the gather, k_fuse_apply and the pass launches
+// of zero blocks: the round is the factor and k_fuse_finish (P_RR and the pose) alone.
+template <typename Front>
+static int fuse_rounds(ekf_batch *h, Filters f, int most, int n_max, HostCopies *hc, int *done, Front front) {
+    const EkfDev &dv = h->dv;
+    const FuseScratch fs = h->map.fuse;
+    hipStream_t s = h->s_chain;
+    const int b0 = f.b0, nb = f.nb, nT = lm_tiles(n_max);
+    HIP_TRY(hipMemsetAsync(fs.done + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
+    HIP_TRY(hipMemsetAsync(fs.m_round + b0, 0, sizeof(int) * (size_t)nb, s));
+    for (int round = 0; round * dv.maxp < most; round++) {
+        front(round, std::min(most - round * dv.maxp, dv.maxp));
+        if (n_max > 0) hipLaunchKernelGGL(k_fuse_apply, dim3((unsigned)cdiv(64 * nT, 256), (unsigned)nb), dim3(256), 0, s, dv, fs, b0);
+        hipLaunchKernelGGL(k_fuse_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0);
+        if (n_max > 0) launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->win.buf_in, h->win.buf_in, nullptr, /*rev*/ 0, b0, nb);
+    }
+    HIP_TRY(hc->copy(done, fs.done + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost));
+    return EKF_OK;
+}
+
 // ---- landmark fusion ------------------------------------------------------------------------------
 // The filters f, filter f.b0 + k with n_pairs[k] pairs at pairs + k * ld_pairs.  The list is checked against the mirror's
 // landmark counts before anything else happens to the handle; a call without a pair returns there.  Then: settle, the pair table
-// up, rounds of at most ekf_window() pairs (ekf_fuse.hip; one dense pass each, in place in the settled buffer in either pipeline
-// mode, also on handles whose chain kernel folds its own windows), the progress record back, and the removal of the fused pairs'
-// j through remove_settled, which ends the rewrite.  Nothing fused anywhere: the rewrite is ended here (slot rows cleared, the
-// pass sizes restored).
+// up, the rounds (fuse_rounds: the gather, then the factor), the progress record back, and the removal of the fused pairs' j
+// through remove_settled, which ends the rewrite.  Nothing fused anywhere: the rewrite is ended here (slot rows cleared, the pass
+// sizes restored).
 static int fuse_impl(ekf_batch *h, Filters f, const ekf_dup_pair *pairs, int ld_pairs, const int *n_pairs, double slack, int *n_fused_out, int *n_lm_out) {
     const int b0 = f.b0, nb = f.nb;
     // the one way out: n_lm[k] landmarks in filter b0 + k now, done[2 k] of its pairs fused (done == nullptr: none anywhere)
@@ -530,18 +557,11 @@ static int fuse_impl(ekf_batch *h, Filters f, const ekf_dup_pair *pairs, int ld_
     HostCopies hc(s);
     HIP_TRY(hc.copy(fs.pairs + (size_t)b0 * fs.pcap * 2, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hc.copy(fs.cnt + b0, n_pairs, sizeof(int) * (size_t)nb, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(fs.done + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
-    HIP_TRY(hipMemsetAsync(fs.m_round + b0, 0, sizeof(int) * (size_t)nb, s));
-    const int nT = lm_tiles(n_max);
-    for (int round = 0; round * dv.maxp < most; round++) {
-        const int m_hi = most - round * dv.maxp < dv.maxp ? most - round * dv.maxp : dv.maxp;
+    // the gather runs BEFORE the factor: S is taken from the gathered rows (a fused pair names two landmarks: n_max > 0)
+    EKF_TRY(fuse_rounds(h, f, most, n_max, &hc, done.data(), [&](int round, int m_hi) {
         hipLaunchKernelGGL(k_fuse_gather, dim3((unsigned)cdiv(n_max, 256), (unsigned)m_hi, (unsigned)nb), dim3(256), 0, s, dv, fs, h->win.buf_in, round, b0);
         hipLaunchKernelGGL(k_fuse_factor, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, round, slack, b0);
-        hipLaunchKernelGGL(k_fuse_apply, dim3((unsigned)cdiv(64 * nT, 256), (unsigned)nb), dim3(256), 0, s, dv, fs, b0);
-        hipLaunchKernelGGL(k_fuse_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0);
-        launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->win.buf_in, h->win.buf_in, nullptr, /*rev*/ 0, b0, nb);
-    }
-    HIP_TRY(hc.copy(done.data(), fs.done + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost));
+    }));
     HIP_TRY(hc.wait());
     EKF_TRY(check_launch());
     // the fused pairs' j go, exactly as ekf_remove_landmarks with keep[j] = 0 removes them
@@ -571,7 +591,7 @@ extern "C" int ekf_batch_fuse_landmarks(ekf_handle h, const ekf_dup_pair *pairs,
     return fuse_impl(h, filters_of(h, -1), pairs, ld_pairs, n_pairs, slack, n_fused_out, n_landmarks_out);
 }
 
-// ---- matched updates ------------------------------------------------------------------------------
+// ---- list updates: matched measurements and absolute fixes -----------------------------------------
 // The call's lists into the scratch of filters [b0, b0 + nb), through the caller's guard (the host tables live until it has waited).
 static int match_upload(ekf_batch *h, const MatchTable &t, int b0, int nb, HostCopies *hc) {
     const MatchScratch &ms = h->map.match;
@@ -594,22 +614,32 @@ static void match_scatter(const MatchTable &t, const std::vector<double> &d2, in
     }
 }
 
-// The filters f, filter f.b0 + k with the n_z measurements at z + k * n_z * 2, R + k * n_z * 4, ids + k * n_z.  The values are
-// checked before anything happens to the handle, the ids against the mirror's landmark counts; a call without a measurement returns
-// there.  Then, with the shape of fuse_impl: settle, the tables up, rounds of at most ekf_window() measurements (ekf_match.hip and the
-// apply / finish kernels of ekf_fuse.hip; one dense pass each, in place in the settled buffer in either pipeline mode), the progress
-// record and the distances back in one copy each, and the end of the rewrite (slot rows cleared, the pass sizes restored, the
-// mirror's pose and P_RR refreshed by k_set_meta).
-static int match_impl(ekf_batch *h, Filters f, const double *z, const double *R, const int *ids, int n_z, int *n_applied_out, double *d2_out) {
+// A list client of the fusion machinery: the checks and the tables of its lists (ekf_map_plan.h) and its two kernels.
+struct ListClient {
+    PlanStatus (*values)(const double *z, const double *R, const int *ids, int n, int b0, int nb, int limit);
+    PlanStatus (*ids)(const int *ids, int n, const int *n_lm, int b0, int nb, int *most);
+    MatchTable (*table)(const double *z, const double *R, const int *ids, int n, int nb, int zcap);
+    void (*factor)(EkfDev dv, FuseScratch fs, MatchScratch ms, int buf, int round, int rs, int apply, int b_off);
+    void (*gather)(EkfDev dv, FuseScratch fs, MatchScratch ms, int buf, int round, int b_off);
+};
+static const ListClient MATCHED = {plan_match_values, plan_match_ids, plan_match_table, k_match_factor, k_match_gather};  // ekf_match.hip
+static const ListClient FIXES = {plan_fix_values, plan_fix_ids, plan_fix_table, k_fix_factor, k_fix_gather};              // ekf_fix.hip; ids carries the kinds
+
+// The filters f, filter f.b0 + k with the n entries at z + k * n * 2, R + k * n * 4, ids + k * n.  The values are checked before
+// anything happens to the handle, the ids against the mirror's landmark counts; a call without an entry returns there.  Then:
+// settle, the tables up, the rounds (fuse_rounds: the client's factor, then its gather), the progress record and the distances back
+// in one copy each, and the end of the rewrite (slot rows cleared, the pass sizes restored, the mirror's pose and P_RR refreshed by
+// k_set_meta).
+static int list_update_impl(const ListClient &c, ekf_batch *h, Filters f, const double *z, const double *R, const int *ids, int n, int *n_applied_out, double *d2_out) {
     const int b0 = f.b0, nb = f.nb;
-    EKF_TRY(set_error(plan_match_values(z, R, ids, n_z, b0, nb, -1)));
+    EKF_TRY(set_error(c.values(z, R, ids, n, b0, nb, -1)));
     HIP_TRY(hipSetDevice(h->device));
     EKF_TRY(refresh_bounds(h, false));
     int most;
-    EKF_TRY(set_error(plan_match_ids(ids, n_z, counts_of(h, b0), b0, nb, &most)));
+    EKF_TRY(set_error(c.ids(ids, n, counts_of(h, b0), b0, nb, &most)));
     if (most == 0) {  // nothing to do: the window stays open
         for (int k = 0; n_applied_out && k < nb; k++) n_applied_out[k] = 0;
-        for (size_t q = 0; d2_out && q < (size_t)nb * n_z; q++) d2_out[q] = __builtin_nan("");
+        for (size_t q = 0; d2_out && q < (size_t)nb * n; q++) d2_out[q] = __builtin_nan("");
         return nb == 1 ? h->h_int[b0] : EKF_OK;
     }
     // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
@@ -617,129 +647,21 @@ static int match_impl(ekf_batch *h, Filters f, const double *z, const double *R,
     EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
     EKF_TRY(fuse_reserve(h));
     EKF_TRY(match_reserve(h, most));
-    EkfDev &dv = h->dv;
+    const EkfDev &dv = h->dv;
     const FuseScratch fs = h->map.fuse;
     const MatchScratch ms = h->map.match;
     hipStream_t s = h->s_chain;
-    const MatchTable tab = plan_match_table(z, R, ids, n_z, nb, ms.zcap);
+    const MatchTable tab = c.table(z, R, ids, n, nb, ms.zcap);
     std::vector<int> done((size_t)2 * nb, 0);
     std::vector<double> d2((size_t)nb * ms.zcap);
     HostCopies hc(s);
     EKF_TRY(match_upload(h, tab, b0, nb, &hc));
-    HIP_TRY(hipMemsetAsync(fs.done + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
-    HIP_TRY(hipMemsetAsync(fs.m_round + b0, 0, sizeof(int) * (size_t)nb, s));
-    const int n_max = most_landmarks(counts_of(h, b0), nb), nT = lm_tiles(n_max);
-    for (int round = 0; round * dv.maxp < most; round++) {
-        const int m_hi = most - round * dv.maxp < dv.maxp ? most - round * dv.maxp : dv.maxp;
-        hipLaunchKernelGGL(k_match_factor, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->win.buf_in, round, dv.maxp, /*apply*/ 1, b0);
-        hipLaunchKernelGGL(k_match_gather, dim3((unsigned)cdiv(n_max, 256), (unsigned)m_hi, (unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->win.buf_in, round, b0);
-        hipLaunchKernelGGL(k_fuse_apply, dim3((unsigned)cdiv(64 * nT, 256), (unsigned)nb), dim3(256), 0, s, dv, fs, b0);
-        hipLaunchKernelGGL(k_fuse_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0);
-        launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->win.buf_in, h->win.buf_in, nullptr, /*rev*/ 0, b0, nb);
-    }
-    HIP_TRY(hc.copy(done.data(), fs.done + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost));
-    HIP_TRY(hc.copy(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(hc.wait());
-    EKF_TRY(check_launch());
-    for (int k = 0; n_applied_out && k < nb; k++) n_applied_out[k] = done[2 * k];  // (filled even where the end of the rewrite fails)
-    match_scatter(tab, d2, ms.zcap, n_z, nb, done.data(), d2_out);
-    const std::vector<int> n_lm(counts_of(h, b0), counts_of(h, b0) + nb);
-    EKF_TRY(finish_rewrite(h, b0, nb, /*rearm*/ true, n_lm.data(), 1, /*flip_buf*/ false));
-    return nb == 1 ? n_lm[0] : EKF_OK;
-}
-
-extern "C" int ekf_update_matched(ekf_handle h, int index, const double *z, const double *R, const int *ids, int n_z, int *n_applied_out, double *d2_out) {
-    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    return match_impl(h, filters_of(h, index), z, R, ids, n_z, n_applied_out, d2_out);
-}
-
-extern "C" int ekf_batch_update_matched(ekf_handle h, const double *z, const double *R, const int *ids, int n_z, int *n_applied_out, double *d2_out) {
-    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
-    const int rc = match_impl(h, filters_of(h, -1), z, R, ids, n_z, n_applied_out, d2_out);
-    return rc < 0 ? rc : EKF_OK;
-}
-
-// The score alone: the rule of ekf_get_state (the streaming launch leaves, every deferred slot is folded, both streams idle), then
-// the settled state is only read: the tables up, k_match_factor with apply = 0 over one round of up to EKF_MAX_PENDING, d2 back.
-static int compat_impl(ekf_batch *h, Filters f, const double *z, const double *R, const int *ids, int n_z, double *d2_out) {
-    const int b0 = f.b0, nb = f.nb;
-    if (!d2_out && n_z > 0) return set_error(EKF_ERR_BAD_ARG, "d2_out is null");
-    EKF_TRY(set_error(plan_match_values(z, R, ids, n_z, b0, nb, EKF_MAX_PENDING)));
-    EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
-    int most;
-    EKF_TRY(set_error(plan_match_ids(ids, n_z, counts_of(h, b0), b0, nb, &most)));
-    for (size_t q = 0; q < (size_t)nb * (n_z > 0 ? n_z : 0); q++) d2_out[q] = __builtin_nan("");
-    if (most == 0) return EKF_OK;  // (nothing is folded)
-    EKF_TRY(settle(h));
-    EKF_TRY(match_reserve(h, most));
-    const MatchScratch ms = h->map.match;
-    hipStream_t s = h->s_chain;
-    const MatchTable tab = plan_match_table(z, R, ids, n_z, nb, ms.zcap);
-    std::vector<double> d2((size_t)nb * ms.zcap);
-    HostCopies hc(s);
-    EKF_TRY(match_upload(h, tab, b0, nb, &hc));
-    hipLaunchKernelGGL(k_match_factor, dim3((unsigned)nb), dim3(256), 0, s, h->dv, h->map.fuse, ms, h->win.buf_in, 0, EKF_MAX_PENDING, /*apply*/ 0, b0);
-    HIP_TRY(hc.copy(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(hc.wait());
-    EKF_TRY(check_launch());
-    match_scatter(tab, d2, ms.zcap, n_z, nb, nullptr, d2_out);
-    return EKF_OK;
-}
-
-extern "C" int ekf_joint_compat(ekf_handle h, int index, const double *z, const double *R, const int *ids, int n_z, double *d2_out) {
-    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    return compat_impl(h, filters_of(h, index), z, R, ids, n_z, d2_out);
-}
-
-extern "C" int ekf_batch_joint_compat(ekf_handle h, const double *z, const double *R, const int *ids, int n_z, double *d2_out) {
-    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
-    return compat_impl(h, filters_of(h, -1), z, R, ids, n_z, d2_out);
-}
-
-// ---- absolute fixes -------------------------------------------------------------------------------
-// match_impl with the kernels of ekf_fix.hip: the same checks in the same order (plan_fix_values before the handle is touched,
-// plan_fix_ids against the mirror's counts), the same scratch (MatchScratch, its ids carrying the kinds), the same rounds and the
-// same end.  What match_impl never meets: a call none of whose filters has a landmark (a position or heading fix on a fresh
-// filter) -- the gather, k_fuse_apply and the pass would be launches of zero blocks, so the round is the factor and k_fuse_finish
-// (P_RR and the pose) alone.
-static int fix_impl(ekf_batch *h, Filters f, const double *z, const double *R, const int *what, int n, int *n_applied_out, double *d2_out) {
-    const int b0 = f.b0, nb = f.nb;
-    EKF_TRY(set_error(plan_fix_values(z, R, what, n, b0, nb, -1)));
-    HIP_TRY(hipSetDevice(h->device));
-    EKF_TRY(refresh_bounds(h, false));
-    int most;
-    EKF_TRY(set_error(plan_fix_ids(what, n, counts_of(h, b0), b0, nb, &most)));
-    if (most == 0) {  // nothing to do: the window stays open
-        for (int k = 0; n_applied_out && k < nb; k++) n_applied_out[k] = 0;
-        for (size_t q = 0; d2_out && q < (size_t)nb * n; q++) d2_out[q] = __builtin_nan("");
-        return nb == 1 ? h->h_int[b0] : EKF_OK;
-    }
-    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
-    EKF_TRY(fuse_reserve(h));
-    EKF_TRY(match_reserve(h, most));
-    EkfDev &dv = h->dv;
-    const FuseScratch fs = h->map.fuse;
-    const MatchScratch ms = h->map.match;
-    hipStream_t s = h->s_chain;
-    const MatchTable tab = plan_fix_table(z, R, what, n, nb, ms.zcap);
-    std::vector<int> done((size_t)2 * nb, 0);
-    std::vector<double> d2((size_t)nb * ms.zcap);
-    HostCopies hc(s);
-    EKF_TRY(match_upload(h, tab, b0, nb, &hc));
-    HIP_TRY(hipMemsetAsync(fs.done + 2 * (size_t)b0, 0, sizeof(int) * 2 * (size_t)nb, s));
-    HIP_TRY(hipMemsetAsync(fs.m_round + b0, 0, sizeof(int) * (size_t)nb, s));
-    const int n_max = most_landmarks(counts_of(h, b0), nb), nT = lm_tiles(n_max);
-    for (int round = 0; round * dv.maxp < most; round++) {
-        const int m_hi = most - round * dv.maxp < dv.maxp ? most - round * dv.maxp : dv.maxp;
-        hipLaunchKernelGGL(k_fix_factor, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->win.buf_in, round, dv.maxp, /*apply*/ 1, b0);
-        if (n_max > 0) {
-            hipLaunchKernelGGL(k_fix_gather, dim3((unsigned)cdiv(n_max, 256), (unsigned)m_hi, (unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->win.buf_in, round, b0);
-            hipLaunchKernelGGL(k_fuse_apply, dim3((unsigned)cdiv(64 * nT, 256), (unsigned)nb), dim3(256), 0, s, dv, fs, b0);
-        }
-        hipLaunchKernelGGL(k_fuse_finish, dim3((unsigned)nb), dim3(64), 0, s, dv, fs, b0);
-        if (n_max > 0) launch_pass(dv, s, nullptr, nullptr, /*interleave*/ false, nT, /*set*/ 0, dv.maxp, h->win.buf_in, h->win.buf_in, nullptr, /*rev*/ 0, b0, nb);
-    }
-    HIP_TRY(hc.copy(done.data(), fs.done + 2 * (size_t)b0, sizeof(int) * 2 * (size_t)nb, hipMemcpyDeviceToHost));
+    const int n_max = most_landmarks(counts_of(h, b0), nb);
+    // The factor runs BEFORE the gather: a filter whose S is refused gathers nothing.
+    EKF_TRY(fuse_rounds(h, f, most, n_max, &hc, done.data(), [&](int round, int m_hi) {
+        hipLaunchKernelGGL(c.factor, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->win.buf_in, round, dv.maxp, /*apply*/ 1, b0);
+        if (n_max > 0) hipLaunchKernelGGL(c.gather, dim3((unsigned)cdiv(n_max, 256), (unsigned)m_hi, (unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->win.buf_in, round, b0);
+    }));
     HIP_TRY(hc.copy(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost));
     HIP_TRY(hc.wait());
     EKF_TRY(check_launch());
@@ -750,36 +672,26 @@ static int fix_impl(ekf_batch *h, Filters f, const double *z, const double *R, c
     return nb == 1 ? n_lm[0] : EKF_OK;
 }
 
-extern "C" int ekf_update_fixes(ekf_handle h, int index, const double *z, const double *R, const int *what, int n, int *n_applied_out, double *d2_out) {
-    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    return fix_impl(h, filters_of(h, index), z, R, what, n, n_applied_out, d2_out);
-}
-
-extern "C" int ekf_batch_update_fixes(ekf_handle h, const double *z, const double *R, const int *what, int n, int *n_applied_out, double *d2_out) {
-    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
-    const int rc = fix_impl(h, filters_of(h, -1), z, R, what, n, n_applied_out, d2_out);
-    return rc < 0 ? rc : EKF_OK;
-}
-
-// The score alone, as compat_impl: k_fix_factor with apply = 0 over one round of up to EKF_MAX_PENDING, d2 back.
-static int fix_compat_impl(ekf_batch *h, Filters f, const double *z, const double *R, const int *what, int n, double *d2_out) {
+// The score alone: the rule of ekf_get_state (the streaming launch leaves, every deferred slot is folded, both streams idle), then
+// the settled state is only read: the tables up, the client's factor with apply = 0 over one round of up to EKF_MAX_PENDING, d2 back.
+static int list_compat_impl(const ListClient &c, ekf_batch *h, Filters f, const double *z, const double *R, const int *ids, int n, double *d2_out) {
     const int b0 = f.b0, nb = f.nb;
     if (!d2_out && n > 0) return set_error(EKF_ERR_BAD_ARG, "d2_out is null");
-    EKF_TRY(set_error(plan_fix_values(z, R, what, n, b0, nb, EKF_MAX_PENDING)));
+    EKF_TRY(set_error(c.values(z, R, ids, n, b0, nb, EKF_MAX_PENDING)));
     EKF_TRY(quiesce(h, QUIET_STREAM, ST_INVALID));
     int most;
-    EKF_TRY(set_error(plan_fix_ids(what, n, counts_of(h, b0), b0, nb, &most)));
+    EKF_TRY(set_error(c.ids(ids, n, counts_of(h, b0), b0, nb, &most)));
     for (size_t q = 0; q < (size_t)nb * (n > 0 ? n : 0); q++) d2_out[q] = __builtin_nan("");
     if (most == 0) return EKF_OK;  // (nothing is folded)
     EKF_TRY(settle(h));
     EKF_TRY(match_reserve(h, most));
     const MatchScratch ms = h->map.match;
     hipStream_t s = h->s_chain;
-    const MatchTable tab = plan_fix_table(z, R, what, n, nb, ms.zcap);
+    const MatchTable tab = c.table(z, R, ids, n, nb, ms.zcap);
     std::vector<double> d2((size_t)nb * ms.zcap);
     HostCopies hc(s);
     EKF_TRY(match_upload(h, tab, b0, nb, &hc));
-    hipLaunchKernelGGL(k_fix_factor, dim3((unsigned)nb), dim3(256), 0, s, h->dv, h->map.fuse, ms, h->win.buf_in, 0, EKF_MAX_PENDING, /*apply*/ 0, b0);
+    hipLaunchKernelGGL(c.factor, dim3((unsigned)nb), dim3(256), 0, s, h->dv, h->map.fuse, ms, h->win.buf_in, 0, EKF_MAX_PENDING, /*apply*/ 0, b0);
     HIP_TRY(hc.copy(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost));
     HIP_TRY(hc.wait());
     EKF_TRY(check_launch());
@@ -787,14 +699,46 @@ static int fix_compat_impl(ekf_batch *h, Filters f, const double *z, const doubl
     return EKF_OK;
 }
 
+extern "C" int ekf_update_matched(ekf_handle h, int index, const double *z, const double *R, const int *ids, int n_z, int *n_applied_out, double *d2_out) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return list_update_impl(MATCHED, h, filters_of(h, index), z, R, ids, n_z, n_applied_out, d2_out);
+}
+
+extern "C" int ekf_batch_update_matched(ekf_handle h, const double *z, const double *R, const int *ids, int n_z, int *n_applied_out, double *d2_out) {
+    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
+    const int rc = list_update_impl(MATCHED, h, filters_of(h, -1), z, R, ids, n_z, n_applied_out, d2_out);
+    return rc < 0 ? rc : EKF_OK;
+}
+
+extern "C" int ekf_joint_compat(ekf_handle h, int index, const double *z, const double *R, const int *ids, int n_z, double *d2_out) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return list_compat_impl(MATCHED, h, filters_of(h, index), z, R, ids, n_z, d2_out);
+}
+
+extern "C" int ekf_batch_joint_compat(ekf_handle h, const double *z, const double *R, const int *ids, int n_z, double *d2_out) {
+    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
+    return list_compat_impl(MATCHED, h, filters_of(h, -1), z, R, ids, n_z, d2_out);
+}
+
+extern "C" int ekf_update_fixes(ekf_handle h, int index, const double *z, const double *R, const int *what, int n, int *n_applied_out, double *d2_out) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return list_update_impl(FIXES, h, filters_of(h, index), z, R, what, n, n_applied_out, d2_out);
+}
+
+extern "C" int ekf_batch_update_fixes(ekf_handle h, const double *z, const double *R, const int *what, int n, int *n_applied_out, double *d2_out) {
+    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
+    const int rc = list_update_impl(FIXES, h, filters_of(h, -1), z, R, what, n, n_applied_out, d2_out);
+    return rc < 0 ? rc : EKF_OK;
+}
+
 extern "C" int ekf_fix_compat(ekf_handle h, int index, const double *z, const double *R, const int *what, int n, double *d2_out) {
     if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
-    return fix_compat_impl(h, filters_of(h, index), z, R, what, n, d2_out);
+    return list_compat_impl(FIXES, h, filters_of(h, index), z, R, what, n, d2_out);
 }
 
 extern "C" int ekf_batch_fix_compat(ekf_handle h, const double *z, const double *R, const int *what, int n, double *d2_out) {
     if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
-    return fix_compat_impl(h, filters_of(h, -1), z, R, what, n, d2_out);
+    return list_compat_impl(FIXES, h, filters_of(h, -1), z, R, what, n, d2_out);
 }
 
 // ---- individual compatibility ---------------------------------------------------------------------
@@ -1022,7 +966,7 @@ extern "C" int ekf_batch_add_landmarks(ekf_handle h, const double *z, const doub
 // ---- the scan step --------------------------------------------------------------------------------
 // ekf_associate_joint, ekf_update_matched and ekf_add_landmarks of one scan as one call: assoc_impl at the entry state (ids and the
 // filter's own gate per measurement), the kinds (plan_joint_kinds), the room for the New ones -- nothing has been applied yet --,
-// match_impl with the pairings, add_impl with the New ones at the state the matched step left.  Every step is the public call's own
+// list_update_impl (MATCHED) with the pairings, add_impl with the New ones at the state the matched step left.  Every step is the public call's own
 // implementation with the public call's arguments: the same bits.
 static int update_joint_impl(ekf_batch *h, Filters f, const double *z, const double *R, const unsigned char *valid, int n_z, double gate, const double *joint_gate,
                              int max_branch, long long max_nodes, int *ids_out, int *kind_out, double *d2_out, ekf_assoc *info_out, int *n_out) {
@@ -1037,7 +981,7 @@ static int update_joint_impl(ekf_batch *h, Filters f, const double *z, const dou
     for (int k = 0; k < nb; k++)
         for (int q = 0; q < n_z; q++) n_add[k] += is_new[(size_t)k * n_z + q];
     EKF_TRY(set_error(plan_add_room(counts_of(h, b0), n_add.data(), b0, nb, h->dv.Ncap, "update")));  // (assoc_impl has refreshed the counts)
-    rc = match_impl(h, f, z, R, ids_out, n_z, applied.data(), d2_out);
+    rc = list_update_impl(MATCHED, h, f, z, R, ids_out, n_z, applied.data(), d2_out);
     if (rc < 0) return rc;
     rc = add_impl(h, f, z, R, is_new.data(), n_z, new_ids.data(), n_out);
     if (rc < 0) return rc;

@@ -204,6 +204,50 @@ inline PlanStatus plan_fuse_table(const ekf_dup_pair *pairs, int ld_pairs, const
     return {};
 }
 
+// ---- the list clients of the fusion machinery: what the two below share ------------------------------------------------------------
+// The check against the landmark counts and the tables have one body each: skip(id) tells the entries that are left out, `noun`
+// names an entry in the texts.
+inline bool plan_match_skip(int id) { return id < 0; }
+inline bool plan_fix_skip(int what) { return what == EKF_FIX_SKIP; }
+inline PlanStatus plan_list_ids(const int *ids, int n, const int *n_lm, int b0, int nb, int *most, bool (*skip)(int), const char *noun) {
+    *most = 0;
+    for (int k = 0; k < nb; k++) {
+        int kept = 0;
+        for (int q = 0; q < n; q++) {
+            const int id = ids[(size_t)k * n + q];
+            if (skip(id)) continue;
+            if (id >= n_lm[k]) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, %s %d: landmark id %d is not one of its %d landmarks", b0 + k, noun, q, id, n_lm[k]);
+            kept++;
+        }
+        *most = std::max(*most, kept);
+    }
+    return {};
+}
+// The tables a list client's factor reads (MatchScratch of the call's filters), nb lists of zcap entries with the skipped ones left
+// out: zt [nb][zcap][2], Rt [nb][zcap][4], idt [nb][zcap] (the ids, or the kinds), cnt [nb]; src [nb][zcap] = the caller's index of
+// each entry.  Of a heading entry z[0] and R[0] alone -- the rest of its row stays 0 (a matched list has none: every id it keeps
+// is a landmark's).
+struct MatchTable {
+    std::vector<double> zt, Rt;
+    std::vector<int> idt, cnt, src;
+};
+inline MatchTable plan_list_table(const double *z, const double *R, const int *ids, int n, int nb, int zcap, bool (*skip)(int)) {
+    MatchTable t;
+    t.zt.assign((size_t)nb * zcap * 2, 0.0), t.Rt.assign((size_t)nb * zcap * 4, 0.0);
+    t.idt.assign((size_t)nb * zcap, 0), t.src.assign((size_t)nb * zcap, -1), t.cnt.assign((size_t)nb, 0);
+    for (int k = 0; k < nb; k++)
+        for (int q = 0; q < n; q++) {
+            const size_t at = (size_t)k * n + q;
+            if (skip(ids[at]) || t.cnt[k] >= zcap) continue;
+            const size_t to = (size_t)k * zcap + t.cnt[k]++;
+            const int width = ids[at] == EKF_FIX_HEADING ? 1 : 2;  // (a kept id is a kind of ekf_update_fixes or a landmark: skip() drops the rest)
+            for (int e = 0; e < width; e++) t.zt[2 * to + e] = z[2 * at + e];
+            for (int e = 0; e < width * width; e++) t.Rt[4 * to + e] = R[4 * at + e];
+            t.idt[to] = ids[at], t.src[to] = q;
+        }
+    return t;
+}
+
 // ---- matched updates (ekf_update_matched, ekf_joint_compat) -----------------------------------------------------------------------
 // The lists of nb filters, filter k's n_z measurements at z + k * n_z * 2, R + k * n_z * 4 and ids + k * n_z; ids[q] == -1: no
 // measurement, skipped (its z and R are not looked at).  Checked before the handle is touched: the pointers, n_z, every id >= -1,
@@ -226,39 +270,10 @@ inline PlanStatus plan_match_values(const double *z, const double *R, const int 
 }
 // ... and against the landmark counts n_lm[k], once they are current.  *most = the most measurements of a filter.
 inline PlanStatus plan_match_ids(const int *ids, int n_z, const int *n_lm, int b0, int nb, int *most) {
-    *most = 0;
-    for (int k = 0; k < nb; k++) {
-        int kept = 0;
-        for (int q = 0; q < n_z; q++) {
-            const int id = ids[(size_t)k * n_z + q];
-            if (id < 0) continue;
-            if (id >= n_lm[k]) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, measurement %d: landmark id %d is not one of its %d landmarks", b0 + k, q, id, n_lm[k]);
-            kept++;
-        }
-        *most = std::max(*most, kept);
-    }
-    return {};
+    return plan_list_ids(ids, n_z, n_lm, b0, nb, most, plan_match_skip, "measurement");
 }
-// The tables k_match_factor reads (MatchScratch of the call's filters), nb lists of zcap entries with the skipped measurements
-// left out: zt [nb][zcap][2], Rt [nb][zcap][4], idt [nb][zcap], cnt [nb]; src [nb][zcap] = the caller's index of each entry.
-struct MatchTable {
-    std::vector<double> zt, Rt;
-    std::vector<int> idt, cnt, src;
-};
 inline MatchTable plan_match_table(const double *z, const double *R, const int *ids, int n_z, int nb, int zcap) {
-    MatchTable t;
-    t.zt.assign((size_t)nb * zcap * 2, 0.0), t.Rt.assign((size_t)nb * zcap * 4, 0.0);
-    t.idt.assign((size_t)nb * zcap, 0), t.src.assign((size_t)nb * zcap, -1), t.cnt.assign((size_t)nb, 0);
-    for (int k = 0; k < nb; k++)
-        for (int q = 0; q < n_z; q++) {
-            const size_t at = (size_t)k * n_z + q;
-            if (ids[at] < 0 || t.cnt[k] >= zcap) continue;
-            const size_t to = (size_t)k * zcap + t.cnt[k]++;
-            t.zt[2 * to] = z[2 * at], t.zt[2 * to + 1] = z[2 * at + 1];
-            for (int e = 0; e < 4; e++) t.Rt[4 * to + e] = R[4 * at + e];
-            t.idt[to] = ids[at], t.src[to] = q;
-        }
-    return t;
+    return plan_list_table(z, R, ids, n_z, nb, zcap, plan_match_skip);
 }
 
 // ---- absolute fixes (ekf_update_fixes, ekf_fix_compat) ----------------------------------------------------------------------------
@@ -291,39 +306,10 @@ inline PlanStatus plan_fix_values(const double *z, const double *R, const int *w
 }
 // ... and the landmark entries against the landmark counts n_lm[k], once they are current.  *most = the most entries of a filter.
 inline PlanStatus plan_fix_ids(const int *what, int n, const int *n_lm, int b0, int nb, int *most) {
-    *most = 0;
-    for (int k = 0; k < nb; k++) {
-        int kept = 0;
-        for (int q = 0; q < n; q++) {
-            const int w = what[(size_t)k * n + q];
-            if (w == EKF_FIX_SKIP) continue;
-            if (w >= n_lm[k]) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, entry %d: landmark id %d is not one of its %d landmarks", b0 + k, q, w, n_lm[k]);
-            kept++;
-        }
-        *most = std::max(*most, kept);
-    }
-    return {};
+    return plan_list_ids(what, n, n_lm, b0, nb, most, plan_fix_skip, "entry");
 }
-// The tables k_fix_factor reads, in the shape of plan_match_table (idt carries the kinds; src the caller's index of each entry):
-// the skipped entries left out, and of a heading entry z[0] and R[0] alone -- the rest of its row stays 0.
 inline MatchTable plan_fix_table(const double *z, const double *R, const int *what, int n, int nb, int zcap) {
-    MatchTable t;
-    t.zt.assign((size_t)nb * zcap * 2, 0.0), t.Rt.assign((size_t)nb * zcap * 4, 0.0);
-    t.idt.assign((size_t)nb * zcap, 0), t.src.assign((size_t)nb * zcap, -1), t.cnt.assign((size_t)nb, 0);
-    for (int k = 0; k < nb; k++)
-        for (int q = 0; q < n; q++) {
-            const size_t at = (size_t)k * n + q;
-            if (what[at] == EKF_FIX_SKIP || t.cnt[k] >= zcap) continue;
-            const size_t to = (size_t)k * zcap + t.cnt[k]++;
-            const bool heading = what[at] == EKF_FIX_HEADING;
-            t.zt[2 * to] = z[2 * at], t.Rt[4 * to] = R[4 * at];
-            if (!heading) {
-                t.zt[2 * to + 1] = z[2 * at + 1];
-                for (int e = 1; e < 4; e++) t.Rt[4 * to + e] = R[4 * at + e];
-            }
-            t.idt[to] = what[at], t.src[to] = q;
-        }
-    return t;
+    return plan_list_table(z, R, what, n, nb, zcap, plan_fix_skip);
 }
 
 // ---- individual compatibility (ekf_gate_candidates) -------------------------------------------------------------------------------

@@ -8,21 +8,15 @@
 // (cos() and sin() of the device library on x[2], in k_match_factor).  d is minus the reference's residual (Update.cpp:110), so
 // x - V y is the reference's x + K res and k_fuse_apply / k_fuse_finish / the dense pass over set 0 run unchanged.
 //
-// Not on the hot path: once per call and round on a settled handle, all streams idle.  Included by ekf_api.hip behind ekf_fuse.hip
-// (FuseScratch, fuse_block, fuse_cholesky, FUSE_MAX_COLS); no index function of its own: blocks of P come through fuse_block, the
-// slot rows through fuse_slot_offset.
-//
-// A round (at most dv.maxp measurements of every filter of the call), on the chain stream:
-//   k_match_factor  one workgroup per filter: the round's table (H_R,k, C, d_k, W's robot rows) from x, the R rows and P_RR; S from
-//                   the blocks (i_k, i_l) directly, m (m + 1) / 2 fuse_block reads -- not from gathered rows, so that the score
-//                   needs no gather and writes nothing to the filter; the Cholesky of k_fuse_factor with the same four extra columns;
-//                   the running sum of y^2 per measurement.  apply != 0: U, y, V's robot rows, the slot flags and the progress
-//                   record as k_fuse_factor leaves them, and the table for the gather
-//   k_match_gather  W's landmark rows into the FA slot rows, one thread per (landmark, measurement) of the filters that take part
-//   k_fuse_apply, k_fuse_finish, k_flush_rb over set 0: as in a fusion round
+// Not on the hot path: once per call and round on a settled handle, all streams idle.  Included by ekf_api.hip behind ekf_fuse.hip,
+// whose header says what the machinery takes from a client and what it gives back (fuse_cholesky, fuse_prefix_d2, fuse_publish,
+// fuse_store_w; blocks of P through fuse_block).  This client's own, per round of at most dv.maxp measurements of every filter:
+//   k_match_factor  the round's table (H_R,k, C, d_k, W's robot rows) from x, the R rows and P_RR; S from the blocks (i_k, i_l)
+//                   directly, m (m + 1) / 2 fuse_block reads -- not from gathered rows, so that the score needs no gather and
+//                   writes nothing to the filter; apply != 0: the table for the gather as well
+//   k_match_gather  W's landmark rows, one thread per (landmark, measurement) of the filters that take part
 // The factor runs BEFORE the gather: a filter whose S is refused gathers nothing.  ekf_joint_compat is k_match_factor alone with
 // apply = 0 and a round of up to EKF_MAX_PENDING: the same code, so the same bits of d2 for a hypothesis that fits one round.
-// One writer per value, every sum in a fixed order, no atomics: the same bits on every call and in the batch form.
 //
 // A pivot counts as positive when it exceeds MATCH_PIVOT_TOL times its own diagonal entry of S: what is left of an exactly singular
 // S after the elimination (the same landmark measured twice with R = 0) is rounding noise of either sign, a few 2^-52 of that entry.
@@ -124,36 +118,9 @@ __global__ __launch_bounds__(256) void k_match_factor(EkfDev dv, FuseScratch fs,
         __syncthreads();
         bad = fuse_cholesky<true>(A, M, NC, tid, sFloor);
     }
-    if (tid == 0 && m > 0) {  // the joint distance of the round cut after each measurement; NaN from the refused pivot on
-        double acc = 0.0;
-        for (int k = 0; k < m; k++) {
-            const bool have = !bad || 2 * k + 1 < bad - 1;
-            acc = acc + A[2 * k][M] * A[2 * k][M];
-            acc = acc + A[2 * k + 1][M] * A[2 * k + 1][M];
-            ms.d2[z0 + k] = have ? acc : __builtin_nan("");
-        }
-    }
+    if (tid == 0 && m > 0) fuse_prefix_d2(ms.d2 + z0, A, m, bad);
     if (!apply) return;
-    const bool ok = m > 0 && !bad;
-    if (ok) {
-        double *U = fs.U + (size_t)b * FUSE_MAX_COLS * FUSE_MAX_COLS;
-        double *wr = fs.wr + (size_t)b * 4 * FUSE_MAX_COLS;
-        for (int idx = tid; idx < M * M; idx += 256) {
-            const int a = idx / M, c = idx - a * M;
-            U[a * FUSE_MAX_COLS + c] = c >= a ? A[a][c] : 0.0;
-        }
-        for (int idx = tid; idx < 4 * M; idx += 256) {
-            const int r = idx / M, a = idx - r * M;
-            wr[(size_t)r * FUSE_MAX_COLS + a] = A[a][M + ((r + 1) & 3)];
-        }
-    }
-    if (tid < dv.maxp) dv.slot_active[((size_t)b * 2) * dv.maxp + tid] = ok && tid < m ? 1 : 0;
-    if (tid == 0) {
-        dv.n_lm_flush[(size_t)b * 2] = ok ? dv.n_lm[b] : 0;  // (0: the pass skips every tile of this filter)
-        fs.m_round[b] = ok ? m : 0;
-        if (ok) fs.done[2 * b] += m;
-        if (bad) fs.done[2 * b + 1] = bad;
-    }
+    fuse_publish(dv, fs, A, b, m, bad, tid);
 }
 
 // grid (landmarks / 256, measurements of the round, filters); behind k_match_factor, which has accepted fs.m_round[b] measurements.
@@ -179,7 +146,5 @@ __global__ __launch_bounds__(256) void k_match_gather(EkfDev dv, FuseScratch fs,
 #pragma unroll
         for (int f = 0; f < 2; f++) w[2 * e + f] = (((p0 * t[3 * f] + p1 * t[3 * f + 1]) + p2 * t[3 * f + 2]) + pb[2 * e] * Cm[f]) + pb[2 * e + 1] * Cm[2 + f];
     }
-    double *fa = dv.FA + (size_t)b * 2 * dv.f_stride;
-    *(double2_t *)(fa + fuse_slot_offset(dv.rows, 2 * l, 2 * k)) = (double2_t){w[0], w[1]};
-    *(double2_t *)(fa + fuse_slot_offset(dv.rows, 2 * l + 1, 2 * k)) = (double2_t){w[2], w[3]};
+    fuse_store_w(dv, b, l, k, w);
 }

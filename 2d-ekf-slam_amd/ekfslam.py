@@ -224,6 +224,12 @@ def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
+def _rect_lists(z, R, a):
+    """(z, Rc, ids, n) as the C list calls take them, from the ids a [..][n] and arrays with two values of z and a 2x2 R per id."""
+    Rc = _f64(np.swapaxes(R.reshape(a.shape + (2, 2)), -1, -2).reshape(a.shape + (4,)))  # column-major blocks
+    return _f64(z.reshape(a.shape + (2,))), Rc, np.ascontiguousarray(a, dtype=np.int32), a.shape[-1]
+
+
 def _greedy_matching(pairs, n_landmarks):
     """The pairs (as DUP_DTYPE) and the positions of the accepted ones, in the order they were accepted: greedy one-to-one
     matching by ascending d2, ties by (i, j)."""
@@ -612,6 +618,20 @@ class FilterBatch:
                                            ctypes.byref(fused)))
         return n, fused.value
 
+    def _list_update(self, lists, index, single, batch):
+        """The call of a list update (ekf_update_matched, ekf_update_fixes: `single`, or `batch` with index=None) on the lists of
+        _matched_lists / _fix_lists, and its results as update_matched documents them."""
+        z, Rc, a, n = lists
+        d2 = np.full(a.shape, np.nan)
+        ptrs = (_p(z), _p(Rc), a.ctypes.data_as(_ip)) if n else (None, None, None)
+        if index is None:
+            applied = np.zeros(self.batch, dtype=np.int32)
+            _chk(batch(self.h, *ptrs, n, applied.ctypes.data_as(_ip), _p(d2) if n else None))
+            return applied, d2
+        applied = ctypes.c_int(0)
+        cnt = _chk(single(self.h, int(index), *ptrs, n, ctypes.byref(applied), _p(d2) if n else None))
+        return cnt, applied.value, d2
+
     def _matched_lists(self, z, R, ids, index):
         """(z, Rc, ids, n_z) as the C calls take them.  With an index: ids [n_z], z [n_z][2], R [n_z][2][2]; index=None: a leading
         batch axis on all three (ragged lists: pad ids with -1)."""
@@ -621,14 +641,10 @@ class FilterBatch:
             raise ValueError("ids must be [batch][n_z]" if lead else "ids must be [n_z]")
         if a.size and (a.min() < -1 or a.max() > np.iinfo(np.int32).max):
             raise ValueError("an id is a landmark number, or -1 to skip the measurement")
-        n_z = a.shape[-1]
         z, R = np.asarray(z, dtype=np.float64), np.asarray(R, dtype=np.float64)
         if z.size != a.size * 2 or R.size != a.size * 4:
-            raise ValueError("z must hold [n_z][2] and R [n_z][2][2] values per filter for %d ids" % n_z)
-        z = _f64(z.reshape(lead + (n_z, 2)))
-        R = R.reshape(lead + (n_z, 2, 2))
-        Rc = _f64(np.swapaxes(R, -1, -2).reshape(lead + (n_z, 4)))  # column-major blocks
-        return z, Rc, np.ascontiguousarray(a, dtype=np.int32), n_z
+            raise ValueError("z must hold [n_z][2] and R [n_z][2][2] values per filter for %d ids" % a.shape[-1])
+        return _rect_lists(z, R, a)
 
     def update_matched(self, z, R, ids, index=0):
         """Apply a scan with the caller's own data association on the device (ekf_update_matched): measurement k is landmark ids[k]
@@ -638,16 +654,7 @@ class FilterBatch:
         applied), d2[k] the joint Mahalanobis distance of k's round up to and including k (NaN: skipped or not applied).
         index=None: every filter in one launch sequence (ekf_batch_update_matched), ids [batch][n_z]; returns (n_applied (batch,),
         d2 (batch, n_z))."""
-        z, Rc, a, n_z = self._matched_lists(z, R, ids, index)
-        d2 = np.full(a.shape, np.nan)
-        ptrs = (_p(z), _p(Rc), a.ctypes.data_as(_ip)) if n_z else (None, None, None)
-        if index is None:
-            applied = np.zeros(self.batch, dtype=np.int32)
-            _chk(self.L.ekf_batch_update_matched(self.h, *ptrs, n_z, applied.ctypes.data_as(_ip), _p(d2) if n_z else None))
-            return applied, d2
-        applied = ctypes.c_int(0)
-        n = _chk(self.L.ekf_update_matched(self.h, int(index), *ptrs, n_z, ctypes.byref(applied), _p(d2) if n_z else None))
-        return n, applied.value, d2
+        return self._list_update(self._matched_lists(z, R, ids, index), index, self.L.ekf_update_matched, self.L.ekf_batch_update_matched)
 
     def joint_compat(self, z, R, ids, index=0):
         """The score of one association hypothesis (ekf_joint_compat), nothing applied: d2[k] is the joint Mahalanobis distance of
@@ -687,9 +694,8 @@ class FilterBatch:
                 return None
 
         za, Ra = as_array(z), as_array(R)
-        if za is not None and Ra is not None and za.size == a.size * 2 and Ra.size == a.size * 4:  # (the lists of _matched_lists)
-            Rc = _f64(np.swapaxes(Ra.reshape(lead + (n, 2, 2)), -1, -2).reshape(lead + (n, 4)))  # column-major blocks
-            return _f64(za.reshape(lead + (n, 2))), Rc, np.ascontiguousarray(a, dtype=np.int32), n
+        if za is not None and Ra is not None and za.size == a.size * 2 and Ra.size == a.size * 4:
+            return _rect_lists(za, Ra, a)
 
         def entries(v, arr, width, name):
             """v as [count][width] values, an entry given as one scalar standing for (scalar, 0, ..); and the mask of those."""
@@ -722,16 +728,7 @@ class FilterBatch:
         definite (that round and the later ones were not applied), d2[k] the joint Mahalanobis distance of k's round up to and
         including k (NaN: skipped or not applied).  index=None: every filter in one launch sequence (ekf_batch_update_fixes), what
         [batch][n]; returns (n_applied (batch,), d2 (batch, n))."""
-        z, Rc, a, n = self._fix_lists(z, R, what, index)
-        d2 = np.full(a.shape, np.nan)
-        ptrs = (_p(z), _p(Rc), a.ctypes.data_as(_ip)) if n else (None, None, None)
-        if index is None:
-            applied = np.zeros(self.batch, dtype=np.int32)
-            _chk(self.L.ekf_batch_update_fixes(self.h, *ptrs, n, applied.ctypes.data_as(_ip), _p(d2) if n else None))
-            return applied, d2
-        applied = ctypes.c_int(0)
-        cnt = _chk(self.L.ekf_update_fixes(self.h, int(index), *ptrs, n, ctypes.byref(applied), _p(d2) if n else None))
-        return cnt, applied.value, d2
+        return self._list_update(self._fix_lists(z, R, what, index), index, self.L.ekf_update_fixes, self.L.ekf_batch_update_fixes)
 
     def fix_compat(self, z, R, what, index=0):
         """The score of one list of fixes (ekf_fix_compat), nothing applied: d2[k] is the joint Mahalanobis distance of the list cut

@@ -239,3 +239,11 @@ def test_python_layer_validates_its_arguments(pkg):
     assert n == 1 and a.tolist() == [H_] and zz.tolist() == [[0.25, 0.0]] and Rc.tolist() == [[0.5, 0.0, 0.0, 0.0]]
     zz, Rc, a, n = f._fix_lists([0.25, 0.3], [0.5, 0.6], [H_, H_], 0)
     assert n == 2 and zz.tolist() == [[0.25, 0.0], [0.3, 0.0]] and Rc[:, 0].tolist() == [0.5, 0.6]
+    # landmark ids alone on rectangular lists, single and batch: the lists of _matched_lists, byte for byte
+    rng = np.random.default_rng(7)
+    for lead, index in (((), 0), ((2,), None)):
+        zr, Rr, ids = rng.normal(size=lead + (3, 2)), rng.normal(size=lead + (3, 2, 2)), rng.integers(0, 9, size=lead + (3,))
+        fixes, matched = f._fix_lists(zr, Rr, ids, index), f._matched_lists(zr, Rr, ids, index)
+        for got, want in zip(fixes[:3], matched[:3]):
+            assert got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes()
+        assert fixes[3] == matched[3] == 3
