@@ -40,6 +40,7 @@
 #include "ekf_fix.hip"
 #include "ekf_extract.hip"
 #include "ekf_gate.hip"
+#include "ekf_locate.hip"
 #include "ekf_assoc.hip"
 
 static thread_local std::string g_last_error;
@@ -129,7 +130,7 @@ struct DevBlock {
     void *p = nullptr;
     size_t bytes = 0;
 };
-enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_MATCH, BLK_GATE, BLK_GATE_LIST, BLK_ASSOC, BLK_ADD, BLK_COUNT };
+enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_MATCH, BLK_GATE, BLK_GATE_LIST, BLK_ASSOC, BLK_ADD, BLK_LOC, BLK_LOC_LIST, BLK_COUNT };
 
 // Everything the map operations keep on a handle: the scratch structs their kernels take (ekf_map_scratch.h: arrays and layout) and
 // the allocations behind them.  A block is built by the first call that needs it (block_build in ekf_map_api.hip) and kept.
@@ -151,10 +152,14 @@ enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_MATCH, BLK_GATE, BLK_GAT
 //   BLK_ASSOC      assoc   ekf_associate_joint that searches           the batch alone                       yes
 //   BLK_ADD        add     ekf_add_landmarks that adds                 the longest list brought (zcap,       yes
 //                                                                      from 64)
+//   BLK_LOC        loc     ekf_locate_scan that searches               the batch alone                       yes
+//   BLK_LOC_LIST   loc     ekf_locate_scan that searches               the candidates found (ccap, from      no
+//                                                                      4096)
 // A capacity that a call outgrows is doubled until it fits (plan_grown_cap) and the block replaced.
 // ekf_reserve (map_scratch_rebuild) builds again, for the new capacity and as large as it was, every block the old buffers had --
 // with one irregularity: BLK_DUP and BLK_DUP_LIST are built together, when the old handle had the LIST (a base whose list never
-// got allocated is not rebuilt); BLK_GATE_LIST follows BLK_GATE's presence with the old ccap (0: no list).
+// got allocated is not rebuilt); BLK_GATE_LIST follows BLK_GATE's presence with the old ccap (0: no list); BLK_LOC and BLK_LOC_LIST
+// are built together by every call, with the old ccap.
 struct MapKept {
     FactorScratch fac = {};
     DupScratch dup = {};
@@ -163,6 +168,7 @@ struct MapKept {
     GateScratch gate = {};
     AssocScratch assoc = {};
     AddScratch add = {};
+    LocScratch loc = {};
     DevBlock blk[BLK_COUNT];
 };
 
@@ -1519,6 +1525,9 @@ static int sticky_status(ekf_batch *h, bool include_capacity) {
 //   ekf_get_submap                                     QUIET_STREAM   ST_INVALID           ids checked; size only: returns; else settle(), the dense gather
 //   ekf_associate_joint (and the batch form)           QUIET_STREAM   ST_INVALID           values checked first; the sweep of ekf_gate_candidates; no candidate: returns;
 //                                                                                          else settle(), the search; the state is only read
+//   ekf_locate_scan (and the batch form)               refresh_bounds alone, as ekf_gate_candidates: values checked first; nothing to search: returns; only x is read
+//   ekf_reset_pose (and the batch form)                QUIET_SETTLED  ST_INVALID_OR_FULL   as ekf_transform_frame
+//   ekf_relocalize (and the batch form)                ekf_locate_scan's; refused: returns; then ekf_reset_pose's, then ekf_update_matched's
 //   ekf_gate_candidates (and the batch form)           refresh_bounds alone (as ekf_get_landmark_covs): values checked first; no measurement: returns;
 //                                                      the chain stream drained, a sticky EKF_ERR_TIMEOUT ends it, EKF_ERR_CAPACITY does not; NO settle():
 //                                                      the open window stays open, x / robot rows / D are only read, the flush stream is untouched

@@ -1,6 +1,7 @@
 // ekf_map_api.hip -- host side of the map operations of include/ekfslam_c.h: removal, frame change and anchoring, joining, extraction
 // and ekf_get_submap, joint consistency, duplicate search, fusion, matched updates and their score, the individual compatibility table,
-// the joint compatibility search, landmark initialisation and the scan step built from those, ekf_get_landmark_covs.  Included
+// the joint compatibility search, landmark initialisation and the scan step built from those, relocalisation (the pose search, the
+// pose reset and the two with a matched update), ekf_get_landmark_covs.  Included
 // by ekf_api.hip (one translation unit: ekf_batch, HIP_TRY / EKF_TRY, quiesce, finish_rewrite, DevTmp, HostCopies and MapKept are
 // that file's).  Every entry point runs once per call on a handle it brings to rest and reads: check, quiesce, plan, upload, launch,
 // finish.  The checks of the caller's lists and the tables the kernels read are pure code in ekf_map_plan.h; the order of those
@@ -77,6 +78,11 @@ static int add_reserve(ekf_batch *h, int n_meas) {
     if (h->map.blk[BLK_ADD].p && zcap == h->map.add.zcap) return EKF_OK;
     return block_build(h, BLK_ADD, /*zero*/ true, &h->map.add, carve_add, zcap);
 }
+static int loc_reserve(ekf_batch *h, int cand) {
+    LocScratch &ls = h->map.loc;
+    if (!h->map.blk[BLK_LOC].p) EKF_TRY(block_build(h, BLK_LOC, /*zero*/ true, &ls, carve_loc));
+    return cand > ls.ccap ? block_build(h, BLK_LOC_LIST, /*zero*/ false, &ls, carve_loc_list, cand) : EKF_OK;
+}
 // The entries of a device list (pairs, candidates) for a call that may hand out up to `want` of them (a call that finds more grows it).
 static int list_cap_for(int want) { return plan_grown_cap(0, want < 4096 ? want : 4096, 256); }
 
@@ -89,6 +95,7 @@ static int map_scratch_rebuild(ekf_batch *h, const MapKept &old) {
     if (old.blk[BLK_GATE].p) EKF_TRY(gate_reserve(h, old.gate.zcap, old.gate.ccap));
     if (old.blk[BLK_ASSOC].p) EKF_TRY(assoc_reserve(h));
     if (old.blk[BLK_ADD].p) EKF_TRY(add_reserve(h, old.add.zcap));
+    if (old.blk[BLK_LOC].p) EKF_TRY(loc_reserve(h, old.loc.ccap));
     return EKF_OK;
 }
 
@@ -1002,6 +1009,201 @@ extern "C" int ekf_batch_update_joint(ekf_handle h, const double *z, const doubl
                                       int max_branch, long long max_nodes, int *ids_out, int *kind_out, double *d2_out, ekf_assoc *info_out, int *n_out) {
     if (!h || !info_out || !n_out) return set_error(EKF_ERR_BAD_ARG, "bad argument");
     return update_joint_impl(h, filters_of(h, -1), z, R, valid, n_z, gate, joint_gate, max_branch, max_nodes, ids_out, kind_out, d2_out, info_out, n_out);
+}
+
+// ---- relocalisation -------------------------------------------------------------------------------
+// The filters f, filter f.b0 + k with the n_z measurements at z + k * n_z * 2 (valid + k * n_z masks them).  The values are checked
+// before anything happens to the handle.  Then the rule of ekf_gate_candidates: the chain stream idle (a resident streaming launch
+// leaves first), NOTHING folded -- x is current inside an open window --, the flush stream untouched.  A call in which no filter has
+// a base pair and two landmarks returns there, without scratch.  The tables up (plan_locate_table), k_loc_pairs and the counts
+// back; a filter beyond EKF_LOCATE_MAX_CAND ends the call (not sticky, the state was only read); a list that does not hold what
+// was found is replaced and the pairs run once more (the state has not moved: the same candidates).  Then the score, the two
+// selection stages and the fit with nothing in between, the records and the ids back in one copy each, the compacted measurement
+// indices turned into the caller's.  hyp_out [nb][max_out], ids_out [nb][max_out][n_z], n_found [nb] = the hypotheses written.
+static int locate_impl(ekf_batch *h, Filters f, const double *z, const unsigned char *valid, int n_z, double tol, double min_sep, int max_base, int max_out,
+                       ekf_locate_hyp *hyp_out, int *ids_out, int *n_found, long long *n_cand_out) {
+    const int b0 = f.b0, nb = f.nb;
+    EKF_TRY(set_error(plan_locate_args(z, valid, n_z, b0, nb, tol, min_sep, max_base, max_out, hyp_out, ids_out, EKF_MAX_PENDING)));
+    for (int k = 0; k < nb; k++) {
+        n_found[k] = 0;
+        if (n_cand_out) n_cand_out[k] = 0;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    EKF_TRY(refresh_bounds(h));  // the chain stream idle; h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT ends it here
+    LocateTable tab = plan_locate_table(z, valid, n_z, nb, min_sep, max_base);
+    bool any = false;
+    for (int k = 0; k < nb; k++) {
+        if (counts_of(h, b0)[k] < 2) tab.nbase[k] = 0;
+        any = any || tab.nbase[k] > 0;
+    }
+    if (!any) return EKF_OK;  // (no scratch either)
+    EKF_TRY(loc_reserve(h, LOC_LIST_FLOOR));
+    const EkfDev &dv = h->dv;
+    hipStream_t s = h->s_chain;
+    const int n_max = most_landmarks(counts_of(h, b0), nb), most = most_landmarks(tab.cnt.data(), nb);
+    const size_t per = EKF_MAX_PENDING, bcap = EKF_LOCATE_MAX_BASE, ocap = EKF_LOCATE_MAX_OUT;
+    std::vector<unsigned long long> cnt((size_t)nb, 0);
+    std::vector<ekf_locate_hyp> hyps((size_t)nb * ocap);
+    std::vector<int> ids((size_t)nb * ocap * per);
+    HostCopies hc(s);
+    {
+        const LocScratch &ls = h->map.loc;
+        HIP_TRY(hc.copy(ls.z + b0 * per * 2, tab.zt.data(), sizeof(double) * nb * per * 2, hipMemcpyHostToDevice));
+        HIP_TRY(hc.copy(ls.blen + b0 * bcap, tab.blen.data(), sizeof(double) * nb * bcap, hipMemcpyHostToDevice));
+        HIP_TRY(hc.copy(ls.base + b0 * bcap * 2, tab.base.data(), sizeof(int) * nb * bcap * 2, hipMemcpyHostToDevice));
+        HIP_TRY(hc.copy(ls.nz + b0, tab.cnt.data(), sizeof(int) * (size_t)nb, hipMemcpyHostToDevice));
+        HIP_TRY(hc.copy(ls.nbase + b0, tab.nbase.data(), sizeof(int) * (size_t)nb, hipMemcpyHostToDevice));
+    }
+    unsigned long long most_found = 0;
+    for (int round = 0;; round++) {
+        const LocScratch ls = h->map.loc;
+        const unsigned side = (unsigned)cdiv(n_max, LOC_THREADS);
+        HIP_TRY(hipMemsetAsync(ls.cnt + b0, 0, sizeof(unsigned long long) * (size_t)nb, s));
+        hipLaunchKernelGGL(k_loc_pairs, dim3(side, side, (unsigned)nb), dim3(LOC_THREADS), 0, s, dv, ls, 2.0 * tol, b0);
+        HIP_TRY(hc.copy(cnt.data(), ls.cnt + b0, sizeof(unsigned long long) * (size_t)nb, hipMemcpyDeviceToHost));
+        HIP_TRY(hc.wait());
+        EKF_TRY(check_launch());
+        most_found = *std::max_element(cnt.begin(), cnt.end());
+        for (int k = 0; n_cand_out && k < nb; k++) n_cand_out[k] = (long long)cnt[k];
+        for (int k = 0; k < nb; k++)
+            if (cnt[k] > (unsigned long long)EKF_LOCATE_MAX_CAND)
+                return set_error(EKF_ERR_CAPACITY, "filter %d: %llu candidates, more than EKF_LOCATE_MAX_CAND = %d: tol too loose for this map", b0 + k, cnt[k], EKF_LOCATE_MAX_CAND);
+        if (most_found <= (unsigned long long)ls.ccap) break;
+        if (round > 0) return set_error(EKF_ERR_STATE, "the candidate count changed between two passes over an unchanged state");
+        EKF_TRY(loc_reserve(h, plan_grown_cap(0, (long long)most_found, LOC_LIST_FLOOR)));
+    }
+    if (most_found > 0) {
+        const LocScratch ls = h->map.loc;
+        const int groups = cdiv((int)most_found, LOC_THREADS / 64), parts = std::min(LOC_PICK_PARTS, cdiv((int)most_found, 4096));
+        const dim3 gs((unsigned)std::min(groups, 2048), (unsigned)nb);
+        const auto k_score = most <= 8 ? k_loc_score<8> : most <= 16 ? k_loc_score<16> : k_loc_score<EKF_MAX_PENDING>;
+        hipLaunchKernelGGL(k_score, gs, dim3(LOC_THREADS), 0, s, dv, ls, tol * tol, b0);
+        hipLaunchKernelGGL(k_loc_pick, dim3((unsigned)parts, (unsigned)nb), dim3(LOC_THREADS), 0, s, ls, 0, max_out, b0);
+        hipLaunchKernelGGL(k_loc_pick, dim3(1, (unsigned)nb), dim3(LOC_THREADS), 0, s, ls, 1, max_out, b0);
+        hipLaunchKernelGGL(k_loc_fit, dim3((unsigned)std::min<unsigned long long>(most_found, (unsigned long long)max_out), (unsigned)nb), dim3(64), 0, s, dv, ls, tol * tol, b0);
+        HIP_TRY(hc.copy(hyps.data(), ls.hyp + b0 * ocap, sizeof(ekf_locate_hyp) * hyps.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hc.copy(ids.data(), ls.ids + b0 * ocap * per, sizeof(int) * ids.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hc.wait());
+        EKF_TRY(check_launch());
+    }
+    for (int k = 0; k < nb; k++) {
+        const int written = (int)std::min<unsigned long long>(cnt[k], (unsigned long long)max_out);
+        const int *src = tab.src.data() + (size_t)k * per;
+        n_found[k] = written;
+        for (int t = 0; t < written; t++) {
+            ekf_locate_hyp hy = hyps[(size_t)k * ocap + t];
+            if (hy.meas_a < 0 || hy.meas_a >= tab.cnt[k] || hy.meas_b < 0 || hy.meas_b >= tab.cnt[k]) return set_error(EKF_ERR_STATE, "a hypothesis names no measurement of the call");
+            hy.meas_a = src[hy.meas_a], hy.meas_b = src[hy.meas_b];
+            hyp_out[(size_t)k * max_out + t] = hy;
+            int *row = ids_out + ((size_t)k * max_out + t) * n_z;
+            for (int q = 0; q < n_z; q++) row[q] = -1;
+            for (int q = 0; q < tab.cnt[k]; q++) row[src[q]] = ids[((size_t)k * ocap + t) * per + q];
+        }
+    }
+    return EKF_OK;
+}
+
+extern "C" int ekf_locate_scan(ekf_handle h, int index, const double *z, int n_z, double tol, double min_sep, int max_base, int max_out, ekf_locate_hyp *hyp_out, int *ids_out,
+                               long long *n_cand_out) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    int found = 0;
+    EKF_TRY(locate_impl(h, filters_of(h, index), z, nullptr, n_z, tol, min_sep, max_base, max_out, hyp_out, ids_out, &found, n_cand_out));
+    return found;
+}
+
+extern "C" int ekf_batch_locate_scan(ekf_handle h, const double *z, const unsigned char *valid, int n_z, double tol, double min_sep, int max_base, int max_out,
+                                     ekf_locate_hyp *hyp_out, int *ids_out, int *n_found_out, long long *n_cand_out) {
+    if (!h || !n_found_out) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return locate_impl(h, filters_of(h, -1), z, valid, n_z, tol, min_sep, max_base, max_out, hyp_out, ids_out, n_found_out, n_cand_out);
+}
+
+// The pose reset on the device (ekf_rewrite.hip: k_reset_pose), the order of steps as in reframe_impl: settle, one launch over the
+// robot rows, the end of the rewrite (slot rows cleared).  pose [nb][3], prr [nb][9] (checked by the caller: plan_reset_args);
+// apply [nb] or null: the filters to reset.  A one-filter call carries its argument in the kernel arguments, the batch form in a
+// transient table (104 bytes per filter).
+static int reset_impl(ekf_batch *h, Filters f, const double *pose, const double *prr, const unsigned char *apply) {
+    // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
+    // every deferred slot folded, both streams idle
+    EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
+    const int b0 = f.b0, nb = f.nb, n_max = most_landmarks(counts_of(h, b0), nb);
+    std::vector<double> vals((size_t)nb * 13);
+    for (int k = 0; k < nb; k++) plan_reset_values(pose + 3 * (size_t)k, prr + 9 * (size_t)k, !apply || apply[k], vals.data() + 13 * (size_t)k);
+    DevTmp<double> tab_d;
+    ResetPose one;
+    EKF_TRY(rewrite_arg(vals, nb, &one, &tab_d));
+    hipLaunchKernelGGL(k_reset_pose, dim3((unsigned)cdiv(3 + 2 * n_max, 256), (unsigned)nb), dim3(256), 0, h->s_chain, h->dv, one, (const double *)tab_d.p, b0);
+    return finish_rewrite(h, b0, nb, /*rearm*/ true, nullptr, 0, /*flip_buf*/ false);
+}
+
+extern "C" int ekf_reset_pose(ekf_handle h, int index, const double pose[3], const double P_RR[9]) {
+    if (!filter_ok(h, index) || !pose) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    EKF_TRY(set_error(plan_reset_args(pose, P_RR, index)));
+    return reset_impl(h, filters_of(h, index), pose, P_RR, nullptr);
+}
+
+extern "C" int ekf_batch_reset_pose(ekf_handle h, const double *pose, const double *P_RR) {
+    if (!h || !pose || !P_RR) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    for (int b = 0; b < h->dv.B; b++) EKF_TRY(set_error(plan_reset_args(pose + 3 * (size_t)b, P_RR + 9 * (size_t)b, b)));
+    return reset_impl(h, filters_of(h, -1), pose, P_RR, nullptr);
+}
+
+// ekf_locate_scan, the acceptance rule, ekf_reset_pose and ekf_update_matched of one scan as one call: every step is the public
+// call's own implementation with the public call's arguments -- the same bits.  Everything the later steps would refuse for their
+// values (R, P_RR) is refused before the search.  No filter accepted: returns behind the search, which only reads.  hyp_out [nb],
+// ids_out [nb][n_z], d2_out [nb][n_z] (may be null), n_out [nb] = the best hypothesis's inliers, or 0: refused.
+static int relocalize_impl(ekf_batch *h, Filters f, const double *z, const double *R, const unsigned char *valid, int n_z, double tol, double min_sep, int max_base,
+                           int max_out, int min_inliers, int lead, const double *prr, ekf_locate_hyp *hyp_out, int *ids_out, double *d2_out, int *n_out) {
+    const int b0 = f.b0, nb = f.nb;
+    if (!hyp_out || !ids_out || !prr || min_inliers < 2 || lead < 0 || n_z < 0 || (n_z > 0 && (!z || !R)) || max_out < 1 || max_out > EKF_LOCATE_MAX_OUT)
+        return set_error(EKF_ERR_BAD_ARG, "bad argument (min_inliers >= 2, lead >= 0, max_out in 1 .. %d, no null list)", EKF_LOCATE_MAX_OUT);
+    for (int k = 0; k < nb; k++) {
+        EKF_TRY(set_error(plan_reset_args(nullptr, prr + 9 * (size_t)k, b0 + k)));
+        for (int q = 0; q < n_z; q++) {
+            const size_t at = (size_t)k * n_z + q;
+            if ((!valid || valid[at]) && !(__builtin_isfinite(z[2 * at]) && __builtin_isfinite(z[2 * at + 1]) && plan_entry_finite(z, R, at)))
+                return set_error(EKF_ERR_BAD_ARG, "filter %d, measurement %d: z or R is not finite", b0 + k, q);
+        }
+    }
+    const size_t all = (size_t)nb * n_z;
+    std::vector<ekf_locate_hyp> hyps((size_t)nb * max_out);
+    std::vector<int> ids((size_t)nb * max_out * (n_z > 0 ? n_z : 1)), found((size_t)nb, 0);
+    EKF_TRY(locate_impl(h, f, z, valid, n_z, tol, min_sep, max_base, max_out, hyps.data(), ids.data(), found.data(), nullptr));
+    const LocateTable tab = plan_locate_table(z, valid, n_z, nb, min_sep, 1);  // (its reach)
+    std::vector<unsigned char> accepted((size_t)nb, 0);
+    std::vector<double> poses((size_t)nb * 3, 0.0);
+    std::vector<int> ids_m(all > 0 ? all : 1, -1);
+    bool any = false;
+    for (int k = 0; k < nb; k++) {
+        const ekf_locate_hyp *mine = hyps.data() + (size_t)k * max_out;
+        accepted[k] = plan_locate_accept(mine, found[k], tol, tab.reach[k], min_inliers, lead);
+        any = any || accepted[k];
+        n_out[k] = accepted[k] ? mine[0].inliers : 0;
+        if (found[k] > 0) hyp_out[k] = mine[0];
+        else memset(&hyp_out[k], 0, sizeof(ekf_locate_hyp));
+        for (int q = 0; q < n_z; q++) ids_out[(size_t)k * n_z + q] = found[k] > 0 ? ids[(size_t)k * max_out * n_z + q] : -1;
+        for (int q = 0; q < n_z; q++) ids_m[(size_t)k * n_z + q] = accepted[k] ? ids_out[(size_t)k * n_z + q] : -1;
+        for (int i = 0; i < 3; i++) poses[3 * (size_t)k + i] = accepted[k] ? mine[0].pose[i] : 0.0;
+    }
+    for (size_t q = 0; d2_out && q < all; q++) d2_out[q] = __builtin_nan("");
+    if (!any) return EKF_OK;
+    EKF_TRY(reset_impl(h, f, poses.data(), prr, nb == 1 ? nullptr : accepted.data()));
+    std::vector<int> applied((size_t)nb, 0);
+    const int rc = list_update_impl(MATCHED, h, f, z, R, ids_m.data(), n_z, applied.data(), d2_out);
+    return rc < 0 ? rc : EKF_OK;
+}
+
+extern "C" int ekf_relocalize(ekf_handle h, int index, const double *z, const double *R, int n_z, double tol, double min_sep, int max_base, int max_out, int min_inliers,
+                              int lead, const double P_RR[9], ekf_locate_hyp *hyp_out, int *ids_out, double *d2_out) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    int n = 0;
+    EKF_TRY(relocalize_impl(h, filters_of(h, index), z, R, nullptr, n_z, tol, min_sep, max_base, max_out, min_inliers, lead, P_RR, hyp_out, ids_out, d2_out, &n));
+    return n;
+}
+
+extern "C" int ekf_batch_relocalize(ekf_handle h, const double *z, const double *R, const unsigned char *valid, int n_z, double tol, double min_sep, int max_base,
+                                    int max_out, int min_inliers, int lead, const double *P_RR, ekf_locate_hyp *hyp_out, int *ids_out, double *d2_out, int *n_out) {
+    if (!h || !n_out) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return relocalize_impl(h, filters_of(h, -1), z, R, valid, n_z, tol, min_sep, max_base, max_out, min_inliers, lead, P_RR, hyp_out, ids_out, d2_out, n_out);
 }
 
 extern "C" int ekf_get_landmark_covs(ekf_handle h, int index, double *cov_out, int n_max) {

@@ -1,9 +1,9 @@
 // ekf_map_plan.h -- the host-side planning of the map operations (ekf_map_api.hip) as pure code: the checks of the lists a caller
-// hands in and the tables the kernels of ekf_rewrite.hip, ekf_extract.hip, ekf_pairs.hip, ekf_fuse.hip, ekf_match.hip, ekf_fix.hip
-// and ekf_gate.hip read.  No HIP call and no handle in here: landmark counts come in as plain arrays, n_lm[k] = landmarks of the k-th filter of the call, whose number in its
+// hands in and the tables the kernels of ekf_rewrite.hip, ekf_extract.hip, ekf_pairs.hip, ekf_fuse.hip, ekf_match.hip, ekf_fix.hip,
+// ekf_gate.hip and ekf_locate.hip read.  No HIP call and no handle in here: landmark counts come in as plain arrays, n_lm[k] = landmarks of the k-th filter of the call, whose number in its
 // handle is b0 + k (error texts name that number).  A check reports a status and a text; the caller hands both to set_error.
 // tests/cpp/map_plan_check.cpp, tests/cpp/match_plan_check.cpp, tests/cpp/fix_plan_check.cpp, tests/cpp/gate_plan_check.cpp,
-// tests/cpp/assoc_plan_check.cpp and tests/cpp/add_plan_check.cpp run all of it on the CPU.
+// tests/cpp/assoc_plan_check.cpp, tests/cpp/add_plan_check.cpp and tests/cpp/locate_plan_check.cpp run all of it on the CPU.
 #pragma once
 #include <math.h>
 #include <stdarg.h>
@@ -578,4 +578,110 @@ inline void plan_joint_merge(const int *applied, const int *new_ids, int n_z, in
             if (kind[at] == EKF_DECISION_NEW) ids[at] = new_ids[at];
         }
     }
+}
+
+// ---- relocalisation (ekf_locate_scan, ekf_reset_pose, ekf_relocalize) -------------------------------------------------------------
+// The scans of nb filters as for plan_gate_args, without R.  Checked before the handle is touched: n_z, the pointers, tol and
+// min_sep finite and positive, max_base and max_out in range, z of every valid entry finite, at most `limit` (EKF_MAX_PENDING) valid
+// entries per filter.
+inline PlanStatus plan_locate_args(const double *z, const unsigned char *valid, int n_z, int b0, int nb, double tol, double min_sep, int max_base, int max_out,
+                                   const ekf_locate_hyp *hyp_out, const int *ids_out, int limit) {
+    if (n_z < 0) return plan_fail(EKF_ERR_BAD_ARG, "negative measurement count");
+    if (n_z > 0 && !z) return plan_fail(EKF_ERR_BAD_ARG, "a null list with n_z > 0");
+    if (!(__builtin_isfinite(tol) && tol > 0.0)) return plan_fail(EKF_ERR_BAD_ARG, "tol is not finite and positive");
+    if (!(__builtin_isfinite(min_sep) && min_sep > 0.0)) return plan_fail(EKF_ERR_BAD_ARG, "min_sep is not finite and positive");
+    if (max_base < 1 || max_base > EKF_LOCATE_MAX_BASE) return plan_fail(EKF_ERR_BAD_ARG, "max_base = %d is not in 1 .. %d", max_base, EKF_LOCATE_MAX_BASE);
+    if (max_out < 1 || max_out > EKF_LOCATE_MAX_OUT) return plan_fail(EKF_ERR_BAD_ARG, "max_out = %d is not in 1 .. %d", max_out, EKF_LOCATE_MAX_OUT);
+    if (!hyp_out || !ids_out) return plan_fail(EKF_ERR_BAD_ARG, "hyp_out or ids_out is null");
+    for (int k = 0; k < nb; k++) {
+        int kept = 0;
+        for (int q = 0; q < n_z; q++) {
+            const size_t at = (size_t)k * n_z + q;
+            if (valid && !valid[at]) continue;
+            if (!(__builtin_isfinite(z[2 * at]) && __builtin_isfinite(z[2 * at + 1]))) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, measurement %d: z is not finite", b0 + k, q);
+            kept++;
+        }
+        if (kept > limit) return plan_fail(EKF_ERR_BAD_ARG, "filter %d: %d valid measurements, a search takes at most %d", b0 + k, kept, limit);
+    }
+    return {};
+}
+// The tables the search reads (LocScratch of the call's filters): zt [nb][32][2] the valid entries compacted, cnt [nb], src [nb][32]
+// the caller's index of each (increasing); the base pairs base [nb][16][2] (compacted indices a < b) with their separations
+// blen [nb][16] = sqrt(dx dx + dy dy), nbase [nb]: the pairs with a separation >= min_sep, by separation descending, then (a, b)
+// ascending, the first max_base; reach [nb] = the largest |z_k| of a valid entry (0: none).
+struct LocateTable {
+    std::vector<double> zt, blen, reach;
+    std::vector<int> cnt, src, base, nbase;
+};
+inline LocateTable plan_locate_table(const double *z, const unsigned char *valid, int n_z, int nb, double min_sep, int max_base) {
+    const int cap = EKF_MAX_PENDING, bcap = EKF_LOCATE_MAX_BASE;
+    LocateTable t;
+    t.zt.assign((size_t)nb * cap * 2, 0.0), t.blen.assign((size_t)nb * bcap, 0.0), t.reach.assign((size_t)nb, 0.0);
+    t.cnt.assign((size_t)nb, 0), t.src.assign((size_t)nb * cap, -1), t.base.assign((size_t)nb * bcap * 2, 0), t.nbase.assign((size_t)nb, 0);
+    struct Pair {
+        double len;
+        int a, b;
+    };
+    for (int k = 0; k < nb; k++) {
+        double *zk = t.zt.data() + (size_t)k * cap * 2;
+        for (int q = 0; q < n_z; q++) {
+            const size_t at = (size_t)k * n_z + q;
+            if ((valid && !valid[at]) || t.cnt[k] >= cap) continue;
+            const int to = t.cnt[k]++;
+            zk[2 * to] = z[2 * at], zk[2 * to + 1] = z[2 * at + 1];
+            t.src[(size_t)k * cap + to] = q;
+            t.reach[k] = std::max(t.reach[k], sqrt(z[2 * at] * z[2 * at] + z[2 * at + 1] * z[2 * at + 1]));
+        }
+        std::vector<Pair> pairs;
+        for (int a = 0; a < t.cnt[k]; a++)
+            for (int b = a + 1; b < t.cnt[k]; b++) {
+                const double dx = zk[2 * b] - zk[2 * a], dy = zk[2 * b + 1] - zk[2 * a + 1];
+                const double len = sqrt(dx * dx + dy * dy);
+                if (len >= min_sep) pairs.push_back({len, a, b});
+            }
+        std::stable_sort(pairs.begin(), pairs.end(), [](const Pair &p, const Pair &q) { return p.len > q.len; });  // (generated in (a, b) order)
+        t.nbase[k] = std::min((int)pairs.size(), max_base);
+        for (int r = 0; r < t.nbase[k]; r++) {
+            t.base[((size_t)k * bcap + r) * 2] = pairs[r].a, t.base[((size_t)k * bcap + r) * 2 + 1] = pairs[r].b;
+            t.blen[(size_t)k * bcap + r] = pairs[r].len;
+        }
+    }
+    return t;
+}
+// Two fitted poses (x, y, heading) are the same pose: positions within 2 tol, headings (their difference wrapped into [-pi, pi])
+// within 2 tol / reach; reach <= 0 (no measurement away from the robot): the heading says nothing.
+inline bool plan_locate_same_pose(const double a[3], const double b[3], double tol, double reach) {
+    const double dx = a[0] - b[0], dy = a[1] - b[1];
+    if (!(sqrt(dx * dx + dy * dy) <= 2.0 * tol)) return false;
+    if (!(reach > 0.0)) return true;
+    const double dphi = remainder(a[2] - b[2], 2.0 * M_PI);
+    return fabs(dphi) <= 2.0 * tol / reach;
+}
+// ekf_relocalize's acceptance over the `n` written hypotheses of a filter, best first: the best has at least min_inliers, and every
+// other one that is not the same pose as the best has at most best - lead.
+inline bool plan_locate_accept(const ekf_locate_hyp *hyps, int n, double tol, double reach, int min_inliers, int lead) {
+    if (n < 1 || hyps[0].inliers < min_inliers) return false;
+    for (int k = 1; k < n; k++)
+        if (hyps[k].inliers > hyps[0].inliers - lead && !plan_locate_same_pose(hyps[k].pose, hyps[0].pose, tol, reach)) return false;
+    return true;
+}
+// ekf_reset_pose's arguments of one filter: every entry finite, no negative diagonal entry of P_RR.  pose == nullptr: P_RR alone
+// (ekf_relocalize, whose pose comes out of the search).
+inline PlanStatus plan_reset_args(const double *pose, const double *prr, int filter) {
+    if (!prr) return plan_fail(EKF_ERR_BAD_ARG, "a null P_RR");
+    for (int i = 0; pose && i < 3; i++)
+        if (!__builtin_isfinite(pose[i])) return plan_fail(EKF_ERR_BAD_ARG, "filter %d: the pose is not finite", filter);
+    for (int i = 0; i < 9; i++)
+        if (!__builtin_isfinite(prr[i])) return plan_fail(EKF_ERR_BAD_ARG, "filter %d: P_RR is not finite", filter);
+    for (int i = 0; i < 3; i++)
+        if (prr[4 * i] < 0.0) return plan_fail(EKF_ERR_BAD_ARG, "filter %d: P_RR[%d][%d] is negative", filter, i, i);
+    return {};
+}
+// ... as the kernel takes them (ekf_rewrite.hip: ResetPose): the pose, P_RR symmetrised row-major (off-diagonals 0.5 * (a + b), as
+// Update.cpp:193), apply (1.0, or 0.0: the filter is left alone).
+inline void plan_reset_values(const double *pose, const double *prr, bool apply, double out[13]) {
+    for (int i = 0; i < 3; i++) out[i] = pose[i];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) out[3 + 3 * i + j] = i == j ? prr[4 * i] : 0.5 * (prr[3 * i + j] + prr[3 * j + i]);
+    out[12] = apply ? 1.0 : 0.0;
 }

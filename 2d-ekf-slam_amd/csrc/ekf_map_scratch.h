@@ -157,6 +157,55 @@ inline void carve_assoc(AssocScratch &as, Carver &c, const ScratchGeom &g) {
     as.ids = c.take<int>(g.B * EKF_MAX_PENDING);
 }
 
+// ---- ekf_locate.hip (ekf_locate_scan) ---------------------------------------------------------------------------------------------
+#define LOC_THREADS 256
+#define LOC_LDS_LM 4096     // landmarks of x a k_loc_score workgroup stages in LDS at a time (64 KB)
+#define LOC_PICK_PARTS 64   // partial lists of the selection per filter
+#define LOC_LIST_FLOOR 4096 // candidates per filter the list starts with
+struct LocScratch {
+    double *z;                // [B][32][2]     the call's valid measurements of each filter, compacted
+    double *blen;             // [B][16]        the base pairs' separations
+    double *pssr;             // [B][LOC_PICK_PARTS][64]  the partial lists of the selection: ssr, ...
+    double *wssr;             // [B][64]        the selected hypotheses, best first
+    ekf_locate_hyp *hyp;      // [B][64]        their records (meas_a, meas_b: compacted indices)
+    unsigned long long *cnt;  // [B]            candidates found by the call
+    unsigned *pkey;           // [B][LOC_PICK_PARTS][64]  ... key (r << 28 | i << 14 | j), ...
+    unsigned *wkey;           // [B][64]
+    int *pinl;                // [B][LOC_PICK_PARTS][64]  ... inliers (-1: no entry)
+    int *winl;                // [B][64]
+    int *ids;                 // [B][64][32]    the landmark of each compacted measurement under each selected hypothesis, -1: none
+    int *nz;                  // [B]            valid measurements of the call
+    int *nbase;               // [B]            base pairs of the call (0: nothing to search)
+    int *base;                // [B][16][2]     their measurements (compacted indices a < b)
+    double *ssr;              // [B][ccap]      the list: the score of candidate q, ...
+    unsigned *key;            // [B][ccap]      ... its key, the first ccap appended, ...
+    int *inl;                 // [B][ccap]      ... its inliers
+    int ccap;
+};
+inline void carve_loc(LocScratch &ls, Carver &c, const ScratchGeom &g) {
+    const size_t B = g.B, sel = B * EKF_LOCATE_MAX_OUT, part = sel * LOC_PICK_PARTS;
+    ls.z = c.take<double>(B * EKF_MAX_PENDING * 2);
+    ls.blen = c.take<double>(B * EKF_LOCATE_MAX_BASE);
+    ls.pssr = c.take<double>(part);
+    ls.wssr = c.take<double>(sel);
+    ls.hyp = c.take<ekf_locate_hyp>(sel);
+    ls.cnt = c.take<unsigned long long>(B);
+    ls.pkey = c.take<unsigned>(part);
+    ls.wkey = c.take<unsigned>(sel);
+    ls.pinl = c.take<int>(part);
+    ls.winl = c.take<int>(sel);
+    ls.ids = c.take<int>(sel * EKF_MAX_PENDING);
+    ls.nz = c.take<int>(B);
+    ls.nbase = c.take<int>(B);
+    ls.base = c.take<int>(B * EKF_LOCATE_MAX_BASE * 2);
+}
+inline void carve_loc_list(LocScratch &ls, Carver &c, const ScratchGeom &g, int ccap) {
+    ls.ssr = c.take<double>(g.B * (size_t)ccap);
+    ls.key = c.take<unsigned>(g.B * (size_t)ccap);
+    ls.inl = c.take<int>(g.B * (size_t)ccap);
+    ls.ccap = ccap;
+}
+
 // ---- ekf_rewrite.hip (ekf_add_landmarks) ------------------------------------------------------------------------------------------
 struct AddScratch {
     double *tab;  // [B][add_tab_stride(zcap)]

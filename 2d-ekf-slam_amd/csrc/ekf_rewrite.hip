@@ -415,6 +415,32 @@ __global__ void k_reframe_finish(EkfDev dv, ReframeFrame one, const double *fr, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Pose reset (ekf_reset_pose): x[0..2] <- pose, P_RR <- the caller's (symmetrised on the host), every robot-landmark block +0.0; the
+// landmarks of x, D and Bm are not touched.  The three robot rows are the only copy of P_RL the kernels keep (the slot rows are
+// cleared behind every rewrite), so one O(N) pass over them is all of it: thread j of filter b_off + blockIdx.y takes column j of the
+// three rows; the thread of column 0 also stores the pose and does the bookkeeping of k_reframe_finish.  The per-filter argument is
+// thirteen doubles: the pose, P_RR row-major, apply (0.0: the filter is left alone -- ekf_batch_relocalize's refused filters).
+// ---------------------------------------------------------------------------------------------
+struct ResetPose {
+    double v[13];
+};
+__global__ __launch_bounds__(256) void k_reset_pose(EkfDev dv, ResetPose one, const double *tab, int b_off) {
+    const int b = b_off + blockIdx.y;
+    if (arg_value(one, tab, blockIdx.y, 12) == 0.0) return;
+    const int n = dv.n_lm[b];
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= 3 + 2 * n) return;
+    double *R0 = filt_R(dv, b);
+    for (int i = 0; i < 3; i++) R0[(size_t)i * dv.xs + j] = j < 3 ? arg_value(one, tab, blockIdx.y, 3 + 3 * i + j) : 0.0;
+    if (j != 0) return;
+    double *x = filt_x(dv, b);
+    double p[9];
+    for (int k = 0; k < 3; k++) x[k] = arg_value(one, tab, blockIdx.y, k);
+    for (int k = 0; k < 9; k++) p[k] = arg_value(one, tab, blockIdx.y, 3 + k);
+    settle_meta(dv, b, n, x, p, 3);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Map joining (ekf_join_map): the Ns landmarks of a source filter, expressed in the frame of the destination's estimated pose
 // p = (t, phi), appended behind the destination's Ng landmarks; the old pose is marginalised out, the source's pose becomes the
 // robot.  With C = Rot(phi), h_k = J C M_k (the third column of G_k = [I | C J M_k]) and g = J C u (of G_R):

@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "ekf_gate_candidates", "ekf_batch_gate_candidates",
     "ekf_associate_joint", "ekf_batch_associate_joint", "ekf_joint_gates",
     "ekf_add_landmarks", "ekf_batch_add_landmarks", "ekf_update_joint", "ekf_batch_update_joint",
+    "ekf_locate_scan", "ekf_batch_locate_scan", "ekf_reset_pose", "ekf_batch_reset_pose", "ekf_relocalize", "ekf_batch_relocalize",
 ]
 
 
@@ -92,6 +93,19 @@ assert ASSOC_DTYPE.itemsize == ctypes.sizeof(EkfAssoc) == 32
 ASSOC_MAX_MEAS, ASSOC_MAX_BRANCH, ASSOC_MAX_NODES = 32, 16, 1 << 20
 DECISION_DTYPE = np.dtype([("decision", "i4"), ("matched", "i4"), ("mahal", "f8")])
 assert DECISION_DTYPE.itemsize == ctypes.sizeof(EkfDecision) == 16
+
+
+
+class EkfLocateHyp(ctypes.Structure):
+    _fields_ = [("pose", ctypes.c_double * 3), ("pair_pose", ctypes.c_double * 3), ("ssr", ctypes.c_double), ("rms", ctypes.c_double),
+                ("inliers", ctypes.c_int), ("meas_a", ctypes.c_int), ("meas_b", ctypes.c_int), ("lm_i", ctypes.c_int), ("lm_j", ctypes.c_int),
+                ("reserved", ctypes.c_int)]
+
+
+LOCATE_DTYPE = np.dtype([("pose", "f8", (3,)), ("pair_pose", "f8", (3,)), ("ssr", "f8"), ("rms", "f8"), ("inliers", "i4"), ("meas_a", "i4"),
+                         ("meas_b", "i4"), ("lm_i", "i4"), ("lm_j", "i4"), ("reserved", "i4")])
+assert LOCATE_DTYPE.itemsize == ctypes.sizeof(EkfLocateHyp) == 88
+LOCATE_MAX_MEAS, LOCATE_MAX_BASE, LOCATE_MAX_OUT, LOCATE_MAX_CAND = 32, 16, 64, 1 << 22
 
 _STATS_DTYPE = np.dtype([(n, "f8" if t is ctypes.c_double else "i8") for n, t in EkfStats._fields_])
 
@@ -188,6 +202,15 @@ def load():
                                    ctypes.POINTER(EkfAssoc)]
     L.ekf_batch_update_joint.argtypes = [_H, _dp, _dp, _up, ctypes.c_int, ctypes.c_double, _dp, ctypes.c_int, ctypes.c_longlong, _ip, _ip, _dp,
                                          ctypes.POINTER(EkfAssoc), _ip]
+    _hp, _llp = ctypes.POINTER(EkfLocateHyp), ctypes.POINTER(ctypes.c_longlong)
+    L.ekf_locate_scan.argtypes = [_H, ctypes.c_int, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, _hp, _ip, _llp]
+    L.ekf_batch_locate_scan.argtypes = [_H, _dp, _up, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, _hp, _ip, _ip, _llp]
+    L.ekf_reset_pose.argtypes = [_H, ctypes.c_int, _dp, _dp]
+    L.ekf_batch_reset_pose.argtypes = [_H, _dp, _dp]
+    L.ekf_relocalize.argtypes = [_H, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                 ctypes.c_int, _dp, _hp, _ip, _dp]
+    L.ekf_batch_relocalize.argtypes = [_H, _dp, _dp, _up, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int, _dp, _hp, _ip, _dp, _ip]
     L.ekf_script_load.argtypes =[_H, ctypes.c_int, ctypes.c_int, _dp, _dp, _dp, _up, _dp]
     L.ekf_script_run.argtypes = [_H, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.ekf_sync.argtypes = [_H]
@@ -286,6 +309,39 @@ def candidate_matching(cands, n_z):
         ids[m] = l
         taken.add(l)
     return ids
+
+
+def same_pose(a, b, tol, reach):
+    """Two poses (x, y, heading) are the same pose for a search of inlier radius tol: positions within 2 tol, headings (their
+    difference wrapped into [-pi, pi]) within 2 tol / reach, reach = the largest |z_k| of the scan (<= 0: the heading says nothing).
+    The rule ekf_relocalize's acceptance applies (plan_locate_same_pose)."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    if not np.hypot(a[0] - b[0], a[1] - b[1]) <= 2.0 * tol:
+        return False
+    if not reach > 0.0:
+        return True
+    return bool(abs(np.remainder(a[2] - b[2] + np.pi, 2.0 * np.pi) - np.pi) <= 2.0 * tol / reach)
+
+
+def distinct_poses(hyps, tol, reach):
+    """The hypotheses of locate_scan with the repeats of one pose merged: the same true pose recurs once per base pair and landmark
+    pair that hits it.  In list order, a hypothesis joins the first kept one whose fitted pose is the same pose (same_pose: within
+    2 tol in position and 2 tol / reach in heading), else it is kept.  Returns (kept, group): the kept records (a LOCATE_DTYPE array,
+    best first, as the list is) and for every input hypothesis the position of its pose in `kept`."""
+    hyps = np.asarray(hyps, dtype=LOCATE_DTYPE).reshape(-1)
+    tol, reach = float(tol), float(reach)
+    if not tol > 0.0:
+        raise ValueError("tol must be positive")
+    keep, group = [], np.empty(len(hyps), dtype=np.int64)
+    for k in range(len(hyps)):
+        for g, first in enumerate(keep):
+            if same_pose(hyps["pose"][k], hyps["pose"][first], tol, reach):
+                group[k] = g
+                break
+        else:
+            group[k] = len(keep)
+            keep.append(k)
+    return hyps[keep].copy(), group
 
 
 def joint_gates(confidence=0.99):
@@ -801,6 +857,103 @@ class FilterBatch:
         out = [(buf[b, :min(int(found[b]), max_cand)].copy(), int(found[b]), near[b].copy(), skip[b].copy()) for b in range(nb)]
         return out if index is None else out[0]
 
+    def _locate_args(self, z, valid, index, tol, min_sep, max_base, max_out):
+        """The arguments of locate_scan / relocalize checked and laid out: (z, valid or None, n_z, filters of the call)."""
+        if not (np.isfinite(tol) and tol > 0.0 and np.isfinite(min_sep) and min_sep > 0.0):
+            raise ValueError("tol and min_sep must be finite and positive")
+        if not 1 <= max_base <= LOCATE_MAX_BASE or not 1 <= max_out <= LOCATE_MAX_OUT:
+            raise ValueError("max_base must lie in 1 .. %d and max_out in 1 .. %d" % (LOCATE_MAX_BASE, LOCATE_MAX_OUT))
+        lead = (self.batch,) if index is None else ()
+        z = np.asarray(z, dtype=np.float64)
+        if z.ndim != len(lead) + 2 or z.shape[:len(lead)] != lead or z.shape[-1] != 2:
+            raise ValueError("z must be [batch][n_z][2]" if lead else "z must be [n_z][2]")
+        n_z = z.shape[-2]
+        if valid is not None:
+            if index is not None:
+                raise ValueError("valid masks the entries of the batch form (index=None)")
+            valid = np.ascontiguousarray(valid, dtype=np.uint8)
+            if valid.shape != lead + (n_z,):
+                raise ValueError("valid must be [batch][n_z]")
+        look = np.ones(lead + (n_z,), dtype=bool) if valid is None else valid != 0
+        if not np.isfinite(z[look]).all():
+            raise ValueError("z of a valid entry must be finite")
+        if int(look.sum(axis=-1).max(initial=0)) > LOCATE_MAX_MEAS:
+            raise ValueError("a search takes at most %d valid measurements per filter" % LOCATE_MAX_MEAS)
+        return _f64(z), valid, n_z, (self.batch if index is None else 1)
+
+    def locate_scan(self, z, tol, min_sep=1.0, max_base=4, max_out=16, index=0, valid=None):
+        """Where am I on this map?  The read-only scan-to-map pose search on the device (ekf_locate_scan): z [n_z][2] robot-frame
+        relative positions (at most 32 valid), tol the inlier radius in metres, min_sep the smallest separation of a base pair,
+        max_base (1 .. 16) base pairs, max_out (1 .. 64) hypotheses.  Only x is read -- the search is Euclidean, P and R play no
+        part -- and an open window stays open.  Returns (hyps, ids, n_candidates): a LOCATE_DTYPE array of the hypotheses written,
+        ordered by (inliers descending, ssr ascending, then base pair and landmark pair), ids [len(hyps)][n_z] int32 (row h: the
+        landmark of each measurement under hypothesis h, -1: none -- the ids update_matched takes) and the number of candidates
+        scored.  The same true pose recurs once per base pair that hits it: distinct_poses merges the repeats.  index=None: every
+        filter in one launch sequence (ekf_batch_locate_scan), a leading batch axis on z, valid [batch][n_z] masks entries; returns a
+        list of such tuples."""
+        tol, min_sep, max_base, max_out = float(tol), float(min_sep), int(max_base), int(max_out)
+        z, valid, n_z, nb = self._locate_args(z, valid, index, tol, min_sep, max_base, max_out)
+        hyps = np.zeros((nb, max_out), dtype=LOCATE_DTYPE)
+        ids = np.full((nb, max_out, n_z), -1, dtype=np.int32)
+        found, ncand = np.zeros(nb, dtype=np.int32), np.zeros(nb, dtype=np.int64)
+        hp, ip, cp = hyps.ctypes.data_as(ctypes.POINTER(EkfLocateHyp)), ids.ctypes.data_as(_ip), ncand.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong))
+        zp = _p(z) if n_z else None
+        if index is None:
+            vp = valid.ctypes.data_as(_up) if valid is not None and n_z else None
+            _chk(self.L.ekf_batch_locate_scan(self.h, zp, vp, n_z, tol, min_sep, max_base, max_out, hp, ip, found.ctypes.data_as(_ip), cp))
+        else:
+            found[0] = _chk(self.L.ekf_locate_scan(self.h, int(index), zp, n_z, tol, min_sep, max_base, max_out, hp, ip, cp))
+        out = [(hyps[b, :found[b]].copy(), ids[b, :found[b]].copy(), int(ncand[b])) for b in range(nb)]
+        return out if index is None else out[0]
+
+    def reset_pose(self, pose, P_RR, index=0):
+        """The pose replaced and its correlation with the map cut, on the device (ekf_reset_pose): x[0:3] = pose, P_RR = the
+        symmetrised P_RR [3][3] (zeros: a known pose), every robot-landmark block of P zero; P_LL and the landmarks stay bit for bit.
+        index=None: pose [batch][3], P_RR [batch][3][3], every filter in one launch (ekf_batch_reset_pose)."""
+        lead = (self.batch,) if index is None else ()
+        pose, P_RR = _f64(pose), _f64(P_RR)
+        if pose.shape != lead + (3,) or P_RR.size != pose.size * 3:
+            raise ValueError("pose must be [batch][3] and P_RR [batch][3][3]" if lead else "pose must be [3] and P_RR [3][3]")
+        P_RR = _f64(P_RR.reshape(lead + (3, 3)))
+        if not (np.isfinite(pose).all() and np.isfinite(P_RR).all()):
+            raise ValueError("pose and P_RR must be finite")
+        if (np.diagonal(P_RR, axis1=-2, axis2=-1) < 0.0).any():
+            raise ValueError("a diagonal entry of P_RR is negative")
+        if index is None:
+            _chk(self.L.ekf_batch_reset_pose(self.h, _p(pose), _p(P_RR)))
+        else:
+            _chk(self.L.ekf_reset_pose(self.h, int(index), _p(pose), _p(P_RR)))
+
+    def relocalize(self, z, R, tol, P_RR, min_sep=1.0, max_base=4, max_out=16, min_inliers=4, lead=2, index=0, valid=None):
+        """locate_scan, the acceptance rule, reset_pose at the best hypothesis's fitted pose with P_RR, update_matched with its ids
+        and R, as one call (ekf_relocalize).  Accepted iff the best hypothesis has at least min_inliers inliers and every other
+        written hypothesis that is not the same pose (same_pose) has at most best - lead.  Returns (n, hyp, ids, d2): n = the best
+        hypothesis's inliers, or 0: refused, the state untouched; hyp a LOCATE_DTYPE record (zeros: nothing found), ids [n_z], d2
+        [n_z] that of update_matched (NaN when refused).  index=None: leading batch axes on z, R, valid and P_RR; returns (n
+        (batch,), hyps (batch,), ids (batch, n_z), d2 (batch, n_z)); the refused filters are left alone."""
+        tol, min_sep, max_base, max_out, min_inliers, lead = float(tol), float(min_sep), int(max_base), int(max_out), int(min_inliers), int(lead)
+        if min_inliers < 2 or lead < 0:
+            raise ValueError("min_inliers must be at least 2 and lead must not be negative")
+        z, Rc, valid, n_z = self._scan_lists(z, R, valid, index)
+        self._locate_args(z, valid, index, tol, min_sep, max_base, max_out)
+        nb = self.batch if index is None else 1
+        P_RR = _f64(P_RR)
+        if P_RR.size != 9 * nb:
+            raise ValueError("P_RR must be [batch][3][3]" if index is None else "P_RR must be [3][3]")
+        P_RR = _f64(P_RR.reshape(nb, 3, 3))
+        if not np.isfinite(P_RR).all() or (np.diagonal(P_RR, axis1=-2, axis2=-1) < 0.0).any():
+            raise ValueError("P_RR must be finite, without a negative diagonal entry")
+        hyp = np.zeros(nb, dtype=LOCATE_DTYPE)
+        ids, d2, n = np.full((nb, n_z), -1, dtype=np.int32), np.full((nb, n_z), np.nan), np.zeros(nb, dtype=np.int32)
+        ptrs = (_p(z), _p(Rc)) if n_z else (None, None)
+        outs = (hyp.ctypes.data_as(ctypes.POINTER(EkfLocateHyp)), ids.ctypes.data_as(_ip), _p(d2) if n_z else None)
+        if index is None:
+            vp = valid.ctypes.data_as(_up) if valid is not None and n_z else None
+            _chk(self.L.ekf_batch_relocalize(self.h, *ptrs, vp, n_z, tol, min_sep, max_base, max_out, min_inliers, lead, _p(P_RR), *outs, n.ctypes.data_as(_ip)))
+            return n, hyp, ids, d2
+        n[0] = _chk(self.L.ekf_relocalize(self.h, int(index), *ptrs, n_z, tol, min_sep, max_base, max_out, min_inliers, lead, _p(P_RR), *outs))
+        return int(n[0]), hyp[0].copy(), ids[0], d2[0]
+
     def _assoc_args(self, z, R, gate, joint_gate, max_branch, max_nodes, index, valid):
         """The arguments of associate_joint / update_joint checked and laid out: (gate, joint gates or None, max_branch, max_nodes,
         z, Rc, valid, n_z, filters of the call)."""
@@ -1120,6 +1273,22 @@ class KalmanFilter:
         """The gate-passing landmarks of every measurement, the filter's own decision for each and the skip counts
         (FilterBatch.gate_candidates): (cands, n_found, nearest, n_skipped); nothing is applied."""
         return self._f.gate_candidates(z, R, gate, 0)
+
+    def locate_scan(self, z, tol, min_sep=1.0, max_base=4, max_out=16):
+        """The scan-to-map pose search (FilterBatch.locate_scan): (hyps, ids, n_candidates); only x is read."""
+        return self._f.locate_scan(z, tol, min_sep, max_base, max_out, 0)
+
+    def reset_pose(self, pose, P_RR):
+        """Replace the pose and cut its correlation with the map (FilterBatch.reset_pose); refreshes X, Y, Phi."""
+        self._f.reset_pose(pose, P_RR, 0)
+        self._mirror()
+
+    def relocalize(self, z, R, tol, P_RR, min_sep=1.0, max_base=4, max_out=16, min_inliers=4, lead=2):
+        """Search, accept, reset the pose and apply the scan (FilterBatch.relocalize): (n, hyp, ids, d2), n = 0: refused, nothing
+        changed; refreshes X, Y, Phi."""
+        out = self._f.relocalize(z, R, tol, P_RR, min_sep, max_base, max_out, min_inliers, lead, 0)
+        self._mirror()
+        return out
 
     def add_landmarks(self, z, R, add=None):
         """Initialise landmarks from measurements (FilterBatch.add_landmarks): (n_landmarks, ids)."""

@@ -660,6 +660,113 @@ int ekf_batch_update_joint(ekf_handle h, const double *z /*[batch][n_z][2]*/, co
                            int max_branch, long long max_nodes, int *ids_out /*[batch][n_z]*/, int *kind_out /*[batch][n_z] or NULL*/,
                            double *d2_out /*[batch][n_z] or NULL*/, ekf_assoc *info_out /*[batch]*/, int *n_out /*[batch]*/);
 
+/* ---- relocalisation: where am I on this map? ---------------------------------------------------
+ * Every association path above starts from a pose prior that is already good.  After a bump, a long blind stretch, or with a saved
+ * map loaded into a robot that does not know where it stands, the gates fail and every measurement is declared New.  The three
+ * calls below answer that case on the device: a Euclidean scan-to-map pose search, the pose reset it ends in, and the two with
+ * ekf_update_matched as one call.
+ *
+ * ekf_locate_scan: the read-only pose search.  z [n_z][2] are robot-frame relative positions in the layout of ekf_update; at most
+ * EKF_MAX_PENDING = 32 valid measurements per filter, more is EKF_ERR_BAD_ARG as for ekf_joint_compat.  ONLY x IS READ: P and R play
+ * no part, the search is Euclidean (tol is a radius in metres, not a chi-square gate).
+ *   BASE PAIRS: the pairs (a, b), a < b, of valid measurements with |z_a - z_b| >= min_sep, ordered by separation descending, then
+ *     by (a, b) ascending; the first max_base (1 .. EKF_LOCATE_MAX_BASE = 16) are kept, rank r = 0 the farthest apart.
+ *   CANDIDATES: for the base pair of rank r, every ordered landmark pair (i, j), i != j, with
+ *     | |L_j - L_i| - |z_b - z_a| | <= 2 tol  (lengths as sqrt of the sum of squares): exactly the pairs for which a and b can both
+ *     be inliers of their own hypothesis.
+ *   PAIR POSE of (r, i, j): dz = z_b - z_a, dl = L_j - L_i, q = |dz| |dl|, c = (dz . dl) / q, s = (dz x dl) / q
+ *     (dz x dl = dz_x dl_y - dz_y dl_x; no sincos is taken), C = [[c, -s], [s, c]], p = (L_i + L_j) / 2 - C (z_a + z_b) / 2;
+ *     pair_pose = (p_x, p_y, atan2(dz x dl, dz . dl)), the angle for the report only.
+ *   SCORE: for every valid k the landmark nearest to p + C z_k in squared distance (ties: the lower index); k is an inlier iff
+ *     that squared distance <= tol^2.  The match is then made one-to-one: where several inliers name one landmark, the one with
+ *     the smallest distance keeps it (ties: the lower k), the others are no inliers.  inliers = their count, ssr = the sum of
+ *     their squared distances, added in ascending k.
+ *   ORDER of the hypotheses: inliers descending, then ssr ascending, then (r, i, j) ascending -- a total order that does not
+ *     depend on how the device appended its candidate list.  The first min(found, max_out) are written (max_out 1 ..
+ *     EKF_LOCATE_MAX_OUT = 64), `found` = the number of candidates.
+ *   REFIT of each written hypothesis, one closed-form least-squares rigid fit over its inliers (the inlier set is not computed
+ *     again): centroids mz, ml of the inliers' z_k and L_k (sums in ascending k, divided by the count), Sd = sum (z_k - mz) . (L_k - ml),
+ *     Sx = sum (z_k - mz) x (L_k - ml), n = sqrt(Sd^2 + Sx^2), c' = Sd / n, s' = Sx / n (n == 0, a single inlier: the pair pose's c
+ *     and s), t = ml - C' mz; pose = (t_x, t_y, atan2(Sx, Sd)) (n == 0: the pair pose's angle), rms = sqrt(sum |t + C' z_k - L_k|^2 /
+ *     inliers) (0 without an inlier, where pose = pair_pose).
+ * hyp_out [max_out]: the records.  meas_a, meas_b are the caller's indices.  ids_out [max_out][n_z]: row h holds the landmark of
+ * each measurement under hypothesis h, or -1 (no inlier, masked) -- ready to be the ids of ekf_update_matched; rows from the number
+ * written on are left alone.  n_cand_out (may be NULL): the candidates scored.
+ * THE SAME TRUE POSE RECURS once per base pair (and landmark pair) that hits it: the list is ordered, not merged.  Hypotheses whose
+ * fitted poses agree within 2 tol in position and 2 tol / reach in heading (reach = the largest |z_k|) are the same pose; the
+ * Python binding's distinct_poses merges them, ekf_relocalize's acceptance rule applies the same test.
+ * The handle is treated exactly as in ekf_gate_candidates: x is current inside an open window; a streaming launch is stopped;
+ * nothing is folded, no dense pass runs, the window stays open; state, counters, decision log, loaded script and host mirror stay
+ * bit for bit; a sticky EKF_ERR_TIMEOUT is returned unchanged, a sticky EKF_ERR_CAPACITY does not block the call.  The call
+ * synchronises.
+ * Zero hypotheses with EKF_OK: fewer than two landmarks, fewer than two valid measurements, no base pair.
+ * EKF_ERR_BAD_ARG, found on the host before the handle is touched: n_z < 0, a NULL z with n_z > 0, a non-finite z of a valid entry,
+ * more than 32 valid entries in a filter, tol or min_sep not finite and positive, max_base or max_out out of range, NULL hyp_out
+ * or ids_out (n_found_out, batch form), an index out of range.
+ * More than EKF_LOCATE_MAX_CAND = 2^22 candidates in a filter: EKF_ERR_CAPACITY, not sticky, nothing written but n_cand_out -- tol
+ * is too loose for this map (a length filter of 2 tol that a fifth of all landmark pairs pass says nothing).
+ * Candidates are appended through an integer counter, every score comes out of fixed-order reductions, the selection follows the
+ * total order above; no floating-point atomics: two calls on an unchanged state give the same bits, and filter b of the batch form
+ * gets the bits of the one-filter call on b.
+ * The scratch -- the measurement and base-pair tables, the candidate list (4096 entries per filter at first; replaced by a larger
+ * one when a call finds more, the search then runs once more) with a score per entry, and the selection's partial lists -- is
+ * allocated at the first call that searches, kept on the handle (ekf_device_bytes counts it, ekf_reserve builds it again) and freed
+ * by ekf_destroy.
+ * ekf_locate_scan returns the number of hypotheses written, or a negative status; the batch form writes filter b's records at
+ * hyp_out + b * max_out, its ids at ids_out + b * max_out * n_z and the number written to n_found_out[b]. */
+#define EKF_LOCATE_MAX_BASE 16
+#define EKF_LOCATE_MAX_OUT 64
+#define EKF_LOCATE_MAX_CAND (1 << 22)
+typedef struct ekf_locate_hyp {
+    double pose[3];       /* the refit: x, y, heading */
+    double pair_pose[3];  /* the pose of the base pair on the landmark pair, which was scored */
+    double ssr;           /* sum of the inliers' squared distances at pair_pose */
+    double rms;           /* of the inliers at pose */
+    int inliers;
+    int meas_a, meas_b;   /* the base pair, the caller's indices */
+    int lm_i, lm_j;       /* the landmark pair: a on i, b on j */
+    int reserved;         /* 0 (the size stays a multiple of 8: 88 bytes) */
+} ekf_locate_hyp;
+int ekf_locate_scan(ekf_handle h, int index, const double *z /*[n_z][2]*/, int n_z, double tol, double min_sep, int max_base, int max_out,
+                    ekf_locate_hyp *hyp_out /*[max_out]*/, int *ids_out /*[max_out][n_z]*/, long long *n_cand_out /* may be NULL */);
+int ekf_batch_locate_scan(ekf_handle h, const double *z /*[batch][n_z][2]*/, const unsigned char *valid /*[batch][n_z] or NULL*/, int n_z,
+                          double tol, double min_sep, int max_base, int max_out, ekf_locate_hyp *hyp_out /*[batch][max_out]*/,
+                          int *ids_out /*[batch][max_out][n_z]*/, int *n_found_out /*[batch]*/, long long *n_cand_out /*[batch] or NULL*/);
+
+/* ekf_reset_pose: the pose replaced and its correlation with the map cut.  x[0..2] <- pose, P_RR <- the symmetrised P_RR (row-major
+ * 3 x 3; off-diagonals averaged, 0.5 * (a + b), as Update.cpp:193 does), every robot-landmark block of P becomes exactly +0.0; P_LL
+ * and the landmarks of x stay bit for bit.  P_RR = 0 is allowed (a known pose); the caller answers for a P_RR that is positive
+ * semi-definite.  Works on a filter without landmarks.
+ * Handle discipline of ekf_transform_frame: deferred slots are folded first, a streaming launch is stopped (immediate-mode calls
+ * stream again afterwards), the call synchronises; counters and decision log stay as they are; the host mirror shows the new pose
+ * and P_RR; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY is returned unchanged with nothing modified.  Every device buffer ends as
+ * ekf_set_state of the result would leave it (the robot rows are the only copy of P_RL the kernels keep).
+ * EKF_ERR_BAD_ARG: a non-finite entry, a negative diagonal entry of P_RR, an index out of range, NULL.  The batch form takes
+ * pose [batch][3] and P_RR [batch][9] and resets every filter in one launch. */
+int ekf_reset_pose(ekf_handle h, int index, const double pose[3], const double P_RR[9]);
+int ekf_batch_reset_pose(ekf_handle h, const double *pose /*[batch][3]*/, const double *P_RR /*[batch][9]*/);
+
+/* ekf_relocalize: the three steps as one call -- ekf_locate_scan (z, n_z, tol, min_sep, max_base, max_out), the acceptance rule,
+ * ekf_reset_pose at the best hypothesis's fitted pose with the caller's P_RR, ekf_update_matched with that hypothesis's ids and
+ * the caller's R (which must be finite for every valid entry: checked first, with the arguments of the search).
+ * ACCEPTED iff the best hypothesis (the first written) has inliers >= min_inliers (>= 2) and every other written hypothesis that
+ * is not the same pose as the best (the rule above: fitted positions within 2 tol, headings within 2 tol / reach) has
+ * inliers <= best - lead (lead >= 0).  A runner-up beyond the max_out written is not seen: keep max_out generous.
+ * Accepted: returns the best hypothesis's inliers; state and outputs are bit for bit those of the three calls made in sequence.
+ * Refused: returns 0 with the state untouched bit for bit and an open window still open (hyp_out and ids_out still show the best
+ * hypothesis, if there is one; d2_out NaN).  Otherwise a negative status; a refusal of ekf_reset_pose or ekf_update_matched
+ * (sticky statuses) comes back as theirs.
+ * hyp_out: the chosen record (all zero when nothing was found); ids_out [n_z]; d2_out [n_z] (may be NULL): that of
+ * ekf_update_matched.  The batch form decides per filter, writes the counts to n_out[b] (0: refused), resets and updates the
+ * accepted filters only -- each as the one-filter calls on it would -- and returns EKF_OK or a negative status. */
+int ekf_relocalize(ekf_handle h, int index, const double *z /*[n_z][2]*/, const double *R /*[n_z][4]*/, int n_z, double tol, double min_sep,
+                   int max_base, int max_out, int min_inliers, int lead, const double P_RR[9], ekf_locate_hyp *hyp_out, int *ids_out /*[n_z]*/,
+                   double *d2_out /*[n_z] or NULL*/);
+int ekf_batch_relocalize(ekf_handle h, const double *z /*[batch][n_z][2]*/, const double *R /*[batch][n_z][4]*/,
+                         const unsigned char *valid /*[batch][n_z] or NULL*/, int n_z, double tol, double min_sep, int max_base, int max_out,
+                         int min_inliers, int lead, const double *P_RR /*[batch][9]*/, ekf_locate_hyp *hyp_out /*[batch]*/,
+                         int *ids_out /*[batch][n_z]*/, double *d2_out /*[batch][n_z] or NULL*/, int *n_out /*[batch]*/);
+
 /* ---- device-resident step scripts (benchmarks, Monte-Carlo runs) ------------------------------
  * A script is `steps` steps; step s of filter b is
  *     Propagate(ctrl[s][b] = v, w, dt)  with Q from params as ekf_propagate does,
