@@ -37,6 +37,7 @@
 #include "ekf_pairs.hip"
 #include "ekf_fuse.hip"
 #include "ekf_match.hip"
+#include "ekf_match_iter.hip"
 #include "ekf_fix.hip"
 #include "ekf_extract.hip"
 #include "ekf_gate.hip"
@@ -130,7 +131,7 @@ struct DevBlock {
     void *p = nullptr;
     size_t bytes = 0;
 };
-enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_MATCH, BLK_GATE, BLK_GATE_LIST, BLK_ASSOC, BLK_ADD, BLK_LOC, BLK_LOC_LIST, BLK_COUNT };
+enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_MATCH, BLK_ITER, BLK_GATE, BLK_GATE_LIST, BLK_ASSOC, BLK_ADD, BLK_LOC, BLK_LOC_LIST, BLK_COUNT };
 
 // Everything the map operations keep on a handle: the scratch structs their kernels take (ekf_map_scratch.h: arrays and layout) and
 // the allocations behind them.  A block is built by the first call that needs it (block_build in ekf_map_api.hip) and kept.
@@ -145,6 +146,8 @@ enum { BLK_FACTOR, BLK_DUP, BLK_DUP_LIST, BLK_FUSE, BLK_MATCH, BLK_GATE, BLK_GAT
 //   BLK_MATCH      match   ekf_update_matched, ekf_joint_compat,       the longest list brought (zcap,       yes
 //                          ekf_associate_joint that searches,          from 64)
 //                          ekf_update_fixes, ekf_fix_compat
+//   BLK_ITER       iter    ekf_update_matched_iter                     the longest list brought (zcap,       yes
+//                                                                      from 64)
 //   BLK_GATE       gate    ekf_gate_candidates with a valid entry      the longest scan brought (zcap, from  yes
 //                                                                      64) and the capacity (npart)
 //   BLK_GATE_LIST  gate    ekf_gate_candidates that hands pairs out,   the pairs asked for or found (ccap,   no
@@ -165,6 +168,7 @@ struct MapKept {
     DupScratch dup = {};
     FuseScratch fuse = {};
     MatchScratch match = {};
+    IterScratch iter = {};
     GateScratch gate = {};
     AssocScratch assoc = {};
     AddScratch add = {};

@@ -66,6 +66,11 @@ static int match_reserve(ekf_batch *h, int n_meas) {
     if (h->map.blk[BLK_MATCH].p && zcap == h->map.match.zcap) return EKF_OK;
     return block_build(h, BLK_MATCH, /*zero*/ true, &h->map.match, carve_match, zcap);
 }
+static int iter_reserve(ekf_batch *h, int n_meas) {
+    const int zcap = plan_grown_cap(h->map.iter.zcap, n_meas, 64);
+    if (h->map.blk[BLK_ITER].p && zcap == h->map.iter.zcap) return EKF_OK;
+    return block_build(h, BLK_ITER, /*zero*/ true, &h->map.iter, carve_iter, zcap);
+}
 static int gate_reserve(ekf_batch *h, int n_meas, int cand) {
     GateScratch &gs = h->map.gate;
     const int zcap = plan_grown_cap(gs.zcap, n_meas, 64);
@@ -92,6 +97,7 @@ static int map_scratch_rebuild(ekf_batch *h, const MapKept &old) {
     if (old.blk[BLK_DUP_LIST].p) EKF_TRY(dup_reserve(h, old.dup.cap));
     if (old.blk[BLK_FUSE].p) EKF_TRY(fuse_reserve(h));
     if (old.blk[BLK_MATCH].p) EKF_TRY(match_reserve(h, old.match.zcap));
+    if (old.blk[BLK_ITER].p) EKF_TRY(iter_reserve(h, old.iter.zcap));
     if (old.blk[BLK_GATE].p) EKF_TRY(gate_reserve(h, old.gate.zcap, old.gate.ccap));
     if (old.blk[BLK_ASSOC].p) EKF_TRY(assoc_reserve(h));
     if (old.blk[BLK_ADD].p) EKF_TRY(add_reserve(h, old.add.zcap));
@@ -621,6 +627,29 @@ static void match_scatter(const MatchTable &t, const std::vector<double> &d2, in
     }
 }
 
+// The iterations of ekf_update_matched_iter (ekf_match_iter.hip) and where their per-measurement results go; a list update without
+// one linearises once, by its client's own factor.
+struct IterArgs {
+    int max_iter;
+    double tol;
+    int *iters_out;    // [nb][n] or null
+    double *step_out;  // [nb][n] or null
+};
+// The iterations' results in the caller's order, as match_scatter places d2: 0 and NaN for the skipped and the unapplied entries.
+static void iter_scatter(const MatchTable &t, const std::vector<int> &iters, const std::vector<double> &step, int tcap, int icap, int n_z, int nb, const int *n_valid,
+                         const IterArgs &it) {
+    for (size_t q = 0; q < (size_t)nb * n_z; q++) {
+        if (it.iters_out) it.iters_out[q] = 0;
+        if (it.step_out) it.step_out[q] = __builtin_nan("");
+    }
+    for (int k = 0; k < nb; k++)
+        for (int q = 0; q < n_valid[2 * k]; q++) {
+            const size_t to = (size_t)k * n_z + t.src[(size_t)k * tcap + q];
+            if (it.iters_out) it.iters_out[to] = iters[(size_t)k * icap + q];
+            if (it.step_out) it.step_out[to] = step[(size_t)k * icap + q];
+        }
+}
+
 // A list client of the fusion machinery: the checks and the tables of its lists (ekf_map_plan.h) and its two kernels.
 struct ListClient {
     PlanStatus (*values)(const double *z, const double *R, const int *ids, int n, int b0, int nb, int limit);
@@ -636,8 +665,10 @@ static const ListClient FIXES = {plan_fix_values, plan_fix_ids, plan_fix_table, 
 // anything happens to the handle, the ids against the mirror's landmark counts; a call without an entry returns there.  Then:
 // settle, the tables up, the rounds (fuse_rounds: the client's factor, then its gather), the progress record and the distances back
 // in one copy each, and the end of the rewrite (slot rows cleared, the pass sizes restored, the mirror's pose and P_RR refreshed by
-// k_set_meta).
-static int list_update_impl(const ListClient &c, ekf_batch *h, Filters f, const double *z, const double *R, const int *ids, int n, int *n_applied_out, double *d2_out) {
+// k_set_meta).  With `it` (the MATCHED client alone) the round's factor is k_match_factor_iter, and the factorisations and the last
+// step of every entry come back with the distances.
+static int list_update_impl(const ListClient &c, ekf_batch *h, Filters f, const double *z, const double *R, const int *ids, int n, int *n_applied_out, double *d2_out,
+                            const IterArgs *it = nullptr) {
     const int b0 = f.b0, nb = f.nb;
     EKF_TRY(set_error(c.values(z, R, ids, n, b0, nb, -1)));
     HIP_TRY(hipSetDevice(h->device));
@@ -647,6 +678,7 @@ static int list_update_impl(const ListClient &c, ekf_batch *h, Filters f, const 
     if (most == 0) {  // nothing to do: the window stays open
         for (int k = 0; n_applied_out && k < nb; k++) n_applied_out[k] = 0;
         for (size_t q = 0; d2_out && q < (size_t)nb * n; q++) d2_out[q] = __builtin_nan("");
+        if (it) iter_scatter({}, {}, {}, 0, 0, n > 0 ? n : 0, nb, std::vector<int>((size_t)2 * nb, 0).data(), *it);
         return nb == 1 ? h->h_int[b0] : EKF_OK;
     }
     // h_int[b] = landmarks of filter b; a sticky EKF_ERR_TIMEOUT or EKF_ERR_CAPACITY ends it here: the state stays as it is; then
@@ -654,26 +686,34 @@ static int list_update_impl(const ListClient &c, ekf_batch *h, Filters f, const 
     EKF_TRY(quiesce(h, QUIET_SETTLED, ST_INVALID_OR_FULL));
     EKF_TRY(fuse_reserve(h));
     EKF_TRY(match_reserve(h, most));
+    if (it) EKF_TRY(iter_reserve(h, most));
     const EkfDev &dv = h->dv;
     const FuseScratch fs = h->map.fuse;
     const MatchScratch ms = h->map.match;
+    const IterScratch is = h->map.iter;
     hipStream_t s = h->s_chain;
     const MatchTable tab = c.table(z, R, ids, n, nb, ms.zcap);
-    std::vector<int> done((size_t)2 * nb, 0);
-    std::vector<double> d2((size_t)nb * ms.zcap);
+    std::vector<int> done((size_t)2 * nb, 0), iters(it ? (size_t)nb * is.zcap : 0);
+    std::vector<double> d2((size_t)nb * ms.zcap), step(iters.size());
     HostCopies hc(s);
     EKF_TRY(match_upload(h, tab, b0, nb, &hc));
     const int n_max = most_landmarks(counts_of(h, b0), nb);
     // The factor runs BEFORE the gather: a filter whose S is refused gathers nothing.
     EKF_TRY(fuse_rounds(h, f, most, n_max, &hc, done.data(), [&](int round, int m_hi) {
-        hipLaunchKernelGGL(c.factor, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->win.buf_in, round, dv.maxp, /*apply*/ 1, b0);
+        if (it) hipLaunchKernelGGL(k_match_factor_iter, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, ms, is, h->win.buf_in, round, dv.maxp, it->max_iter, it->tol, b0);
+        else hipLaunchKernelGGL(c.factor, dim3((unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->win.buf_in, round, dv.maxp, /*apply*/ 1, b0);
         if (n_max > 0) hipLaunchKernelGGL(c.gather, dim3((unsigned)cdiv(n_max, 256), (unsigned)m_hi, (unsigned)nb), dim3(256), 0, s, dv, fs, ms, h->win.buf_in, round, b0);
     }));
     HIP_TRY(hc.copy(d2.data(), ms.d2 + (size_t)b0 * ms.zcap, sizeof(double) * d2.size(), hipMemcpyDeviceToHost));
+    if (it) {
+        HIP_TRY(hc.copy(iters.data(), is.iters + (size_t)b0 * is.zcap, sizeof(int) * iters.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hc.copy(step.data(), is.step + (size_t)b0 * is.zcap, sizeof(double) * step.size(), hipMemcpyDeviceToHost));
+    }
     HIP_TRY(hc.wait());
     EKF_TRY(check_launch());
     for (int k = 0; n_applied_out && k < nb; k++) n_applied_out[k] = done[2 * k];  // (filled even where the end of the rewrite fails)
     match_scatter(tab, d2, ms.zcap, n, nb, done.data(), d2_out);
+    if (it) iter_scatter(tab, iters, step, ms.zcap, is.zcap, n, nb, done.data(), *it);
     const std::vector<int> n_lm(counts_of(h, b0), counts_of(h, b0) + nb);
     EKF_TRY(finish_rewrite(h, b0, nb, /*rearm*/ true, n_lm.data(), 1, /*flip_buf*/ false));
     return nb == 1 ? n_lm[0] : EKF_OK;
@@ -714,6 +754,23 @@ extern "C" int ekf_update_matched(ekf_handle h, int index, const double *z, cons
 extern "C" int ekf_batch_update_matched(ekf_handle h, const double *z, const double *R, const int *ids, int n_z, int *n_applied_out, double *d2_out) {
     if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
     const int rc = list_update_impl(MATCHED, h, filters_of(h, -1), z, R, ids, n_z, n_applied_out, d2_out);
+    return rc < 0 ? rc : EKF_OK;
+}
+
+extern "C" int ekf_update_matched_iter(ekf_handle h, int index, const double *z, const double *R, const int *ids, int n_z, int max_iter, double tol, int *n_applied_out,
+                                       double *d2_out, int *iters_out, double *step_out) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    EKF_TRY(set_error(plan_iter_args(max_iter, tol)));
+    const IterArgs it = {max_iter, tol, iters_out, step_out};
+    return list_update_impl(MATCHED, h, filters_of(h, index), z, R, ids, n_z, n_applied_out, d2_out, &it);
+}
+
+extern "C" int ekf_batch_update_matched_iter(ekf_handle h, const double *z, const double *R, const int *ids, int n_z, int max_iter, double tol, int *n_applied_out,
+                                             double *d2_out, int *iters_out, double *step_out) {
+    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
+    EKF_TRY(set_error(plan_iter_args(max_iter, tol)));
+    const IterArgs it = {max_iter, tol, iters_out, step_out};
+    const int rc = list_update_impl(MATCHED, h, filters_of(h, -1), z, R, ids, n_z, n_applied_out, d2_out, &it);
     return rc < 0 ? rc : EKF_OK;
 }
 

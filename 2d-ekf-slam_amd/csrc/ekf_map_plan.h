@@ -3,7 +3,8 @@
 // ekf_gate.hip and ekf_locate.hip read.  No HIP call and no handle in here: landmark counts come in as plain arrays, n_lm[k] = landmarks of the k-th filter of the call, whose number in its
 // handle is b0 + k (error texts name that number).  A check reports a status and a text; the caller hands both to set_error.
 // tests/cpp/map_plan_check.cpp, tests/cpp/match_plan_check.cpp, tests/cpp/fix_plan_check.cpp, tests/cpp/gate_plan_check.cpp,
-// tests/cpp/assoc_plan_check.cpp, tests/cpp/add_plan_check.cpp and tests/cpp/locate_plan_check.cpp run all of it on the CPU.
+// tests/cpp/assoc_plan_check.cpp, tests/cpp/add_plan_check.cpp, tests/cpp/locate_plan_check.cpp and tests/cpp/iter_plan_check.cpp run all of
+// it on the CPU.
 #pragma once
 #include <math.h>
 #include <stdarg.h>
@@ -274,6 +275,14 @@ inline PlanStatus plan_match_ids(const int *ids, int n_z, const int *n_lm, int b
 }
 inline MatchTable plan_match_table(const double *z, const double *R, const int *ids, int n_z, int nb, int zcap) {
     return plan_list_table(z, R, ids, n_z, nb, zcap, plan_match_skip);
+}
+
+// The iterations of ekf_update_matched_iter: 1 .. EKF_ITER_MAX factorisations per round, a step bound that is finite and not negative
+// (0: every round runs to max_iter).
+inline PlanStatus plan_iter_args(int max_iter, double tol) {
+    if (max_iter < 1 || max_iter > EKF_ITER_MAX) return plan_fail(EKF_ERR_BAD_ARG, "max_iter = %d is not in 1 .. %d", max_iter, EKF_ITER_MAX);
+    if (!(__builtin_isfinite(tol) && tol >= 0.0)) return plan_fail(EKF_ERR_BAD_ARG, "tol is not finite and not negative");
+    return {};
 }
 
 // ---- absolute fixes (ekf_update_fixes, ekf_fix_compat) ----------------------------------------------------------------------------

@@ -108,6 +108,19 @@ inline void carve_match(MatchScratch &ms, Carver &c, const ScratchGeom &g, int z
     ms.zcap = zcap;
 }
 
+// ---- ekf_match_iter.hip (ekf_update_matched_iter): what the iterating factor tells of each measurement's round, beside MatchScratch ---
+struct IterScratch {
+    double *step;  // [B][zcap]  the last step of the measurement's round
+    int *iters;    // [B][zcap]  the factorisations of its round
+    int zcap;
+};
+inline void carve_iter(IterScratch &is, Carver &c, const ScratchGeom &g, int zcap) {
+    const size_t nz = g.B * (size_t)zcap;
+    is.step = c.take<double>(nz);
+    is.iters = c.take<int>(nz);
+    is.zcap = zcap;
+}
+
 // ---- ekf_gate.hip (ekf_gate_candidates) -------------------------------------------------------------------------------------------
 #define GATE_THREADS 256
 struct GateScratch {

@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "ekf_joint_consistency", "ekf_batch_joint_consistency", "ekf_debug_joint_factor",
     "ekf_find_duplicates", "ekf_batch_find_duplicates",
     "ekf_fuse_landmarks", "ekf_batch_fuse_landmarks",
-    "ekf_update_matched", "ekf_batch_update_matched", "ekf_joint_compat", "ekf_batch_joint_compat",
+    "ekf_update_matched", "ekf_batch_update_matched", "ekf_joint_compat", "ekf_batch_joint_compat", "ekf_update_matched_iter", "ekf_batch_update_matched_iter",
     "ekf_update_fixes", "ekf_batch_update_fixes", "ekf_fix_compat", "ekf_batch_fix_compat",
     "ekf_gate_candidates", "ekf_batch_gate_candidates",
     "ekf_associate_joint", "ekf_batch_associate_joint", "ekf_joint_gates",
@@ -106,6 +106,7 @@ LOCATE_DTYPE = np.dtype([("pose", "f8", (3,)), ("pair_pose", "f8", (3,)), ("ssr"
                          ("meas_b", "i4"), ("lm_i", "i4"), ("lm_j", "i4"), ("reserved", "i4")])
 assert LOCATE_DTYPE.itemsize == ctypes.sizeof(EkfLocateHyp) == 88
 LOCATE_MAX_MEAS, LOCATE_MAX_BASE, LOCATE_MAX_OUT, LOCATE_MAX_CAND = 32, 16, 64, 1 << 22
+ITER_MAX = 16  # EKF_ITER_MAX: the most factorisations of a round of update_matched_iter
 
 _STATS_DTYPE = np.dtype([(n, "f8" if t is ctypes.c_double else "i8") for n, t in EkfStats._fields_])
 
@@ -182,6 +183,8 @@ def load():
     L.ekf_update_matched.argtypes = [_H, ctypes.c_int, _dp, _dp, _ip, ctypes.c_int, _ip, _dp]
     L.ekf_batch_update_matched.argtypes = [_H, _dp, _dp, _ip, ctypes.c_int, _ip, _dp]
     L.ekf_joint_compat.argtypes = [_H, ctypes.c_int, _dp, _dp, _ip, ctypes.c_int, _dp]
+    L.ekf_update_matched_iter.argtypes = [_H, ctypes.c_int, _dp, _dp, _ip, ctypes.c_int, ctypes.c_int, ctypes.c_double, _ip, _dp, _ip, _dp]
+    L.ekf_batch_update_matched_iter.argtypes = [_H, _dp, _dp, _ip, ctypes.c_int, ctypes.c_int, ctypes.c_double, _ip, _dp, _ip, _dp]
     L.ekf_batch_joint_compat.argtypes = [_H, _dp, _dp, _ip, ctypes.c_int, _dp]
     L.ekf_update_fixes.argtypes = [_H, ctypes.c_int, _dp, _dp, _ip, ctypes.c_int, _ip, _dp]
     L.ekf_batch_update_fixes.argtypes = [_H, _dp, _dp, _ip, ctypes.c_int, _ip, _dp]
@@ -711,6 +714,31 @@ class FilterBatch:
         index=None: every filter in one launch sequence (ekf_batch_update_matched), ids [batch][n_z]; returns (n_applied (batch,),
         d2 (batch, n_z))."""
         return self._list_update(self._matched_lists(z, R, ids, index), index, self.L.ekf_update_matched, self.L.ekf_batch_update_matched)
+
+    def update_matched_iter(self, z, R, ids, max_iter=8, tol=1e-8, index=0):
+        """update_matched with every round iterated (ekf_update_matched_iter): the round is relinearised -- on the pose and its own
+        landmarks alone, inside one kernel -- until the largest change of a touched component is at most tol or max_iter (1 ..
+        ITER_MAX) factorisations have run; the last linearisation is applied.  Returns what update_matched returns and two arrays
+        more, (n_landmarks, n_applied, d2, iters, step): iters[k] int32, the factorisations of k's round (0: skipped or not
+        applied), step[k] its last step (NaN: skipped or not applied; above tol: out of iterations); d2 is the prior's joint
+        distance, from the first linearisation.  max_iter=1 is update_matched bit for bit.  index=None: (n_applied (batch,), d2,
+        iters, step (batch, n_z))."""
+        max_iter, tol = int(max_iter), float(tol)
+        if not 1 <= max_iter <= ITER_MAX:
+            raise ValueError("max_iter must be in 1 .. %d" % ITER_MAX)
+        if not (np.isfinite(tol) and tol >= 0.0):
+            raise ValueError("tol must be finite and not negative")
+        lists = self._matched_lists(z, R, ids, index)
+        iters, step = np.zeros(lists[2].shape, dtype=np.int32), np.full(lists[2].shape, np.nan)
+        more = (iters.ctypes.data_as(_ip), _p(step)) if lists[3] else (None, None)
+
+        def single(h, i, z, R, a, n, applied, d2):
+            return self.L.ekf_update_matched_iter(h, i, z, R, a, n, max_iter, tol, applied, d2, *more)
+
+        def batch(h, z, R, a, n, applied, d2):
+            return self.L.ekf_batch_update_matched_iter(h, z, R, a, n, max_iter, tol, applied, d2, *more)
+
+        return self._list_update(lists, index, single, batch) + (iters, step)
 
     def joint_compat(self, z, R, ids, index=0):
         """The score of one association hypothesis (ekf_joint_compat), nothing applied: d2[k] is the joint Mahalanobis distance of
@@ -1246,6 +1274,13 @@ class KalmanFilter:
         """Apply measurements with given landmarks as joint updates (FilterBatch.update_matched): (n_landmarks, n_applied, d2);
         refreshes X, Y, Phi."""
         out = self._f.update_matched(z, R, ids, 0)
+        self._mirror()
+        return out
+
+    def update_matched_iter(self, z, R, ids, max_iter=8, tol=1e-8):
+        """update_matched with every round iterated (FilterBatch.update_matched_iter): (n_landmarks, n_applied, d2, iters, step);
+        refreshes X, Y, Phi."""
+        out = self._f.update_matched_iter(z, R, ids, max_iter, tol, 0)
         self._mirror()
         return out
 

@@ -437,6 +437,36 @@ int ekf_batch_update_matched(ekf_handle h, const double *z /*[batch][n_z][2]*/, 
 int ekf_joint_compat(ekf_handle h, int index, const double *z, const double *R, const int *ids, int n_z, double *d2_out /*[n_z]*/);
 int ekf_batch_joint_compat(ekf_handle h, const double *z, const double *R, const int *ids, int n_z, double *d2_out /*[batch][n_z]*/);
 
+/* ekf_update_matched with every round ITERATED (the iterated EKF update, Gauss-Newton on the round's MAP cost): the measurement
+ * model is bilinear in heading and offset, so one linearisation at a heading that is off by e misplaces a landmark at range r by
+ * about r e^2 / 2 -- decimetres behind a blind stretch or a coarse ekf_reset_pose.  Rounds, skips, layouts, host checks, settling,
+ * streaming, sticky statuses, the mirror and the synchronising behaviour are exactly those of ekf_update_matched.  One round, entry
+ * state (x^, P), linearisation points xi_0 = x^, xi_1, ... (held for the pose and the round's landmarks: nothing else enters H, d):
+ *     H_i, h(xi_i): as in ekf_update_matched, at xi_i; cos and sin of xi_i[2] from the device library, once per iteration;
+ *     d_0 = h(x^) - z, by ekf_update_matched's own expression;   i > 0:  d_i = (h(xi_i) - z) + H_i (x^ - xi_i);
+ *     W_i = P H_i^T;   S_i = H_i W_i + blockdiag(R_k) = U_i^T U_i  (the 2^-44 pivot rule, in every iteration);   y_i = U_i^-T d_i;
+ *     xi_i+1 = x^ - W_i S_i^-1 d_i  on the touched components;   step_i = max |xi_i+1 - xi_i| over them, metres and radians alike;
+ * the round stops behind iteration i when step_i <= tol or i + 1 == max_iter, and then
+ *     x <- x^ - V_i y_i,   P <- P - V_i V_i^T,   V_i = W_i U_i^-1.
+ * A pivot refused in ANY iteration refuses the round and all later ones, as in ekf_update_matched: a result, not an error.
+ * iters_out[k] (may be NULL): the factorisations of k's round; 0 for skipped and unapplied entries.  step_out[k] (may be NULL): the
+ * last step of k's round, NaN for skipped and unapplied entries; a value above tol says that the round ran out of iterations.
+ * d2_out: the running joint distance from iteration 0 -- the PRIOR's compatibility, the bits ekf_joint_compat gives at the round's
+ * entry state.  max_iter outside 1 .. EKF_ITER_MAX, or a tol that is negative or not finite, is EKF_ERR_BAD_ARG, found on the host
+ * before the handle is touched.  With max_iter = 1 the call is ekf_update_matched bit for bit.  The same bits on every call, and
+ * filter b of the batch form gets the bits of the one-filter call on b.  The whole iteration runs inside the round's one factor
+ * kernel, on the pose and the matched landmarks alone: an iteration more costs one factorisation, not a pass over the state.
+ * The scratch of ekf_update_matched and 12 bytes more per measurement (for at least 64 per filter), allocated at the first iterated
+ * call with a measurement, kept on the handle (ekf_device_bytes counts it, ekf_reserve builds it again) and freed by ekf_destroy. */
+#define EKF_ITER_MAX 16
+int ekf_update_matched_iter(ekf_handle h, int index, const double *z, const double *R, const int *ids, int n_z, int max_iter, double tol,
+                            int *n_applied_out /* may be NULL */, double *d2_out /*[n_z] or NULL*/, int *iters_out /*[n_z] or NULL*/,
+                            double *step_out /*[n_z] or NULL*/);
+int ekf_batch_update_matched_iter(ekf_handle h, const double *z /*[batch][n_z][2]*/, const double *R /*[batch][n_z][4]*/,
+                                  const int *ids /*[batch][n_z]*/, int n_z, int max_iter, double tol, int *n_applied_out /*[batch] or NULL*/,
+                                  double *d2_out /*[batch][n_z] or NULL*/, int *iters_out /*[batch][n_z] or NULL*/,
+                                  double *step_out /*[batch][n_z] or NULL*/);
+
 /* Absolute observations, applied on the device as joint updates: a position fix of the robot (GNSS, an overhead camera), a heading
  * from another source, a surveyed position of a landmark.  The reference's one absolute observation is its scalar compass
  * (kalmanfilter.cpp:96-130, called at slam.cpp:144-147; here ekf_update_compass); this is its generalisation, the contract that of
