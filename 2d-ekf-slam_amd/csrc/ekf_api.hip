@@ -39,6 +39,7 @@
 #include "ekf_match.hip"
 #include "ekf_match_iter.hip"
 #include "ekf_fix.hip"
+#include "ekf_polar.hip"
 #include "ekf_extract.hip"
 #include "ekf_gate.hip"
 #include "ekf_locate.hip"

@@ -28,6 +28,11 @@
 #define EKF_INF 999999999999.0 /* kalmanfilter.h:17 */
 #define EKF_MAX_PENDING 32
 #define EKF_MAX_PAIRS (EKF_MAX_PENDING / 2)
+// An entry of ekf_update_polar on its way to the device (MatchScratch::ids of that call): the landmark in the low bits, the kind
+// (EKF_POLAR_*) above them -- a landmark number stays below EKF_MAX_CAPACITY = 16 000 < 2^14.  A skipped entry stays -1.
+#define POLAR_KIND_SHIFT 14
+#define POLAR_ID_MASK ((1 << POLAR_KIND_SHIFT) - 1)
+static_assert(EKF_MAX_CAPACITY <= (1 << POLAR_KIND_SHIFT), "a landmark number must fit below the kind");
 #define EKF_CHAIN_MAX_THREADS 256 /* one control wave + up to 192 workers: one wave per SIMD, 512-VGPR budget */
 #define EKF_CHAIN_MAX_WGS 64 /* workgroups sharing one filter in k_chain: one lane of a wave polls each */
 #define EKF_CHAIN_MAX_OPS 64 /* operations per k_chain launch */

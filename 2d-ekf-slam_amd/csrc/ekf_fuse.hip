@@ -22,7 +22,7 @@
 // to zero tiles; this round and the later ones return at once for it, and nothing of it but the slot rows (cleared at the end of
 // the call) has been written.
 //
-// The machinery and its clients (fusion here, ekf_match.hip, ekf_fix.hip).  A client supplies, per round, a factor kernel -- one
+// The machinery and its clients (fusion here, ekf_match.hip, ekf_match_iter.hip, ekf_fix.hip, ekf_polar.hip).  A client supplies, per round, a factor kernel -- one
 // workgroup per filter that fills A = [S | d | W_R^T] in LDS, runs fuse_cholesky and ends in fuse_publish -- and a gather kernel
 // that leaves W's landmark rows in the FA slot rows (fuse_store_w), for the entries fuse_publish accepted (fs.m_round) or, in front
 // of the factor, for all of them.  It gets back x -= V y and P -= V V^T from k_fuse_apply, k_fuse_finish and the pass, the count

@@ -660,6 +660,8 @@ struct ListClient {
 };
 static const ListClient MATCHED = {plan_match_values, plan_match_ids, plan_match_table, k_match_factor, k_match_gather};  // ekf_match.hip
 static const ListClient FIXES = {plan_fix_values, plan_fix_ids, plan_fix_table, k_fix_factor, k_fix_gather};              // ekf_fix.hip; ids carries the kinds
+// ekf_polar.hip; ids is the packed list of polar_front: the landmark with its kind above it
+static const ListClient POLAR = {plan_polar_values, plan_polar_ids, plan_polar_table, k_polar_factor, k_polar_gather};
 
 // The filters f, filter f.b0 + k with the n entries at z + k * n * 2, R + k * n * 4, ids + k * n.  The values are checked before
 // anything happens to the handle, the ids against the mirror's landmark counts; a call without an entry returns there.  Then:
@@ -803,6 +805,36 @@ extern "C" int ekf_fix_compat(ekf_handle h, int index, const double *z, const do
 extern "C" int ekf_batch_fix_compat(ekf_handle h, const double *z, const double *R, const int *what, int n, double *d2_out) {
     if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
     return list_compat_impl(FIXES, h, filters_of(h, -1), z, R, what, n, d2_out);
+}
+
+// The polar calls' front: the caller's ids and kinds into the one list a ListClient takes (plan_polar_pack: its checks run here,
+// before the handle is touched, the POLAR client's own behind them), then the update or, with apply == 0, the score.
+static int polar_front(ekf_batch *h, Filters f, const double *z, const double *R, const int *ids, const int *kind, int n, int *n_applied_out, double *d2_out, int apply) {
+    std::vector<int> packed;
+    EKF_TRY(set_error(plan_polar_pack(ids, kind, n, f.b0, f.nb, &packed)));
+    const int *p = n > 0 ? packed.data() : nullptr;
+    return apply ? list_update_impl(POLAR, h, f, z, R, p, n, n_applied_out, d2_out) : list_compat_impl(POLAR, h, f, z, R, p, n, d2_out);
+}
+
+extern "C" int ekf_update_polar(ekf_handle h, int index, const double *z, const double *R, const int *ids, const int *kind, int n, int *n_applied_out, double *d2_out) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return polar_front(h, filters_of(h, index), z, R, ids, kind, n, n_applied_out, d2_out, /*apply*/ 1);
+}
+
+extern "C" int ekf_batch_update_polar(ekf_handle h, const double *z, const double *R, const int *ids, const int *kind, int n, int *n_applied_out, double *d2_out) {
+    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
+    const int rc = polar_front(h, filters_of(h, -1), z, R, ids, kind, n, n_applied_out, d2_out, /*apply*/ 1);
+    return rc < 0 ? rc : EKF_OK;
+}
+
+extern "C" int ekf_polar_compat(ekf_handle h, int index, const double *z, const double *R, const int *ids, const int *kind, int n, double *d2_out) {
+    if (!filter_ok(h, index)) return set_error(EKF_ERR_BAD_ARG, "bad argument");
+    return polar_front(h, filters_of(h, index), z, R, ids, kind, n, nullptr, d2_out, /*apply*/ 0);
+}
+
+extern "C" int ekf_batch_polar_compat(ekf_handle h, const double *z, const double *R, const int *ids, const int *kind, int n, double *d2_out) {
+    if (!h) return set_error(EKF_ERR_BAD_ARG, "null handle");
+    return polar_front(h, filters_of(h, -1), z, R, ids, kind, n, nullptr, d2_out, /*apply*/ 0);
 }
 
 // ---- individual compatibility ---------------------------------------------------------------------

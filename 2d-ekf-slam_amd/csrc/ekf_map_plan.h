@@ -1,9 +1,9 @@
 // ekf_map_plan.h -- the host-side planning of the map operations (ekf_map_api.hip) as pure code: the checks of the lists a caller
-// hands in and the tables the kernels of ekf_rewrite.hip, ekf_extract.hip, ekf_pairs.hip, ekf_fuse.hip, ekf_match.hip, ekf_fix.hip,
+// hands in and the tables the kernels of ekf_rewrite.hip, ekf_extract.hip, ekf_pairs.hip, ekf_fuse.hip, ekf_match.hip, ekf_fix.hip, ekf_polar.hip,
 // ekf_gate.hip and ekf_locate.hip read.  No HIP call and no handle in here: landmark counts come in as plain arrays, n_lm[k] = landmarks of the k-th filter of the call, whose number in its
 // handle is b0 + k (error texts name that number).  A check reports a status and a text; the caller hands both to set_error.
 // tests/cpp/map_plan_check.cpp, tests/cpp/match_plan_check.cpp, tests/cpp/fix_plan_check.cpp, tests/cpp/gate_plan_check.cpp,
-// tests/cpp/assoc_plan_check.cpp, tests/cpp/add_plan_check.cpp, tests/cpp/locate_plan_check.cpp and tests/cpp/iter_plan_check.cpp run all of
+// tests/cpp/assoc_plan_check.cpp, tests/cpp/add_plan_check.cpp, tests/cpp/locate_plan_check.cpp, tests/cpp/iter_plan_check.cpp and tests/cpp/polar_plan_check.cpp run all of
 // it on the CPU.
 #pragma once
 #include <math.h>
@@ -319,6 +319,94 @@ inline PlanStatus plan_fix_ids(const int *what, int n, const int *n_lm, int b0, 
 }
 inline MatchTable plan_fix_table(const double *z, const double *R, const int *what, int n, int nb, int zcap) {
     return plan_list_table(z, R, what, n, nb, zcap, plan_fix_skip);
+}
+
+// ---- polar measurements (ekf_update_polar, ekf_polar_compat) ----------------------------------------------------------------------
+// The lists of nb filters, filter k's n entries at ids + k * n and kind + k * n; ids[q] == -1: no entry (its kind is not looked at).
+// The structural checks -- n, the two pointers, every id >= -1, the kind of every kept entry one of EKF_POLAR_* -- and the list the
+// device takes: *packed [nb][n], -1 for a skipped entry, else the landmark with its kind above it (POLAR_KIND_SHIFT, ekf_device.h).
+// An id that does not fit below the kind is no landmark of any handle: it is packed as POLAR_ID_MASK, which plan_polar_ids refuses
+// under its own number.
+inline int plan_polar_id(int packed) { return packed & POLAR_ID_MASK; }
+inline int plan_polar_kind(int packed) { return packed >> POLAR_KIND_SHIFT; }
+inline PlanStatus plan_polar_pack(const int *ids, const int *kind, int n, int b0, int nb, std::vector<int> *packed) {
+    packed->clear();
+    if (n < 0) return plan_fail(EKF_ERR_BAD_ARG, "negative entry count");
+    if (n > 0 && (!ids || !kind)) return plan_fail(EKF_ERR_BAD_ARG, "a null list with n > 0");
+    packed->assign((size_t)nb * n, -1);
+    for (int k = 0; k < nb; k++)
+        for (int q = 0; q < n; q++) {
+            const size_t at = (size_t)k * n + q;
+            if (ids[at] < -1) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, entry %d: id %d (a landmark, or -1 to skip)", b0 + k, q, ids[at]);
+            if (ids[at] < 0) continue;
+            if (kind[at] < EKF_POLAR_RANGE || kind[at] > EKF_POLAR_BOTH)
+                return plan_fail(EKF_ERR_BAD_ARG, "filter %d, entry %d: kind %d (EKF_POLAR_RANGE, EKF_POLAR_BEARING or EKF_POLAR_BOTH)", b0 + k, q, kind[at]);
+            (*packed)[at] = std::min(ids[at], POLAR_ID_MASK) | kind[at] << POLAR_KIND_SHIFT;
+        }
+    return {};
+}
+// The values of a packed list, z + k * n * 2 and R + k * n * 4: the pointers, the values a kind reads finite (RANGE: z[0] and R[0];
+// BEARING: z[1] and R[3]; BOTH: all six), no negative variance of a one-component entry, and at most `limit` entries per filter
+// (limit < 0: any number).  With plan_polar_pack: everything that is checked before the handle is touched.
+inline PlanStatus plan_polar_values(const double *z, const double *R, const int *packed, int n, int b0, int nb, int limit) {
+    if (n < 0) return plan_fail(EKF_ERR_BAD_ARG, "negative entry count");
+    if (n > 0 && (!z || !R || !packed)) return plan_fail(EKF_ERR_BAD_ARG, "a null list with n > 0");
+    for (int k = 0; k < nb; k++) {
+        int kept = 0;
+        for (int q = 0; q < n; q++) {
+            const size_t at = (size_t)k * n + q;
+            if (packed[at] < 0) continue;
+            kept++;
+            const int kd = plan_polar_kind(packed[at]);
+            if (kd == EKF_POLAR_BOTH) {
+                if (!plan_entry_finite(z, R, at)) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, entry %d: z or R is not finite", b0 + k, q);
+                continue;
+            }
+            const int e = kd == EKF_POLAR_BEARING;  // the component read: z[e], R[3 e]
+            if (!__builtin_isfinite(z[2 * at + e]) || !__builtin_isfinite(R[4 * at + 3 * e])) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, entry %d: z or R is not finite", b0 + k, q);
+            if (R[4 * at + 3 * e] < 0.0) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, entry %d: a negative %s variance", b0 + k, q, e ? "bearing" : "range");
+        }
+        if (limit >= 0 && kept > limit) return plan_fail(EKF_ERR_BAD_ARG, "filter %d: %d entries in one list (at most %d)", b0 + k, kept, limit);
+    }
+    return {};
+}
+// ... and the landmarks against the landmark counts n_lm[k], once they are current.  *most = the most entries of a filter.
+inline PlanStatus plan_polar_ids(const int *packed, int n, const int *n_lm, int b0, int nb, int *most) {
+    *most = 0;
+    for (int k = 0; k < nb; k++) {
+        int kept = 0;
+        for (int q = 0; q < n; q++) {
+            const int p = packed[(size_t)k * n + q];
+            if (p < 0) continue;
+            if (plan_polar_id(p) >= n_lm[k]) return plan_fail(EKF_ERR_BAD_ARG, "filter %d, entry %d: landmark id %d is not one of its %d landmarks", b0 + k, q, plan_polar_id(p), n_lm[k]);
+            kept++;
+        }
+        *most = std::max(*most, kept);
+    }
+    return {};
+}
+// The tables k_polar_factor reads, as plan_list_table builds them, idt the packed entries: the live component of a one-component
+// entry in row 0 -- of a RANGE entry z[0] and R[0], of a BEARING entry z[1] and R[3] moved to z[0] and R[0] --, zeros behind it.
+inline MatchTable plan_polar_table(const double *z, const double *R, const int *packed, int n, int nb, int zcap) {
+    MatchTable t;
+    t.zt.assign((size_t)nb * zcap * 2, 0.0), t.Rt.assign((size_t)nb * zcap * 4, 0.0);
+    t.idt.assign((size_t)nb * zcap, 0), t.src.assign((size_t)nb * zcap, -1), t.cnt.assign((size_t)nb, 0);
+    for (int k = 0; k < nb; k++)
+        for (int q = 0; q < n; q++) {
+            const size_t at = (size_t)k * n + q;
+            if (packed[at] < 0 || t.cnt[k] >= zcap) continue;
+            const size_t to = (size_t)k * zcap + t.cnt[k]++;
+            const int kd = plan_polar_kind(packed[at]);
+            if (kd == EKF_POLAR_BOTH) {
+                for (int e = 0; e < 2; e++) t.zt[2 * to + e] = z[2 * at + e];
+                for (int e = 0; e < 4; e++) t.Rt[4 * to + e] = R[4 * at + e];
+            } else {
+                const int e = kd == EKF_POLAR_BEARING;
+                t.zt[2 * to] = z[2 * at + e], t.Rt[4 * to] = R[4 * at + 3 * e];
+            }
+            t.idt[to] = packed[at], t.src[to] = q;
+        }
+    return t;
 }
 
 // ---- individual compatibility (ekf_gate_candidates) -------------------------------------------------------------------------------

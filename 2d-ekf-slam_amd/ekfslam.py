@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("EKFSLAM_LIB", os.path.join(_HERE, "lib", "libekfslam_
 OK, ERR_BAD_ARG, ERR_CAPACITY, ERR_HIP, ERR_NO_DEVICE, ERR_STATE, ERR_TIMEOUT = 0, -1, -2, -3, -4, -5, -6
 NEW, OLD, IGNORE = 1, 2, 3
 FIX_SKIP, FIX_POSITION, FIX_HEADING = -1, -2, -3  # the kinds of ekf_update_fixes beside a landmark number
+POLAR_RANGE, POLAR_BEARING, POLAR_BOTH = 1, 2, 3  # the kinds of ekf_update_polar
 
 # every symbol include/ekfslam_c.h declares
 ABI_SYMBOLS = [
@@ -33,6 +34,7 @@ ABI_SYMBOLS = [
     "ekf_fuse_landmarks", "ekf_batch_fuse_landmarks",
     "ekf_update_matched", "ekf_batch_update_matched", "ekf_joint_compat", "ekf_batch_joint_compat", "ekf_update_matched_iter", "ekf_batch_update_matched_iter",
     "ekf_update_fixes", "ekf_batch_update_fixes", "ekf_fix_compat", "ekf_batch_fix_compat",
+    "ekf_update_polar", "ekf_batch_update_polar", "ekf_polar_compat", "ekf_batch_polar_compat",
     "ekf_gate_candidates", "ekf_batch_gate_candidates",
     "ekf_associate_joint", "ekf_batch_associate_joint", "ekf_joint_gates",
     "ekf_add_landmarks", "ekf_batch_add_landmarks", "ekf_update_joint", "ekf_batch_update_joint",
@@ -190,6 +192,10 @@ def load():
     L.ekf_batch_update_fixes.argtypes = [_H, _dp, _dp, _ip, ctypes.c_int, _ip, _dp]
     L.ekf_fix_compat.argtypes = [_H, ctypes.c_int, _dp, _dp, _ip, ctypes.c_int, _dp]
     L.ekf_batch_fix_compat.argtypes = [_H, _dp, _dp, _ip, ctypes.c_int, _dp]
+    L.ekf_update_polar.argtypes = [_H, ctypes.c_int, _dp, _dp, _ip, _ip, ctypes.c_int, _ip, _dp]
+    L.ekf_batch_update_polar.argtypes = [_H, _dp, _dp, _ip, _ip, ctypes.c_int, _ip, _dp]
+    L.ekf_polar_compat.argtypes = [_H, ctypes.c_int, _dp, _dp, _ip, _ip, ctypes.c_int, _dp]
+    L.ekf_batch_polar_compat.argtypes = [_H, _dp, _dp, _ip, _ip, ctypes.c_int, _dp]
     L.ekf_gate_candidates.argtypes = [_H, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_double, ctypes.POINTER(EkfCandidate), ctypes.c_int,
                                       ctypes.POINTER(EkfDecision), _ip]
     L.ekf_batch_gate_candidates.argtypes = [_H, _dp, _dp, _up, ctypes.c_int, ctypes.c_double, ctypes.POINTER(EkfCandidate), ctypes.c_int, _ip,
@@ -254,6 +260,21 @@ def _rect_lists(z, R, a):
     """(z, Rc, ids, n) as the C list calls take them, from the ids a [..][n] and arrays with two values of z and a 2x2 R per id."""
     Rc = _f64(np.swapaxes(R.reshape(a.shape + (2, 2)), -1, -2).reshape(a.shape + (4,)))  # column-major blocks
     return _f64(z.reshape(a.shape + (2,))), Rc, np.ascontiguousarray(a, dtype=np.int32), a.shape[-1]
+
+
+def polar_to_cartesian(z, R):
+    """Range-bearing measurements as the Cartesian calls take them (add_landmarks, gate_candidates, locate_scan, update_matched):
+    z [..][2] = (range, bearing in the robot frame), R [..][2][2] over (range, bearing).  Returns (z_xy, R_xy): the robot-frame offset
+    (r cos b, r sin b) and J R J^T with J = [[cos b, -r sin b], [sin b, r cos b]], the noise linearised at the measurement.  Host
+    arithmetic; update_polar takes the polar form itself, without this linearisation."""
+    z, R = np.asarray(z, dtype=np.float64), np.asarray(R, dtype=np.float64)
+    if z.shape[-1:] != (2,) or R.shape != z.shape[:-1] + (2, 2):
+        raise ValueError("z must be [..][2] and R [..][2][2]")
+    r, b = z[..., 0], z[..., 1]
+    c, s = np.cos(b), np.sin(b)
+    J = np.stack([np.stack([c, -r * s], axis=-1), np.stack([s, r * c], axis=-1)], axis=-2)
+    C = J @ R @ np.swapaxes(J, -1, -2)
+    return np.stack([r * c, r * s], axis=-1), 0.5 * (C + np.swapaxes(C, -1, -2))  # (symmetric to the bit)
 
 
 def _greedy_matching(pairs, n_landmarks):
@@ -831,6 +852,55 @@ class FilterBatch:
             _chk(self.L.ekf_fix_compat(self.h, int(index), _p(z), _p(Rc), a.ctypes.data_as(_ip), n, _p(d2)))
         return d2
 
+    def _polar_lists(self, z, R, ids, kind, index):
+        """((z, Rc, ids, n), kind) as ekf_update_polar takes them.  With an index: ids and kind [n], z [n][2] = (range, bearing),
+        R [n][2][2] over (range, bearing); index=None: a leading batch axis on all four (ragged lists: pad ids with -1).  A RANGE
+        entry reads z[k][0] and R[k][0][0] alone, a BEARING entry z[k][1] and R[k][1][1]: the rest may be anything."""
+        lists = self._matched_lists(z, R, ids, index)
+        kd = np.asarray(kind, dtype=np.int64)
+        if kd.shape != lists[2].shape:
+            raise ValueError("kind must have the shape of ids")
+        if np.any((lists[2] >= 0) & ((kd < POLAR_RANGE) | (kd > POLAR_BOTH))):
+            raise ValueError("a kind is POLAR_RANGE, POLAR_BEARING or POLAR_BOTH")
+        return lists, np.ascontiguousarray(np.where(lists[2] >= 0, kd, 0), dtype=np.int32)
+
+    def update_polar(self, z, R, ids, kind, index=0):
+        """Apply landmark measurements in polar form on the device (ekf_update_polar): entry k measures landmark ids[k] (-1:
+        skipped) by kind[k] -- POLAR_RANGE (z[k][0] = the distance, R[k][0][0] its variance), POLAR_BEARING (z[k][1] = the bearing
+        in the robot frame, R[k][1][1] its variance) or POLAR_BOTH (z[k] = (range, bearing), R[k] 2x2).  The entries run as joint
+        updates in rounds of `window`, each linearised at its entry state; gates, counters and the decision log are not involved.
+        Returns (n_landmarks, n_applied, d2) as update_matched: n_applied < the number of non-skipped entries when a round was
+        refused (S not positive definite, or a landmark exactly at the robot's position; that round and the later ones were not
+        applied), d2[k] the joint Mahalanobis distance of k's round up to and including k (NaN: skipped or not applied).
+        index=None: every filter in one launch sequence (ekf_batch_update_polar), ids and kind [batch][n]; returns (n_applied
+        (batch,), d2 (batch, n))."""
+        lists, kd = self._polar_lists(z, R, ids, kind, index)
+        kp = kd.ctypes.data_as(_ip) if lists[3] else None
+
+        def single(h, i, z, R, a, n, applied, d2):
+            return self.L.ekf_update_polar(h, i, z, R, a, kp, n, applied, d2)
+
+        def batch(h, z, R, a, n, applied, d2):
+            return self.L.ekf_batch_update_polar(h, z, R, a, kp, n, applied, d2)
+
+        return self._list_update(lists, index, single, batch)
+
+    def polar_compat(self, z, R, ids, kind, index=0):
+        """The score of one list of polar measurements (ekf_polar_compat), nothing applied: d2[k] is the joint Mahalanobis distance
+        of the list cut after entry k (at most 32 non-skipped entries; NaN: skipped, or behind a refused pivot of S).  The same
+        bits as update_polar's d2 for a list that fits one round.  index=None: ids and kind [batch][n], returns d2 (batch, n)."""
+        (z, Rc, a, n), kd = self._polar_lists(z, R, ids, kind, index)
+        if int((a >= 0).sum(axis=-1).max(initial=0)) > 32:
+            raise ValueError("a list to score holds at most 32 entries")
+        d2 = np.full(a.shape, np.nan)
+        if n == 0:
+            return d2
+        if index is None:
+            _chk(self.L.ekf_batch_polar_compat(self.h, _p(z), _p(Rc), a.ctypes.data_as(_ip), kd.ctypes.data_as(_ip), n, _p(d2)))
+        else:
+            _chk(self.L.ekf_polar_compat(self.h, int(index), _p(z), _p(Rc), a.ctypes.data_as(_ip), kd.ctypes.data_as(_ip), n, _p(d2)))
+        return d2
+
     def _scan_lists(self, z, R, valid, index):
         """(z, Rc, valid or None, n_z) as ekf_gate_candidates takes them.  With an index: z [n_z][2], R [n_z][2][2]; index=None: a
         leading batch axis on both, and on valid [batch][n_z]."""
@@ -1298,6 +1368,17 @@ class KalmanFilter:
     def fix_compat(self, z, R, what):
         """The running joint Mahalanobis distance of one list of fixes (FilterBatch.fix_compat); nothing is applied."""
         return self._f.fix_compat(z, R, what, 0)
+
+    def update_polar(self, z, R, ids, kind):
+        """Apply range, bearing and range-bearing measurements of known landmarks as joint updates (FilterBatch.update_polar):
+        (n_landmarks, n_applied, d2); refreshes X, Y, Phi."""
+        out = self._f.update_polar(z, R, ids, kind, 0)
+        self._mirror()
+        return out
+
+    def polar_compat(self, z, R, ids, kind):
+        """The running joint Mahalanobis distance of one list of polar measurements (FilterBatch.polar_compat); nothing is applied."""
+        return self._f.polar_compat(z, R, ids, kind, 0)
 
     def associate_joint(self, z, R, gate=9.21, joint_gate=None, max_branch=8, max_nodes=65536):
         """The joint-compatibility search of a scan (FilterBatch.associate_joint): (ids, d2, info, nearest, n_skipped); nothing is

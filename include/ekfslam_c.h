@@ -520,6 +520,61 @@ int ekf_batch_update_fixes(ekf_handle h, const double *z /*[batch][n][2]*/, cons
 int ekf_fix_compat(ekf_handle h, int index, const double *z, const double *R, const int *what, int n, double *d2_out /*[n]*/);
 int ekf_batch_fix_compat(ekf_handle h, const double *z, const double *R, const int *what, int n, double *d2_out /*[batch][n]*/);
 
+/* Landmark measurements in POLAR form with known ids, applied on the device as joint updates: a range alone (UWB, radio or acoustic
+ * beacons), a bearing alone (a camera), or both with the noise in polar coordinates (laser, radar) -- no host-side conversion that
+ * linearises the noise first.  The contract is that of ekf_update_matched / ekf_joint_compat with another h and H; everything not
+ * said here is theirs word for word.  Entry k measures landmark ids[k] (-1: skipped, its z, R and kind not looked at) by kind[k]: */
+#define EKF_POLAR_RANGE   1   /* z[0] = |L_i - p| + v,                  var(v) = R[0];  z[1], R[1..3] not looked at */
+#define EKF_POLAR_BEARING 2   /* z[1] = atan2(dy, dx) - phi + v,        var(v) = R[3];  z[0], R[0..2] not looked at */
+#define EKF_POLAR_BOTH    3   /* z = (range, bearing) + v,  cov(v) = R  (2x2 column-major over (range, bearing)) */
+/* The non-skipped entries run in rounds of at most ekf_window(h) in list order.  A round is ONE update, every entry linearised at
+ * the round's entry state, one slot and two columns of W each; with dx = L_i.x - x_R, dy = L_i.y - y_R, q = dx^2 + dy^2, r = sqrt(q):
+ *     range row:    h = r,                     H_R = [-dx / r, -dy / r,  0],   d = r - z_range;
+ *     bearing row:  h = atan2(dy, dx) - phi,   H_R = [ dy / q, -dx / q, -1],   d = wrap(h - z_bearing);
+ *     H_L = -H_R[0:2] for either row;   column pair k of W = P[:, 0:3] H_R,k^T + P[:, L_i] H_L,k^T;
+ *     S = H W + blockdiag(R_k) = U^T U (from the upper triangle);   V = W U^-1;   y = U^-T d;   x <- x - V y;   P <- P - V V^T.
+ * wrap is ekf_update_fixes' expression with the same constants; the heading itself stays unwrapped.  sqrt and atan2 are taken once
+ * per entry and round ON THE DEVICE (the device library's sqrt() and atan2(), which may differ from the host's libm by an ulp).
+ * BOTH: row 0 of the slot is the range row, row 1 the bearing row.  A RANGE or BEARING entry keeps the two-column shape: its one
+ * live row is row 0 of the slot, row 1 is the inert row of EKF_FIX_HEADING -- a zero row and column of S, the diagonal entry
+ * exactly 1, d = 0 --, so its pivot is 1 and its y and its column of V are exact zeros: its d2 adds exactly 0.  The same landmark
+ * may appear several times in a round, under different kinds too.
+ * S of a round counts as not positive definite by ekf_update_matched's rule: a pivot not above 2^-44 of its own diagonal entry of S
+ * (or NaN), e.g. the same landmark's range twice with R = 0.  A landmark exactly at the robot's position (q == 0) has no defined H:
+ * its pivot is NaN and its round is refused the same way.  That round and all later ones are then NOT applied: the state is that
+ * after the completed rounds, *n_applied_out (may be NULL) counts their entries, their d2 stays valid, the refused and later entries
+ * get NaN, and no NaN or Inf is written into the filter.  A result, not an error.
+ * d2_out[k] (may be NULL): the running sum of y^2 of k's round up to and including k; NaN for skipped and for unapplied entries.  A
+ * RANGE entry alone in a round: (r - z)^2 / (H P H^T + R).
+ * Checked on the host before the handle is touched: n < 0, a NULL z / R / ids / kind with n > 0, an id < -1, a kind outside 1..3 of
+ * a non-skipped entry, a non-finite value among those the kind reads, a negative variance of a RANGE or BEARING entry, an index out
+ * of range -- EKF_ERR_BAD_ARG; then the ids against the landmark count (id >= N: EKF_ERR_BAD_ARG, the state untouched).  n = 0, or
+ * every entry skipped, is a no-op that leaves an open window open.
+ * Otherwise, as ekf_update_matched: deferred slots are folded first, a streaming launch is stopped (immediate-mode calls stream
+ * again afterwards), each round costs one dense pass over P_LL, a sticky EKF_ERR_TIMEOUT / EKF_ERR_CAPACITY is returned unchanged
+ * with nothing modified, gates, counters and the decision log are not involved, the host mirror shows the new pose and P_RR, every
+ * device buffer ends as ekf_set_state of the result would leave it, and the call synchronises.  No atomics, one writer per value,
+ * every sum in a fixed order: the same bits on every call, and filter b of the batch form gets the bits of the one-filter call on b.
+ * ekf_update_polar returns the landmark count (unchanged) or a negative status; the batch form takes filter b's lists at
+ * z + b * n * 2, R + b * n * 4, ids + b * n, kind + b * n (ragged lists: pad ids with -1) and returns EKF_OK or a negative status.
+ * The scratch is that of ekf_update_matched (the same blocks: a handle that has made either call has them). */
+int ekf_update_polar(ekf_handle h, int index, const double *z /*[n][2]*/, const double *R /*[n][4], column-major 2x2*/,
+                     const int *ids /*[n]*/, const int *kind /*[n]*/, int n, int *n_applied_out /* may be NULL */,
+                     double *d2_out /*[n] or NULL*/);
+int ekf_batch_update_polar(ekf_handle h, const double *z /*[batch][n][2]*/, const double *R /*[batch][n][4]*/,
+                           const int *ids /*[batch][n]*/, const int *kind /*[batch][n]*/, int n, int *n_applied_out /*[batch] or NULL*/,
+                           double *d2_out /*[batch][n] or NULL*/);
+
+/* The score of ONE list of polar measurements, nothing applied: the same S, factor and y as a round of ekf_update_polar (the same
+ * kernel) for at most EKF_MAX_PENDING = 32 non-skipped entries, whatever the window; more is EKF_ERR_BAD_ARG, and so is everything
+ * ekf_update_polar refuses, and a NULL d2_out with n > 0.  d2_out[k]: the joint distance of the list cut after entry k; NaN for
+ * skipped entries, and from the first refused pivot on (the call still returns EKF_OK).  For a list that fits one round of
+ * ekf_update_polar the two calls give the same bits of d2.  The filter is only read, behind the rule of ekf_joint_compat. */
+int ekf_polar_compat(ekf_handle h, int index, const double *z, const double *R, const int *ids, const int *kind, int n,
+                     double *d2_out /*[n]*/);
+int ekf_batch_polar_compat(ekf_handle h, const double *z, const double *R, const int *ids, const int *kind, int n,
+                           double *d2_out /*[batch][n]*/);
+
 /* Where the hypotheses come from: the individual compatibility table of a scan.  For every measurement k and every landmark l of
  * the filter, res, S (symmetrised) and d2 = res^T S^-1 res of the association sweep (Update.cpp:103-136), EVERY measurement against
  * the same, unchanged state -- not the sequential chain of ekf_update.  z and R use the layouts of ekf_batch_update; cos phi and
